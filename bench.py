@@ -17,15 +17,23 @@ the circular buffer (near target 510); step times before and after it are report
 bytes are exchanged over RCCL and the streams gathered to rank 0. Inputs are resident in HBM before the timed region. One
 JSON line is printed by rank 0.
 
+A step is that round at every --steps, so `ms_per_step` means the same whatever the count. The collection's rounds are
+generated once (1023 targets at one GPU: more than twice what the buffer holds); a run of more rounds goes through them again,
+every genome long after its earlier copy has left the buffer, and laps the buffer as often as it needs.
+
 `python bench.py --gpus N` starts its own N ranks (children, before anything in this process touches a GPU) and watches
 them: a rank that dies ends the run within seconds with a line that says `"value": null` and why (spawn_ranks); under
 `python -m torch.distributed.run` (WORLD_SIZE set) it is one of the ranks, with a 120 s process-group timeout.
 
-Beside the headline, N = 1 only and never inside its timed region (`--no-extras` skips them): `cpp_host` — the product's C++
+A plain run times the headline and nothing else. `--full` (N = 1 only, never inside the timed region; `--no-extras` then keeps only
+the CPU baseline) adds what stands beside it: `scaling_reference` — the step of the scaling curve; `cpp_host` — the product's C++
 host (`mbgc-hip c --bench`) on the same collection from FASTA files; `configs` — BASELINE configs[1] (128 genomes, matcher
 only), the configs[4] data class and sizing (mixed-species genomes, `-m 3`, 4.5e9-byte reference with 40-bit offsets)
 and the same genomes in `-m1` rounds (rounds on a divergent collection go on in units) through the C++ host, each
 with its match-finding kernel's roofline; `cpu_baseline` — the reference's own OpenMP path.
+
+`--dump-outputs DIR` writes what the last timed step gave its caller (match counts, processMatches' counters, the six streams)
+as .npy files after the timed region (dump_outputs).
 
 Diagnostics (never the headline): --no-emit (matcher only), --from-host (queries cross PCIe inside the timed region),
 --check (first round against the oracle); environment: MBGC_BENCH_MAX_REF (another buffer size), MBGC_BENCH_BLOCK_STATS
@@ -540,12 +548,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--round", type=int, default=0, help="targets per GPU per step (default: what fits the sliding window, at most 64, divided by the GPUs)")
     ap.add_argument("--length", type=int, default=GENOME_LEN)
-    ap.add_argument("--cpu-sample", type=int, default=128, help="targets timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=128, help="targets timed on the CPU baseline (0 = skip; with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure what stands beside the headline (the constant-step line for the scaling curve, the C++ "
+                         "host on the same collection, the other configs' lines, the CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one gave its caller to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--check", action="store_true", help="compare the first step's matches with the oracle")
     ap.add_argument("--no-emit", action="store_true", help="matcher only (no stream emission) inside the step")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1 only: skip what is measured beside the headline (the constant-step line for the scaling curve, the C++ host "
-                         "on the same collection, the other configs' lines)")
+                    help="with --full: skip what is measured beside the headline (the constant-step line for the scaling curve, the C++ host "
+                         "on the same collection, the other configs' lines) but keep the CPU baseline")
     ap.add_argument("--from-host", action="store_true",
                     help="diagnostic, not the headline: every timed round's queries start in pinned host memory and cross PCIe "
                          "inside the timed region (double-buffered on a copy stream); reported under its own metric name")
@@ -571,23 +584,30 @@ def main():
     # can be read — the largest multiple of 8 the window allows (24), dealt 12 / 6 / 3 per GPU at N = 2 / 4 / 8; the one-GPU run
     # times that step too, beside its headline ("scaling_reference").
     SCALE_STEP = max(8, cap // 8 * 8)
+    # A step is that round whatever --steps is, so that ms_per_step means the same at every step count. The rounds of the
+    # collection (at most COLLECTION targets, and at least twice what the buffer holds) are generated once; a run with more rounds
+    # than that goes through them again, each genome long after its first copy has left the buffer (--round n: every target a
+    # genome of its own, as many as the run asks for).
     if args.round > 0:
         R = args.round
     elif world == 1:
-        R = max(1, min(cap, COLLECTION // (steps + warm)))
+        R = cap
     else:
-        R = max(1, min(SCALE_STEP, COLLECTION // (steps + warm)) // world)
-    n_targets = (steps + warm) * R * world
-    extras = (world == 1 and rank == 0 and not args.no_extras and not args.from_host and not args.no_emit and args.round <= 0 and
+        R = max(1, SCALE_STEP // world)
+    n_rounds = steps + warm
+    pool = n_rounds if args.round > 0 else max(1, min(n_rounds, max(COLLECTION, 2 * max_ref // args.length) // (R * world)))
+    n_targets = n_rounds * R * world                # targets the run matches
+    n_pool = pool * R * world                       # genomes it generates (targets 1..n_pool, then 1.. again)
+    extras = (args.full and world == 1 and rank == 0 and not args.no_extras and not args.from_host and not args.no_emit and args.round <= 0 and
               args.length == GENOME_LEN and "MBGC_BENCH_MAX_REF" not in os.environ and not os.environ.get("MBGC_BENCH_SERIAL"))
     REF_WARM, REF_STEPS = 2, 6
     ref_R = min(SCALE_STEP, R)
-    n_ref = (REF_WARM + REF_STEPS) * ref_R if extras and n_targets + (REF_WARM + REF_STEPS) * ref_R <= COLLECTION else 0
+    n_ref = (REF_WARM + REF_STEPS) * ref_R if extras and n_pool + (REF_WARM + REF_STEPS) * ref_R <= COLLECTION else 0
     # synthetic collection (SURVEY.md §8d recipe), generated by forked workers BEFORE this process touches the GPU:
     # this rank's targets of every round, one host array per round
     base = synth.base_codes(args.length)
-    sched = round_schedule(n_targets, R, world)
-    sched_ref = [[[n_targets + r0 + t for t in range(ref_R)]] for r0 in range(0, n_ref, ref_R)]
+    sched = round_schedule(n_pool, R, world)
+    sched_ref = [[[n_pool + r0 + t for t in range(ref_R)]] for r0 in range(0, n_ref, ref_R)]
     mine_all = [1 + t for rnd in sched + sched_ref for t in rnd[rank]]
     if os.environ.get("MBGC_BENCH_SAME"):               # experiment: every target of a round is the same genome (perfect inter-target locality)
         mine_all = [1 + rnd[rank][0] for rnd in sched for t in rnd[rank]]
@@ -665,6 +685,10 @@ def main():
         bufs.append((torch.from_numpy(host_rounds[ri]).to(dev), offs))
         host_rounds[ri] = None
     torch.cuda.synchronize()
+
+    def inp(s):                                        # round s of the run: the pool's rounds in turn, then the scaling reference's
+        return bufs[s % pool] if s < n_rounds else bufs[pool + s - n_rounds]
+    n_run = n_rounds + len(sched_ref)
     hostbufs, copy_stream, slots, copied = None, None, None, None
     if args.from_host:
         hostbufs = [b.cpu().pin_memory() for b, _ in bufs]
@@ -678,7 +702,7 @@ def main():
     ep = binding.emit_params(1, enable40bitReference=1 if bit40 else 0) if emit else None
     runner = RoundRunner(m, rank, world, None, dev, lazy=True, emit_params=ep, keep_streams=False)
     runner.start()
-    tot_matches = 0
+    tot_matches, last_counts = 0, None
 
     def barrier():
         torch.cuda.synchronize()
@@ -688,7 +712,7 @@ def main():
 
     for s in range(warm):
         runner.keep_streams = bool(args.check and s == 0)
-        runner.run_round(*bufs[s], next_batch=bufs[s + 1] if s + 1 < len(bufs) else None)
+        runner.run_round(*inp(s), next_batch=inp(s + 1) if s + 1 < n_run else None)
         runner.flush()
         if args.check and s == 0 and rank == 0 and world == 1:
             check_against_oracle(runner, base, sched[0][0], args.length, emit, max_ref)
@@ -703,23 +727,25 @@ def main():
     replayed = 0
     def stage(r):                                        # host -> device copy of round r's queries, on the copy stream
         with torch.cuda.stream(copy_stream):
-            slots[r % 3].copy_(hostbufs[r], non_blocking=True)
+            slots[r % 3].copy_(hostbufs[r % pool], non_blocking=True)
             copied[r % 3].record(copy_stream)
 
     if args.from_host:
         stage(warm)
         for s in range(warm, warm + steps):
             torch.cuda.current_stream().wait_event(copied[s % 3])
-            cur = (slots[s % 3], bufs[s][1])
+            cur = (slots[s % 3], inp(s)[1])
             if s + 1 < warm + steps:
                 copy_stream.wait_stream(torch.cuda.current_stream())    # (round s-2, the slot's last reader, is long done)
                 stage(s + 1)
-            tot_matches += int(runner.run_round(*cur).sum())
+            last_counts = runner.run_round(*cur)
+            tot_matches += int(last_counts.sum())
             replayed += m.batch_stats()["replayed_blocks"]
             marks[s - warm + 1].record()
             laps_at.append(m.ref_length() == m.max_ref_length())
     for s in range(warm, warm + steps) if not args.from_host else ():
-        tot_matches += int(runner.run_round(*bufs[s], next_batch=bufs[s + 1] if s + 1 < len(bufs) else None).sum())
+        last_counts = runner.run_round(*inp(s), next_batch=inp(s + 1) if s + 1 < n_run else None)
+        tot_matches += int(last_counts.sum())
         replayed += m.batch_stats()["replayed_blocks"]
         if os.environ.get("MBGC_BENCH_SERIAL"):         # diagnostics: every kernel alone on the device (the line is marked)
             runner.flush()
@@ -733,18 +759,20 @@ def main():
     m.profile_enable(False)
     dropped = m.dropped_bytes() - dropped0
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
+    if args.dump_outputs and rank == 0:                 # before anything else runs on the handle (scaling_reference emits again)
+        dump_outputs(args.dump_outputs, m, last_counts, emit, dev)
     # the step of the scaling curve (SCALE_STEP targets whatever N is) on this one GPU: the collection's next rounds, timed the same way
     scaling_ref = None
     if sched_ref:
-        first = len(sched)
+        first = n_rounds
         d0 = m.dropped_bytes()
         for s_ in range(first, first + REF_WARM):
-            runner.run_round(*bufs[s_], next_batch=bufs[s_ + 1])
+            runner.run_round(*inp(s_), next_batch=inp(s_ + 1))
         runner.flush()
         barrier()
         t1 = time.perf_counter()
         for s_ in range(first + REF_WARM, first + REF_WARM + REF_STEPS):
-            runner.run_round(*bufs[s_], next_batch=bufs[s_ + 1] if s_ + 1 < len(bufs) else None)
+            runner.run_round(*inp(s_), next_batch=inp(s_ + 1) if s_ + 1 < n_run else None)
         runner.flush()
         barrier()
         dt1 = time.perf_counter() - t1
@@ -752,7 +780,7 @@ def main():
                        "value": round(ref_R * args.length * REF_STEPS / dt1 / 1e9, 4), "unit": "Gbases/s",
                        "extension_bytes_dropped": m.dropped_bytes() - d0,
                        "what": "the step bench.py --gpus N times at every N > 1 (%d targets: the largest multiple of 8 the window allows), on one GPU; "
-                               "targets %d..%d of the same collection" % (ref_R, n_targets + 1, n_targets + n_ref)}
+                               "targets %d..%d of the same collection" % (ref_R, n_pool + 1, n_pool + n_ref)}
     if os.environ.get("MBGC_BENCH_BLOCK_STATS"):          # diagnostics of the last round's resolve blocks, to stderr
         import ctypes as C
         from mbgc_amd import binding as _b
@@ -804,7 +832,7 @@ def main():
             "config": {"workload": ("configs[%d]: %d synthetic 5 Mbp genomes @99%% identity%s, %.4g-byte circular reference "
                                     "(the buffer `mbgc c` gives %d files); step = matchTexts%s + loadRef of one round of %d "
                                     "targets%s (the sliding window holds %d); timed: targets %d..%d of the collection, through the buffer's wrap") %
-                                   (3 if world > 1 else 2, n_targets, " sharded file-per-GPU over %d GPUs" % world if world > 1 else "", float(max_ref),
+                                   (3 if world > 1 else 2, n_pool, " sharded file-per-GPU over %d GPUs" % world if world > 1 else "", float(max_ref),
                                     1 + coll, " + processMatches (six streams, %s)" %
                                     ("gathered to rank 0 over RCCL" if world > 1 else "left packed in HBM for the host backend") if emit else "",
                                     R * world, " (%d per GPU)" % R if world > 1 else "", cap, first_coll, n_targets),
@@ -836,6 +864,9 @@ def main():
             **({"scaling_reference": scaling_ref} if scaling_ref else {}),
             **({"INVALID": "MBGC_BENCH_SERIAL: the device was drained after every step (diagnostics)"} if os.environ.get("MBGC_BENCH_SERIAL") else {}),
         }
+        if n_pool < n_targets:
+            out["config"]["workload"] += ("; target t > %d is genome 1 + (t - 1) %% %d again, long after its first copy has left the buffer"
+                                          % (n_pool, n_pool))
         if os.environ.get("MBGC_BENCH_BLOCK_TIMES"):                  # diagnostics: how even the last launch's resolve blocks were
             import ctypes
             L = binding.lib()
@@ -869,14 +900,14 @@ def main():
             del bufs
             torch.cuda.empty_cache()
             try:
-                out["cpp_host"] = cpp_host_line(fasta_dir, n_targets, warm, value)
+                out["cpp_host"] = cpp_host_line(fasta_dir, n_pool, warm, value)
                 out["configs"] = [config1_line(), config4_line(mixed_dir), config4_line(mixed_dir, rounds=True)]
             finally:
                 import shutil
                 for d_ in (fasta_dir, mixed_dir):
                     if d_:
                         shutil.rmtree(d_, ignore_errors=True)
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.length, emit, max_ref)
         if dropped and not os.environ.get("MBGC_BENCH_ALLOW_DROPS"):
             # a round larger than the window discards part of its reference extensions: less replicated work, a worse ratio —
@@ -886,6 +917,62 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1 or forced:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 97
+DUMP_STREAM_CAP = 1 << 21            # bytes of one stream written whole; of a longer stream, this many at fixed seeded positions
+
+
+def dump_outputs(d, m, counts, emit, dev):
+    """--dump-outputs DIR: what the last timed step gave its caller, as .npy files, so that two builds can be compared output
+    for output (with the same arguments the inputs are the same from run to run). Rank 0's handle: with several GPUs, rank 0's
+    share of the round. Taken after the timed region from the emission the step left in HBM; nothing is recomputed.
+      match_counts         float64 [contigs]        exact matches per contig (what run_round returns)
+      emit_counters        float64 [contigs, 6]     processMatches' counters: unmatchedChars, extensionsMatchedChars,
+                                                    extensionsMismatches, totalMatched, removedGapBreakingMatches, matches
+      stream_sizes         float64 [contigs, 6]     bytes of each stream (binding.STREAM_NAMES order)
+      stream_fingerprints  float64 [contigs, 6, 2]  sum of the bytes, and of byte x (position mod 65521 + 1): every byte counts
+      <stream>             float32                  the stream's bytes over the round's contigs in order; beyond DUMP_STREAM_CAP
+                                                    bytes, the bytes at DUMP_STREAM_CAP positions drawn without replacement by
+                                                    np.random.default_rng(DUMP_SEED), in increasing order; a stream the
+                                                    step left empty (mapOff5th without 40-bit offsets) has no file
+    At most six streams of 8 MB and a few KB besides."""
+    import ctypes as C
+    import torch
+    from mbgc_amd import binding
+    os.makedirs(d, exist_ok=True)
+    counts = np.asarray(counts if counts is not None else [], dtype=np.float64)
+    np.save(os.path.join(d, "match_counts.npy"), counts)
+    written = ["match_counts"]
+    if emit and counts.size:
+        n = counts.size                                    # contigs of the last round: the emission holds at most these
+        sizes, total = m.emit_pack_sizes(n)
+        ctr = np.zeros(n * 6, dtype=np.uint64)
+        binding._chk(binding.lib().swsem_emit_counters(m.h, ctr.ctypes.data_as(C.POINTER(C.c_uint64))))
+        buf = torch.empty(max(int(total), 1), dtype=torch.uint8, device=dev)
+        m.emit_pack_dev(buf.data_ptr(), buf.numel())       # (waited for: the bytes are there when it returns)
+        host = buf[: int(total)].cpu().numpy()
+        starts = np.zeros(n * 6 + 1, dtype=np.int64)
+        starts[1:] = np.cumsum(sizes.reshape(-1).astype(np.int64))
+        fp = np.zeros((n, 6, 2), dtype=np.float64)
+        for k in range(n):
+            for st in range(6):
+                seg = host[starts[k * 6 + st]: starts[k * 6 + st + 1]].astype(np.int64)
+                fp[k, st] = (seg.sum(), (seg * (np.arange(seg.size, dtype=np.int64) % 65521 + 1)).sum())
+        np.save(os.path.join(d, "emit_counters.npy"), ctr.reshape(n, 6).astype(np.float64))
+        np.save(os.path.join(d, "stream_sizes.npy"), sizes.astype(np.float64))
+        np.save(os.path.join(d, "stream_fingerprints.npy"), fp)
+        written += ["emit_counters", "stream_sizes", "stream_fingerprints"]
+        for st, name in enumerate(binding.STREAM_NAMES):
+            a = np.concatenate([host[starts[k * 6 + st]: starts[k * 6 + st + 1]] for k in range(n)])
+            if a.size == 0:
+                continue
+            if a.size > DUMP_STREAM_CAP:
+                a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_STREAM_CAP, replace=False))]
+            np.save(os.path.join(d, name + ".npy"), a.astype(np.float32))
+            written.append(name)
+    mb = sum(os.path.getsize(os.path.join(d, w + ".npy")) for w in written) / 1e6
+    print("bench.py: the last step's outputs written to %s (%s; %.1f MB)" % (d, ", ".join(written), mb), file=sys.stderr)
 
 
 def check_against_oracle(runner, base, targets, length, emit, max_ref):

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r01f
 rm -rf $O; mkdir -p $O
 cd $R
 timeout -k 10 300 python3 bench.py --check > $O/bench_check.json 2>$O/bench_check.err
-timeout -k 10 300 python3 bench.py > $O/bench_full.json 2>$O/bench_full.err
+timeout -k 10 300 python3 bench.py --full > $O/bench_full.json 2>$O/bench_full.err
 timeout -k 10 200 python3 bench.py --no-emit --cpu-sample 0 > $O/bench_matcher.json 2>$O/bench_matcher.err
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --cpu-sample 0 > $O/bench_rocprof.json 2>$O/kt.err

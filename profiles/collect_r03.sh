@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03final
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 600 python3 bench.py > $O/bench_full.json 2>$O/bench_full.err || exit 1
+timeout -k 10 600 python3 bench.py --full > $O/bench_full.json 2>$O/bench_full.err || exit 1
 timeout -k 10 300 python3 bench.py --check --steps 2 --warmup 1 --cpu-sample 0 > $O/bench_check.json 2>$O/bench_check.err || exit 1
 timeout -k 10 300 python3 bench.py --no-emit --cpu-sample 0 > $O/bench_matcher.json 2>$O/bench_matcher.err || exit 1
 MBGC_BENCH_ALLOW_DROPS=1 timeout -k 10 300 python3 bench.py --round 40 --cpu-sample 0 > $O/bench_round40.json 2>$O/bench_round40.err || exit 1

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r04final
 mkdir -p $O
 cd $R
 if [ "$1" = a ]; then
-timeout -k 10 600 python3 bench.py > $O/bench_full.json 2>$O/bench_full.err || exit 1
+timeout -k 10 600 python3 bench.py --full > $O/bench_full.json 2>$O/bench_full.err || exit 1
 timeout -k 10 300 python3 bench.py --check --steps 2 --warmup 1 --cpu-sample 0 --no-extras > $O/bench_check.json 2>$O/bench_check.err || exit 1
 timeout -k 10 300 python3 bench.py --no-emit --cpu-sample 0 --no-extras > $O/bench_matcher.json 2>$O/bench_matcher.err || exit 1
 MBGC_BENCH_ALLOW_DROPS=1 timeout -k 10 300 python3 bench.py --round 40 --cpu-sample 0 --no-extras > $O/bench_round40.json 2>$O/bench_round40.err || exit 1

@@ -123,3 +123,65 @@ def test_the_lines_beside_the_headline_are_put_together(tmp_path, monkeypatch):
     line = bench.config1_line()
     assert "error" not in line, line
     assert line["value"] == 56.4 and "99% identity" in line["workload"] and "1.28e+09-byte" in line["workload"]
+
+
+# ---- --dump-outputs: what the last timed step gave its caller, written from a stand-in for the handle's last emission
+def test_dump_outputs_writes_the_last_steps_streams(tmp_path, monkeypatch):
+    import ctypes
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from mbgc_amd import binding
+    rng = np.random.default_rng(5)
+    n = 3
+    sizes = rng.integers(0, 400, (n, 6)).astype(np.uint64)
+    sizes[1, 0] = 3000                                   # one stream longer than the cap below: sampled
+    sizes[:, 2] = 0                                      # one stream empty in every contig (mapOff5th without 40-bit offsets): no file
+    packed = rng.integers(0, 256, int(sizes.sum())).astype(np.uint8)
+    counters = np.arange(n * 6, dtype=np.uint64)
+
+    class FakeMatcher:
+        h = None
+
+        def emit_pack_sizes(self, k):
+            assert k == n
+            return sizes.copy(), int(sizes.sum())
+
+        def emit_pack_dev(self, ptr, cap):
+            assert cap >= packed.size
+            ctypes.memmove(ptr, packed.ctypes.data, packed.size)
+            return packed.size
+
+    class FakeLib:
+        @staticmethod
+        def swsem_emit_counters(h, out):
+            ctypes.memmove(out, counters.ctypes.data, counters.nbytes)
+            return 0
+    monkeypatch.setattr(binding, "lib", lambda: FakeLib)
+    monkeypatch.setattr(bench, "DUMP_STREAM_CAP", 1000)
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), FakeMatcher(), np.array([7, 8, 9], dtype=np.uint64), True, "cpu")
+    got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert set(got) == {"match_counts", "emit_counters", "stream_sizes", "stream_fingerprints"} | (set(binding.STREAM_NAMES) - {binding.STREAM_NAMES[2]})
+    assert all(a.dtype in (np.float32, np.float64) and a.size for a in got.values())
+    assert got["match_counts"].tolist() == [7, 8, 9] and got["emit_counters"].tolist() == counters.reshape(n, 6).tolist()
+    assert np.array_equal(got["stream_sizes"], sizes.astype(np.float64))
+    starts = np.concatenate([[0], np.cumsum(sizes.reshape(-1).astype(np.int64))])
+    for st, name in enumerate(binding.STREAM_NAMES):
+        whole = np.concatenate([packed[starts[k * 6 + st]: starts[k * 6 + st + 1]] for k in range(n)])
+        if not whole.size:
+            assert name not in got
+        elif whole.size <= 1000:
+            assert np.array_equal(got[name], whole.astype(np.float32)), name
+        else:                                            # a fixed sample, the same in every run
+            idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(whole.size, 1000, replace=False))
+            assert np.array_equal(got[name], whole[idx].astype(np.float32)), name
+        for k in range(n):
+            seg = packed[starts[k * 6 + st]: starts[k * 6 + st + 1]].astype(np.int64)
+            assert got["stream_fingerprints"][k, st, 0] == seg.sum()
+            assert got["stream_fingerprints"][k, st, 1] == (seg * (np.arange(seg.size) + 1)).sum()
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

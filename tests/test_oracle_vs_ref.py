@@ -300,14 +300,22 @@ def test_five_laps_of_the_buffer(refh, round_size, laps):
     assert o.loaded_ref_length() > laps * lim
 
 
-LISTERIA = "/root/reference/example-scripts"
+LISTERIA_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "listeria")
 
 
-@pytest.mark.skipif(not os.path.isdir(LISTERIA), reason="reference example data not on this host")
 def test_listeria_streams_equal_reference_cli_dumps(refh, tmp_path):
     """`mbgc c -t1` on the three bundled Listeria genomes: archive md5 of SURVEY.md §8c, and every raw
-    stream dumped by the developer build (`v -D`) equals driver + oracle."""
+    stream dumped by the developer build (`v -D`) equals driver + oracle. The genomes are the reference's example
+    files, stored compressed under tests/golden/listeria and unpacked here byte for byte."""
+    import lzma
+    LISTERIA = str(tmp_path / "listeria")
+    os.mkdir(LISTERIA)
+    for f in sorted(os.listdir(LISTERIA_GOLDEN)):
+        if f.endswith(".fna.xz"):
+            with lzma.open(os.path.join(LISTERIA_GOLDEN, f)) as src, open(os.path.join(LISTERIA, f[:-3]), "wb") as dst:
+                dst.write(src.read())
     names = sorted(f for f in os.listdir(LISTERIA) if f.endswith(".fna"))
+    assert len(names) == 3, names
     listing = tmp_path / "seqlist.txt"
     listing.write_text("".join(os.path.join(LISTERIA, n) + "\n" for n in names))
     arch = tmp_path / "lm.mbgc"
