@@ -48,7 +48,7 @@ int swsem_device_numa_node(int device);
 
 /* SlidingWindowExpSparseEMMatcher::SlidingWindowExpSparseEMMatcher, SlidingWindowSparseEMMatcher.cpp:494-519
  * (+ base ctor :325-359, initParams :74-104). maxRefLength is explicit: the 60 %-of-RAM cap of
- * utils/helper.h:324-339 is host policy. k1 must be even, k2 must be 1 (the only values MBGC uses). */
+ * utils/helper.h:324-339 is host policy. k1 is positive (an odd one is the base class's sampling, MGMP.cpp:170-176), k2 must be 1 (the only value MBGC uses). */
 int swsem_create(swsem_t **out, uint64_t maxRefLength, int L, int k1, int k2, int skipMargin, int device);
 void swsem_destroy(swsem_t *h);                                   /* ~SlidingWindowSparseEMMatcher, .cpp:460-467 */
 /* Run every launch of this handle on an existing HIP stream (hipStream_t), e.g. the caller's. */
