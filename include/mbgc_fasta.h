@@ -56,6 +56,31 @@ int mbgc_fasta_parse_host(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n,
                           uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
                           uint64_t *dnaLineLen, int *status);
 
+/* Single-FASTA input (`mbgc c -i`): the rule by which the reference cuts one multi-FASTA byte stream into the initial reference
+ * and the targets, mgmpInSplit_next(iter, minSplitSize, '>') (matching/input_with_libdeflate_wrapper.cpp:150-171), on a window of
+ * the file in HBM. bytes_dev[0..n) starts at an element start. Element j starts where element j - 1 ended (element 0 at 0) and
+ * ends at the first byte equal to '>' at an offset >= its start + (j ? nextMin : firstMin) — any '>', also one inside a header
+ * line; when its start + the minimum >= the file's size, or no such byte follows, it runs to the end of the file; an element
+ * never starts at the end of the file. ends[j] (capacity maxElems) = end of element j relative to the window.
+ * isFileEnd = 0: the window is not the file's end, and the call returns the elements whose end lies inside the window — *nElems
+ * may be 0 (a contig longer than the window); the caller extends the window and asks again. isFileEnd != 0: the last element ends
+ * at n. Synchronous, like its neighbours. */
+int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, int isFileEnd, uint64_t firstMin, uint64_t nextMin,
+                         int maxElems, uint64_t *ends, int *nElems);
+
+/* The same for a window that grows: buf_dev[0..n) is the buffer, the elements start at `start`, ends[] are offsets in the buffer.
+ * scannedBefore: the caller's promise that buf_dev[0..scannedBefore) has not changed since the last call of this handle, which
+ * covered at least that much from a `start` not behind this one — the streaming pass then reads only what was appended (and the tile that was not whole). 0: none. */
+int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
+                             uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems);
+
+/* Device memory for the windows of a single-FASTA input, before a matcher exists (the initial reference is cut from the first
+ * window): plain allocation, a device-to-device copy and a download on the input stage's stream, each synchronous. */
+int mbgc_fasta_dev_alloc(mbgc_fasta_t *p, uint64_t bytes, uint8_t **out);
+int mbgc_fasta_dev_free(mbgc_fasta_t *p, uint8_t *ptr);
+int mbgc_fasta_dev_copy(mbgc_fasta_t *p, uint8_t *dst_dev, const uint8_t *src_dev, uint64_t bytes);
+int mbgc_fasta_download(mbgc_fasta_t *p, void *dst_host, const uint8_t *src_dev, uint64_t bytes);
+
 /* The way into HBM ("fed by pinned-memory reads"): page-locked host memory for the reader threads to
  * read files into, and its copy to the device on the input stage's own stream — it returns when the bytes have arrived
  * and waits for nothing the matcher has queued. */

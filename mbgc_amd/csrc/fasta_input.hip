@@ -320,6 +320,104 @@ __global__ void __launch_bounds__(THREADS) k_fa_emit(const uint8_t *__restrict__
     }
 }
 
+// ---- single-FASTA input: mgmpInSplit_next (matching/input_with_libdeflate_wrapper.cpp:150-171) on a window in HBM.
+// An element ends at the first '>' at or behind its start + minSplitSize, whatever line that '>' stands in. (1) a streaming
+// pass leaves every 4096-byte tile's first '>' (one wave per tile, 16 bytes per lane and load, all four loads of a tile in
+// flight before the first compare; no LDS); (2) one wave walks the chain of elements: the rest of the threshold's own tile
+// byte by byte, then the tile array 64 tiles per ballot.
+constexpr uint32_t NO_GT = 0xffffffffu;
+constexpr int TILE_LOADS = CHUNK / (WAVE * PER);                     // 4 loads of 1 KiB per wave and tile
+
+// index of the first byte of w equal to '>' (0..3), 4: none
+__device__ __forceinline__ uint32_t first_gt_in_word(uint32_t w) {
+    const uint32_t x = w ^ 0x3e3e3e3eu;
+    const uint32_t z = (x - 0x01010101u) & ~x & 0x80808080u;       // the lowest set bit marks the first zero byte of x
+    return z ? (uint32_t) (__builtin_ctz(z) >> 3) : 4u;
+}
+
+__global__ void __launch_bounds__(THREADS) k_fa_first_gt(const uint8_t *__restrict__ f, uint64_t n, uint32_t tile0, uint32_t ntiles,
+                                                         uint32_t *__restrict__ tileFirst) {       // tiles [tile0, ntiles)
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint32_t tile = tile0 + blockIdx.x * (THREADS / WAVE) + threadIdx.x / WAVE;
+    if (tile >= ntiles) return;                                     // (whole waves: a wave has one tile)
+    const uint64_t ts = (uint64_t) tile * CHUNK;
+    const uint32_t len = (uint32_t) (n - ts < CHUNK ? n - ts : CHUNK);
+    const uint8_t *src = f + ts;
+    uint4 v[TILE_LOADS];
+#pragma unroll
+    for (int i = 0; i < TILE_LOADS; i++) {
+        const uint32_t o = (uint32_t) i * (WAVE * PER) + lane * PER;
+        v[i] = make_uint4(0, 0, 0, 0);
+        if (o + PER <= len) memcpy(&v[i], src + o, PER);
+        else if (o < len) {                                        // the window's last, partial 16 bytes
+            uint8_t t[PER] = {};
+            for (uint32_t k = 0; o + k < len; k++) t[k] = src[o + k];
+            memcpy(&v[i], t, PER);
+        }
+    }
+    uint32_t first = NO_GT;
+#pragma unroll
+    for (int i = 0; i < TILE_LOADS; i++) {
+        const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+        uint32_t mine = NO_GT;
+#pragma unroll
+        for (int k = 3; k >= 0; k--) {
+            const uint32_t b = first_gt_in_word(w[k]);
+            if (b < 4) mine = (uint32_t) k * 4 + b;
+        }
+        const unsigned long long m = __ballot(mine != NO_GT);
+        if (m && first == NO_GT) {
+            const int l = __builtin_ctzll(m);
+            first = (uint32_t) i * (WAVE * PER) + (uint32_t) l * PER + (uint32_t) __shfl((int) mine, l);
+        }
+    }
+    if (lane == 0) tileFirst[tile] = first;
+}
+
+__global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restrict__ f, uint64_t n, const uint32_t *__restrict__ tileFirst,
+                                                         uint32_t ntiles, uint64_t start, int isFileEnd, uint64_t firstMin, uint64_t nextMin,
+                                                         int maxElems, uint64_t *__restrict__ res) {   // res[0] = elements found, res[1 + j] = end of element j
+    const uint32_t lane = threadIdx.x;
+    const uint64_t NONE = ~0ull;
+    uint64_t s = start;
+    int j = 0;
+    for (; j < maxElems && s != n; j++) {                           // (every branch below is taken by the whole wave)
+        const uint64_t mn = j ? nextMin : firstMin;
+        uint64_t e = NONE;
+        if (mn < n - s) {
+            const uint64_t thr = s + mn;
+            const uint32_t t = (uint32_t) (thr / CHUNK);
+            const uint64_t tbase = (uint64_t) t * CHUNK;
+            const uint32_t tf = tileFirst[t];
+            if (tf != NO_GT && tbase + tf >= thr) e = tbase + tf;
+            else if (tf != NO_GT) {                                // the tile's first '>' stands before the threshold: the rest of the tile
+                const uint64_t tend = tbase + CHUNK < n ? tbase + CHUNK : n;
+                for (uint64_t b = thr; b < tend && e == NONE; b += WAVE) {
+                    const uint64_t p = b + lane;
+                    const unsigned long long m = __ballot(p < tend && f[p] == '>');
+                    if (m) e = b + (uint64_t) __builtin_ctzll(m);
+                }
+            }
+            for (uint32_t tb = t + 1; tb < ntiles && e == NONE; tb += WAVE) {
+                const uint32_t ti = tb + lane;
+                const uint32_t v = ti < ntiles ? tileFirst[ti] : NO_GT;
+                const unsigned long long m = __ballot(v != NO_GT);
+                if (m) {
+                    const int l = __builtin_ctzll(m);
+                    e = (uint64_t) (tb + (uint32_t) l) * CHUNK + (uint32_t) __shfl((int) v, l);
+                }
+            }
+        }
+        if (e == NONE) {                                            // the threshold or the search ran off the window
+            if (!isFileEnd) break;
+            e = n;
+        }
+        if (lane == 0) res[1 + j] = e;
+        s = e;
+    }
+    if (lane == 0) res[0] = (uint64_t) j;
+}
+
 std::string g_err;
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -360,6 +458,8 @@ struct mbgc_fasta {
     fa::Buf<uint64_t> dBases;
     fa::Buf<mbgc_fasta_record_t> dRecs;
     fa::Buf<uint8_t> dHostIn, dHostOut;         // mbgc_fasta_parse_host: the file and its sequences on the device
+    fa::Buf<uint32_t> dTileFirst;               // mbgc_fasta_split_dev: first '>' of every tile, and its result
+    fa::Buf<uint64_t> dSplit;
 };
 
 extern "C" {
@@ -384,6 +484,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     (void) hipSetDevice(p->device);
     if (p->stream) { (void) hipStreamSynchronize(p->stream); (void) hipStreamDestroy(p->stream); }
     p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dHostIn.release(); p->dHostOut.release();
+    p->dTileFirst.release(); p->dSplit.release();
     delete p;
 }
 
@@ -466,6 +567,79 @@ int mbgc_fasta_parse_host(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n,
     if (r) { *nrec = rb[1]; return r; }
     *nrec = rb[1]; *seqBytes = sb[1];
     if (sb[1]) FCHK(hipMemcpy(seq_out_host, p->dHostOut.p, sb[1], hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
+                             uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems) {
+    using namespace fa;
+    *nElems = 0;
+    if (maxElems <= 0 || firstMin == 0 || nextMin == 0) return fail(-103, "split: maxElems and the minimal element sizes must be positive");
+    if (start > n || scannedBefore > n) return fail(-103, "split: the window starts or was scanned behind its end");
+    if (n == start) return 0;
+    if (n > ((uint64_t) 1 << 40)) return fail(-103, "split: a window of %llu bytes", (unsigned long long) n);
+    FCHK(hipSetDevice(p->device));
+    const uint32_t ntiles = (uint32_t) ((n + CHUNK - 1) / CHUNK);
+    if (ntiles > p->dTileFirst.cap) scannedBefore = 0;              // (the tile array is made anew: nothing of it is kept)
+    int r;
+    if ((r = p->dTileFirst.reserve(ntiles)) || (r = p->dSplit.reserve((size_t) maxElems + 1))) return r;
+    // the tiles that were whole at the last call stand; the pass starts at the first one that was not, or that lies before the
+    // window's start (nothing reads those)
+    const uint32_t tile0 = (uint32_t) (std::max(scannedBefore, start / CHUNK * CHUNK) / CHUNK);
+    if (tile0 < ntiles)
+        k_fa_first_gt<<<dim3((ntiles - tile0 + THREADS / WAVE - 1) / (THREADS / WAVE)), dim3(THREADS), 0, p->stream>>>(buf_dev, n, tile0, ntiles, p->dTileFirst.p);
+    k_fa_split_chain<<<dim3(1), dim3(WAVE), 0, p->stream>>>(buf_dev, n, p->dTileFirst.p, ntiles, start, isFileEnd, firstMin, nextMin, maxElems, p->dSplit.p);
+    FCHK(hipGetLastError());
+    // the count and the ends in one copy (a round's elements are a handful; a longer list takes a second one)
+    const size_t FIRST = 256;
+    uint64_t res[FIRST + 1];
+    const size_t first = std::min<size_t>((size_t) maxElems, FIRST);
+    FCHK(hipMemcpyAsync(res, p->dSplit.p, (first + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    const uint64_t ne = res[0];
+    if (ne > (uint64_t) maxElems) return fail(-100, "split: %llu elements for a capacity of %d", (unsigned long long) ne, maxElems);
+    memcpy(ends, res + 1, std::min<size_t>(ne, first) * sizeof(uint64_t));
+    if (ne > first) {
+        FCHK(hipMemcpyAsync(ends + first, p->dSplit.p + 1 + first, (ne - first) * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+    }
+    *nElems = (int) ne;
+    return 0;
+}
+
+int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, int isFileEnd, uint64_t firstMin, uint64_t nextMin,
+                         int maxElems, uint64_t *ends, int *nElems) {
+    return mbgc_fasta_split_buf_dev(p, bytes_dev, 0, n, 0, isFileEnd, firstMin, nextMin, maxElems, ends, nElems);
+}
+
+int mbgc_fasta_dev_alloc(mbgc_fasta_t *p, uint64_t bytes, uint8_t **out) {
+    using namespace fa;
+    *out = nullptr;
+    FCHK(hipSetDevice(p->device));
+    if (hipMalloc((void **) out, bytes ? bytes : 1) != hipSuccess) { (void) hipGetLastError(); return fail(-101, "device allocation of %llu bytes failed", (unsigned long long) bytes); }
+    return 0;
+}
+
+int mbgc_fasta_dev_free(mbgc_fasta_t *p, uint8_t *ptr) {
+    using namespace fa;
+    FCHK(hipSetDevice(p->device));
+    if (ptr) FCHK(hipFree(ptr));
+    return 0;
+}
+
+int mbgc_fasta_dev_copy(mbgc_fasta_t *p, uint8_t *dst_dev, const uint8_t *src_dev, uint64_t bytes) {
+    using namespace fa;
+    FCHK(hipSetDevice(p->device));
+    if (bytes) FCHK(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int mbgc_fasta_download(mbgc_fasta_t *p, void *dst_host, const uint8_t *src_dev, uint64_t bytes) {
+    using namespace fa;
+    FCHK(hipSetDevice(p->device));
+    if (bytes) FCHK(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
     return 0;
 }
 

@@ -5,7 +5,8 @@ import numpy as np
 
 from . import binding
 
-EXPORTS = "mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload".split()
+EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
+           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download""".split()
 
 
 class Record(C.Structure):
@@ -21,6 +22,10 @@ def _lib():
         L.mbgc_fasta_parse_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64), C.POINTER(Record), C.c_uint64, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mbgc_fasta_split_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mbgc_fasta_split_buf_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L._fasta_ready = True
     return L
 
@@ -66,3 +71,24 @@ class FastaParser:
         n = int(rec_base[-1])
         arr = np.frombuffer(recs, dtype=[("headerOff", "<u8"), ("headerLen", "<u8"), ("seqOff", "<u8"), ("seqLen", "<u8")], count=n).copy()
         return dict(seq_base=seq_base, rec_base=rec_base, records=arr, dna_line_len=line, status=status)
+
+    def split_dev(self, bytes_ptr, n, is_file_end, first_min, next_min, max_elems):
+        """mgmpInSplit_next over the window bytes_ptr[0..n) in HBM (it starts at an element start): the end offsets of the
+        elements whose end the window decides, at most max_elems. Fewer than asked for (none, even) when the window is not the
+        file's end and the search ran off it: extend the window and call again."""
+        ends = np.zeros(max(int(max_elems), 1), dtype=np.uint64)
+        ne = C.c_int(0)
+        if _lib().mbgc_fasta_split_dev(self.h, bytes_ptr, int(n), int(bool(is_file_end)), int(first_min), int(next_min), int(max_elems),
+                                       ends.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ne)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return [int(e) for e in ends[:ne.value]]
+
+    def split_buf_dev(self, buf_ptr, start, n, scanned_before, is_file_end, first_min, next_min, max_elems):
+        """split_dev for a buffer that grows: elements from `start`, ends as offsets in the buffer; buf[0..scanned_before) is
+        unchanged since this parser's last call and is not read again by the streaming pass"""
+        ends = np.zeros(max(int(max_elems), 1), dtype=np.uint64)
+        ne = C.c_int(0)
+        if _lib().mbgc_fasta_split_buf_dev(self.h, buf_ptr, int(start), int(n), int(scanned_before), int(bool(is_file_end)), int(first_min),
+                                           int(next_min), int(max_elems), ends.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ne)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return [int(e) for e in ends[:ne.value]]

@@ -82,6 +82,8 @@ int main(int argc, char **argv) {
             params.k1 = atoi(argv[++i]);
             if (params.k1 <= 0) { fprintf(stderr, "s - reference sampling step - should be a positive integer.\n\n"); return EXIT_FAILURE; }
         }
+        else if (a == "-i" && i + 1 < argc) params.inputFileName = argv[++i];      // single fasta file mode (MBGC_Params.h:793-803)
+        else if (a == "--window-kib" && i + 1 < argc) params.singleFileWindow = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "-L") params.lazyDecompressionSupport = false;             // disable lazy decompression support
         else if (a == "-U") params.uppercaseDNA = true;                          // MBGC_Params.h: converts bases to uppercase
@@ -100,15 +102,26 @@ int main(int argc, char **argv) {
         else if (a == "--coder-threads" && i + 1 < argc) coderThreads = atoi(argv[++i]);
         else pos.push_back(a);
     }
-    if (pos.size() != 2) {
+    const bool single = !params.inputFileName.empty();
+    if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
+    if (pos.size() != 2 || (single && !pos[0].empty())) {
         fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
+                        "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
+                        "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
+                        "  2 MiB at '>' bytes, on the device, while it travels to the GPU in windows of K KiB (default 32768; host memory is bounded by two\n"
+                        "  windows, except for a gzip file, which is inflated on the host and held whole in memory); also prints `single-file elements: <n>`\n"
+                        "  and writes <outputPrefix>.seqCounts (one little-endian u32 per target: its records)\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
         fprintf(stderr, "--gpus needs a positive count, --exchange rccl or hostmem, and the round mode (not -t1 / -m 3: those match sequentially)\n");
+        return EXIT_FAILURE;
+    }
+    if (single && (gpus > 1 || transport == "hostmem")) {
+        fprintf(stderr, "-i (single fasta file mode) runs on one GPU: the rounds sharded over --gpus N take a file list\n");
         return EXIT_FAILURE;
     }
     if (gpus > 1 && params.verifyEmissions) {
@@ -118,7 +131,7 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     std::vector<std::string> files;
-    {
+    if (!single) {
         std::ifstream lst(pos[0]);
         if (!lst) { fprintf(stderr, "cannot open sequences list file %s\n", pos[0].c_str()); return EXIT_FAILURE; }
         std::string line;
@@ -219,6 +232,11 @@ int main(int argc, char **argv) {
     dump(pos[1], "mapOff5th", enc.mapOff5thByte);
     dump(pos[1], "mapLen", enc.mapLen);
     dump(pos[1], "refExtSize", enc.refExtSizeStream);
+    if (enc.singleFastaFile()) {
+        const std::vector<uint32_t> &counts = enc.sequenceCounts();
+        dump(pos[1], "seqCounts", std::string((const char *) counts.data(), counts.size() * sizeof(uint32_t)));
+        printf("single-file elements: %u\n", enc.singleFastaElements());
+    }
     if (!backend.empty()) {
         // the streams through the backend's job table and container framing (include/mbgc_backend.h), entropy-coded by the
         // library given
@@ -244,7 +262,7 @@ int main(int argc, char **argv) {
     if (params.verifyEmissions) {
         printf("verified on the device: %llu contigs, %llu bases decoded back to their bytes\n",
                (unsigned long long) params.verifiedContigs, (unsigned long long) params.verifiedBases);
-        if (params.verifiedContigs == 0 && files.size() > 1) {
+        if (params.verifiedContigs == 0 && (files.size() > 1 || single)) {    // (-i: the file is a target itself, or holds some)
             fprintf(stderr, "--verify was asked for and no emission was verified\n");
             return finish(EXIT_FAILURE);
         }

@@ -136,6 +136,10 @@ MultipleGenomeMatchingProcessor::~MultipleGenomeMatchingProcessor() {
     if (matcher && extScratch) matcher->devFree(extScratch);
     if (ahead.active) ahead.done.wait();
     if (readAhead.active) readAhead.done.wait();
+    if (sf.readActive) sf.reading.wait();
+    if (sf.fd >= 0) close(sf.fd);
+    if (fasta && sf.dev) mbgc_fasta_dev_free(fasta, sf.dev);
+    if (fasta && sf.spare) mbgc_fasta_dev_free(fasta, sf.spare);
     for (StagedFiles &S : staged) if (fasta && S.pin) mbgc_fasta_host_free(fasta, S.pin);
     if (fasta) mbgc_fasta_destroy(fasta);
     delete matcher;
@@ -154,6 +158,11 @@ void MultipleGenomeMatchingProcessor::readG0(const std::string &path, std::vecto
     std::string data;
     if (!readWholeFile(path, data)) { fprintf(stderr, "cannot open file %s\n", path.c_str()); exit(EXIT_FAILURE); }
     if (fileSize) *fileSize = data.size();
+    parseHostBytes(data, path, out);
+}
+
+void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, const std::string &path, std::vector<Contig> &out) {
+    openInputStage();
     std::string seq(data.size(), '\0');
     uint64_t seqBytes = 0, nrec = 0, lineLen = 0;
     int status = 0;
@@ -302,7 +311,7 @@ void MultipleGenomeMatchingProcessor::loadRound(uint32_t f0, uint32_t f1, RoundB
     }
     g_tWait += nowSeconds() - t0;
     if (!have) { const double tp0 = nowSeconds(); prepareRound(f0, f1, B, nextF0, nextF1); g_tPrepareSync += nowSeconds() - tp0; }
-    if (nextB && nextF1 > nextF0) {
+    if (nextB && nextF1 > nextF0 && !(singleFastaFileMode && B.endOfInput)) {
         // the round after the next one: the callers' rounds are ranges of equal length at equal distance (a wrong guess
         // costs a read that nobody takes)
         const uint64_t stride = nextF0 - f0, count = nextF1 - nextF0;
@@ -316,6 +325,7 @@ void MultipleGenomeMatchingProcessor::loadRound(uint32_t f0, uint32_t f1, RoundB
 // files [f0, f1) of the list -> their contigs back to back in B.seqDev; contig c belongs to target targetBase + (file - f0)
 void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t afterF0, uint32_t afterF1) {
     openInputStage();
+    if (singleFastaFileMode) { prepareRoundSingleFasta(f0, f1, B); return; }
     const int nf = (int) (f1 - f0);
     if (nf <= 0) {                                           // (a rank without targets in a short last round)
         B.offsets.assign(1, 0); B.targetOf.clear(); B.bytes = 0;
@@ -378,6 +388,278 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
     g_tParse += nowSeconds() - tParse0;
 }
 
+// ---------------------------------------------------------------- single fasta file mode (`-i`)
+static void inputStageCheck(int rc) {
+    if (rc != 0) { fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error()); exit(EXIT_FAILURE); }
+}
+
+void MultipleGenomeMatchingProcessor::sfOpen(const std::string &path) {
+    openInputStage();
+    sf.fd = open(path.c_str(), O_RDONLY);
+    struct stat st;
+    if (sf.fd < 0 || fstat(sf.fd, &st) != 0) { fprintf(stderr, "cannot open file %s\n", path.c_str()); exit(EXIT_FAILURE); }
+    sf.fileSize = (uint64_t) st.st_size;
+    uint8_t head[18];
+    if (sf.fileSize >= 18 && pread(sf.fd, head, 18, 0) == 18 && isGzip(head, 18)) {      // mgmpInOpen: inflated whole, on the host
+        if (!readWholeFile(path, sf.inflated)) { fprintf(stderr, "Problem reading from file: %s\n", path.c_str()); exit(EXIT_FAILURE); }
+        sf.gz = true;
+        sf.fileSize = sf.inflated.size();
+    }
+    const uint64_t W = std::max<uint64_t>(params->singleFileWindow, 4096);
+    params->singleFileWindow = W;
+    for (StagedFiles &S : staged) {
+        void *p = nullptr;
+        inputStageCheck(mbgc_fasta_host_alloc(fasta, W + 64, &p));
+        S.pin = (uint8_t *) p; S.cap = W + 64;
+    }
+}
+
+void MultipleGenomeMatchingProcessor::sfStartRead() {
+    if (sf.readActive || sf.readPos >= sf.fileSize) return;
+    const uint64_t at = sf.readPos, len = std::min<uint64_t>(params->singleFileWindow, sf.fileSize - at);
+    uint8_t *dst = staged[sf.readSlot].pin;
+    sf.readPos = at + len;
+    sf.readActive = true;
+    sf.reading = std::async(std::launch::async, [this, dst, at, len]() -> uint64_t {
+        const double t0 = nowSeconds();
+        if (sf.gz) memcpy(dst, sf.inflated.data() + at, len);
+        else {
+            uint64_t got = 0;
+            while (got < len) { const ssize_t k = pread(sf.fd, dst + got, len - got, (off_t) (at + got)); if (k <= 0) break; got += (uint64_t) k; }
+            if (got != len) sf.error = "Problem reading from file: " + params->inputFileName;
+        }
+        g_tRead += nowSeconds() - t0;                             // (one reader at a time)
+        return len;
+    });
+}
+
+bool MultipleGenomeMatchingProcessor::sfExtend() {
+    if (sfAtEnd()) return false;
+    sfStartRead();
+    const double t0 = nowSeconds();
+    const uint64_t len = sf.reading.get();
+    sf.readActive = false;
+    g_tReadWait += nowSeconds() - t0;
+    if (!sf.error.empty()) { fprintf(stderr, "%s\n", sf.error.c_str()); exit(EXIT_FAILURE); }
+    const uint8_t *src = staged[sf.readSlot].pin;
+    sf.readSlot ^= 1;
+    sfStartRead();                                                // the window after this one, into the other staging buffer, meanwhile
+    const double t1 = nowSeconds();
+    if (sf.have + len + 64 > sf.devCap) {                         // grow-only (a batch of long elements)
+        const size_t cap = (sf.have + len) + (sf.have + len) / 4 + 64;
+        uint8_t *d = nullptr;
+        inputStageCheck(mbgc_fasta_dev_alloc(fasta, cap, &d));
+        if (sf.have) inputStageCheck(mbgc_fasta_dev_copy(fasta, d, sf.dev, sf.have));
+        if (sf.dev) inputStageCheck(mbgc_fasta_dev_free(fasta, sf.dev));
+        sf.dev = d; sf.devCap = cap;
+    }
+    inputStageCheck(mbgc_fasta_upload(fasta, sf.dev + sf.have, src, len));
+    sf.have += len;
+    g_tParse += nowSeconds() - t1;
+    return true;
+}
+
+void MultipleGenomeMatchingProcessor::sfConsume(uint64_t bytes) {
+    const uint64_t left = sf.have - bytes;
+    if (left) {
+        if (left + 64 > sf.spareCap) {
+            if (sf.spare) inputStageCheck(mbgc_fasta_dev_free(fasta, sf.spare));
+            sf.spareCap = std::max<size_t>(left + left / 4, sf.devCap) + 64;
+            inputStageCheck(mbgc_fasta_dev_alloc(fasta, sf.spareCap, &sf.spare));
+        }
+        inputStageCheck(mbgc_fasta_dev_copy(fasta, sf.spare, sf.dev + bytes, left));
+        std::swap(sf.dev, sf.spare); std::swap(sf.devCap, sf.spareCap);
+    }
+    sf.devBase += bytes; sf.have = left;
+    if (bytes) sf.scanned = 0;                                    // (what is left has moved)
+}
+
+void MultipleGenomeMatchingProcessor::sfRewind() {
+    if (sf.readActive) { sf.reading.get(); sf.readActive = false; }
+    sf.readPos = 0; sf.devBase = 0; sf.have = 0; sf.nextElem = 0; sf.scanned = 0;
+}
+
+// mgmpInSplit_next for the next `want` elements (fewer when the file ends): the window grows until the device has found
+// their ends
+void MultipleGenomeMatchingProcessor::sfElements(uint32_t want, uint64_t firstMin, uint64_t nextMin, std::vector<uint64_t> &ends) {
+    ends.clear();
+    uint64_t done = 0;
+    std::vector<uint64_t> e(want);
+    while (true) {
+        const bool end = sfAtEnd();
+        if (sf.have > done) {
+            int n = 0;
+            const double t0 = nowSeconds();
+            // (only what the last window added is scanned again: the tiles of the bytes before it stand)
+            inputStageCheck(mbgc_fasta_split_buf_dev(fasta, sf.dev, done, sf.have, sf.scanned, end, ends.empty() ? firstMin : nextMin, nextMin,
+                                                     (int) (want - ends.size()), e.data(), &n));
+            sf.scanned = sf.have;
+            g_tParse += nowSeconds() - t0;
+            for (int k = 0; k < n; k++) ends.push_back(e[k]);
+            if (n) done = ends.back();
+        }
+        if (ends.size() == want || end) return;
+        sfExtend();
+    }
+}
+
+// the file's first record (the sequential schedule's initial reference, MGMP.cpp:91-100): up to the first line that starts
+// with '>' behind the first byte — read on the host, it is needed there
+std::string MultipleGenomeMatchingProcessor::sfFirstRecord() {
+    std::string data;
+    const uint64_t step = 1 << 20;
+    for (uint64_t at = 0; at < sf.fileSize;) {
+        const uint64_t len = std::min(step, sf.fileSize - at);
+        const size_t from = data.empty() ? 0 : data.size() - 1;
+        data.resize(at + len);
+        if (sf.gz) memcpy(&data[at], sf.inflated.data() + at, len);
+        else {
+            uint64_t got = 0;
+            while (got < len) { const ssize_t k = pread(sf.fd, &data[at + got], len - got, (off_t) (at + got)); if (k <= 0) break; got += (uint64_t) k; }
+            if (got != len) { fprintf(stderr, "Problem reading from file: %s\n", params->inputFileName.c_str()); exit(EXIT_FAILURE); }
+        }
+        at += len;
+        const size_t hit = data.find("\n>", from);
+        if (hit != std::string::npos) { data.resize(hit + 1); break; }
+    }
+    return data;
+}
+
+void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
+    const std::string &name = params->inputFileName;
+    sfOpen(name);
+    const uint64_t BLOCK = MGMP_Params::MIN_BASIC_BLOCK_SIZE;
+    while (true) {
+        std::vector<Contig> contigs;
+        std::string refStr;
+        uint64_t g0Bytes = 0;
+        initStreamsForG0Ref();
+        largestContigSize = 0;
+        if (params->sequentialMatching) {                                                      // MGMP.cpp:91-100: the first contig; the file is target 0
+            parseHostBytes(sfFirstRecord(), name, contigs);
+            if (contigs.empty()) validate_kseq_status(name, MBGC_FASTA_ENOTFASTA);
+            contigs.resize(1);
+        } else {                                                                               // :73-76: element 0
+            std::vector<uint64_t> ends;
+            sfElements(1, MGMP_Params::MIN_REF_INIT_SIZE, BLOCK, ends);
+            g0Bytes = ends.empty() ? 0 : ends[0];
+            std::string data(g0Bytes, '\0');
+            if (g0Bytes) inputStageCheck(mbgc_fasta_download(fasta, &data[0], sf.dev, g0Bytes));
+            parseHostBytes(data, name, contigs);
+            sfConsume(g0Bytes);
+            sf.nextElem = 1;
+            totalFilesLength += g0Bytes;
+        }
+        for (const Contig &c : contigs) {
+            largestContigSize = std::max<uint64_t>(largestContigSize, c.seq.size());
+            refStr.append(c.seq);
+            processG0RefContig(c.seq.data(), c.seq.size());
+        }
+        refG0InitPos = refStr.size();
+        const size_t basicRefLength = std::max<size_t>(refStr.size(), BLOCK);                  // :109-110
+        const int64_t remaining = (int64_t) sf.fileSize - (int64_t) (params->sequentialMatching ? BLOCK : g0Bytes);   // :113-115
+        const int64_t elementsCount = 1 + (remaining + (int64_t) BLOCK - 1) / (int64_t) BLOCK;
+        targetsCount = params->sequentialMatching ? 1 : (uint32_t) (elementsCount - 1);        // :118
+        if (!params->sequentialMatching && targetsCount < (uint32_t) MGMP_Params::SINGLEFILE_PARALLEL_MIN_TARGETS) {   // :119-129
+            fprintf(stderr, "Switching to sequential matching mode (input file too small).\n");
+            totalFilesLength = 0;
+            params->sequentialMatching = true;
+            sfRewind();
+            continue;
+        }
+        if (params->referenceFactor < 1) {                                                     // :130-134
+            int tmp = 15 - (__builtin_clz((unsigned) elementsCount) / 3);
+            tmp = tmp < 5 ? 5 : (tmp > 12 ? 12 : tmp);
+            params->referenceFactor = 1 << tmp;
+        }
+        initMatcher(refStr.data(), refStr.size(), basicRefLength);
+        return;
+    }
+}
+
+// The next batch of the file. Rounds: elements f0 .. f1 - 1 (they follow each other: the cut of one is the start of the next), each
+// a target, parsed on its own as the reference parses its split files. Sequential schedule: the file is ONE target, and a batch is
+// whatever whole records the window holds — the split proposes cuts, and a cut is taken where a line starts (a '>' inside a header
+// line would make two records of one).
+void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint32_t f1, RoundBatch &B) {
+    const uint64_t BLOCK = MGMP_Params::MIN_BASIC_BLOCK_SIZE;
+    B.offsets.assign(1, 0); B.targetOf.clear(); B.recCounts.clear(); B.bytes = 0; B.endOfInput = false;
+    std::vector<uint64_t> fileOff(1, 0), ends;
+    if (params->sequentialMatching) {
+        uint64_t cut = 0;
+        while (true) {
+            const bool end = sfAtEnd();
+            if (end) { cut = sf.have; break; }
+            if (sf.have > BLOCK) {
+                const uint32_t most = (uint32_t) (sf.have / BLOCK) + 1;
+                std::vector<uint64_t> e(most);
+                int n = 0;
+                const double t0 = nowSeconds();
+                inputStageCheck(mbgc_fasta_split_buf_dev(fasta, sf.dev, 0, sf.have, sf.scanned, 0, BLOCK, BLOCK, (int) most, e.data(), &n));
+                sf.scanned = sf.have;
+                g_tParse += nowSeconds() - t0;
+                for (int k = n - 1; k >= 0 && !cut; k--) {
+                    uint8_t before = 0;
+                    inputStageCheck(mbgc_fasta_download(fasta, &before, sf.dev + e[k] - 1, 1));
+                    if (before == '\n') cut = e[k];
+                }
+                if (cut) break;
+            }
+            sfExtend();
+        }
+        if (cut) fileOff.push_back(cut);
+    } else {
+        if (f0 != sf.nextElem) { fprintf(stderr, "internal error: element %u asked for, element %u is next in the file\n", f0, sf.nextElem); exit(EXIT_FAILURE); }
+        if (f1 > f0) sfElements(f1 - f0, BLOCK, BLOCK, ends);
+        fileOff.insert(fileOff.end(), ends.begin(), ends.end());
+    }
+    const int nf = (int) fileOff.size() - 1;
+    if (nf > 0) {
+        const double tParse0 = nowSeconds();
+        const size_t n = fileOff[nf];
+        totalFilesLength += n;
+        if (n + 64 > B.seqCap) {
+            if (B.seqDev) matcher->devFree(B.seqDev);
+            B.seqCap = n + n / 4 + 64;
+            B.seqDev = matcher->devAlloc(B.seqCap);
+        }
+        std::vector<uint64_t> seqBase(nf + 1), recBase(nf + 1), lineLen(nf);
+        std::vector<int> status(nf);
+        if (records.size() < 4096) records.resize(4096);
+        int rc = mbgc_fasta_parse_batch_dev(fasta, sf.dev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
+                                            records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+        if (rc == -104) {
+            records.resize(recBase[nf] + recBase[nf] / 4 + 16);
+            rc = mbgc_fasta_parse_batch_dev(fasta, sf.dev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
+                                            records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+        }
+        inputStageCheck(rc);
+        for (int f = 0; f < nf; f++) {
+            validate_kseq_status(params->inputFileName, status[f]);
+            for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) {
+                largestContigSize = std::max<uint64_t>(largestContigSize, records[k].seqLen);
+                B.offsets.push_back(seqBase[f] + records[k].seqOff + records[k].seqLen);
+                B.targetOf.push_back((uint32_t) f);
+            }
+            B.recCounts.push_back((uint32_t) (recBase[f + 1] - recBase[f]));
+        }
+        B.bytes = seqBase[nf];
+        g_tParse += nowSeconds() - tParse0;
+        sfConsume(n);
+        sf.nextElem += (uint32_t) nf;
+    }
+    B.endOfInput = sfAtEnd() && sf.have == 0;
+}
+
+bool MultipleGenomeMatchingProcessor::settleSingleFastaRound(RoundBatch &B) {
+    B.t1 = B.t0 + (uint32_t) B.recCounts.size();
+    seqsCounts.insert(seqsCounts.end(), B.recCounts.begin(), B.recCounts.end());
+    // MGMP.cpp:495-497: the first empty element ends the target list. (A batch without elements always is the file's end: an
+    // element is found as soon as a byte is left, and endOfInput says that none is.)
+    if (B.endOfInput || B.recCounts.empty()) targetsCount = B.t1;
+    return B.t1 > B.t0;
+}
+
 // ---------------------------------------------------------------- MultipleGenomeMatchingProcessor
 
 size_t MultipleGenomeMatchingProcessor::refLengthLimitFor(size_t basicRefLength, bool *bit40) const {
@@ -398,7 +680,7 @@ size_t MultipleGenomeMatchingProcessor::refLengthLimitFor(size_t basicRefLength,
 // its size) — a round whose extensions outgrow the window anyway (reverse complements of dissimilar contigs) loses the excess
 // as the reference's workers would, and the tool reports the bytes.
 uint32_t MultipleGenomeMatchingProcessor::windowRoundSize(uint64_t window, int gpus) const {
-    uint64_t largest = 0;
+    uint64_t largest = singleFastaFileMode ? 2 * MGMP_Params::MIN_BASIC_BLOCK_SIZE : 0;     // (elements: a block and the rest of a contig)
     for (uint32_t f = 1; f < filesCount; f++) {
         struct stat st;
         if (stat(fileNames[f].c_str(), &st) != 0) continue;
@@ -422,6 +704,7 @@ void MultipleGenomeMatchingProcessor::initMatcher(const char *refStr, size_t ref
 }
 
 void MultipleGenomeMatchingProcessor::loadG0Ref(const std::string &refName) {
+    if (singleFastaFileMode) { loadG0RefSingleFasta(); return; }
     std::vector<Contig> contigs;
     uint64_t fileSize = 0;
     readG0(refName, contigs, &fileSize);
@@ -486,13 +769,20 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
         prev.valid = false; prev.fileSeps = 0;
     };
     const std::vector<uint64_t> noLock(1, UINT64_MAX);                                          // :274 (no lock in this mode)
-    for (uint32_t i = 0; i < filesCount; i++) {
+    // single fasta file mode: the file is ONE target that arrives in batches of whole records, as many as it takes
+    const bool single = singleFastaFileMode;
+    if (single) seqsCounts.assign(1, 0);
+    size_t startPos = 0;
+    for (uint32_t i = 0; single || i < filesCount; i++) {
         RoundBatch &B = three[i % 3];
         if (prev.valid && prev.buf == (i + 1) % 3) { matcher->emitEnd(); collectPrev(false); }  // (files without records in between: the arriving file would overwrite what that emission reads)
-        loadRound(i, i + 1, B, i + 1, std::min(filesCount, i + 2), &three[(i + 1) % 3]);        // MGMP.cpp:247-250
-        const size_t startPos = matcher->getLoadedRefLength();                                 // :251
-        unmatchedFractionFactors.push_back(params->currentUnmatchedFractionFactor < 256 ? params->currentUnmatchedFractionFactor : 0);
-        unmatchedFractionFactors.push_back((uint8_t) params->unmatchedFractionRCFactor);
+        loadRound(i, i + 1, B, i + 1, single ? i + 2 : std::min(filesCount, i + 2), &three[(i + 1) % 3]);   // MGMP.cpp:247-250
+        if (single && !B.recCounts.empty()) seqsCounts[0] += B.recCounts[0];
+        if (!single || i == 0) {
+            startPos = matcher->getLoadedRefLength();                                          // :251
+            unmatchedFractionFactors.push_back(params->currentUnmatchedFractionFactor < 256 ? params->currentUnmatchedFractionFactor : 0);
+            unmatchedFractionFactors.push_back((uint8_t) params->unmatchedFractionRCFactor);
+        }
         for (size_t c = 0; c + 1 < B.offsets.size(); c++) {
             const size_t bSize = B.offsets[c + 1] - B.offsets[c];
             const uint8_t *seq = B.seqDev + B.offsets[c];
@@ -512,8 +802,10 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
             matcher->loadRefDev(seq, loadContigToRef ? bSize : 0, loadContigRCToRef, params->refRegionSeparators, REF_REGION_SEPARATOR);
             prev.valid = true; prev.buf = i % 3;
         }
+        if (single && !B.endOfInput) continue;                                                  // (the target goes on in the next batch)
         prev.fileSeps++;                                                                        // (behind the file's last contig)
         afterTargetWithParallelIO(startPos);                                                    // :306 without processAfterTarget
+        if (single) break;
     }
     if (prev.valid) matcher->emitEnd();
     collectPrev(false);
@@ -593,7 +885,7 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
     matchingLocksPos.assign(targetsCount, SIZE_MAX);
     unmatchedFractionFactors.assign(2 * (size_t) targetsCount, 0);
     const uint32_t R = (uint32_t) std::max(1, params->roundSize);
-    const uint32_t nRounds = (targetsCount + R - 1) / R;
+    uint32_t nRounds = (targetsCount + R - 1) / R;                           // (single fasta file mode: an estimate from above until the file has ended)
     const bool bench = params->benchMode;
     // round r lives in slot r % 3: its bytes are read by the emission's second phase while round r + 1 is matched, and
     // round r + 2 may already be arriving (bench: every round resident before the clock starts)
@@ -604,6 +896,10 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
             slots[r].t0 = r * R; slots[r].t1 = std::min(targetsCount, (r + 1) * R);
             loadRound(1 + slots[r].t0, 1 + slots[r].t1, slots[r], 1 + std::min(targetsCount, (r + 1) * R), 1 + std::min(targetsCount, (r + 2) * R),
                       r + 1 < nRounds ? &slots[r + 1] : nullptr);
+            if (singleFastaFileMode) {
+                const bool any = settleSingleFastaRound(slots[r]);
+                if (slots[r].endOfInput || !any) { nRounds = any ? r + 1 : r; break; }
+            }
         }
     // an emission whose streams have not been taken yet: targets [u0, u1) of batch B, its contigs [c0, c1). `tail`: targets that
     // follow it and whose streams the host holds already (they kept what the batch's first pass found, see below) — appended
@@ -669,6 +965,11 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
             B.t0 = r * R; B.t1 = std::min(targetsCount, (r + 1) * R);
             loadRound(1 + B.t0, 1 + B.t1, B, 1 + std::min(targetsCount, (r + 1) * R), 1 + std::min(targetsCount, (r + 2) * R),
                       r + 1 < nRounds ? &slots[(r + 1) % 3] : nullptr);
+            if (singleFastaFileMode) {
+                const bool any = settleSingleFastaRound(B);
+                if (B.endOfInput) nRounds = r + 1;
+                if (!any) break;
+            }
         } else if ((int) r == params->benchWarmup) {
             if (prev.valid) { matcher->emitEnd(); collect(prev, false); prev.valid = false; }
             matcher->synchronize();
@@ -862,6 +1163,12 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
         params->benchBases = 0;
         for (uint32_t r = (uint32_t) params->benchWarmup; r < nRounds; r++) params->benchBases += slots[r].bytes;
     }
+    if (ahead.active) { ahead.done.wait(); ahead.active = false; }
+    if (singleFastaFileMode) {                                              // finalizeParallelProcessingInSingleFastaFileMode, MGMP.cpp:329-338
+        unmatchedFractionFactors.resize(2 * (size_t) targetsCount);
+        matchingLocksPos.resize(targetsCount);
+        seqsCounts.resize(targetsCount);
+    }
     for (auto &B : slots) if (B.seqDev) matcher->devFree(B.seqDev);
 }
 
@@ -1054,19 +1361,25 @@ void MBGC_Encoder::appendTargetStreams(uint32_t targetIdx) {
 }
 
 void MBGC_Encoder::encode(const std::vector<std::string> &files) {
-    fileNames = files;
+    singleFastaFileMode = !params->inputFileName.empty();                                       // ENC.cpp:775
+    fileNames = singleFastaFileMode ? std::vector<std::string>(1, params->inputFileName) : files;
     filesCount = (uint32_t) fileNames.size();
     if (!filesCount) {
         fprintf(stderr, "ERROR: filelist is empty.\n");
         exit(EXIT_FAILURE);
     }
-    if (filesCount == 1) params->sequentialMatching = true;                                     // no targets for the round loop
+    if (singleFastaFileMode && params->exchange) {
+        fprintf(stderr, "single fasta file mode (-i) runs on one GPU: the rounds sharded over several GPUs take a file list\n");
+        exit(EXIT_FAILURE);
+    }
+    if (singleFastaFileMode) params->lazyDecompressionSupport = false;                          // "single file compression mode", ENC.cpp:462-466
+    if (filesCount == 1 && !singleFastaFileMode) params->sequentialMatching = true;                                     // no targets for the round loop
     params->emit.lazyDecompressionSupport = params->lazyDecompressionSupport;
     // the first round's files are read (and their page-locked buffer allocated) while the reference file is parsed and the
     // matcher's reference buffer and table are set up
     const int gpus = params->exchange ? mbgc_xchg_world(params->exchange) : 1;
     const bool autoRound = params->roundSize <= 0 && !params->sequentialMatching;
-    if (autoRound) {                                                                            // a first guess from the file's size (the sequence is a little shorter): what the read-ahead starts with
+    if (autoRound && !singleFastaFileMode) {                                                    // a first guess from the file's size (the sequence is a little shorter): what the read-ahead starts with
         struct stat st;
         const uint64_t g0 = stat(fileNames[0].c_str(), &st) == 0 ? (uint64_t) st.st_size : 0;
         MBGC_Params guessParams = *params;
@@ -1082,7 +1395,7 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
         MultipleGenomeMatchingProcessor::params = keep;
         params->roundSize = (int) windowRoundSize(params->circularReference ? lim / (size_t) params->referenceSlidingWindowFactor : 0, gpus);
     }
-    if (!params->sequentialMatching && !params->exchange)
+    if (!params->sequentialMatching && !params->exchange && !singleFastaFileMode)
         startReadAhead(1, std::min<uint32_t>(filesCount, 1 + (uint32_t) std::max(1, params->roundSize)), 1, readBesideUpload());
     const double tG0 = nowSeconds();
     loadG0Ref(fileNames[0]);

@@ -54,6 +54,13 @@ struct MGMP_Params {                                   // matching/MGMP_Params.h
     int specRounds = 0;                                // rounds whose finalize ran on the ranks' device-side verdicts (diagnostics)
     int headRounds = 0;                                // rounds whose extension exchange was cut to the loadable head (diagnostics)
     static constexpr uint64_t MIN_BASIC_BLOCK_SIZE = 1 << 21;             // :48
+    // single fasta file mode (`mbgc c -i`, MBGC_Encoder.cpp:775): the collection is ONE multi-FASTA file, cut into the initial
+    // reference (an element of at least MIN_REF_INIT_SIZE bytes) and targets (elements of at least MIN_BASIC_BLOCK_SIZE bytes) by
+    // mgmpInSplit_next — on the device here (mbgc_fasta_split_dev), window by window
+    std::string inputFileName;
+    uint64_t singleFileWindow = 32u << 20;             // bytes of the file read, uploaded and split at a time (mbgc-hip --window-kib)
+    static constexpr uint64_t MIN_REF_INIT_SIZE = 1 << 16;                // :47
+    static constexpr int SINGLEFILE_PARALLEL_MIN_TARGETS = 4;             // :19
     static constexpr uint64_t REFERENCE_LENGTH_LIMIT = (uint64_t) UINT32_MAX << 8;   // :55
     bool isContigProperForRefExtension(uint64_t len, uint64_t unmatched, int f) const { return unmatched * f > len; }      // :179-186
     bool isContigProperForRefRCExtension(uint64_t len, uint64_t unmatched, int f) const { return unmatched * f > len; }    // :188-190
@@ -79,6 +86,10 @@ struct RoundBatch {
     std::vector<uint64_t> offsets;                     // ncont + 1
     std::vector<uint32_t> targetOf;                    // target index of every contig
     uint32_t t0 = 0, t1 = 0;                           // targets [t0, t1)
+    // single fasta file mode: the records of every element found for the batch (it may hold fewer elements than asked for),
+    // and whether the file ends with it
+    std::vector<uint32_t> recCounts;
+    bool endOfInput = false;
 };
 
 class MultipleGenomeMatchingProcessor {
@@ -93,10 +104,13 @@ protected:
     std::vector<size_t> matchingLocksPos;
     std::vector<uint8_t> unmatchedFractionFactors;
     int device = 0;
+    bool singleFastaFileMode = false;                                                   // MGMP.h:45
+    std::vector<uint32_t> seqsCounts;                                                   // records of every target (single fasta file mode)
 
     const size_t PROCESSING_MATCHES_SKIPPED_DUE_TO_CONTIG_DISSIMILARITY = SIZE_MAX;     // MGMP.h:97
 
     void loadG0Ref(const std::string &refName);                                        // MGMP.cpp:66-150
+    void loadG0RefSingleFasta();                                                        // the same in single fasta file mode (:73-76, :109-129)
     void initMatcher(const char *refStr, size_t refStrSize, size_t basicRefLength);     // :152-192
     size_t refLengthLimitFor(size_t basicRefLength, bool *bit40) const;                 // :154-168
     uint32_t windowRoundSize(uint64_t window, int gpus) const;                          // MGMP_Params::roundSize == 0
@@ -130,6 +144,32 @@ protected:
     std::vector<mbgc_fasta_record_t> records;
     void openInputStage();
     void readG0(const std::string &path, std::vector<Contig> &out, uint64_t *fileSize);
+    void parseHostBytes(const std::string &data, const std::string &name, std::vector<Contig> &out);
+    // Single fasta file mode: the file travels through the two staging buffers in windows of params->singleFileWindow bytes (the
+    // next one is read while this one is uploaded and split) into a device buffer that starts at an element start; what a batch
+    // leaves behind its last element is moved to the front of a second buffer and the two change places. Host memory is bounded
+    // by the windows (a gzip file is inflated whole, as mgmpInOpen does).
+    struct SingleFile {
+        int fd = -1;
+        bool gz = false;
+        std::string inflated, error;
+        uint64_t fileSize = 0, readPos = 0;                                             // readPos: behind the last window read or being read
+        uint8_t *dev = nullptr, *spare = nullptr; size_t devCap = 0, spareCap = 0;
+        uint64_t devBase = 0, have = 0;                                                 // dev[0, have) = bytes [devBase, devBase + have) of the file
+        uint64_t scanned = 0;                                                           // dev[0, scanned): the split's streaming pass has been over it
+        uint32_t nextElem = 0;
+        std::future<uint64_t> reading; int readSlot = 0; bool readActive = false;
+    } sf;
+    void sfOpen(const std::string &path);
+    void sfStartRead();
+    bool sfExtend();                                                                    // one more window behind dev[have); false: the file has ended
+    bool sfAtEnd() const { return sf.devBase + sf.have == sf.fileSize; }
+    void sfConsume(uint64_t bytes);                                                     // the buffer now starts `bytes` further on
+    void sfRewind();
+    void sfElements(uint32_t want, uint64_t firstMin, uint64_t nextMin, std::vector<uint64_t> &ends);   // ends of the next elements, relative to sf.dev
+    std::string sfFirstRecord();
+    void prepareRoundSingleFasta(uint32_t f0, uint32_t f1, RoundBatch &B);
+    bool settleSingleFastaRound(RoundBatch &B);                                         // what the batch really holds -> B.t1, seqsCounts, targetsCount; false: it is empty
     // files [f0, f1) parsed into B; [nextF0, nextF1) into *nextB = what will be asked for next (prepared meanwhile)
     void loadRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t nextF0 = 0, uint32_t nextF1 = 0, RoundBatch *nextB = nullptr);
 
@@ -214,6 +254,9 @@ public:
     void feedBackendStream(bool everything);
     std::string finishBackendStream(uint64_t *blocksCodedEarly);
     void backendParams(mbgc_backend_params_t &bp, int blocksScale, int numberOfThreads) const;
+    bool singleFastaFile() const { return singleFastaFileMode; }
+    uint32_t singleFastaElements() const { return params->sequentialMatching ? 1 : targetsCount + 1; }
+    const std::vector<uint32_t> &sequenceCounts() const { return seqsCounts; }
     size_t exactMatches() const { return resCount; }
     size_t finalReferenceLength() const { return refFinalTotalLength; }          // writeStats' refFinalTotalLength, ENC.cpp:734-743
     size_t droppedExtensionBytes() const { return matcher ? matcher->getDroppedBytes() : 0; }
