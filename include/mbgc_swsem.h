@@ -239,6 +239,45 @@ int swsem_decode_contigs_dev(swsem_t *h, const swsem_emit_params_t *p, int n, co
  * i.e. before the rounds after it start overwriting it (a circular buffer that has wrapped). Waits for the emission. */
 int swsem_emit_verify(swsem_t *h, int *nbad, int *firstBad, uint64_t *firstDiff);
 
+/* ---- the decoder's side of a whole collection (`mbgc-hip d`, mbgc_amd/host/mbgc_decoder.cpp): MBGC_Decoder::decodeTarget's walk
+ * from contig to contig (mbgccoder/MBGC_Decoder.cpp:535-634) and MBGC_Decoder::loadRef (:651-675).
+ * swsem_create_decoder: a handle with the reference buffer (zeroed, maxRefLength bytes) and NO hash table and none of the
+ * matcher's side state; swsem_destroy frees it. Every matcher or emit entry point that can report an error refuses such a
+ * handle with SWSEM_EINVAL; the decode calls, swsem_dev_*, swsem_synchronize, swsem_revcomp_dev and swsem_debug_copy_ref take it. */
+int swsem_create_decoder(swsem_t **out, uint64_t maxRefLength, int device);
+/* The chained plan over the collection's six streams, device resident (literals with SEQ_SEPARATOR_MARK behind every contig,
+ * flags with FILE_SEPARATOR_MARK behind every target when extensions are on). One wave per chain start walks the contigs of
+ * targets [firstTarget, firstTarget + nTargets) from the cursors `cur`; the chains cover the targets in order without gaps.
+ * checkEnd: the chain must end exactly on `end` (the next target's offsets in a stream index, the streams' sizes at the
+ * collection's end). seqCount[t] / lockPos[t]: contigs and matching-lock position of target t. out[c], c = the contig's number
+ * in the collection: destLen, unmatched (-1: the chain was malformed at or before it: a stream ran out, bytes were left
+ * over, the chain missed its end), the cursors at its start, its literal end, the read hull [minSrc, maxSrcEnd) of its
+ * records in the reference buffer (UINT64_MAX, 0: none). *firstBadChain = the first malformed chain or -1. The plan reads
+ * no reference byte. Records and plan rows stay in the handle for swsem_decode_fill_range_dev until the next plan. */
+typedef struct {
+    uint64_t cur[SWSEM_NSTREAMS], end[SWSEM_NSTREAMS];
+    uint32_t firstTarget, nTargets, checkEnd, pad;
+} swsem_chain_start_t;
+typedef struct {
+    uint64_t destLen; int64_t unmatched;
+    uint64_t cur[SWSEM_NSTREAMS];
+    uint64_t litEnd, minSrc, maxSrcEnd, nrec;
+} swsem_chain_contig_t;
+int swsem_decode_plan_chain_dev(swsem_t *h, const swsem_emit_params_t *p, const uint8_t *const stream_dev[SWSEM_NSTREAMS],
+                                const uint64_t size[SWSEM_NSTREAMS], int nstarts, const swsem_chain_start_t *starts, int ntargets,
+                                const uint32_t *seqCount, const uint64_t *lockPos, uint64_t ncontigs, swsem_chain_contig_t *out,
+                                int *firstBadChain);
+/* The bytes of planned contigs [c0, c1): contig c to dest_dev + destOff[c] (destOff: host, one entry per planned contig + 1),
+ * against the reference buffer as it stands, one launch for the range, queued on the handle's stream. *nbad (may be NULL; then
+ * nothing is waited for) = contigs of the range whose bytes did not come out as planned. */
+int swsem_decode_fill_range_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *dest_dev, const uint64_t *destOff, uint64_t *nbad);
+/* MBGC_Decoder::loadRef as a schedule: segments applied to the reference buffer in order. src: offset into src_dev (the decoded
+ * contigs), or a reference position (FROM_REF: the per-target reverse complement of :608-616); dst: reference position;
+ * RC: upperReverseComplement of the len source bytes; BYTE: the single byte `src & 0xFF` (a region separator). */
+enum { SWSEM_SEG_RC = 1, SWSEM_SEG_FROM_REF = 2, SWSEM_SEG_BYTE = 4 };
+typedef struct { uint64_t src, dst, len; uint32_t flags, pad; } swsem_load_seg_t;
+int swsem_decode_load_dev(swsem_t *h, const uint8_t *src_dev, int n, const swsem_load_seg_t *segs);
+
 /* ---- device-memory plumbing for host code that stays free of HIP headers (the C++ facade) */
 int swsem_dev_malloc(swsem_t *h, uint64_t bytes, void **out_dev);
 int swsem_dev_free(swsem_t *h, void *p_dev);

@@ -22,7 +22,8 @@ swsem_get_loading_position swsem_get_loaded_ref_length swsem_get_max_ref_length 
 swsem_acquire_lock swsem_release_lock swsem_get_K swsem_get_hash_size swsem_load_ref swsem_load_ref_dev
 swsem_load_separator swsem_finalize_targets swsem_revcomp_dev swsem_match swsem_match_batch_dev swsem_batch_counts swsem_batch_matches
 swsem_batch_fingerprint swsem_emit_params_default swsem_emit swsem_emit_batch swsem_emit_batch_begin swsem_emit_batch_begin_spec swsem_emit_batch_end swsem_emit_select swsem_emit_result swsem_emit_set_host_copy swsem_emit_unmatched swsem_emit_pack_dev swsem_emit_pack_dev_on swsem_emit_counters swsem_debug_copy_ref swsem_debug_write_ref swsem_debug_copy_ht swsem_debug_emit_stats
-swsem_profile_enable swsem_profile_get swsem_batch_stats swsem_dev_malloc swsem_dev_free swsem_dev_upload swsem_dev_download swsem_dev_copy swsem_decode_contigs_dev swsem_emit_verify""".split()
+swsem_profile_enable swsem_profile_get swsem_batch_stats swsem_dev_malloc swsem_dev_free swsem_dev_upload swsem_dev_download swsem_dev_copy swsem_decode_contigs_dev swsem_emit_verify
+swsem_create_decoder swsem_decode_plan_chain_dev swsem_decode_fill_range_dev swsem_decode_load_dev""".split()
 
 
 class SpecFinalize(C.Structure):
@@ -54,6 +55,23 @@ class EmitParams(C.Structure):
 class DecodeJob(C.Structure):
     _fields_ = [("stream_dev", C.c_void_p * 6), ("size", C.c_uint64 * 6), ("refLockPos", C.c_uint64), ("dest_dev", C.c_void_p),
                 ("destCap", C.c_uint64)]
+
+
+class ChainStart(C.Structure):
+    _fields_ = [("cur", C.c_uint64 * 6), ("end", C.c_uint64 * 6), ("firstTarget", C.c_uint32), ("nTargets", C.c_uint32),
+                ("checkEnd", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ChainContig(C.Structure):
+    _fields_ = [("destLen", C.c_uint64), ("unmatched", C.c_int64), ("cur", C.c_uint64 * 6), ("litEnd", C.c_uint64),
+                ("minSrc", C.c_uint64), ("maxSrcEnd", C.c_uint64), ("nrec", C.c_uint64)]
+
+
+class LoadSeg(C.Structure):
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("len", C.c_uint64), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+SEG_RC, SEG_FROM_REF, SEG_BYTE = 1, 2, 4
 
 
 class Streams(C.Structure):
@@ -127,6 +145,11 @@ def lib():
         L.swsem_emit_unmatched.argtypes = [vp, pu64]
         L.swsem_emit_verify.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), pu64]
         L.swsem_decode_contigs_dev.argtypes = [vp, C.POINTER(EmitParams), ci, vp, pu64, C.POINTER(C.c_int64)]
+        L.swsem_create_decoder.argtypes = [C.POINTER(vp), u64, ci]
+        L.swsem_decode_plan_chain_dev.argtypes = [vp, C.POINTER(EmitParams), C.POINTER(vp), pu64, ci, C.POINTER(ChainStart), ci,
+                                                  C.POINTER(C.c_uint32), pu64, u64, C.POINTER(ChainContig), C.POINTER(ci)]
+        L.swsem_decode_fill_range_dev.argtypes = [vp, u64, u64, vp, pu64, pu64]
+        L.swsem_decode_load_dev.argtypes = [vp, vp, ci, C.POINTER(LoadSeg)]
         L.swsem_debug_copy_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_write_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_copy_ht.argtypes = [vp, vp]
@@ -413,3 +436,45 @@ class SlidingWindowSparseEMMatcher:
         n = (C.c_uint64 * 7)()
         _chk(lib().swsem_profile_get(self.h, ms, n))
         return {KERNEL_FAMILIES[i]: (ms[i], n[i]) for i in range(7)}
+
+
+class Decoder(SlidingWindowSparseEMMatcher):
+    """The decoder's handle (swsem_create_decoder): a reference buffer and no hash table. The matcher's and the emission's
+    calls on it raise SwsemError (SWSEM_EINVAL)."""
+
+    def __init__(self, max_ref_len, device=0):
+        self.h = C.c_void_p()
+        _chk(lib().swsem_create_decoder(C.byref(self.h), max_ref_len, device))
+
+    def plan_chain(self, params, streams, starts, seq_counts, locks):
+        """streams: six (device pointer, size) pairs; starts: list of (cur[6], end[6], firstTarget, nTargets, checkEnd).
+        -> (list of ChainContig, first malformed chain or -1)"""
+        ptrs = (C.c_void_p * 6)(*[int(p) for p, _ in streams])
+        sizes = (C.c_uint64 * 6)(*[int(n) for _, n in streams])
+        st = (ChainStart * len(starts))()
+        for k, (cur, end, t0, nt, chk) in enumerate(starts):
+            for i in range(6):
+                st[k].cur[i], st[k].end[i] = int(cur[i]), int(end[i])
+            st[k].firstTarget, st[k].nTargets, st[k].checkEnd = t0, nt, int(chk)
+        sc = np.ascontiguousarray(seq_counts, dtype=np.uint32)
+        lk = np.ascontiguousarray(locks, dtype=np.uint64)
+        n = int(sc.sum())
+        out = (ChainContig * max(n, 1))()
+        bad = C.c_int(-1)
+        _chk(lib().swsem_decode_plan_chain_dev(self.h, C.byref(params), ptrs, sizes, len(starts), st, sc.size,
+                                               sc.ctypes.data_as(C.POINTER(C.c_uint32)), lk.ctypes.data_as(C.POINTER(C.c_uint64)), n, out, C.byref(bad)))
+        return list(out[:n]), bad.value
+
+    def fill_range(self, c0, c1, dest_ptr, dest_off):
+        """planned contigs [c0, c1) to dest_ptr + dest_off[c]; -> contigs whose bytes did not come out as planned"""
+        off = np.ascontiguousarray(dest_off, dtype=np.uint64)
+        nbad = C.c_uint64()
+        _chk(lib().swsem_decode_fill_range_dev(self.h, c0, c1, dest_ptr, off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(nbad)))
+        return nbad.value
+
+    def load_segments(self, src_ptr, segs):
+        """segs: list of (src, dst, len, flags) — flags: SEG_RC, SEG_FROM_REF, SEG_BYTE"""
+        arr = (LoadSeg * max(len(segs), 1))()
+        for k, (src, dst, ln, fl) in enumerate(segs):
+            arr[k].src, arr[k].dst, arr[k].len, arr[k].flags = int(src), int(dst), int(ln), int(fl)
+        _chk(lib().swsem_decode_load_dev(self.h, src_ptr, len(segs), arr))

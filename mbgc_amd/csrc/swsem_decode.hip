@@ -14,9 +14,15 @@
 //                   match copied out of the reference buffer, the right extension — dec_left_write / dec_extend_right, the
 //                   same functions the one-wave form runs, now thousands at a time;
 //   k_decode_check  (verification) the contig against the bytes it was encoded from.
+// A whole collection (`mbgc-hip d`, mbgc_amd/host/mbgc_decoder.cpp): the plan's body is plan_contig, shared by
+//   k_decode_plan_chain  one wave per chain start walks consecutive contigs of the collection's concatenated streams
+//                   (MBGC_Decoder::decodeTarget :535-634) and carries the six cursors from one to the next — per target with the
+//                   stream index of <prefix>.meta, one chain for everything without; no reference byte is read;
+//   k_decode_load   MBGC_Decoder::loadRef (:651-675) as the host scheduled it: copies, reverse complements, separator bytes;
+// k_decode_fill then fills a wave of planned contigs against the decoder's reference buffer (swsem_create_decoder: no table).
 // The contigs of a round are independent (each stands against the reference as its lock position froze it) and are decoded
 // side by side. Used as the device-side check of an emission (swsem_emit_verify: what was just emitted must decode to the
-// query, with no encoder logic in the loop) and as the building block of an accelerated `mbgc d`.
+// query, with no encoder logic in the loop) and by `mbgc-hip d`.
 #include "swsem_device.h"
 #include "../../include/mbgc_swsem.h"
 
@@ -335,29 +341,17 @@ __device__ uint32_t plan_next_len(Plan &d, bool frugal) {
     return lo;
 }
 
-__global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, const DecodeJob *__restrict__ jobs, DecRec *__restrict__ recs,
-                                                      const uint64_t *__restrict__ recBase, DecPlanOut *__restrict__ outs, uint64_t refBytes) {
-    __shared__ int64_t paired[DEC_MAX_GAP_DEPTH];
-    const DecodeJob jb = jobs[blockIdx.x];
-    DecRec *out = recs + recBase[blockIdx.x];
-    const uint64_t recCap = recBase[blockIdx.x + 1] - recBase[blockIdx.x];
-    Plan d;
-    d.lit.p = jb.stream[SWSEM_LIT]; d.lit.n = d.nLit = jb.size[SWSEM_LIT];
-    d.fl.p = jb.stream[SWSEM_FLAGS]; d.fl.n = d.nFlags = jb.size[SWSEM_FLAGS];
-    d.off.p = jb.stream[SWSEM_OFF]; d.off.n = d.nOff = jb.size[SWSEM_OFF];
-    d.off5.p = jb.stream[SWSEM_OFF5]; d.off5.n = d.nOff5 = jb.size[SWSEM_OFF5];
-    d.len.p = jb.stream[SWSEM_LEN]; d.len.n = d.nLen = jb.size[SWSEM_LEN];
-    d.gap.p = jb.stream[SWSEM_GAP]; d.gap.n = d.nGap = jb.size[SWSEM_GAP];
-    d.litPos = d.offPos = d.off5Pos = d.lenPos = d.gapPos = d.flPos = 0;
-    d.destLen = 0; d.destCap = jb.destCap;
-    d.bad = 0;
-    d.initialScore = p.mmsMismatchesInitialScore; d.penalty = p.mmsMismatchPenalty; d.bonus = p.mmsMatchBonus; d.threshold = p.mmsMismatchesScoreThreshold;
-    bw_load<true>(d.lit, 0); bw_load<false>(d.fl, 0);
-    dw_load(d.len, 0); dw_load(d.off, 0); dw_load(d.off5, 0); dw_load(d.gap, 0);
+// what the records of a contig read of the reference buffer: matches and both extensions (a little wider at the right
+// extension's ends, never narrower)
+struct DecHull { uint64_t minSrc, maxSrcEnd; };
+// The automaton over one contig: d stands at the contig's start in every stream (its windows loaded anywhere), the contig's
+// literals end at seqEnd; the other streams go on as far as the contig reads them. Leaves the records in out[0, *nrec) and
+// d at the contig's end (d.bad set: malformed, nothing else valid).
+__device__ void plan_contig(const swsem_emit_params_t &p, Plan &d, const uint64_t seqEnd, const uint64_t refLockPos, int64_t *paired,
+                            DecRec *__restrict__ out, const uint64_t recCap, const uint64_t refBytes, uint64_t *nrec, uint32_t *unmatched, DecHull &hull) {
     for (int i = threadIdx.x; i < DEC_MAX_GAP_DEPTH; i += WAVE) paired[i] = INT64_MAX;
     __builtin_amdgcn_s_waitcnt(0);
     const bool l0 = threadIdx.x == 0;
-    const uint64_t seqEnd = d.nLit;
     uint32_t unmatchedChars = 0;
     int64_t gapStartIdx = -1, gapEndIdx = -1;
     int gapCurIdx = 0;
@@ -391,7 +385,7 @@ __global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, con
         if (p.enableExtensionsWithMismatches) {
             if (!isGap && literalsLeft) {
                 uint64_t flEnd = d.flPos;
-                const LeftExt e = plan_left_measure(d, &matchSrcPos, skipOffset, jb.refLockPos, markPos, &flEnd);
+                const LeftExt e = plan_left_measure(d, &matchSrcPos, skipOffset, refLockPos, markPos, &flEnd);
                 if (!d.bad && e.len) {
                     if (e.codes > literalsLeft) { d.bad = 1; break; }
                     rec.leftLen = (uint32_t) e.len; rec.leftCodes = (uint32_t) e.codes; rec.leftSrcMatch = e.srcMatch; rec.leftSrcGuard = e.srcGuard;
@@ -415,6 +409,13 @@ __global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, con
         if (matchSrcPos > refBytes || matchLength > refBytes - matchSrcPos) d.bad = 1;   // (a match outside the reference buffer: malformed)
         if (d.bad) break;
         rec.src = matchSrcPos; rec.len = matchLength;
+        if (matchSrcPos < hull.minSrc) hull.minSrc = matchSrcPos;
+        if (matchSrcPos + matchLength > hull.maxSrcEnd) hull.maxSrcEnd = matchSrcPos + matchLength;
+        if (rec.leftLen) {                                                    // (dec_left_write reads leftLen bytes downwards from leftSrcMatch - 1)
+            const uint64_t lo = (uint64_t) (rec.leftSrcMatch - (int64_t) rec.leftLen);
+            if (lo < hull.minSrc) hull.minSrc = lo;
+            if ((uint64_t) rec.leftSrcMatch > hull.maxSrcEnd) hull.maxSrcEnd = (uint64_t) rec.leftSrcMatch;
+        }
         markPos = plan_find_mark(d, d.litPos);
         uint32_t gapDelta = 0;
         if (p.gapDepthOffsetEncoding && markPos != DEC_NPOS && markPos < seqEnd) {
@@ -456,6 +457,12 @@ __global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, con
             rec.flags |= REC_RIGHT; rec.offsetDelta = offsetDelta; rec.guardLit = guardLit;
             extRightLen = plan_extend_right(d, isGap, gapStart, gapMiddle, gapEnd, guardLit);
             rec.rightLen = (uint32_t) extRightLen;
+            if (extRightLen) {                                                // (dec_extend_right reads from the contig position + offsetDelta on)
+                const int64_t lo = (int64_t) (d.destLen - extRightLen) + offsetDelta - 1;
+                if (lo < 0) hull.minSrc = 0; else if ((uint64_t) lo < hull.minSrc) hull.minSrc = (uint64_t) lo;
+                const uint64_t hi = (uint64_t) (lo < 0 ? 0 : lo) + extRightLen + 2;
+                if (hi > hull.maxSrcEnd) hull.maxSrcEnd = hi;
+            }
         }
         if (l0) out[j] = rec;
         j++;
@@ -470,12 +477,156 @@ __global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, con
         if (l0 && !d.bad) out[j] = rec;
         j++;
     }
+    *nrec = (uint64_t) j; *unmatched = unmatchedChars;
+}
+
+__global__ void __launch_bounds__(WAVE) k_decode_plan(swsem_emit_params_t p, const DecodeJob *__restrict__ jobs, DecRec *__restrict__ recs,
+                                                      const uint64_t *__restrict__ recBase, DecPlanOut *__restrict__ outs, uint64_t refBytes) {
+    __shared__ int64_t paired[DEC_MAX_GAP_DEPTH];
+    const DecodeJob jb = jobs[blockIdx.x];
+    DecRec *out = recs + recBase[blockIdx.x];
+    const uint64_t recCap = recBase[blockIdx.x + 1] - recBase[blockIdx.x];
+    Plan d;
+    d.lit.p = jb.stream[SWSEM_LIT]; d.lit.n = d.nLit = jb.size[SWSEM_LIT];
+    d.fl.p = jb.stream[SWSEM_FLAGS]; d.fl.n = d.nFlags = jb.size[SWSEM_FLAGS];
+    d.off.p = jb.stream[SWSEM_OFF]; d.off.n = d.nOff = jb.size[SWSEM_OFF];
+    d.off5.p = jb.stream[SWSEM_OFF5]; d.off5.n = d.nOff5 = jb.size[SWSEM_OFF5];
+    d.len.p = jb.stream[SWSEM_LEN]; d.len.n = d.nLen = jb.size[SWSEM_LEN];
+    d.gap.p = jb.stream[SWSEM_GAP]; d.gap.n = d.nGap = jb.size[SWSEM_GAP];
+    d.litPos = d.offPos = d.off5Pos = d.lenPos = d.gapPos = d.flPos = 0;
+    d.destLen = 0; d.destCap = jb.destCap;
+    d.bad = 0;
+    d.initialScore = p.mmsMismatchesInitialScore; d.penalty = p.mmsMismatchPenalty; d.bonus = p.mmsMatchBonus; d.threshold = p.mmsMismatchesScoreThreshold;
+    bw_load<true>(d.lit, 0); bw_load<false>(d.fl, 0);
+    dw_load(d.len, 0); dw_load(d.off, 0); dw_load(d.off5, 0); dw_load(d.gap, 0);
+    const bool l0 = threadIdx.x == 0;
+    uint64_t j = 0;
+    uint32_t unmatchedChars = 0;
+    DecHull hull = {DEC_NPOS, 0};
+    plan_contig(p, d, d.nLit, jb.refLockPos, paired, out, recCap, refBytes, &j, &unmatchedChars, hull);
     if (!d.bad && (d.offPos != d.nOff || d.off5Pos != d.nOff5 || d.lenPos != d.nLen || d.gapPos != d.nGap || d.flPos != d.nFlags)) d.bad = 1;
     if (l0) {
         DecPlanOut o;
         o.nrec = d.bad ? 0 : (uint64_t) j; o.destLen = d.destLen; o.unmatched = d.bad ? -1 : (int64_t) unmatchedChars; o.pad = 0;
         outs[blockIdx.x] = o;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// pass 1 over a collection: the chained plan — MBGC_Decoder::decodeTarget's walk from contig to contig (:535-634) without
+// its bytes. In the collection's streams only the literals (SEQ_SEPARATOR_MARK behind every contig) and the flags
+// (FILE_SEPARATOR_MARK behind every target, extensions on) are delimited: where the other four end for a contig is known
+// once it has been planned. One wave per chain start carries the six cursors from contig to contig.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr uint8_t DEC_SEQ_SEPARATOR_MARK = 0xA2;          // '"' + 128, MBGC_Params.h:46
+constexpr uint8_t DEC_FILE_SEPARATOR_MARK = 0xBB;         // ';' + 128, MBGC_Params.h:47
+constexpr uint64_t DEC_CHAIN_DEST_CAP = 1ull << 40;       // no contig is longer (a stream set that says so is malformed)
+
+struct ChainStreams { const uint8_t *p[SWSEM_NSTREAMS]; uint64_t n[SWSEM_NSTREAMS]; };
+struct ChainStart {                                       // == swsem_chain_start_t
+    uint64_t cur[SWSEM_NSTREAMS];                         // the six cursors at the chain's first contig
+    uint64_t end[SWSEM_NSTREAMS];                         // ... and where the chain must end (checkEnd)
+    uint32_t firstTarget, nTargets, checkEnd, pad;
+    uint64_t firstContig, recBase, recCap;
+};
+struct ChainContig {                                      // == swsem_chain_contig_t
+    uint64_t destLen; int64_t unmatched;
+    uint64_t cur[SWSEM_NSTREAMS];                         // the cursors at the contig's start
+    uint64_t litEnd;                                      // its separator in the literal stream
+    uint64_t minSrc, maxSrcEnd;                           // read hull of its records (DEC_NPOS, 0: it reads nothing)
+    uint64_t nrec;
+};
+
+__device__ __forceinline__ void bw_load_byte(DecByteWin &w, uint64_t pos, uint8_t value) {
+    const uint64_t i = pos + (threadIdx.x & (WAVE - 1));
+    const uint8_t b = i < w.n ? w.p[i] : (uint8_t) 0;
+    w.base = pos;
+    w.mask = __ballot(b == value);
+}
+
+// outs / cc / recBaseOut are indexed by the contig's number in the collection; the caller has set every outs[c].unmatched to -1:
+// a chain that ends malformed leaves its remaining contigs that way and raises chainBad[chain].
+__global__ void __launch_bounds__(WAVE) k_decode_plan_chain(swsem_emit_params_t p, ChainStreams S, const ChainStart *__restrict__ starts,
+                                                            const uint32_t *__restrict__ seqCount, const uint64_t *__restrict__ lockPos,
+                                                            DecRec *__restrict__ recs, DecPlanOut *__restrict__ outs, ChainContig *__restrict__ cc,
+                                                            uint64_t *__restrict__ recBaseOut, uint32_t *__restrict__ chainBad, uint64_t refBytes) {
+    __shared__ int64_t paired[DEC_MAX_GAP_DEPTH];
+    const ChainStart st = starts[blockIdx.x];
+    const bool l0 = threadIdx.x == 0;
+    Plan d;
+    d.lit.p = S.p[SWSEM_LIT]; d.lit.n = S.n[SWSEM_LIT];
+    d.fl.p = S.p[SWSEM_FLAGS]; d.fl.n = d.nFlags = S.n[SWSEM_FLAGS];
+    d.off.p = S.p[SWSEM_OFF]; d.off.n = d.nOff = S.n[SWSEM_OFF];
+    d.off5.p = S.p[SWSEM_OFF5]; d.off5.n = d.nOff5 = S.n[SWSEM_OFF5];
+    d.len.p = S.p[SWSEM_LEN]; d.len.n = d.nLen = S.n[SWSEM_LEN];
+    d.gap.p = S.p[SWSEM_GAP]; d.gap.n = d.nGap = S.n[SWSEM_GAP];
+    d.litPos = st.cur[SWSEM_LIT]; d.offPos = st.cur[SWSEM_OFF]; d.off5Pos = st.cur[SWSEM_OFF5];
+    d.lenPos = st.cur[SWSEM_LEN]; d.gapPos = st.cur[SWSEM_GAP]; d.flPos = st.cur[SWSEM_FLAGS];
+    d.bad = 0;
+    d.initialScore = p.mmsMismatchesInitialScore; d.penalty = p.mmsMismatchPenalty; d.bonus = p.mmsMatchBonus; d.threshold = p.mmsMismatchesScoreThreshold;
+    if (d.litPos > d.lit.n || d.offPos > d.nOff || d.off5Pos > d.nOff5 || d.lenPos > d.nLen || d.gapPos > d.nGap || d.flPos > d.nFlags) d.bad = 1;
+    DecByteWin sep; sep.p = d.lit.p; sep.n = d.lit.n;
+    if (!d.bad) {
+        bw_load<true>(d.lit, d.litPos); bw_load<false>(d.fl, d.flPos); bw_load_byte(sep, d.litPos, DEC_SEQ_SEPARATOR_MARK);
+        dw_load(d.len, d.lenPos); dw_load(d.off, d.offPos); dw_load(d.off5, d.off5Pos); dw_load(d.gap, d.gapPos);
+    }
+    uint64_t c = st.firstContig, recAt = st.recBase;
+    const uint64_t recEnd = st.recBase + st.recCap;
+    for (uint32_t t = st.firstTarget; t < st.firstTarget + st.nTargets && !d.bad; t++) {
+        const uint32_t nseq = seqCount[t];
+        const uint64_t lock = lockPos[t];
+        for (uint32_t s = 0; s < nseq && !d.bad; s++, c++) {
+            // the contig's literals end at its separator
+            uint64_t seqEnd = DEC_NPOS;
+            for (uint64_t from = d.litPos; from < sep.n;) {
+                if (from - sep.base >= (uint64_t) WAVE) bw_load_byte(sep, from, DEC_SEQ_SEPARATOR_MARK);
+                const unsigned long long m = sep.mask >> (from - sep.base);
+                if (m) { seqEnd = from + (uint64_t) __builtin_ctzll(m); break; }
+                from = sep.base + WAVE;
+            }
+            if (seqEnd == DEC_NPOS) { d.bad = 1; break; }                      // (the literals ran out)
+            ChainContig k;
+            k.cur[SWSEM_LIT] = d.litPos; k.cur[SWSEM_OFF] = d.offPos; k.cur[SWSEM_OFF5] = d.off5Pos;
+            k.cur[SWSEM_LEN] = d.lenPos; k.cur[SWSEM_GAP] = d.gapPos; k.cur[SWSEM_FLAGS] = d.flPos;
+            k.litEnd = seqEnd;
+            d.nLit = seqEnd;
+            d.destLen = 0; d.destCap = DEC_CHAIN_DEST_CAP;
+            uint64_t nrec = 0;
+            uint32_t unmatched = 0;
+            DecHull hull = {DEC_NPOS, 0};
+            plan_contig(p, d, seqEnd, lock, paired, recs + recAt, recEnd - recAt, refBytes, &nrec, &unmatched, hull);
+            if (d.bad) break;
+            k.destLen = d.destLen; k.unmatched = (int64_t) unmatched; k.minSrc = hull.minSrc; k.maxSrcEnd = hull.maxSrcEnd; k.nrec = nrec;
+            if (l0) {
+                DecPlanOut o;
+                o.nrec = nrec; o.destLen = d.destLen; o.unmatched = (int64_t) unmatched; o.pad = 0;
+                outs[c] = o; cc[c] = k; recBaseOut[c] = recAt;
+            }
+            recAt += nrec;
+            d.litPos = seqEnd + 1;                                             // (over the separator)
+        }
+        if (!d.bad && p.enableExtensionsWithMismatches) {                     // tIdGapMismatchesFlagsPtr[tId]++, :624-625: over the target's mark
+            if (d.flPos >= d.nFlags || d.fl.p[d.flPos] != DEC_FILE_SEPARATOR_MARK) d.bad = 1;   // (one byte per target, wave-uniform)
+            else d.flPos++;
+        }
+    }
+    if (!d.bad && st.checkEnd &&
+        (d.litPos != st.end[SWSEM_LIT] || d.offPos != st.end[SWSEM_OFF] || d.off5Pos != st.end[SWSEM_OFF5] || d.lenPos != st.end[SWSEM_LEN] ||
+         d.gapPos != st.end[SWSEM_GAP] || d.flPos != st.end[SWSEM_FLAGS])) d.bad = 1;
+    if (l0) chainBad[blockIdx.x] = d.bad ? 1u : 0u;
+}
+
+// The decoder's loadRef (MBGC_Decoder.cpp:651-675) as the host has scheduled it: a launch's segments do not overlap. One block
+// per segment (the host cuts long ones): a copy, upperReverseComplement written backwards (utils/helper.cpp:405-410), or one byte.
+struct LoadSeg { const uint8_t *src; uint8_t *dst; uint64_t len; uint32_t flags, value; };
+enum { LSEG_RC = 1, LSEG_BYTE = 4 };
+__global__ void __launch_bounds__(256) k_decode_load(const LoadSeg *__restrict__ segs, const uint8_t *__restrict__ lut) {
+    const LoadSeg s = segs[blockIdx.x];
+    if (s.flags & LSEG_BYTE) { if (threadIdx.x == 0) s.dst[0] = (uint8_t) s.value; return; }
+    if (s.flags & LSEG_RC)
+        for (uint64_t i = threadIdx.x; i < s.len; i += blockDim.x) s.dst[i] = lut[s.src[s.len - 1 - i]];
+    else
+        for (uint64_t i = threadIdx.x; i < s.len; i += blockDim.x) s.dst[i] = s.src[i];
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -62,6 +62,9 @@ void build_lut(uint8_t *lut) {
 
 }  // namespace
 
+// a decoder's handle (swsem_create_decoder) has a reference buffer and nothing of the matcher
+#define MATCHER_ONLY(h) do { if ((h)->decoder) return fail(SWSEM_EINVAL, "%s: the handle is a decoder's (swsem_create_decoder): it has no hash table", __func__); } while (0)
+
 extern "C" {
 
 const char *swsem_last_error(void) { return g_err.c_str(); }
@@ -169,7 +172,7 @@ void swsem_destroy(swsem_t *h) {
     delete h;                                                        // every buffer and event it owns goes with it
 }
 
-int swsem_set_stream(swsem_t *h, void *s) {
+int swsem_set_stream(swsem_t *h, void *s) { MATCHER_ONLY(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->ownStream) (void) hipStreamDestroy(h->stream);
     h->stream = (hipStream_t) s;
@@ -204,9 +207,9 @@ uint64_t swsem_acquire_lock(swsem_t *h) {
     return w;
 }
 
-int swsem_release_lock(swsem_t *h, uint64_t v) { return release_lock(h, v); }
+int swsem_release_lock(swsem_t *h, uint64_t v) { MATCHER_ONLY(h); return release_lock(h, v); }
 
-int swsem_load_ref_dev(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, int addSep, int sep) {
+int swsem_load_ref_dev(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, int addSep, int sep) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     int r = load_pieces(h, t, len, false, addSep != 0, sep);
     if (r) return r;
@@ -214,7 +217,7 @@ int swsem_load_ref_dev(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, i
     return r;
 }
 
-int swsem_load_ref(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, int addSep, int sep) {
+int swsem_load_ref(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, int addSep, int sep) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     if (len == 0) return SWSEM_OK;
     int r = h->stage.reserve(len + 64);
@@ -225,29 +228,29 @@ int swsem_load_ref(swsem_t *h, const uint8_t *t, uint64_t len, int loadRC, int a
     HIPCHK(hipStreamSynchronize(h->stream));   // the staging buffer is reused by the next call
     return SWSEM_OK;
 }
-int swsem_load_separator(swsem_t *h, int sep) {
+int swsem_load_separator(swsem_t *h, int sep) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     return load_separator(h, sep);
 }
 
 int swsem_finalize_targets(swsem_t *h, int n, const uint8_t *const *ext_dev, const uint64_t *ext_len, int addSep, int sep,
-                           int lazySeparator, const uint64_t *lockPos, uint64_t *loadedAfter) {
+                           int lazySeparator, const uint64_t *lockPos, uint64_t *loadedAfter) { MATCHER_ONLY(h);
     return finalize_impl(h, n, ext_dev, ext_len, addSep, sep, lazySeparator, lockPos, loadedAfter, nullptr);
 }
 
-int swsem_match_batch_dev(swsem_t *h, const uint8_t *q, const uint64_t *offsets, int n, uint32_t minLen, const uint64_t *lockPos) {
+int swsem_match_batch_dev(swsem_t *h, const uint8_t *q, const uint64_t *offsets, int n, uint32_t minLen, const uint64_t *lockPos) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     return run_batch(h, q, offsets, n, minLen, lockPos);
 }
 
-int swsem_batch_counts(swsem_t *h, uint64_t *nm) {
+int swsem_batch_counts(swsem_t *h, uint64_t *nm) { MATCHER_ONLY(h);
     if (!h->batchValid) return fail(SWSEM_EINVAL, "no batch results");
     if (h->matchCount.size() != h->contigs.size()) { int r = fetch_counts(h); if (r) return r; }
     for (size_t c = 0; c < h->contigs.size(); c++) nm[c] = h->matchCount[c];
     return SWSEM_OK;
 }
 
-int swsem_batch_matches(swsem_t *h, int c, swsem_match_t *out, uint64_t cap) {
+int swsem_batch_matches(swsem_t *h, int c, swsem_match_t *out, uint64_t cap) { MATCHER_ONLY(h);
     if (!h->batchValid || c < 0 || c >= (int) h->contigs.size()) return fail(SWSEM_EINVAL, "no such contig in the batch");
     if (h->matchCount.size() != h->contigs.size()) { int r = fetch_counts(h); if (r) return r; }
     const uint64_t n = std::min<uint64_t>(cap, h->matchCount[c]);
@@ -255,7 +258,7 @@ int swsem_batch_matches(swsem_t *h, int c, swsem_match_t *out, uint64_t cap) {
     return SWSEM_OK;
 }
 
-int swsem_batch_fingerprint(swsem_t *h, uint64_t *fp, uint64_t *tot, uint64_t *len) {
+int swsem_batch_fingerprint(swsem_t *h, uint64_t *fp, uint64_t *tot, uint64_t *len) { MATCHER_ONLY(h);
     if (!h->batchValid) return fail(SWSEM_EINVAL, "no batch results");
     k_fingerprint<<<1, 1, 0, h->stream>>>(h->dContigs.p, (int) h->contigs.size(), h->dMatches.p, h->dMatchCount.p, h->dStats.p + 4);
     unsigned long long o[3];
@@ -267,7 +270,7 @@ int swsem_batch_fingerprint(swsem_t *h, uint64_t *fp, uint64_t *tot, uint64_t *l
 }
 
 int swsem_match(swsem_t *h, const uint8_t *query, uint64_t len, uint32_t minLen, uint64_t lockPos,
-                const swsem_match_t **matches, uint64_t *nmatches) {
+                const swsem_match_t **matches, uint64_t *nmatches) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     *matches = nullptr; *nmatches = 0;
     int r = swsem_emit_batch_end(h);                   // an emission still running reads the staged query
@@ -336,7 +339,7 @@ int swsem_debug_copy_ref(swsem_t *h, uint64_t from, uint64_t n, uint8_t *out) {
     return SWSEM_OK;
 }
 
-int swsem_debug_write_ref(swsem_t *h, uint64_t from, uint64_t n, const uint8_t *in) {
+int swsem_debug_write_ref(swsem_t *h, uint64_t from, uint64_t n, const uint8_t *in) { MATCHER_ONLY(h);
     if (from + n > h->maxRefLength) return fail(SWSEM_EINVAL, "swsem_debug_write_ref: beyond the buffer");
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->stream2));
@@ -348,7 +351,7 @@ int swsem_debug_write_ref(swsem_t *h, uint64_t from, uint64_t n, const uint8_t *
     return SWSEM_OK;
 }
 
-int swsem_debug_copy_ht(swsem_t *h, uint32_t *out) {
+int swsem_debug_copy_ht(swsem_t *h, uint32_t *out) { MATCHER_ONLY(h);
     DevBuf<uint32_t> tmp;
     int r = tmp.reserve(h->hash_size);
     if (r) return r;
@@ -359,7 +362,7 @@ int swsem_debug_copy_ht(swsem_t *h, uint32_t *out) {
 }
 
 // diagnostics: per resolve block of the last batch {ticks, candidates visited, rows on the stack}
-int swsem_debug_block_times(swsem_t *h, uint64_t *out, uint64_t cap, uint64_t *n) {
+int swsem_debug_block_times(swsem_t *h, uint64_t *out, uint64_t cap, uint64_t *n) { MATCHER_ONLY(h);
     uint64_t nb = 0;
     for (auto &c : h->contigs) nb += c.nrb;
     *n = nb;
@@ -374,7 +377,7 @@ int swsem_debug_block_times(swsem_t *h, uint64_t *out, uint64_t cap, uint64_t *n
 // counters of the emission's pairing chain since the handle was made, summed over the emission slots:
 // out[4] steps that went by an inherited boundary other than the match's own, out[5] blocks of the speculative pass that were
 // not accepted, out[6] groups of 64 matches the stitch replayed, out[7] blocks given up for too many inherited boundaries
-int swsem_debug_emit_stats(swsem_t *h, uint64_t out[8]) {
+int swsem_debug_emit_stats(swsem_t *h, uint64_t out[8]) { MATCHER_ONLY(h);
     HIPCHK(hipDeviceSynchronize());
     for (int k = 0; k < 8; k++) out[k] = 0;
     for (auto &E : h->slot) {
@@ -411,7 +414,7 @@ int swsem_profile_get(swsem_t *h, double ms[SWSEM_K_COUNT], uint64_t n[SWSEM_K_C
     return SWSEM_OK;
 }
 
-int swsem_batch_stats(swsem_t *h, uint64_t s[6]) {
+int swsem_batch_stats(swsem_t *h, uint64_t s[6]) { MATCHER_ONLY(h);
     if (!h->batchValid) return fail(SWSEM_EINVAL, "no batch results");
     for (int i = 0; i < 6; i++) s[i] = h->stats[i];
     return SWSEM_OK;
@@ -447,32 +450,32 @@ void swsem_emit_params_default(swsem_emit_params_t *p, int mode) {
 
 int swsem_emit_batch_begin(swsem_t *h, const swsem_emit_params_t *p, int n, const int *contigIdx, const uint64_t *lockPos,
                            const int *factor, const int64_t *processed, const int64_t *targetIdx,
-                           const uint64_t *refExtLoadedPos, uint64_t nLoaded) {
+                           const uint64_t *refExtLoadedPos, uint64_t nLoaded) { MATCHER_ONLY(h);
     return emit_begin_impl(h, p, n, contigIdx, lockPos, factor, processed, targetIdx, refExtLoadedPos, nLoaded, nullptr, nullptr);
 }
 
 int swsem_emit_batch_begin_spec(swsem_t *h, const swsem_emit_params_t *p, int n, const int *contigIdx, const uint64_t *lockPos,
                                 const int *factor, const int64_t *processed, const int64_t *targetIdx,
-                                const uint64_t *refExtLoadedPos, uint64_t nLoaded, const swsem_spec_finalize_t *spec, int *applied) {
+                                const uint64_t *refExtLoadedPos, uint64_t nLoaded, const swsem_spec_finalize_t *spec, int *applied) { MATCHER_ONLY(h);
     return emit_begin_impl(h, p, n, contigIdx, lockPos, factor, processed, targetIdx, refExtLoadedPos, nLoaded, spec, applied);
 }
 
 // waits for every emission still in its second phase (oldest first); afterwards their streams can be fetched
-int swsem_emit_batch_end(swsem_t *h) {
+int swsem_emit_batch_end(swsem_t *h) { MATCHER_ONLY(h);
     int r = end_slot(h, h->latest ^ 1);
     return r ? r : end_slot(h, h->latest);
 }
 
 // result calls read the latest emission (previous = 0) or the one before it (previous = 1), which may have been
 // left running across the next swsem_emit_batch_begin
-int swsem_emit_select(swsem_t *h, int previous) {
+int swsem_emit_select(swsem_t *h, int previous) { MATCHER_ONLY(h);
     h->selected = previous ? (h->latest ^ 1) : -1;
     return SWSEM_OK;
 }
 
 int swsem_emit_batch(swsem_t *h, const swsem_emit_params_t *p, int n, const int *contigIdx, const uint64_t *lockPos,
                      const int *factor, const int64_t *processed, const int64_t *targetIdx,
-                     const uint64_t *refExtLoadedPos, uint64_t nLoaded) {
+                     const uint64_t *refExtLoadedPos, uint64_t nLoaded) { MATCHER_ONLY(h);
     int r = swsem_emit_batch_begin(h, p, n, contigIdx, lockPos, factor, processed, targetIdx, refExtLoadedPos, nLoaded);
     return r ? r : swsem_emit_batch_end(h);
 }
@@ -480,7 +483,7 @@ int swsem_emit_batch(swsem_t *h, const swsem_emit_params_t *p, int n, const int 
 void swsem_emit_set_host_copy(swsem_t *h, int on) { h->emitHostCopy = on != 0; }
 
 // unmatchedChars (the return value of processMatches, SWSEM_SKIPPED when skipped) of every result
-int swsem_emit_unmatched(swsem_t *h, uint64_t *unmatched) {
+int swsem_emit_unmatched(swsem_t *h, uint64_t *unmatched) { MATCHER_ONLY(h);
     EmitSlot &E = h->slot[h->latest];
     for (size_t k = 0; k < E.eout.size(); k++) unmatched[k] = E.eout[k].unmatchedChars;
     return SWSEM_OK;
@@ -488,7 +491,7 @@ int swsem_emit_unmatched(swsem_t *h, uint64_t *unmatched) {
 
 // The arena is written packed — every stream of the last emit batch back to back, (result, stream)
 // major — so handing it on is one device-to-device copy.
-int swsem_emit_pack_dev(swsem_t *h, uint8_t *dst_dev, uint64_t cap, uint64_t *sizes, uint64_t *total) {
+int swsem_emit_pack_dev(swsem_t *h, uint8_t *dst_dev, uint64_t cap, uint64_t *sizes, uint64_t *total) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     EmitSlot &E = h->sel();
     { int e = end_slot(h, (int) (&E - h->slot)); if (e) return e; }
@@ -506,7 +509,7 @@ int swsem_emit_pack_dev(swsem_t *h, uint8_t *dst_dev, uint64_t cap, uint64_t *si
     return SWSEM_OK;
 }
 
-int swsem_emit_pack_dev_on(swsem_t *h, uint8_t *dst_dev, uint64_t cap, void *stream) {
+int swsem_emit_pack_dev_on(swsem_t *h, uint8_t *dst_dev, uint64_t cap, void *stream) { MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     EmitSlot &E = h->sel();
     { int e = end_slot(h, (int) (&E - h->slot)); if (e) return e; }       // (the emission has finished: its event was waited for)
@@ -516,7 +519,7 @@ int swsem_emit_pack_dev_on(swsem_t *h, uint8_t *dst_dev, uint64_t cap, void *str
     return SWSEM_OK;
 }
 
-int swsem_emit_counters(swsem_t *h, uint64_t *out) {
+int swsem_emit_counters(swsem_t *h, uint64_t *out) { MATCHER_ONLY(h);
     EmitSlot &E = h->sel();
     { int e = end_slot(h, (int) (&E - h->slot)); if (e) return e; }
     for (size_t k = 0; k < E.eout.size(); k++) {
@@ -527,7 +530,7 @@ int swsem_emit_counters(swsem_t *h, uint64_t *out) {
     return SWSEM_OK;
 }
 
-int swsem_emit_result(swsem_t *h, int k, swsem_streams_t *out) {
+int swsem_emit_result(swsem_t *h, int k, swsem_streams_t *out) { MATCHER_ONLY(h);
     EmitSlot &E = h->sel();
     { int e = end_slot(h, (int) (&E - h->slot)); if (e) return e; }
     if (k < 0 || k >= (int) E.eout.size()) return fail(SWSEM_EINVAL, "swsem_emit_result: no result %d", k);
@@ -566,7 +569,63 @@ int swsem_decode_contigs_dev(swsem_t *h, const swsem_emit_params_t *p, int n, co
     return SWSEM_OK;
 }
 
+int swsem_create_decoder(swsem_t **out, uint64_t maxRefLength, int device) {
+    *out = nullptr;
+    if (maxRefLength < 64) return fail(SWSEM_EINVAL, "reference length limit %llu out of range", (unsigned long long) maxRefLength);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev)
+        return fail(SWSEM_ENODEV, "no HIP device %d (the HIP path has no CPU fallback)", device);
+    HIPCHK(hipSetDevice(device));
+    g_eventsFailed = false;
+    swsem *h = new swsem();
+    h->device = device;
+    h->decoder = true;
+    if (g_eventsFailed) { swsem_destroy(h); return fail(SWSEM_EHIP, "hipEventCreate failed"); }
+    h->maxRefLength = maxRefLength;
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { swsem_destroy(h); return fail(SWSEM_EHIP, "hipStreamCreate failed"); }
+    h->ownStream = true;
+    if (hipMalloc((void **) &h->ref, maxRefLength + REF_SLACK) != hipSuccess || hipMalloc((void **) &h->lut, 256) != hipSuccess) {
+        swsem_destroy(h);
+        return fail(SWSEM_ENOMEM, "cannot allocate %llu B reference in HBM", (unsigned long long) maxRefLength);
+    }
+    uint8_t lut[256];
+    build_lut(lut);
+    HIPCHK(hipMemcpy(h->lut, lut, 256, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(h->ref, 0, maxRefLength + REF_SLACK, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out = h;
+    return SWSEM_OK;
+}
+
+int swsem_decode_plan_chain_dev(swsem_t *h, const swsem_emit_params_t *p, const uint8_t *const stream_dev[SWSEM_NSTREAMS], const uint64_t size[SWSEM_NSTREAMS],
+                                int nstarts, const swsem_chain_start_t *starts, int ntargets, const uint32_t *seqCount, const uint64_t *lockPos,
+                                uint64_t ncontigs, swsem_chain_contig_t *out, int *firstBadChain) {
+    HIPCHK(hipSetDevice(h->device));
+    if (nstarts <= 0 || ntargets <= 0 || !firstBadChain) return fail(SWSEM_EINVAL, "swsem_decode_plan_chain_dev: no chain start");
+    ChainStreams S;
+    for (int st = 0; st < SWSEM_NSTREAMS; st++) { S.p[st] = stream_dev[st]; S.n[st] = size[st]; }
+    return decode_plan_chain(h, p, S, nstarts, starts, ntargets, seqCount, lockPos, ncontigs, out, firstBadChain);
+}
+
+int swsem_decode_fill_range_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *dest_dev, const uint64_t *destOff, uint64_t *nbad) {
+    HIPCHK(hipSetDevice(h->device));
+    int r = decode_fill_range(h, c0, c1, dest_dev, destOff);
+    if (r || !nbad) return r;
+    std::vector<uint32_t> bad(c1 - c0);
+    if (c1 > c0) HIPCHK(hipMemcpyAsync(bad.data(), h->chain.dBad.p + c0, (c1 - c0) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *nbad = 0;
+    for (uint32_t b : bad) *nbad += b != 0;
+    return SWSEM_OK;
+}
+
+int swsem_decode_load_dev(swsem_t *h, const uint8_t *src_dev, int n, const swsem_load_seg_t *segs) {
+    HIPCHK(hipSetDevice(h->device));
+    return decode_load(h, src_dev, n, segs);
+}
+
 int swsem_emit_verify(swsem_t *h, int *nbad, int *firstBad, uint64_t *firstDiff) {
+    MATCHER_ONLY(h);
     HIPCHK(hipSetDevice(h->device));
     EmitSlot &E = h->sel();
     { int e = end_slot(h, (int) (&E - h->slot)); if (e) return e; }
@@ -604,7 +663,7 @@ int swsem_emit_verify(swsem_t *h, int *nbad, int *firstBad, uint64_t *firstDiff)
 }
 
 int swsem_emit(swsem_t *h, const swsem_emit_params_t *p, int contig, uint64_t lockPos, int factor, int64_t processed,
-               int64_t targetIdx, const uint64_t *loaded, uint64_t nLoaded, swsem_streams_t *out) {
+               int64_t targetIdx, const uint64_t *loaded, uint64_t nLoaded, swsem_streams_t *out) { MATCHER_ONLY(h);
     int r = swsem_emit_batch(h, p, 1, &contig, &lockPos, &factor, &processed, &targetIdx, loaded, nLoaded);
     if (r) return r;
     return swsem_emit_result(h, 0, out);

@@ -49,4 +49,138 @@ int decode_jobs(swsem *h, const swsem_emit_params_t *p, int n, const std::vector
     return SWSEM_OK;
 }
 
+// The chained plan of a collection (k_decode_plan_chain): records, plan rows and record bases stay in HBM for the fills.
+int decode_plan_chain(swsem *h, const swsem_emit_params_t *p, const ChainStreams &S, int nstarts, const swsem_chain_start_t *starts, int ntargets,
+                      const uint32_t *seqCount, const uint64_t *lockPos, uint64_t ncontigs, swsem_chain_contig_t *out, int *firstBadChain) {
+    static_assert(sizeof(ChainContig) == sizeof(swsem_chain_contig_t), "swsem_chain_contig_t");
+    auto &C = h->chain;
+    C.n = 0; C.jobsDest = nullptr;
+    int r;
+    const uint64_t w = p->frugal64bitLenEncoding ? 2 : 4;
+    // records a chain can need: one per mapLen entry of its span (two bytes at least, four without the frugal encoding) and a
+    // tail per contig, + 1 (decode_jobs: the same per contig)
+    std::vector<ChainStart> cs(nstarts);
+    std::vector<uint64_t> lockOf(ncontigs);
+    uint64_t recTotal = 0, contigAt = 0;
+    uint32_t targetAt = 0;
+    for (int k = 0; k < nstarts; k++) {
+        const swsem_chain_start_t &a = starts[k];
+        if (a.firstTarget != targetAt || (uint64_t) a.firstTarget + a.nTargets > (uint64_t) ntargets)
+            return fail(SWSEM_EINVAL, "swsem_decode_plan_chain_dev: chain %d does not start where chain %d ended", k, k - 1);
+        ChainStart &c = cs[k];
+        uint64_t nc = 0;
+        for (uint32_t t = a.firstTarget; t < a.firstTarget + a.nTargets; t++) {
+            for (uint32_t s = 0; s < seqCount[t]; s++) { if (contigAt + nc >= ncontigs) return fail(SWSEM_EINVAL, "swsem_decode_plan_chain_dev: more sequences than contigs"); lockOf[contigAt + nc++] = lockPos[t]; }
+        }
+        for (int st = 0; st < SWSEM_NSTREAMS; st++) { c.cur[st] = a.cur[st]; c.end[st] = a.end[st]; }
+        // the span of mapLen bytes: up to the chain's end where it is known, else to the stream's
+        const uint64_t lenEnd = a.checkEnd && a.end[SWSEM_LEN] <= S.n[SWSEM_LEN] ? a.end[SWSEM_LEN] : S.n[SWSEM_LEN];
+        const uint64_t span = lenEnd > a.cur[SWSEM_LEN] ? lenEnd - a.cur[SWSEM_LEN] : 0;
+        c.firstTarget = a.firstTarget; c.nTargets = a.nTargets; c.checkEnd = a.checkEnd; c.pad = 0;
+        c.firstContig = contigAt; c.recBase = recTotal; c.recCap = span / w + 2 * nc + 2;
+        recTotal += c.recCap; contigAt += nc; targetAt += a.nTargets;
+    }
+    if (contigAt != ncontigs || targetAt != (uint32_t) ntargets) return fail(SWSEM_EINVAL, "swsem_decode_plan_chain_dev: the chains cover %llu contigs of %llu", (unsigned long long) contigAt, (unsigned long long) ncontigs);
+    if (ncontigs == 0) return SWSEM_OK;
+    if ((r = C.dStarts.reserve(nstarts)) || (r = C.dContigs.reserve(ncontigs)) || (r = C.dSeqCount.reserve(ntargets)) || (r = C.dLock.reserve(ntargets)) ||
+        (r = C.dRecBase.reserve(ncontigs)) || (r = C.dChainBad.reserve(nstarts)) || (r = C.dBad.reserve(ncontigs)) ||
+        (r = h->dDecPlan.reserve(ncontigs)) || (r = h->dDecRecs.reserve(recTotal))) return r;
+    HIPCHK(hipMemcpyAsync(C.dStarts.p, cs.data(), cs.size() * sizeof(ChainStart), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dSeqCount.p, seqCount, (size_t) ntargets * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dLock.p, lockPos, (size_t) ntargets * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->dDecPlan.p, 0xFF, ncontigs * sizeof(DecPlanOut), h->stream));          // (unmatched = -1 until planned)
+    HIPCHK(hipMemsetAsync(C.dContigs.p, 0xFF, ncontigs * sizeof(ChainContig), h->stream));
+    HIPCHK(hipMemsetAsync(C.dRecBase.p, 0, ncontigs * sizeof(uint64_t), h->stream));
+    HIPCHK(hipMemsetAsync(C.dBad.p, 0, ncontigs * sizeof(uint32_t), h->stream));
+    k_decode_plan_chain<<<dim3((unsigned) nstarts), dim3(WAVE), 0, h->stream>>>(*p, S, C.dStarts.p, C.dSeqCount.p, C.dLock.p, h->dDecRecs.p, h->dDecPlan.p,
+                                                                                  C.dContigs.p, C.dRecBase.p, C.dChainBad.p, h->maxRefLength + REF_SLACK);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> bad(nstarts);
+    HIPCHK(hipMemcpyAsync(out, C.dContigs.p, ncontigs * sizeof(ChainContig), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(bad.data(), C.dChainBad.p, (size_t) nstarts * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    C.streams = S; C.params = *p; C.n = ncontigs;
+    C.nrec.resize(ncontigs); C.destLen.resize(ncontigs); C.litEnd.resize(ncontigs); C.lock = lockOf;
+    for (uint64_t c = 0; c < ncontigs; c++) { C.nrec[c] = out[c].unmatched < 0 ? 0 : out[c].nrec; C.destLen[c] = out[c].destLen; C.litEnd[c] = out[c].litEnd; }
+    *firstBadChain = -1;
+    for (int k = nstarts - 1; k >= 0; k--) if (bad[k]) *firstBadChain = k;
+    return SWSEM_OK;
+}
+
+// contigs [c0, c1) of the planned collection into dest + destOff[c]: one k_decode_fill launch (slices of 65 535 contigs)
+int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const uint64_t *destOff) {
+    auto &C = h->chain;
+    if (c1 > C.n || c0 > c1) return fail(SWSEM_EINVAL, "swsem_decode_fill_range_dev: contigs [%llu, %llu) of %llu planned", (unsigned long long) c0, (unsigned long long) c1, (unsigned long long) C.n);
+    int r;
+    if (C.jobsDest != dest || !dest) {
+        std::vector<DecodeJob> jobs(C.n);
+        for (uint64_t c = 0; c < C.n; c++) {
+            DecodeJob &j = jobs[c];
+            for (int st = 0; st < SWSEM_NSTREAMS; st++) { j.stream[st] = C.streams.p[st]; j.size[st] = C.streams.n[st]; }
+            j.size[SWSEM_LIT] = C.litEnd[c];                                  // (the fill reads literals up to the contig's separator, flags as far as the plan said)
+            j.refLockPos = C.lock[c]; j.dest = dest + destOff[c]; j.destCap = destOff[c + 1] - destOff[c]; j.expect = nullptr;
+            if (j.destCap < C.destLen[c]) return fail(SWSEM_EINVAL, "swsem_decode_fill_range_dev: contig %llu does not fit its place", (unsigned long long) c);
+        }
+        if ((r = h->dJobs.reserve(C.n))) return r;
+        HIPCHK(hipMemcpyAsync(h->dJobs.p, jobs.data(), C.n * sizeof(DecodeJob), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));                               // (the table is pageable host memory)
+        C.jobsDest = dest;
+    }
+    constexpr uint64_t YMAX = 65535;
+    for (uint64_t a = c0; a < c1; a += YMAX) {
+        const uint64_t cn = std::min<uint64_t>(YMAX, c1 - a);
+        uint64_t maxRec = 0;
+        for (uint64_t c = a; c < a + cn; c++) maxRec = std::max(maxRec, C.nrec[c]);
+        if ((maxRec + 255) / 256 > 0x7FFFFFFFull) return fail(SWSEM_EINVAL, "swsem decode: a contig too long for one launch");
+        if (maxRec) k_decode_fill<<<dim3((unsigned) ((maxRec + 255) / 256), (unsigned) cn), dim3(256), 0, h->stream>>>(h->ref, C.params, h->dJobs.p, h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dBad.p, h->maxRefLength + REF_SLACK, (uint32_t) a);
+    }
+    HIPCHK(hipGetLastError());
+    return SWSEM_OK;
+}
+
+// segments of the decoder's load schedule, in order: what overlaps something queued before it in the call waits for a launch of
+// its own (a separator over a loaded byte, a reverse complement that reads what the target has just loaded)
+int decode_load(swsem *h, const uint8_t *src, int n, const swsem_load_seg_t *segs) {
+    constexpr uint64_t CHUNK = 1 << 15;
+    auto &C = h->chain;
+    std::vector<LoadSeg> batch;
+    std::vector<std::pair<uint64_t, uint64_t>> written;                         // [from, to) of the reference buffer, this launch
+    auto flush = [&]() -> int {
+        if (batch.empty()) return SWSEM_OK;
+        int r = C.dSegs.reserve(batch.size());
+        if (r) return r;
+        HIPCHK(hipMemcpyAsync(C.dSegs.p, batch.data(), batch.size() * sizeof(LoadSeg), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));                               // (pageable memory; the table is reused by the next launch)
+        k_decode_load<<<dim3((unsigned) batch.size()), dim3(256), 0, h->stream>>>(C.dSegs.p, h->lut);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        batch.clear(); written.clear();
+        return SWSEM_OK;
+    };
+    const uint64_t refBytes = h->maxRefLength;
+    for (int k = 0; k < n; k++) {
+        const swsem_load_seg_t &s = segs[k];
+        const bool byte = (s.flags & SWSEM_SEG_BYTE) != 0, fromRef = (s.flags & SWSEM_SEG_FROM_REF) != 0;
+        const uint64_t len = byte ? 1 : s.len;
+        if (len == 0) continue;
+        if (s.dst > refBytes || len > refBytes - s.dst || (fromRef && !byte && (s.src > refBytes || len > refBytes - s.src)))
+            return fail(SWSEM_EINVAL, "swsem_decode_load_dev: segment %d leaves the reference buffer", k);
+        bool clash = false;
+        for (auto &w : written)
+            if ((s.dst < w.second && w.first < s.dst + len) || (fromRef && !byte && s.src < w.second && w.first < s.src + len)) { clash = true; break; }
+        if (clash || batch.size() + len / CHUNK + 1 > 60000 || written.size() > 4096) { int r = flush(); if (r) return r; }
+        written.emplace_back(s.dst, s.dst + len);
+        if (byte) { LoadSeg g = {nullptr, h->ref + s.dst, 1, LSEG_BYTE, (uint32_t) (s.src & 0xFF)}; batch.push_back(g); continue; }
+        const uint8_t *from = (fromRef ? h->ref : src) + s.src;
+        const bool rc = (s.flags & SWSEM_SEG_RC) != 0;
+        for (uint64_t o = 0; o < len; o += CHUNK) {
+            const uint64_t m = std::min(CHUNK, len - o);
+            // (reverse complement: destination bytes [o, o + m) are the complement of source bytes [len - o - m, len - o), backwards)
+            LoadSeg g = {rc ? from + (len - o - m) : from + o, h->ref + s.dst + o, m, rc ? (uint32_t) LSEG_RC : 0u, 0u};
+            batch.push_back(g);
+        }
+    }
+    return flush();
+}
+
 }  // namespace

@@ -262,6 +262,20 @@ struct swsem {
     DevBuf<DecRec> dDecRecs;                 // the plan pass's records, contig after contig (swsem_decode.hip)
     DevBuf<DecPlanOut> dDecPlan;
     DevBuf<uint64_t> dDecAux;                // per contig: record base (n + 1), first differing byte (n), malformed flag (n, as u32 pairs)
+    // --- the decoder's side (swsem_create_decoder): a reference buffer, no table; the chained plan of a collection
+    bool decoder = false;
+    struct ChainState {
+        DevBuf<ChainStart> dStarts;
+        DevBuf<ChainContig> dContigs;
+        DevBuf<uint32_t> dSeqCount, dChainBad, dBad;
+        DevBuf<uint64_t> dLock, dRecBase;
+        DevBuf<LoadSeg> dSegs;
+        ChainStreams streams = {};
+        swsem_emit_params_t params = {};
+        uint64_t n = 0;                      // contigs planned
+        std::vector<uint64_t> nrec, destLen, litEnd, lock;
+        const uint8_t *jobsDest = nullptr;   // dJobs has been filled for this destination
+    } chain;
     // --- emission
     EmitSlot slot[2];
     int latest = 0;                          // slot of the last swsem_emit_batch_begin

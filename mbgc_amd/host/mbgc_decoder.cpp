@@ -1,0 +1,525 @@
+#include "mbgc_decoder.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <time.h>
+
+static const uint64_t REF_SHIFT = 1;                           // SlidingWindowSparseEMMatcher.h:14
+static const uint8_t SEQ_SEPARATOR_MARK = (uint8_t) ('"' + 128);   // MBGC_Params.h:46
+static const uint8_t REF_REGION_SEPARATOR = 0;                 // MGMP_Params.h:14
+
+// ---------------------------------------------------------------- <prefix>.meta
+// little endian: "MBGCHIPM", u32 version, u32 flags, u32 coderMode, k, k1, g0Contigs, u64 maxRefLength, swSize, finalRefLength,
+// reachedRefLengthCount, the 15 fields of swsem_emit_params_t as i64, u32 targets, u32 indexed, per target {u32 seqsCount,
+// u8 unmatchedFractionFactor, u8 unmatchedFractionRCFactor, u16 0}, then (indexed) (targets + 1) x 6 u64 stream offsets
+static const char META_MAGIC[9] = "MBGCHIPM";
+enum { MF_SEQUENTIAL = 1, MF_RC_IN_REF = 2, MF_CONTIGS_REVERSED = 4, MF_UPPERCASE = 8, MF_SINGLE_FASTA = 16, MF_RC_REDUNDANCY = 32 };
+
+template <typename T> static void put(std::string &s, T v) { s.append((const char *) &v, sizeof v); }
+template <typename T> static bool get(const std::string &s, size_t &at, T &v) {
+    if (at + sizeof v > s.size()) return false;
+    memcpy(&v, s.data() + at, sizeof v); at += sizeof v;
+    return true;
+}
+static void emitFields(const swsem_emit_params_t &e, int64_t f[15]) {
+    const int64_t v[15] = {e.enableExtensionsWithMismatches, e.mismatchesWithExclusion, e.lazyDecompressionSupport, e.enable40bitReference,
+                           e.frugal64bitLenEncoding, e.gapDepthOffsetEncoding, e.gapDepthMismatchesEncoding, (int64_t) e.gapBreakingMatchMinLength,
+                           e.mmsMatchBonus, e.mmsMismatchPenalty, e.mmsMismatchesScoreThreshold, e.mmsMismatchesInitialScore,
+                           e.allowedTargetsOutrunForDissimilarContigs, (int64_t) e.minimalLengthForDissimilarContigs,
+                           e.unmatchedFractionFactorTweakForDissimilarContigs};
+    memcpy(f, v, sizeof v);
+}
+
+std::string MbgcMeta::serialize() const {
+    std::string s(META_MAGIC, 8);
+    put<uint32_t>(s, VERSION);
+    put<uint32_t>(s, (sequentialMatching ? MF_SEQUENTIAL : 0) | (rcInReference ? MF_RC_IN_REF : 0) | (contigsIndividuallyReversed ? MF_CONTIGS_REVERSED : 0) |
+                         (uppercaseDNA ? MF_UPPERCASE : 0) | (singleFastaFile ? MF_SINGLE_FASTA : 0) | (rcRedundancyRemoval ? MF_RC_REDUNDANCY : 0));
+    put<uint32_t>(s, coderMode); put<uint32_t>(s, k); put<uint32_t>(s, k1); put<uint32_t>(s, g0Contigs);
+    put<uint64_t>(s, maxRefLength); put<uint64_t>(s, swSize); put<uint64_t>(s, finalRefLength); put<uint64_t>(s, reachedRefLengthCount);
+    int64_t f[15];
+    emitFields(emit, f);
+    for (int64_t v : f) put<int64_t>(s, v);
+    put<uint32_t>(s, (uint32_t) targets.size());
+    put<uint32_t>(s, index.empty() ? 0u : 1u);
+    for (const Target &t : targets) { put<uint32_t>(s, t.seqsCount); put<uint8_t>(s, t.unmatchedFractionFactor); put<uint8_t>(s, t.unmatchedFractionRCFactor); put<uint16_t>(s, 0); }
+    for (uint64_t v : index) put<uint64_t>(s, v);
+    return s;
+}
+
+bool MbgcMeta::parse(const std::string &b, std::string *error) {
+    auto bad = [&](const char *what) { if (error) *error = std::string("malformed .meta: ") + what; return false; };
+    if (b.size() < 8 || memcmp(b.data(), META_MAGIC, 8) != 0) return bad("not a meta file of mbgc-hip c");
+    size_t at = 8;
+    uint32_t version = 0, flags = 0, n = 0, indexed = 0;
+    if (!get(b, at, version) || version != VERSION) return bad("unknown version");
+    if (!get(b, at, flags) || !get(b, at, coderMode) || !get(b, at, k) || !get(b, at, k1) || !get(b, at, g0Contigs) || !get(b, at, maxRefLength) ||
+        !get(b, at, swSize) || !get(b, at, finalRefLength) || !get(b, at, reachedRefLengthCount)) return bad("truncated header");
+    sequentialMatching = flags & MF_SEQUENTIAL; rcInReference = flags & MF_RC_IN_REF; contigsIndividuallyReversed = flags & MF_CONTIGS_REVERSED;
+    uppercaseDNA = flags & MF_UPPERCASE; singleFastaFile = flags & MF_SINGLE_FASTA; rcRedundancyRemoval = flags & MF_RC_REDUNDANCY;
+    int64_t f[15];
+    for (int64_t &v : f) if (!get(b, at, v)) return bad("truncated emit parameters");
+    emit.enableExtensionsWithMismatches = (int) f[0]; emit.mismatchesWithExclusion = (int) f[1]; emit.lazyDecompressionSupport = (int) f[2];
+    emit.enable40bitReference = (int) f[3]; emit.frugal64bitLenEncoding = (int) f[4]; emit.gapDepthOffsetEncoding = (int) f[5];
+    emit.gapDepthMismatchesEncoding = (int) f[6]; emit.gapBreakingMatchMinLength = (uint64_t) f[7]; emit.mmsMatchBonus = (int) f[8];
+    emit.mmsMismatchPenalty = (int) f[9]; emit.mmsMismatchesScoreThreshold = (int) f[10]; emit.mmsMismatchesInitialScore = (int) f[11];
+    emit.allowedTargetsOutrunForDissimilarContigs = (int) f[12]; emit.minimalLengthForDissimilarContigs = (uint64_t) f[13];
+    emit.unmatchedFractionFactorTweakForDissimilarContigs = (int) f[14];
+    if (!get(b, at, n) || !get(b, at, indexed) || indexed > 1) return bad("truncated target table");
+    if ((b.size() - at) / 8 < n) return bad("truncated target table");
+    targets.assign(n, Target());
+    for (Target &t : targets) {
+        uint16_t pad = 0;
+        if (!get(b, at, t.seqsCount) || !get(b, at, t.unmatchedFractionFactor) || !get(b, at, t.unmatchedFractionRCFactor) || !get(b, at, pad)) return bad("truncated target table");
+    }
+    index.clear();
+    if (indexed) {
+        index.assign(((size_t) n + 1) * SWSEM_NSTREAMS, 0);
+        for (uint64_t &v : index) if (!get(b, at, v)) return bad("truncated stream index");
+    }
+    if (at != b.size()) return bad("bytes left over");
+    return true;
+}
+
+// ---------------------------------------------------------------- the load schedule
+bool MBGC_Decoder::loadRef(RefState &st, int64_t contig, uint64_t textOffset, uint64_t seqLength, uint64_t refLockPos, bool loadRCRef,
+                           std::vector<LoadSegment> &out) {
+    while (seqLength != 0) {                                                                    // :653-654
+        if (st.refPos == st.refTotalLength && refLockPos != st.refTotalLength) {                 // :655-658
+            st.reachedRefLengthCount++;
+            st.refPos = REF_SHIFT;
+        }
+        uint64_t tmpLength = seqLength;                                                        // :659
+        const uint64_t tmpMax = refLockPos < st.refPos ? st.refTotalLength : refLockPos;         // :660
+        if (st.refPos > tmpMax) return false;
+        if (st.refPos + tmpLength > tmpMax) tmpLength = tmpMax - st.refPos;                      // :661-663
+        if (tmpLength == 0 && st.refPos != refLockPos) return false;                            // (the recursion would not end)
+        if (tmpLength) {
+            // :664-668: upperReverseComplement(seqText + seqLength - tmpLength, tmpLength, ...) or the copy of the text's head
+            LoadSegment s = {contig, loadRCRef ? textOffset + seqLength - tmpLength : textOffset, tmpLength, st.refPos, loadRCRef};
+            if (contig == LoadSegment::SEPARATOR) s.offset = 0;
+            out.push_back(s);
+        }
+        st.refPos += tmpLength;                                                                 // :669
+        if (!loadRCRef) textOffset += tmpLength;                                                // :670
+        seqLength = st.refPos == refLockPos ? 0 : seqLength - tmpLength;                         // :671
+        if (st.lazyDecompressionSupport && st.refPos == refLockPos) {                           // :672-673
+            const LoadSegment sep = {LoadSegment::SEPARATOR, 0, 1, refLockPos - 1, false};
+            out.push_back(sep);
+        }
+    }
+    return true;
+}
+
+bool MBGC_Decoder::scheduleTarget(RefState &st, uint64_t firstContig, const std::vector<ContigInfo> &contigs, uint8_t unmatchedFractionFactor,
+                                  uint8_t unmatchedFractionRCFactor, bool rcInReference, bool contigsIndividuallyReversed, uint64_t refLockPos,
+                                  std::vector<LoadSegment> &out) {
+    const uint64_t startPos = st.refPos;                                                        // :564
+    for (size_t i = 0; i < contigs.size(); i++) {
+        const ContigInfo &c = contigs[i];
+        // MGMP_Params::isContigProperForRefExtension / ...RCExtension (MGMP_Params.h:179-190)
+        const bool loadContigToRef = c.unmatched * (uint64_t) unmatchedFractionFactor > c.length;   // :591
+        const uint64_t extSize = loadContigToRef ? c.length : 0;                                // :596-597 (the literal extension is empty outside developer builds)
+        if (!loadRef(st, (int64_t) (firstContig + i), 0, extSize, refLockPos, false, out)) return false;   // :598
+        if (rcInReference && contigsIndividuallyReversed && c.unmatched * (uint64_t) unmatchedFractionRCFactor > c.length)   // :599-601
+            if (!loadRef(st, (int64_t) (firstContig + i), 0, extSize, refLockPos, true, out)) return false;
+    }
+    if (rcInReference && !contigsIndividuallyReversed) {                                       // :608-616
+        if (st.refPos >= startPos) {
+            if (!loadRef(st, LoadSegment::FROM_REF, startPos, st.refPos - startPos, refLockPos, true, out)) return false;
+        } else {
+            const uint64_t tmpStartPos = startPos;
+            if (!loadRef(st, LoadSegment::FROM_REF, 1, st.refPos - 1, refLockPos, true, out)) return false;
+            if (!loadRef(st, LoadSegment::FROM_REF, tmpStartPos, st.refTotalLength - tmpStartPos, refLockPos, true, out)) return false;
+        }
+    }
+    if (st.lazyDecompressionSupport)                                                            // :617-620
+        if (!loadRef(st, LoadSegment::SEPARATOR, 0, 1, refLockPos, false, out)) return false;
+    return true;
+}
+
+bool MBGC_Decoder::scheduleG0(RefState &st, uint64_t g0Bytes, bool rcInReference, bool sequentialMatching, std::vector<LoadSegment> &out) {
+    // SlidingWindowSparseEMMatcher::loadRef with swEnd as initMatcher leaves it: disableSlidingWindow() puts it at 0 before the load
+    // (-t1), otherwise it is the buffer's end; no separator of lazy mode belongs to this load
+    RefState g = st;
+    g.lazyDecompressionSupport = false;
+    const uint64_t swEnd = sequentialMatching ? 0 : st.refTotalLength;
+    if (!loadRef(g, 0, 0, g0Bytes, swEnd, false, out)) return false;
+    if (rcInReference && !loadRef(g, 0, 0, g0Bytes, swEnd, true, out)) return false;
+    st.refPos = g.refPos; st.reachedRefLengthCount = g.reachedRefLengthCount;
+    return true;
+}
+
+// ---------------------------------------------------------------- the driver
+static bool readFile(const std::string &path, std::string &dest) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) return false;
+    const std::streamoff n = f.tellg();
+    f.seekg(0);
+    dest.resize((size_t) n);
+    if (n) f.read(&dest[0], n);
+    return (bool) f;
+}
+static bool writeFile(const std::string &path, const void *p, size_t n) {
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    f.write((const char *) p, (std::streamsize) n);
+    return (bool) f;
+}
+static double nowMs() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+// PgHelpers::readUInt64Frugal, utils/helper.h:256-272
+static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
+    uint16_t y16; uint32_t y32;
+    if (!get(s, at, y16)) return false;
+    if (y16 < UINT16_MAX) { v = y16; return true; }
+    if (!get(s, at, y32)) return false;
+    if (y32 < UINT32_MAX) { v = y32; return true; }
+    return get(s, at, v);
+}
+
+namespace {
+struct DevFree {
+    swsem_t *h; std::vector<void *> ptrs;
+    ~DevFree() { for (void *p : ptrs) if (p) swsem_dev_free(h, p); if (h) swsem_destroy(h); }
+};
+struct Interval { uint64_t from, to; };
+struct PassTimes { double plan = 0, fill = 0, load = 0; uint64_t waves = 0, widest = 0; };
+}
+
+int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix, const Options &opt, std::string *error) {
+    auto fail = [&](const std::string &m) { if (error) *error = m; return 1; };
+    std::string metaBytes;
+    if (!readFile(prefix + ".meta", metaBytes)) return fail("cannot open " + prefix + ".meta (written by mbgc-hip c beside the streams)");
+    MbgcMeta meta;
+    { std::string e; if (!meta.parse(metaBytes, &e)) return fail(e); }
+    if (meta.rcRedundancyRemoval)
+        return fail("the streams were written with -m 3: its reverse-complement pass over the literal stream (rcMapOff / rcMapLen) is not inverted by mbgc-hip d");
+    static const char *NAMES[SWSEM_NSTREAMS] = {"literals", "mapOff", "mapOff5th", "mapLen", "gapDelta", "flags"};
+    std::string stream[SWSEM_NSTREAMS], locksPos, refExtSize;
+    for (int s = 0; s < SWSEM_NSTREAMS; s++)
+        if (!readFile(prefix + "." + NAMES[s], stream[s])) return fail("cannot open " + prefix + "." + NAMES[s]);
+    if (!readFile(prefix + ".locksPos", locksPos) || !readFile(prefix + ".refExtSize", refExtSize)) return fail("cannot open " + prefix + ".locksPos / .refExtSize");
+    const size_t T = meta.targets.size();
+    if (T == 0) return fail("malformed stream set: no target");
+    if (locksPos.size() != T * sizeof(uint64_t)) return fail("malformed stream set: locksPos does not hold one position per target");
+    if (meta.maxRefLength < 64) return fail("malformed .meta: reference length");
+    std::vector<uint64_t> lock(T);
+    memcpy(lock.data(), locksPos.data(), locksPos.size());
+    const bool lazy = meta.emit.lazyDecompressionSupport != 0;
+    std::vector<uint64_t> extSize(T, 0);
+    if (lazy) {
+        size_t at = 0;
+        for (size_t t = 0; t < T; t++) if (!readUInt64Frugal(refExtSize, at, extSize[t])) return fail("malformed stream set: refExtSize ends early");
+        if (at != refExtSize.size()) return fail("malformed stream set: bytes left over in refExtSize");
+    }
+    // G0: the contigs at the head of the literal stream (MBGC_Decoder::decodeReference :265-317 / initReference :243-263)
+    std::vector<uint64_t> contigLen;
+    uint64_t lit0 = 0;
+    for (uint32_t g = 0; g < meta.g0Contigs; g++) {
+        const void *sep = lit0 < stream[SWSEM_LIT].size() ? memchr(stream[SWSEM_LIT].data() + lit0, SEQ_SEPARATOR_MARK, stream[SWSEM_LIT].size() - lit0) : nullptr;
+        if (!sep) return fail("malformed stream set: the literals end inside the initial reference");
+        const uint64_t end = (uint64_t) ((const char *) sep - stream[SWSEM_LIT].data());
+        contigLen.push_back(end - lit0);
+        lit0 = end + 1;
+    }
+    const uint64_t g0n = meta.g0Contigs, g0Bytes = lit0 - g0n;
+    uint64_t planned = 0;
+    std::vector<uint32_t> seqCount(T);
+    for (size_t t = 0; t < T; t++) { seqCount[t] = meta.targets[t].seqsCount; planned += seqCount[t]; }
+    if (planned > stream[SWSEM_LIT].size()) return fail("malformed .meta: more sequences than literal bytes");
+    uint64_t sizes[SWSEM_NSTREAMS];
+    for (int s = 0; s < SWSEM_NSTREAMS; s++) sizes[s] = stream[s].size();
+    // chain starts
+    const bool useIndex = !opt.noIndex && !meta.index.empty();
+    std::vector<swsem_chain_start_t> starts;
+    if (useIndex) {
+        const uint64_t *ix = meta.index.data();
+        if (ix[SWSEM_LIT] != lit0) return fail("malformed .meta: the stream index does not start behind the initial reference");
+        for (size_t t = 0; t <= T; t++)
+            for (int s = 0; s < SWSEM_NSTREAMS; s++)
+                if (ix[t * SWSEM_NSTREAMS + s] > sizes[s] || (t && ix[t * SWSEM_NSTREAMS + s] < ix[(t - 1) * SWSEM_NSTREAMS + s]) || (t == T && ix[t * SWSEM_NSTREAMS + s] != sizes[s]))
+                    return fail(std::string("malformed stream set: the index of ") + NAMES[s] + " does not fit the stream (target " + std::to_string(t) + ")");
+        for (size_t t = 0; t < T; t++) {
+            swsem_chain_start_t c = {};
+            for (int s = 0; s < SWSEM_NSTREAMS; s++) { c.cur[s] = ix[t * SWSEM_NSTREAMS + s]; c.end[s] = ix[(t + 1) * SWSEM_NSTREAMS + s]; }
+            c.firstTarget = (uint32_t) t; c.nTargets = 1; c.checkEnd = 1;
+            starts.push_back(c);
+        }
+    } else {
+        swsem_chain_start_t c = {};
+        c.cur[SWSEM_LIT] = lit0;
+        for (int s = 0; s < SWSEM_NSTREAMS; s++) c.end[s] = sizes[s];
+        c.firstTarget = 0; c.nTargets = (uint32_t) T; c.checkEnd = 1;
+        starts.push_back(c);
+    }
+
+    PassTimes times;
+    uint64_t totalBases = 0, outBases = 0;
+    const int passes = opt.bench ? 2 : 1;                                                        // (bench: the second pass is the timed one)
+    for (int pass = 0; pass < passes; pass++) {
+        times = PassTimes();
+        DevFree dev = {nullptr, {}};
+        auto hipFail = [&](const char *what) { return fail(std::string(what) + ": " + swsem_last_error()); };
+        if (swsem_create_decoder(&dev.h, meta.maxRefLength, opt.device)) return hipFail("decoder");
+        swsem_t *h = dev.h;
+        const uint8_t *sdev[SWSEM_NSTREAMS];
+        for (int s = 0; s < SWSEM_NSTREAMS; s++) {
+            void *p = nullptr;
+            if (swsem_dev_malloc(h, sizes[s] + 64, &p)) return hipFail("streams");
+            dev.ptrs.push_back(p);
+            if (swsem_dev_upload(h, p, stream[s].data(), sizes[s])) return hipFail("streams");
+            sdev[s] = (const uint8_t *) p;
+        }
+        // ---- the plan: once, ahead, for the whole collection
+        std::vector<swsem_chain_contig_t> cc(planned);
+        int firstBad = -1;
+        double t0 = nowMs();
+        if (planned && swsem_decode_plan_chain_dev(h, &meta.emit, sdev, sizes, (int) starts.size(), starts.data(), (int) T, seqCount.data(), lock.data(), planned, cc.data(), &firstBad))
+            return hipFail("plan");
+        times.plan = nowMs() - t0;
+        if (firstBad >= 0)
+            return fail("malformed stream set: " + (useIndex ? "target " + std::to_string(firstBad) + " does not decode from its offsets to the next target's"
+                                                             : std::string("the collection's chain does not end with its streams")) + " (a stream ran out, or bytes were left over)");
+        for (uint64_t c = 0; c < planned; c++) if (cc[c].unmatched < 0) return fail("malformed stream set: contig " + std::to_string(c) + " was not reached");
+        contigLen.resize(g0n);
+        for (uint64_t c = 0; c < planned; c++) contigLen.push_back(cc[c].destLen);
+        const uint64_t N = g0n + planned;
+        std::vector<uint64_t> seqOff(N + 1, 0);
+        for (uint64_t c = 0; c < N; c++) seqOff[c + 1] = seqOff[c] + contigLen[c];
+        totalBases = seqOff[N];
+        void *seqp = nullptr;
+        if (swsem_dev_malloc(h, totalBases + 64, &seqp)) return hipFail("sequences");
+        dev.ptrs.push_back(seqp);
+        uint8_t *seqDev = (uint8_t *) seqp;
+        {   // G0's bytes are literals
+            uint64_t at = 0;
+            for (uint64_t g = 0; g < g0n; g++) {
+                if (swsem_dev_copy(h, seqDev + seqOff[g], sdev[SWSEM_LIT] + at, contigLen[g])) return hipFail("initial reference");
+                at += contigLen[g] + 1;
+            }
+        }
+        // ---- the load schedule: complete before a base exists
+        RefState st;
+        st.refTotalLength = meta.maxRefLength; st.lazyDecompressionSupport = lazy;
+        std::vector<LoadSegment> g0Segs;
+        if (!scheduleG0(st, g0Bytes, meta.rcInReference, meta.sequentialMatching, g0Segs)) return fail("malformed stream set: the initial reference does not fit the buffer");
+        std::vector<std::vector<LoadSegment>> tSegs(T);
+        {
+            uint64_t c = 0;
+            for (size_t t = 0; t < T; t++) {
+                std::vector<ContigInfo> info(seqCount[t]);
+                for (uint32_t s = 0; s < seqCount[t]; s++) info[s] = {cc[c + s].destLen, (uint64_t) cc[c + s].unmatched};
+                const uint64_t before = st.loaded();
+                if (!scheduleTarget(st, g0n + c, info, meta.targets[t].unmatchedFractionFactor, meta.targets[t].unmatchedFractionRCFactor, meta.rcInReference,
+                                    meta.contigsIndividuallyReversed, lock[t], tSegs[t]))
+                    return fail("malformed stream set: the loads of target " + std::to_string(t) + " do not fit its lock position");
+                if (lazy && st.loaded() - before != extSize[t])
+                    return fail("malformed stream set: target " + std::to_string(t) + " extends the reference by " + std::to_string(st.loaded() - before) +
+                                " bytes, refExtSize says " + std::to_string(extSize[t]));
+                c += seqCount[t];
+            }
+        }
+        auto toAbi = [&](const std::vector<LoadSegment> &in, size_t a, size_t b, std::vector<swsem_load_seg_t> &out) {
+            for (size_t i = a; i < b; i++) {
+                const LoadSegment &s = in[i];
+                swsem_load_seg_t g = {};
+                g.dst = s.refPos; g.len = s.length;
+                if (s.contig == LoadSegment::SEPARATOR) { g.flags = SWSEM_SEG_BYTE; g.src = REF_REGION_SEPARATOR; }
+                else if (s.contig == LoadSegment::FROM_REF) { g.flags = SWSEM_SEG_FROM_REF | (s.reverseComplement ? SWSEM_SEG_RC : 0); g.src = s.offset; }
+                else { g.flags = s.reverseComplement ? SWSEM_SEG_RC : 0; g.src = seqOff[s.contig] + s.offset; }
+                out.push_back(g);
+            }
+        };
+        auto load = [&](std::vector<swsem_load_seg_t> &segs) -> bool {
+            if (segs.empty()) return true;
+            const double a = nowMs();
+            const int r = swsem_decode_load_dev(h, seqDev, (int) segs.size(), segs.data());
+            times.load += nowMs() - a;
+            segs.clear();
+            return r == 0;
+        };
+        auto fill = [&](uint64_t c0, uint64_t c1) -> int {                                      // planned contigs [c0, c1); 0 ok, 1 HIP, 2 bytes not as planned
+            if (c1 == c0) return 0;
+            const double a = nowMs();
+            uint64_t nbad = 0;
+            const int r = swsem_decode_fill_range_dev(h, c0, c1, seqDev, seqOff.data() + g0n, &nbad);
+            times.fill += nowMs() - a;
+            return r ? 1 : (nbad ? 2 : 0);
+        };
+        std::vector<swsem_load_seg_t> abi;
+        toAbi(g0Segs, 0, g0Segs.size(), abi);
+        if (!load(abi)) return hipFail("initial reference");
+        // ---- waves: targets whose contigs stand against the same frozen buffer are filled by one launch
+        std::vector<Interval> written;                                                          // what the current wave's loads will write
+        auto addWrites = [&](std::vector<Interval> &w, const std::vector<LoadSegment> &segs, size_t a, size_t b) {
+            for (size_t i = a; i < b; i++) {
+                if (!w.empty() && w.back().to == segs[i].refPos) w.back().to += segs[i].length;
+                else w.push_back({segs[i].refPos, segs[i].refPos + segs[i].length});
+            }
+        };
+        auto reads = [&](const std::vector<Interval> &w, uint64_t c) {
+            if (cc[c].minSrc >= cc[c].maxSrcEnd) return false;
+            for (const Interval &i : w) if (cc[c].minSrc < i.to && i.from < cc[c].maxSrcEnd) return true;
+            return false;
+        };
+        uint64_t waveC0 = 0, waveC1 = 0, waveLock = 0, waveTargets = 0;
+        std::vector<swsem_load_seg_t> waveSegs;
+        auto closeWave = [&]() -> int {
+            if (!waveTargets) return 0;
+            const int r = fill(waveC0, waveC1);
+            if (r) return r;
+            if (!load(waveSegs)) return 1;
+            times.waves++; times.widest = std::max(times.widest, waveTargets);
+            waveTargets = 0; written.clear();
+            return 0;
+        };
+        uint64_t c = 0;
+        for (size_t t = 0; t < T; t++) {
+            const uint64_t c1 = c + seqCount[t];
+            const std::vector<LoadSegment> &segs = tSegs[t];
+            // segments [segAt[i], segAt[i + 1]) belong to contig i of the target; what follows its last contig goes with that one
+            // — a separator written at the lock position goes with the contig whose load reached it
+            std::vector<size_t> segAt(seqCount[t] + 1, segs.size());
+            {
+                size_t lastOwn = 0;                                                             // behind the last segment that is a contig's
+                for (size_t i = 0; i < segs.size(); i++) if (segs[i].contig >= 0) lastOwn = i + 1;
+                size_t i = 0;
+                for (uint32_t s = 0; s < seqCount[t]; s++) {
+                    segAt[s] = i;
+                    if (s + 1 == seqCount[t]) break;
+                    while (i < lastOwn && (segs[i].contig < 0 || segs[i].contig <= (int64_t) (g0n + c + s))) i++;
+                }
+            }
+            // Every target of an encoder round holds one lock position and was matched against the buffer the round found: it may be
+            // filled beside the targets in front of it as long as nothing it reads is written by their loads. -t1 streams carry the
+            // window's end 0 (no window): contig c + 1 may match contig c, the target goes alone, contig by contig.
+            bool side = !opt.serial && !meta.sequentialMatching && lock[t] != 0;
+            std::vector<Interval> own;
+            for (uint32_t s = 0; side && s < seqCount[t]; s++) {
+                if (reads(own, c + s)) side = false;
+                addWrites(own, segs, segAt[s], segAt[s + 1]);
+            }
+            bool join = side && waveTargets && lock[t] == waveLock;
+            for (uint64_t k = c; join && k < c1; k++) if (reads(written, k)) join = false;
+            if (!join) {
+                const int r = closeWave();
+                if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
+            }
+            if (side) {
+                if (!waveTargets) { waveC0 = c; waveLock = lock[t]; }
+                waveC1 = c1; waveTargets++;
+                addWrites(written, segs, 0, segs.size());
+                toAbi(segs, 0, segs.size(), waveSegs);
+            } else {
+                for (uint32_t s = 0; s < seqCount[t]; s++) {
+                    const int r = fill(c + s, c + s + 1);
+                    if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
+                    toAbi(segs, segAt[s], segAt[s + 1], abi);
+                    if (!load(abi)) return hipFail("load");
+                }
+                if (seqCount[t] == 0) { toAbi(segs, 0, segs.size(), abi); if (!load(abi)) return hipFail("load"); }
+                times.waves++; times.widest = std::max<uint64_t>(times.widest, 1);
+            }
+            c = c1;
+        }
+        {
+            const int r = closeWave();
+            if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
+        }
+        if (swsem_synchronize(h)) return hipFail("decode");
+        if (st.reachedRefLengthCount != meta.reachedRefLengthCount || (meta.finalRefLength && (st.reachedRefLengthCount ? st.refTotalLength : st.refPos) != meta.finalRefLength))
+            return fail("malformed stream set: the rebuilt reference ends at " + std::to_string(st.refPos) + " after " + std::to_string(st.reachedRefLengthCount) +
+                        " laps, the encoder's at " + std::to_string(meta.finalRefLength) + " after " + std::to_string(meta.reachedRefLengthCount));
+        const uint64_t outFrom = meta.sequentialMatching ? g0n : 0;                               // (-t1: the initial reference is the first contig of target 0 again)
+        outBases = totalBases - seqOff[outFrom];
+        if (pass + 1 == passes && !opt.bench) {
+            std::string seq(outBases, '\0');
+            if (outBases && swsem_dev_download(h, &seq[0], seqDev + seqOff[outFrom], outBases)) return hipFail("download");
+            std::vector<uint32_t> counts;
+            if (!meta.sequentialMatching) counts.push_back(meta.g0Contigs);
+            for (size_t t = 0; t < T; t++) counts.push_back(seqCount[t]);
+            if (!writeFile(outPrefix + ".seq", seq.data(), seq.size()) ||
+                !writeFile(outPrefix + ".contigLens", contigLen.data() + outFrom, (contigLen.size() - outFrom) * sizeof(uint64_t)) ||
+                !writeFile(outPrefix + ".seqCounts", counts.data(), counts.size() * sizeof(uint32_t)))
+                return fail("cannot write " + outPrefix + ".seq / .contigLens / .seqCounts");
+        }
+    }
+    if (opt.bench) {
+        const double ms = times.plan + times.fill + times.load;
+        printf("{\"metric\": \"output Gbases/s (decompress: streams in HBM to sequences in HBM)\", \"value\": %.4f, \"unit\": \"Gbases/s\", \"bases\": %llu, "
+               "\"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, \"chain_starts\": %zu, \"plan_ms_per_target\": %.4f, \"waves\": %llu, "
+               "\"serial\": %s, \"index\": %s}\n",
+               outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, starts.size(), times.plan / (double) T,
+               (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false");
+    }
+    printf("waves: %llu for %zu targets\n", (unsigned long long) times.waves, T);
+    printf("widest wave: %llu targets\n", (unsigned long long) times.widest);
+    printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) (contigLen.size() - (meta.sequentialMatching ? g0n : 0)), (unsigned long long) outBases);
+    return 0;
+}
+
+int mbgc_hip_decompress_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    std::vector<std::string> pos;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--serial") opt.serial = true;
+        else if (a == "--no-index") opt.noIndex = true;
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
+        else pos.push_back(a);
+    }
+    if (pos.size() != 2) {
+        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [-d device] <streamsPrefix> <outputPrefix>\n"
+                        "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
+                        "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
+                        "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n");
+        return EXIT_FAILURE;
+    }
+    std::string error;
+    if (MBGC_Decoder::decode(pos[0], pos[1], opt, &error) != 0) {
+        fprintf(stderr, "mbgc-hip d: %s\n", error.c_str());
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
+// ---------------------------------------------------------------- C exports for tests (host only, no device)
+extern "C" {
+
+// scheduleG0 (g0Bytes > 0 or ncontigs == 0) then scheduleTarget for one target; segs: rows of {contig, offset, length, refPos, rc}
+int mbgc_decoder_schedule(uint64_t *refPos, uint64_t *reachedRefLengthCount, uint64_t refTotalLength, int lazy, int rcInReference,
+                          int contigsIndividuallyReversed, uint64_t refLockPos, uint64_t firstContig, int ncontigs, const uint64_t *length,
+                          const uint64_t *unmatched, int factor, int rcFactor, int64_t *segs, uint64_t cap, uint64_t *nsegs) {
+    MBGC_Decoder::RefState st;
+    st.refPos = *refPos; st.reachedRefLengthCount = *reachedRefLengthCount; st.refTotalLength = refTotalLength; st.lazyDecompressionSupport = lazy != 0;
+    std::vector<MBGC_Decoder::ContigInfo> info;
+    for (int i = 0; i < ncontigs; i++) info.push_back({length[i], unmatched[i]});
+    std::vector<LoadSegment> out;
+    if (!MBGC_Decoder::scheduleTarget(st, firstContig, info, (uint8_t) factor, (uint8_t) rcFactor, rcInReference != 0, contigsIndividuallyReversed != 0, refLockPos, out)) return -1;
+    *nsegs = out.size();
+    if (out.size() > cap) return -2;
+    for (size_t i = 0; i < out.size(); i++) {
+        const int64_t row[5] = {out[i].contig, (int64_t) out[i].offset, (int64_t) out[i].length, (int64_t) out[i].refPos, out[i].reverseComplement ? 1 : 0};
+        memcpy(segs + 5 * i, row, sizeof row);
+    }
+    *refPos = st.refPos; *reachedRefLengthCount = st.reachedRefLengthCount;
+    return 0;
+}
+
+// parse + serialize: 0 and the bytes again, or -1 (malformed; the message in err)
+int mbgc_meta_roundtrip(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *nout, char *err, uint64_t errCap) {
+    MbgcMeta m;
+    std::string e;
+    if (!m.parse(std::string((const char *) in, n), &e)) { if (err && errCap) snprintf(err, errCap, "%s", e.c_str()); return -1; }
+    const std::string s = m.serialize();
+    *nout = s.size();
+    if (s.size() > cap) return -2;
+    memcpy(out, s.data(), s.size());
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,70 @@
+// `mbgc-hip d`: a collection back from the raw streams `mbgc-hip c` wrote, on the device.
+//   MbgcMeta       <prefix>.meta: what a decoder needs beyond the streams (the reference CLI keeps the same facts in its
+//                  archive header and header-side streams: MBGC_Decoder::readParams / readStats, MBGC_Decoder.cpp:1291-1323)
+//   MBGC_Decoder   mbgccoder/MBGC_Decoder.{h,cpp}: decodeTarget (:535-634) and loadRef (:651-675) restated as a load
+//                  SCHEDULE — computed from the plan's lengths and unmatched counts before a base exists — and the driver
+//                  that runs plan, fills and loads through the C ABI (include/mbgc_swsem.h). No HIP headers here.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/mbgc_swsem.h"
+
+struct MbgcMeta {
+    static constexpr uint32_t VERSION = 1;
+    bool sequentialMatching = false, rcInReference = true, contigsIndividuallyReversed = true, uppercaseDNA = false;
+    bool singleFastaFile = false, rcRedundancyRemoval = false;
+    uint32_t coderMode = 1, k = 32, k1 = 16;
+    uint32_t g0Contigs = 0;                              // contigs at the head of the literal stream that form the initial reference
+    uint64_t maxRefLength = 0, swSize = 0, finalRefLength = 0, reachedRefLengthCount = 0;
+    swsem_emit_params_t emit = {};
+    struct Target { uint32_t seqsCount = 0; uint8_t unmatchedFractionFactor = 0, unmatchedFractionRCFactor = 0; };
+    std::vector<Target> targets;                         // the targets after G0 (-t1: every file)
+    // stream index: (targets + 1) x SWSEM_NSTREAMS byte offsets — row t: where target t starts in literals, mapOff, mapOff5th,
+    // mapLen, gapDelta, flags; the last row: the streams' sizes. Empty: no index.
+    std::vector<uint64_t> index;
+
+    std::string serialize() const;
+    bool parse(const std::string &bytes, std::string *error);
+};
+
+// One step of the load schedule. A copy of `length` decoded bytes that start `offset` bytes into contig `contig` (G0's loads run on
+// over its contigs, which lie back to back) to reference position refPos; reverseComplement: upperReverseComplement of those
+// bytes. contig == SEPARATOR: the single region separator byte; contig == FROM_REF: the source is reference position `offset`
+// (the per-target reverse complement of :608-616).
+struct LoadSegment {
+    static constexpr int64_t SEPARATOR = -1, FROM_REF = -2;
+    int64_t contig;
+    uint64_t offset, length, refPos;
+    bool reverseComplement;
+};
+
+class MBGC_Decoder {
+public:
+    struct RefState {                                    // MBGC_Decoder.h: refPos, refTotalLength, reachedRefLengthCount
+        uint64_t refPos = 1;                             // REF_SHIFT
+        uint64_t refTotalLength = 0;
+        uint64_t reachedRefLengthCount = 0;
+        bool lazyDecompressionSupport = true;
+        uint64_t loaded() const { return reachedRefLengthCount * (refTotalLength - 1) + (refPos - 1); }
+    };
+    struct ContigInfo { uint64_t length, unmatched; };
+    struct Options { bool serial = false, noIndex = false, bench = false; int device = 0; };
+
+    // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
+    static bool loadRef(RefState &st, int64_t contig, uint64_t textOffset, uint64_t seqLength, uint64_t refLockPos, bool loadRCRef,
+                        std::vector<LoadSegment> &out);
+    // the loads of decodeTarget, :564-620, for a target whose first contig has number firstContig
+    static bool scheduleTarget(RefState &st, uint64_t firstContig, const std::vector<ContigInfo> &contigs, uint8_t unmatchedFractionFactor,
+                               uint8_t unmatchedFractionRCFactor, bool rcInReference, bool contigsIndividuallyReversed, uint64_t refLockPos,
+                               std::vector<LoadSegment> &out);
+    // G0 as the encoder host loaded it (MultipleGenomeMatchingProcessor::initMatcher, mgmp_driver.cpp: one loadRef of the
+    // contigs back to back, then their reverse complement as one text; the window's end is 0 under -t1, the buffer's end otherwise)
+    static bool scheduleG0(RefState &st, uint64_t g0Bytes, bool rcInReference, bool sequentialMatching, std::vector<LoadSegment> &out);
+
+    // streams under streamsPrefix -> outputPrefix.{seq,contigLens,seqCounts}; the message of a failure in *error
+    static int decode(const std::string &streamsPrefix, const std::string &outputPrefix, const Options &opt, std::string *error);
+};
+
+int mbgc_hip_decompress_main(int argc, char **argv);

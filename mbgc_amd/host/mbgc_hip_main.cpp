@@ -26,6 +26,7 @@
 #include <unistd.h>
 
 #include "mgmp_driver.h"
+#include "mbgc_decoder.h"
 
 // what the ranks share before their exchange exists: the RCCL ids rank 0 makes, then (host-memory transport) its mapping
 struct Bootstrap {
@@ -64,6 +65,7 @@ static void dump(const std::string &prefix, const char *name, const std::string 
 }
 
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "d") return mbgc_hip_decompress_main(argc, argv);   // the streams back to the collection (mbgc_decoder.cpp)
     MBGC_Params params;
     std::vector<std::string> pos;
     int gpus = 1;
@@ -114,6 +116,7 @@ int main(int argc, char **argv) {
                         "  and writes <outputPrefix>.seqCounts (one little-endian u32 per target: its records)\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
+        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [-d device] <streamsPrefix> <outputPrefix>\n");
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
@@ -232,6 +235,7 @@ int main(int argc, char **argv) {
     dump(pos[1], "mapOff5th", enc.mapOff5thByte);
     dump(pos[1], "mapLen", enc.mapLen);
     dump(pos[1], "refExtSize", enc.refExtSizeStream);
+    dump(pos[1], "meta", enc.metaBytes());                                      // what `mbgc-hip d` needs beyond the streams
     if (enc.singleFastaFile()) {
         const std::vector<uint32_t> &counts = enc.sequenceCounts();
         dump(pos[1], "seqCounts", std::string((const char *) counts.data(), counts.size() * sizeof(uint32_t)));

@@ -1,5 +1,6 @@
 #include "mgmp_driver.h"
 #include "simple_sequence_matcher.h"
+#include "mbgc_decoder.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1214,6 +1215,35 @@ void MBGC_Encoder::initStreamsForG0Ref() { literals.clear(); }
 void MBGC_Encoder::processG0RefContig(const char *seq, size_t len) {
     literals.append(seq, len);
     literals.push_back(SEQ_SEPARATOR_MARK);
+    metaG0Contigs++;
+}
+
+void MBGC_Encoder::noteStreamOffsets() {
+    const std::string *six[SWSEM_NSTREAMS] = {&literals, &mapOff, &mapOff5thByte, &mapLen, &gapDeltas, &gapMismatchesFlags};   // SWSEM_LIT .. SWSEM_FLAGS
+    for (const std::string *s : six) metaIndex.push_back(s->size());
+}
+void MBGC_Encoder::noteTargetAppended() {
+    metaSeqCounts.push_back(metaContigsInTarget);
+    metaContigsInTarget = 0;
+    noteStreamOffsets();
+}
+
+std::string MBGC_Encoder::metaBytes() const {
+    MbgcMeta m;
+    m.sequentialMatching = params->sequentialMatching; m.rcInReference = params->rcInReference; m.contigsIndividuallyReversed = true;   // MGMP_Params.h:75
+    m.uppercaseDNA = params->uppercaseDNA; m.singleFastaFile = singleFastaFileMode; m.rcRedundancyRemoval = params->rcRedundancyRemoval;
+    m.coderMode = params->coderMode; m.k = (uint32_t) params->k; m.k1 = (uint32_t) params->k1; m.g0Contigs = metaG0Contigs;
+    m.maxRefLength = matcher->getMaxRefLength(); m.swSize = matcher->getSlidingWindowSize(); m.finalRefLength = refFinalTotalLength;
+    m.reachedRefLengthCount = (matcher->getLoadedRefLength() - (matcher->getLoadingPosition() - 1)) / (matcher->getMaxRefLength() - 1);
+    m.emit = params->emit;
+    for (size_t t = 0; t < metaSeqCounts.size(); t++) {
+        MbgcMeta::Target x;
+        x.seqsCount = metaSeqCounts[t];
+        if (2 * t + 1 < unmatchedFractionFactors.size()) { x.unmatchedFractionFactor = unmatchedFractionFactors[2 * t]; x.unmatchedFractionRCFactor = unmatchedFractionFactors[2 * t + 1]; }
+        m.targets.push_back(x);
+    }
+    m.index = metaIndex;
+    return m.serialize();
 }
 
 static const uint32_t BACKEND_FEED_EVERY = 8;                      // targets between two hand-overs to a backend that runs beside the matching
@@ -1285,6 +1315,7 @@ void MBGC_Encoder::appendContigInOrder(const swsem_streams_t &st) {
     mapLen.append((const char *) st.data[SWSEM_LEN], st.size[SWSEM_LEN]);
     gapDeltas.append((const char *) st.data[SWSEM_GAP], st.size[SWSEM_GAP]);
     gapMismatchesFlags.append((const char *) st.data[SWSEM_FLAGS], st.size[SWSEM_FLAGS]);
+    metaContigsInTarget++;
     unmatchedCharsAll += st.unmatchedChars;
     extensionsMatchedCharsAll += st.extensionsMatchedChars;
     extensionsMismatchesAll += st.extensionsMismatches;
@@ -1295,12 +1326,13 @@ void MBGC_Encoder::appendContigInOrder(const swsem_streams_t &st) {
 void MBGC_Encoder::endTargetInOrder() {
     targetsAppended++;
     if (params->emit.enableExtensionsWithMismatches) gapMismatchesFlags.push_back(FILE_SEPARATOR_MARK);
+    noteTargetAppended();
     if (backendStream && targetsAppended % BACKEND_FEED_EVERY == 0) feedBackendStream(false);
 }
 
 void MBGC_Encoder::processAfterSequence(uint32_t targetIdx) {
     if (params->sequentialMatching) literals.push_back(SEQ_SEPARATOR_MARK);
-    else targetStreams[targetIdx].s[SWSEM_LIT].push_back(SEQ_SEPARATOR_MARK);
+    else { targetStreams[targetIdx].s[SWSEM_LIT].push_back(SEQ_SEPARATOR_MARK); metaContigsInTarget++; }
 }
 
 void MBGC_Encoder::processAfterTarget(uint32_t targetIdx) {
@@ -1335,6 +1367,7 @@ void MBGC_Encoder::finalizeParallelProcessingOfTarget(uint32_t targetIdx, size_t
     appendStreams(*this, targetStreams[targetIdx]);                                             // ENC.cpp:543-556
     targetStreams[targetIdx] = EmittedStreams();
     targetsAppended++;
+    noteTargetAppended();
     if (backendStream && targetsAppended % BACKEND_FEED_EVERY == 0) feedBackendStream(false);
     if (params->lazyDecompressionSupport) {
         matcher->loadSeparator(REF_REGION_SEPARATOR);
@@ -1357,6 +1390,7 @@ void MBGC_Encoder::appendTargetStreams(uint32_t targetIdx) {
     appendStreams(*this, targetStreams[targetIdx]);                                             // ENC.cpp:543-556
     targetStreams[targetIdx] = EmittedStreams();
     targetsAppended++;
+    noteTargetAppended();
     if (backendStream && targetsAppended % BACKEND_FEED_EVERY == 0) feedBackendStream(false);
 }
 
@@ -1405,6 +1439,7 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
     if (getenv("MBGC_HIP_TIMES") && autoRound) fprintf(stderr, "  round size: %d (guessed %d for the first read-ahead)\n", params->roundSize, guessed);
     params->emit.enable40bitReference = params->enable40bitReference;
     if (params->lazyDecompressionSupport) refExtLoadedPosArr.emplace_back(matcher->getLoadingPosition());   // ENC.cpp:789-791
+    noteStreamOffsets();                                                                        // (the first target starts behind G0's literals)
     performMatching();
     // prepareAndCompressStreams' first step on this path, ENC.cpp:636-638: the reverse-complement pass over the literals
     if (params->rcRedundancyRemoval && !params->benchMode && (!params->exchange || mbgc_xchg_rank(params->exchange) == 0))

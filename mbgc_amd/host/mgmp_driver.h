@@ -211,6 +211,13 @@ class MBGC_Encoder : public MultipleGenomeMatchingProcessor {
     std::vector<EmittedStreams> targetStreams;                                          // per-target streams (round mode)
     uint32_t targetsAppended = 0;                                                       // targets whose streams arrived in order
     uint32_t sequentialTargetsDone = 0;
+    // <prefix>.meta (mbgc_decoder.h): per target its sequences and where its bytes start in the six streams, taken where the bytes
+    // land in the collection's streams (the three places that append a target's streams)
+    std::vector<uint32_t> metaSeqCounts;
+    std::vector<uint64_t> metaIndex;
+    uint32_t metaContigsInTarget = 0, metaG0Contigs = 0;
+    void noteStreamOffsets();
+    void noteTargetAppended();
     size_t backendFed[MBGC_ST_COUNT] = {};                                              // bytes of every stream the backend has been handed
 
     void initStreamsForG0Ref() override;                                                // ENC.cpp:25-32
@@ -254,6 +261,7 @@ public:
     void feedBackendStream(bool everything);
     std::string finishBackendStream(uint64_t *blocksCodedEarly);
     void backendParams(mbgc_backend_params_t &bp, int blocksScale, int numberOfThreads) const;
+    std::string metaBytes() const;                                                      // what `mbgc-hip d` needs beyond the streams
     bool singleFastaFile() const { return singleFastaFileMode; }
     uint32_t singleFastaElements() const { return params->sequentialMatching ? 1 : targetsCount + 1; }
     const std::vector<uint32_t> &sequenceCounts() const { return seqsCounts; }
