@@ -74,6 +74,38 @@ int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, 
 int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
                              uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems);
 
+/* The way back (`mbgc-hip d --fasta`): FASTA text from contigs in HBM. seq_dev[0..seqBytes) holds the contigs, headers_dev[0..
+ * headerBytes) a copy of the header bytes, recs (host, nrec entries) says for every record of the text, in order, where its contig
+ * and its header lie and the line length of its unit (KSEQ_DNA_LINE_LENGTH; 0: every sequence on one line). A record's text is
+ * '>' header '\n', then the sequence as the reference's writeDNA breaks it (MBGC_Decoder.cpp:76-92): lineLen bytes and '\n' per
+ * full line, the remainder and '\n' if bytes are left, NOTHING for an empty sequence — 2 + headerLen + seqLen + ceil(seqLen /
+ * lineLen) bytes ((seqLen > 0) for the last term when lineLen is 0). textOff (host, nrec + 1 entries) receives every record's
+ * offset in the text and, last, the total. text_dev has capacity textCap: when the text is longer the call writes nothing to it
+ * and returns -104 with the size needed in textOff[nrec] (as the record table of the parser does). Any alignment of text_dev.
+ * kernelMs (may be NULL): the kernel's time from events on the stream. Runs on the input stage's stream; synchronous. */
+typedef struct {
+    uint64_t seqOff, seqLen;         /* the contig, bytes of seq_dev     */
+    uint64_t headerOff, headerLen;   /* its header, bytes of headers_dev */
+    uint64_t lineLen;
+} mbgc_fasta_format_rec_t;
+int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const uint8_t *headers_dev, uint64_t headerBytes,
+                          const mbgc_fasta_format_rec_t *recs, uint64_t nrec, uint8_t *text_dev, uint64_t textCap, uint64_t *textOff,
+                          double *kernelMs);
+
+/* A download that runs beside the kernels of the input stage's stream (the decoder's text batches: batch b travels while batch b + 1
+ * is formatted): begin queues the copy on a stream of its own and returns; wait returns when it has arrived, with the copy's time
+ * from events on that stream in *copyMs (may be NULL). One download at a time: begin before the last one's wait is refused (-103).
+ * dst_host should be page-locked (mbgc_fasta_host_alloc), or the copy is not asynchronous. The caller orders the copy behind the
+ * kernels that write src_dev: mbgc_fasta_format_dev has returned, so they have finished. */
+int mbgc_fasta_download_begin(mbgc_fasta_t *p, void *dst_host, const uint8_t *src_dev, uint64_t bytes);
+int mbgc_fasta_download_wait(mbgc_fasta_t *p, double *copyMs);
+
+/* n pieces src_dev[off[k] .. off[k] + len[k]) of a device buffer of srcBytes bytes, packed back to back on the device, each followed
+ * by the byte sep, and downloaded: out_host (capacity outCap) receives *outBytes = sum(len) + n bytes; -104 with *outBytes set when
+ * it is too small. What `mbgc-hip c -i` keeps of a batch's elements: the header lines, not the elements. Synchronous. */
+int mbgc_fasta_gather_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcBytes, const uint64_t *off, const uint64_t *len, uint64_t n,
+                          uint8_t sep, uint8_t *out_host, uint64_t outCap, uint64_t *outBytes);
+
 /* Device memory for the windows of a single-FASTA input, before a matcher exists (the initial reference is cut from the first
  * window): plain allocation, a device-to-device copy and a download on the input stage's stream, each synchronous. */
 int mbgc_fasta_dev_alloc(mbgc_fasta_t *p, uint64_t bytes, uint8_t **out);

@@ -418,6 +418,19 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
     if (lane == 0) res[0] = (uint64_t) j;
 }
 
+#include "fasta_format.h"
+
+// pieces of a device buffer packed back to back, each followed by one separator byte (the headers of a -i batch: only they travel
+// back to the host, not the elements): one workgroup per piece
+__global__ void __launch_bounds__(THREADS) k_fa_gather(const uint8_t *__restrict__ src, const uint64_t *__restrict__ tab, uint32_t piece0, uint32_t npieces,
+                                                       uint8_t sep, uint8_t *__restrict__ dst) {       // tab: rows of {source offset, length, destination offset}
+    const uint32_t k = piece0 + blockIdx.x;
+    if (k >= npieces) return;
+    const uint64_t so = tab[3 * (uint64_t) k], len = tab[3 * (uint64_t) k + 1], to = tab[3 * (uint64_t) k + 2];
+    for (uint64_t i = threadIdx.x; i < len; i += THREADS) dst[to + i] = src[so + i];
+    if (threadIdx.x == 0) dst[to + len] = sep;
+}
+
 std::string g_err;
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -460,6 +473,14 @@ struct mbgc_fasta {
     fa::Buf<uint8_t> dHostIn, dHostOut;         // mbgc_fasta_parse_host: the file and its sequences on the device
     fa::Buf<uint32_t> dTileFirst;               // mbgc_fasta_split_dev: first '>' of every tile, and its result
     fa::Buf<uint64_t> dSplit;
+    fa::Buf<fa::FmtRec> dFmtRecs;               // mbgc_fasta_format_dev: the record table and the tiles' owners
+    fa::Buf<uint32_t> dFmtOwner;
+    hipEvent_t fmtEv[2] = {nullptr, nullptr};   // around the format launches (made at the first call that asks for the time)
+    hipStream_t copyStream = nullptr;           // mbgc_fasta_download_begin / _wait: a download beside the kernels of `stream`
+    hipEvent_t copyEv[2] = {nullptr, nullptr};
+    bool copyPending = false;
+    fa::Buf<uint64_t> dGatherTab;               // mbgc_fasta_gather_dev
+    fa::Buf<uint8_t> dGatherOut;
 };
 
 extern "C" {
@@ -484,7 +505,10 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     (void) hipSetDevice(p->device);
     if (p->stream) { (void) hipStreamSynchronize(p->stream); (void) hipStreamDestroy(p->stream); }
     p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dHostIn.release(); p->dHostOut.release();
-    p->dTileFirst.release(); p->dSplit.release();
+    p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
+    if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
+    for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
     delete p;
 }
 
@@ -610,6 +634,98 @@ int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t s
 int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, int isFileEnd, uint64_t firstMin, uint64_t nextMin,
                          int maxElems, uint64_t *ends, int *nElems) {
     return mbgc_fasta_split_buf_dev(p, bytes_dev, 0, n, 0, isFileEnd, firstMin, nextMin, maxElems, ends, nElems);
+}
+
+int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const uint8_t *headers_dev, uint64_t headerBytes,
+                          const mbgc_fasta_format_rec_t *recs, uint64_t nrec, uint8_t *text_dev, uint64_t textCap, uint64_t *textOff,
+                          double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(FmtIn) == sizeof(mbgc_fasta_format_rec_t), "the table builder reads the ABI's records");
+    if (kernelMs) *kernelMs = 0;
+    if (nrec >= 0xffffffffull) return fail(-103, "format: %llu records in one call", (unsigned long long) nrec);
+    for (uint64_t k = 0; k < nrec; k++) {
+        const mbgc_fasta_format_rec_t &x = recs[k];
+        if (x.seqOff > seqBytes || x.seqLen > seqBytes - x.seqOff || x.headerOff > headerBytes || x.headerLen > headerBytes - x.headerOff)
+            return fail(-103, "format: record %llu lies outside the sequences or the headers", (unsigned long long) k);
+    }
+    std::vector<FmtRec> table;
+    const uint64_t total = fmt_build_table((const FmtIn *) recs, nrec, table, textOff);
+    if (total > textCap) return fail(-104, "text output needs %llu bytes, capacity %llu", (unsigned long long) total, (unsigned long long) textCap);
+    if (total == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    const uint32_t mis = (uint32_t) ((uintptr_t) text_dev & (PER - 1));
+    const uint64_t nt64 = (total + mis + CHUNK - 1) / CHUNK;
+    if (nt64 >= 0xffffffffull) return fail(-103, "format: %llu bytes of text in one call", (unsigned long long) total);
+    const uint32_t ntiles = (uint32_t) nt64;
+    std::vector<uint32_t> owner;
+    fmt_build_owner(table, nrec, mis, ntiles, owner);
+    int rc;
+    if ((rc = p->dFmtRecs.reserve(nrec + 1)) || (rc = p->dFmtOwner.reserve((size_t) ntiles + 1))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }   // (the handle's: freed with it)
+    FCHK(hipMemcpyAsync(p->dFmtRecs.p, table.data(), (nrec + 1) * sizeof(FmtRec), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFmtOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
+        k_fa_format<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(seq_dev, seqBytes, headers_dev, p->dFmtRecs.p, p->dFmtOwner.p,
+                                                                                            t0, ntiles, mis, total, text_dev);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    return 0;
+}
+
+int mbgc_fasta_download_begin(mbgc_fasta_t *p, void *dst_host, const uint8_t *src_dev, uint64_t bytes) {
+    using namespace fa;
+    if (p->copyPending) return fail(-103, "download_begin: the download before this one has not been waited for");
+    FCHK(hipSetDevice(p->device));
+    if (!p->copyStream) {
+        FCHK(hipStreamCreateWithFlags(&p->copyStream, hipStreamNonBlocking));
+        FCHK(hipEventCreate(&p->copyEv[0])); FCHK(hipEventCreate(&p->copyEv[1]));
+    }
+    FCHK(hipEventRecord(p->copyEv[0], p->copyStream));
+    if (bytes) FCHK(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, p->copyStream));
+    FCHK(hipEventRecord(p->copyEv[1], p->copyStream));
+    p->copyPending = true;
+    return 0;
+}
+
+int mbgc_fasta_download_wait(mbgc_fasta_t *p, double *copyMs) {
+    using namespace fa;
+    if (copyMs) *copyMs = 0;
+    if (!p->copyPending) return 0;
+    FCHK(hipSetDevice(p->device));
+    p->copyPending = false;
+    FCHK(hipStreamSynchronize(p->copyStream));
+    if (copyMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->copyEv[0], p->copyEv[1])); *copyMs = ms; }
+    return 0;
+}
+
+int mbgc_fasta_gather_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcBytes, const uint64_t *off, const uint64_t *len, uint64_t n,
+                          uint8_t sep, uint8_t *out_host, uint64_t outCap, uint64_t *outBytes) {
+    using namespace fa;
+    *outBytes = 0;
+    if (n >= 0xffffffffull) return fail(-103, "gather: %llu pieces in one call", (unsigned long long) n);
+    std::vector<uint64_t> tab(3 * (size_t) n);
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        if (off[k] > srcBytes || len[k] > srcBytes - off[k]) return fail(-103, "gather: piece %llu lies outside the buffer", (unsigned long long) k);
+        tab[3 * k] = off[k]; tab[3 * k + 1] = len[k]; tab[3 * k + 2] = total;
+        total += len[k] + 1;
+    }
+    *outBytes = total;
+    if (total > outCap) return fail(-104, "gather needs %llu bytes, capacity %llu", (unsigned long long) total, (unsigned long long) outCap);
+    if (n == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dGatherTab.reserve(tab.size())) || (rc = p->dGatherOut.reserve(total))) return rc;
+    FCHK(hipMemcpyAsync(p->dGatherTab.p, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    for (uint64_t k0 = 0; k0 < n; k0 += FMT_SLICE)
+        k_fa_gather<<<dim3((uint32_t) std::min<uint64_t>(FMT_SLICE, n - k0)), dim3(THREADS), 0, p->stream>>>(src_dev, p->dGatherTab.p, (uint32_t) k0, (uint32_t) n, sep, p->dGatherOut.p);
+    FCHK(hipGetLastError());
+    FCHK(hipMemcpyAsync(out_host, p->dGatherOut.p, total, hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 int mbgc_fasta_dev_alloc(mbgc_fasta_t *p, uint64_t bytes, uint8_t **out) {

@@ -6,11 +6,22 @@ import numpy as np
 from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
-           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download""".split()
+           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download""".split()
 
 
 class Record(C.Structure):
     _fields_ = [("headerOff", C.c_uint64), ("headerLen", C.c_uint64), ("seqOff", C.c_uint64), ("seqLen", C.c_uint64)]
+
+
+class FormatRecord(C.Structure):
+    _fields_ = [("seqOff", C.c_uint64), ("seqLen", C.c_uint64), ("headerOff", C.c_uint64), ("headerLen", C.c_uint64), ("lineLen", C.c_uint64)]
+
+
+class TextTooSmall(binding.SwsemError):
+    """format_dev: the text does not fit the buffer; .needed = its size"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
 
 
 def _lib():
@@ -26,6 +37,10 @@ def _lib():
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mbgc_fasta_split_buf_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mbgc_fasta_format_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(FormatRecord), C.c_uint64,
+                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_gather_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint8,
+                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L._fasta_ready = True
     return L
 
@@ -92,3 +107,31 @@ class FastaParser:
                                            int(next_min), int(max_elems), ends.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ne)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return [int(e) for e in ends[:ne.value]]
+
+    def format_dev(self, seq_ptr, seq_bytes, headers_ptr, header_bytes, records, text_ptr, text_cap):
+        """the inverse of parse_batch_dev: records = rows of (seqOff, seqLen, headerOff, headerLen, lineLen) -> (text offsets
+        [nrec + 1], the last one the total; the kernel's ms). TextTooSmall when the text does not fit text_cap (nothing written)."""
+        rows = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 5)
+        n = rows.shape[0]
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        ms = C.c_double(0)
+        r = _lib().mbgc_fasta_format_dev(self.h, seq_ptr, int(seq_bytes), headers_ptr, int(header_bytes),
+                                         rows.ctypes.data_as(C.POINTER(FormatRecord)), n, text_ptr, int(text_cap),
+                                         offs.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ms))
+        if r == -104:
+            raise TextTooSmall(_lib().mbgc_fasta_last_error().decode(), int(offs[-1]))
+        if r:
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return offs, ms.value
+
+    def gather_dev(self, src_ptr, src_bytes, offsets, lengths, sep=10):
+        """pieces of a device buffer, each followed by the byte sep, packed on the device and downloaded -> bytes"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        out = np.zeros(int(ln.sum()) + off.size + 1, dtype=np.uint8)
+        n = C.c_uint64(0)
+        P = C.POINTER(C.c_uint64)
+        if _lib().mbgc_fasta_gather_dev(self.h, src_ptr, int(src_bytes), off.ctypes.data_as(P), ln.ctypes.data_as(P), off.size, sep,
+                                        out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return out[: n.value].tobytes()

@@ -1,10 +1,14 @@
 #include "mbgc_decoder.h"
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <future>
+#include <set>
+#include <sys/stat.h>
 #include <time.h>
 
 static const uint64_t REF_SHIFT = 1;                           // SlidingWindowSparseEMMatcher.h:14
@@ -187,7 +191,90 @@ struct DevFree {
 };
 struct Interval { uint64_t from, to; };
 struct PassTimes { double plan = 0, fill = 0, load = 0; uint64_t waves = 0, widest = 0; };
+
+// ---- --fasta: the layout beside the streams (<prefix>.names / .headers / .dnaLineLengths, written by mbgc-hip c)
+static const uint64_t FASTA_BATCH_TEXT = 256ull << 20;            // text bytes of a batch of whole units (a larger unit is a batch of its own)
+struct FastaUnit { uint64_t c0, c1; uint64_t lineLen; size_t file; uint64_t text; };   // contigs [c0, c1) of the collection, its output file
+struct FastaLayout {
+    std::string headers;                                           // the bytes of <prefix>.headers
+    std::vector<uint64_t> hdrOff, hdrLen;                          // per contig, G0's first
+    std::vector<uint64_t> lineLen;                                 // per unit, G0 first
+    std::vector<std::string> names;                                // per unit (one for a single-FASTA collection)
+    std::vector<std::string> outNames;                             // the files to write, in order
+};
+struct FastaTimes { double format = 0, download = 0, write = 0; uint64_t text = 0, batches = 0; };
+struct FastaBuffers {                                              // freed on every way out
+    mbgc_fasta_t *fa = nullptr; uint8_t *hdrDev = nullptr, *textDev[2] = {nullptr, nullptr}; void *pin[2] = {nullptr, nullptr};
+    std::future<bool> writing;
+    ~FastaBuffers() {
+        if (writing.valid()) writing.wait();
+        if (!fa) return;
+        mbgc_fasta_download_wait(fa, nullptr);                     // (a way out between begin and wait)
+        if (hdrDev) mbgc_fasta_dev_free(fa, hdrDev);
+        for (uint8_t *t : textDev) if (t) mbgc_fasta_dev_free(fa, t);
+        for (void *p : pin) if (p) mbgc_fasta_host_free(fa, p);
+        mbgc_fasta_destroy(fa);
+    }
+};
+
+static uint64_t recordText(uint64_t headerLen, uint64_t seqLen, uint64_t lineLen) {
+    const uint64_t line = (lineLen == 0 || lineLen > seqLen) ? seqLen : lineLen;
+    return 2 + headerLen + (seqLen ? seqLen + (seqLen - 1) / line + 1 : 0);
 }
+
+// the file a unit goes to: the basename of its name (the reference's ignoreFastaFilesPath: nothing is written outside the
+// directory), without a .gz suffix — the text is written inflated
+static std::string outputName(const std::string &name) {
+    std::string b = name.substr(name.find_last_of('/') == std::string::npos ? 0 : name.find_last_of('/') + 1);
+    if (b.size() >= 3 && b.compare(b.size() - 3, 3, ".gz") == 0) b.resize(b.size() - 3);
+    return b;
+}
+}
+
+// reads and checks the three side files against the meta: false and a message, or the layout
+static bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t contigs, FastaLayout &L, std::string &msg) {
+    std::string names, lens;
+    for (const char *ext : {"names", "headers", "dnaLineLengths"})
+        if (!readFile(prefix + "." + ext, ext[0] == 'n' ? names : (ext[0] == 'h' ? L.headers : lens))) {
+            msg = "malformed stream set: cannot open " + prefix + "." + ext + " (--fasta needs the names, headers and line lengths mbgc-hip c writes beside the streams)";
+            return false;
+        }
+    const size_t T = meta.targets.size();
+    if (!names.empty() && names.back() != '\n') { msg = "malformed .names: the last line does not end"; return false; }
+    for (size_t at = 0; at < names.size();) { const size_t e = names.find('\n', at); L.names.push_back(names.substr(at, e - at)); at = e + 1; }
+    if (L.names.size() != (meta.singleFastaFile ? 1 : T + 1)) {
+        msg = "malformed .names: " + std::to_string(L.names.size()) + " names for " + std::to_string(meta.singleFastaFile ? 1 : T + 1) + " units";
+        return false;
+    }
+    if (!L.headers.empty() && L.headers.back() != '\n') { msg = "malformed .headers: the last header does not end"; return false; }
+    for (size_t at = 0; at < L.headers.size();) {
+        const char *e = (const char *) memchr(L.headers.data() + at, '\n', L.headers.size() - at);
+        const size_t end = (size_t) (e - L.headers.data());
+        L.hdrOff.push_back(at); L.hdrLen.push_back(end - at);
+        at = end + 1;
+    }
+    if (L.hdrOff.size() != contigs) {
+        msg = "malformed .headers: " + std::to_string(L.hdrOff.size()) + " headers for " + std::to_string(contigs) + " contigs";
+        return false;
+    }
+    if (lens.size() != (T + 1) * sizeof(uint64_t)) {
+        msg = "malformed .dnaLineLengths: " + std::to_string(lens.size()) + " bytes for " + std::to_string(T + 1) + " units";
+        return false;
+    }
+    L.lineLen.resize(T + 1);
+    memcpy(L.lineLen.data(), lens.data(), lens.size());
+    // the files: one for a single-FASTA collection; else one per unit that is written (under -t1 the initial reference is the first
+    // contig of target 0 again and is no file of its own)
+    std::set<std::string> seen;
+    for (size_t u = meta.singleFastaFile ? 0 : (meta.sequentialMatching ? 1 : 0); u < L.names.size(); u++) {
+        const std::string o = outputName(L.names[u]);
+        if (o.empty() || o == "." || o == "..") { msg = "naming: the unit '" + L.names[u] + "' has no file name to be written under"; return false; }
+        if (!seen.insert(o).second) { msg = "naming: two units would be written to the same file " + o + " (the paths of the list are dropped)"; return false; }
+        L.outNames.push_back(o);
+    }
+    return true;
+}
+
 
 int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix, const Options &opt, std::string *error) {
     auto fail = [&](const std::string &m) { if (error) *error = m; return 1; };
@@ -232,6 +319,10 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     if (planned > stream[SWSEM_LIT].size()) return fail("malformed .meta: more sequences than literal bytes");
     uint64_t sizes[SWSEM_NSTREAMS];
     for (int s = 0; s < SWSEM_NSTREAMS; s++) sizes[s] = stream[s].size();
+    const bool wantFasta = !opt.fastaDir.empty();
+    FastaLayout layout;
+    if (wantFasta) { std::string m; if (!readFastaLayout(prefix, meta, g0n + planned, layout, m)) return fail(m); }
+    FastaTimes ftimes;
     // chain starts
     const bool useIndex = !opt.noIndex && !meta.index.empty();
     std::vector<swsem_chain_start_t> starts;
@@ -435,6 +526,128 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                         " laps, the encoder's at " + std::to_string(meta.finalRefLength) + " after " + std::to_string(meta.reachedRefLengthCount));
         const uint64_t outFrom = meta.sequentialMatching ? g0n : 0;                               // (-t1: the initial reference is the first contig of target 0 again)
         outBases = totalBases - seqOff[outFrom];
+        if (wantFasta) {
+            // ---- the FASTA files again: units in order, batches of whole units of at most FASTA_BATCH_TEXT bytes of
+            // text; a batch is formatted on the device, downloaded into one of two page-locked buffers, and written by a thread of
+            // its own while the next batch is formatted and downloaded into the other
+            ftimes = FastaTimes();
+            auto faFail = [&](const char *what) { return fail(std::string(what) + ": " + mbgc_fasta_last_error()); };
+            std::vector<FastaUnit> units;
+            {
+                uint64_t c = 0;
+                for (size_t u = 0; u <= T; u++) {
+                    const uint64_t n = u == 0 ? g0n : seqCount[u - 1];
+                    FastaUnit x = {c, c + n, layout.lineLen[u], 0, 0};
+                    c += n;
+                    if (u == 0 && meta.sequentialMatching) continue;
+                    x.file = meta.singleFastaFile ? 0 : u - (meta.sequentialMatching ? 1 : 0);
+                    for (uint64_t k = x.c0; k < x.c1; k++) x.text += recordText(layout.hdrLen[k], contigLen[k], x.lineLen);
+                    units.push_back(x);
+                }
+            }
+            uint64_t maxBatch = 0;
+            std::vector<size_t> batchEnd;                                                       // units [batchEnd[b - 1], batchEnd[b])
+            {
+                uint64_t cur = 0;
+                for (size_t u = 0; u < units.size(); u++) {
+                    if (cur && cur + units[u].text > FASTA_BATCH_TEXT) { batchEnd.push_back(u); maxBatch = std::max(maxBatch, cur); cur = 0; }
+                    cur += units[u].text;
+                }
+                batchEnd.push_back(units.size()); maxBatch = std::max(maxBatch, cur);
+            }
+            const bool writeFiles = !opt.bench || pass == 0;                                    // (bench: the timed pass formats and downloads only)
+            if (writeFiles) {                                                                   // the directory, with the ones above it
+                for (size_t at = 1; at <= opt.fastaDir.size(); at++)
+                    if (at == opt.fastaDir.size() || opt.fastaDir[at] == '/')
+                        if (mkdir(opt.fastaDir.substr(0, at).c_str(), 0777) != 0 && errno != EEXIST) return fail("cannot create the directory " + opt.fastaDir.substr(0, at));
+            }
+            FastaBuffers fb;
+            if (mbgc_fasta_create(&fb.fa, opt.device)) return faFail("--fasta");
+            if (mbgc_fasta_dev_alloc(fb.fa, layout.headers.size() + 64, &fb.hdrDev)) return faFail("--fasta");
+            for (uint8_t *&t : fb.textDev) if (mbgc_fasta_dev_alloc(fb.fa, maxBatch + 64, &t)) return faFail("--fasta");
+            for (void *&p : fb.pin) if (mbgc_fasta_host_alloc(fb.fa, std::max<uint64_t>(maxBatch, layout.headers.size()) + 64, &p)) return faFail("--fasta");
+            {   // the headers go up through page-locked memory like everything else
+                memcpy(fb.pin[0], layout.headers.data(), layout.headers.size());
+                if (mbgc_fasta_upload(fb.fa, fb.hdrDev, fb.pin[0], layout.headers.size())) return faFail("--fasta");
+            }
+            // Batch b: formatted into device buffer b & 1; its download into page-locked buffer b & 1 begins at once, on a stream of
+            // its own, and is waited for after batch b + 1 has been formatted into the other device buffer; then its writer starts,
+            // once the writer of batch b - 1 has ended. So the download of b and the writes of b - 1 run beside the format of b + 1,
+            // and page-locked buffer b & 1 is free again (writer b - 2 was waited for) before download b begins.
+            struct Piece { size_t file; uint64_t off, len; bool first; };
+            std::vector<char> opened(layout.outNames.size(), 0);
+            std::vector<mbgc_fasta_format_rec_t> recs;
+            std::vector<uint64_t> textOff;
+            std::vector<Piece> inFlight;                                                         // the pieces of the batch whose download runs
+            uint8_t *inFlightHost = nullptr;
+            bool downloading = false;
+            auto settle = [&]() -> int {                                                        // the running download -> its writer; 0 ok, 1 device, 2 write
+                if (!downloading) return 0;
+                double cms = 0;
+                if (mbgc_fasta_download_wait(fb.fa, &cms)) return 1;
+                ftimes.download += cms;
+                downloading = false;
+                const double w0 = nowMs();
+                const bool ok = !fb.writing.valid() || fb.writing.get();
+                ftimes.write += nowMs() - w0;                                                   // (what the writes hold the pipeline up by)
+                if (!ok) return 2;
+                if (writeFiles) {
+                    const std::string dir = opt.fastaDir;
+                    const std::vector<std::string> *outNames = &layout.outNames;
+                    const std::vector<Piece> pieces = inFlight;
+                    const uint8_t *host = inFlightHost;
+                    fb.writing = std::async(std::launch::async, [pieces, host, dir, outNames] {
+                        for (const Piece &p : pieces) {
+                            std::ofstream f(dir + "/" + (*outNames)[p.file], std::ios::binary | (p.first ? std::ios::trunc : std::ios::app));
+                            f.write((const char *) host + p.off, (std::streamsize) p.len);
+                            f.close();                                                          // (an error may only show when the last bytes leave the buffer)
+                            if (!f) return false;
+                        }
+                        return true;
+                    });
+                }
+                return 0;
+            };
+            auto settleFail = [&](int r) { return r == 1 ? faFail("download") : fail("cannot write under " + opt.fastaDir); };
+            size_t u0 = 0;
+            for (size_t b = 0; b < batchEnd.size(); b++) {
+                const size_t u1 = batchEnd[b];
+                recs.clear();
+                for (size_t u = u0; u < u1; u++)
+                    for (uint64_t k = units[u].c0; k < units[u].c1; k++)
+                        recs.push_back({seqOff[k], contigLen[k], layout.hdrOff[k], layout.hdrLen[k], units[u].lineLen});
+                textOff.assign(recs.size() + 1, 0);
+                double kms = 0;
+                if (mbgc_fasta_format_dev(fb.fa, seqDev, totalBases, fb.hdrDev, layout.headers.size(), recs.data(), recs.size(), fb.textDev[b & 1], maxBatch,
+                                          textOff.data(), &kms)) return faFail("format");
+                ftimes.format += kms;
+                const uint64_t bytes = textOff[recs.size()];
+                ftimes.text += bytes; ftimes.batches++;
+                if (const int r = settle()) return settleFail(r);                               // batch b - 1: it travelled beside this batch's format
+                // (the writer of b - 2, which read page-locked buffer b & 1, was waited for by that settle or the one before)
+                inFlight.clear();
+                uint64_t at = 0;
+                for (size_t u = u0; u < u1; u++) {
+                    inFlight.push_back({units[u].file, at, units[u].text, !opened[units[u].file]});
+                    opened[units[u].file] = 1;
+                    at += units[u].text;
+                }
+                if (at != bytes) return fail("internal error: the text of a batch is not the sum of its units");
+                inFlightHost = (uint8_t *) fb.pin[b & 1];
+                if (mbgc_fasta_download_begin(fb.fa, inFlightHost, fb.textDev[b & 1], bytes)) return faFail("download");
+                downloading = true;
+                u0 = u1;
+            }
+            if (const int r = settle()) return settleFail(r);
+            const double w0 = nowMs();
+            if (fb.writing.valid() && !fb.writing.get()) return fail("cannot write under " + opt.fastaDir);
+            ftimes.write += nowMs() - w0;
+            // (files of units without a record exist too, empty)
+            if (writeFiles)
+                for (size_t f = 0; f < opened.size(); f++)
+                    if (!opened[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f], "", 0)) return fail("cannot write under " + opt.fastaDir);
+        }
+
         if (pass + 1 == passes && !opt.bench) {
             std::string seq(outBases, '\0');
             if (outBases && swsem_dev_download(h, &seq[0], seqDev + seqOff[outFrom], outBases)) return hipFail("download");
@@ -455,6 +668,11 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, starts.size(), times.plan / (double) T,
                (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false");
     }
+    if (opt.bench && wantFasta)
+        printf("{\"metric\": \"FASTA text GB/s (format kernel)\", \"value\": %.4f, \"unit\": \"GB/s\", \"text_bytes\": %llu, \"batches\": %llu, "
+               "\"format_kernel_ms\": %.3f, \"download_ms\": %.3f, \"write_ms\": %.3f}\n",
+               ftimes.format > 0 ? ftimes.text / (ftimes.format * 1e-3) / 1e9 : 0.0, (unsigned long long) ftimes.text, (unsigned long long) ftimes.batches,
+               ftimes.format, ftimes.download, ftimes.write);
     printf("waves: %llu for %zu targets\n", (unsigned long long) times.waves, T);
     printf("widest wave: %llu targets\n", (unsigned long long) times.widest);
     printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) (contigLen.size() - (meta.sequentialMatching ? g0n : 0)), (unsigned long long) outBases);
@@ -469,13 +687,16 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         if (a == "--serial") opt.serial = true;
         else if (a == "--no-index") opt.noIndex = true;
         else if (a == "--bench") opt.bench = true;
+        else if (a == "--fasta" && i + 1 < argc) opt.fastaDir = argv[++i];
         else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
         else pos.push_back(a);
     }
     if (pos.size() != 2) {
-        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [-d device] <streamsPrefix> <outputPrefix>\n"
+        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n"
                         "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
                         "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
+                        "  --fasta dir: also the input FASTA files again, formatted on the device, as <dir>/<basename of each name of the list> (a .gz suffix\n"
+                        "  is dropped: the text is written inflated; -i: the one file) from <streamsPrefix>.names / .headers / .dnaLineLengths\n"
                         "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n");
         return EXIT_FAILURE;
     }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mbgc_swsem.h"
+#include "../../include/mbgc_fasta.h"
 
 struct MbgcMeta {
     static constexpr uint32_t VERSION = 1;
@@ -50,7 +51,7 @@ public:
         uint64_t loaded() const { return reachedRefLengthCount * (refTotalLength - 1) + (refPos - 1); }
     };
     struct ContigInfo { uint64_t length, unmatched; };
-    struct Options { bool serial = false, noIndex = false, bench = false; int device = 0; };
+    struct Options { bool serial = false, noIndex = false, bench = false; int device = 0; std::string fastaDir; };   // fastaDir: --fasta, empty = not asked for
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
     static bool loadRef(RefState &st, int64_t contig, uint64_t textOffset, uint64_t seqLength, uint64_t refLockPos, bool loadRCRef,
@@ -63,7 +64,9 @@ public:
     // contigs back to back, then their reverse complement as one text; the window's end is 0 under -t1, the buffer's end otherwise)
     static bool scheduleG0(RefState &st, uint64_t g0Bytes, bool rcInReference, bool sequentialMatching, std::vector<LoadSegment> &out);
 
-    // streams under streamsPrefix -> outputPrefix.{seq,contigLens,seqCounts}; the message of a failure in *error
+    // streams under streamsPrefix -> outputPrefix.{seq,contigLens,seqCounts}; the message of a failure in *error.
+    // opt.fastaDir: also the input FASTA files again, under that directory, from <streamsPrefix>.names / .headers / .dnaLineLengths
+    // (formatted on the device: mbgc_fasta_format_dev, include/mbgc_fasta.h)
     static int decode(const std::string &streamsPrefix, const std::string &outputPrefix, const Options &opt, std::string *error);
 };
 

@@ -116,7 +116,7 @@ int main(int argc, char **argv) {
                         "  and writes <outputPrefix>.seqCounts (one little-endian u32 per target: its records)\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [-d device] <streamsPrefix> <outputPrefix>\n");
+        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n");
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
@@ -236,6 +236,11 @@ int main(int argc, char **argv) {
     dump(pos[1], "mapLen", enc.mapLen);
     dump(pos[1], "refExtSize", enc.refExtSizeStream);
     dump(pos[1], "meta", enc.metaBytes());                                      // what `mbgc-hip d` needs beyond the streams
+    if (!params.exchange) {                                                     // ... and `d --fasta` beyond that: names, headers, line lengths
+        dump(pos[1], "names", enc.namesStream);
+        dump(pos[1], "headers", enc.headersStream);
+        dump(pos[1], "dnaLineLengths", enc.lineLengthsStream);
+    }
     if (enc.singleFastaFile()) {
         const std::vector<uint32_t> &counts = enc.sequenceCounts();
         dump(pos[1], "seqCounts", std::string((const char *) counts.data(), counts.size() * sizeof(uint32_t)));

@@ -182,6 +182,7 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
         exit(EXIT_FAILURE);
     }
     validate_kseq_status(path, status);
+    hostLineLen = lineLen;
     out.clear();
     for (uint64_t k = 0; k < nrec; k++) {
         Contig c;
@@ -323,6 +324,39 @@ void MultipleGenomeMatchingProcessor::loadRound(uint32_t f0, uint32_t f1, RoundB
     }
 }
 
+// the headers of a parsed batch, out of the file bytes the host holds (records[] as the parser left it)
+void MultipleGenomeMatchingProcessor::keepHeaders(RoundBatch &B, const uint8_t *fileBytes, const uint64_t *fileOff, const uint64_t *recBase,
+                                                  const uint64_t *lineLen, int nf) {
+    B.unitHeaders.assign((size_t) std::max(nf, 0), std::string());
+    B.unitLineLen.assign(lineLen, lineLen + std::max(nf, 0));
+    for (int f = 0; f < nf; f++) {
+        std::string &h = B.unitHeaders[f];
+        size_t need = 0;
+        for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) need += records[k].headerLen + 1;
+        h.reserve(need);
+        for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) {
+            h.append((const char *) fileBytes + fileOff[f] + records[k].headerOff, records[k].headerLen);
+            h.push_back('\n');
+        }
+    }
+}
+
+void MultipleGenomeMatchingProcessor::noteUnitArrived(LayoutUnit &&u) {
+    std::lock_guard<std::mutex> g(layoutMu);
+    u.target = layoutArrived++;
+    layoutPending.push_back(std::move(u));
+}
+
+void MultipleGenomeMatchingProcessor::noteUnitsArrived(const RoundBatch &B, uint32_t firstFile) {
+    if (!keepsLayout()) return;
+    for (size_t u = 0; u < B.unitHeaders.size(); u++) {
+        LayoutUnit x;
+        if (!singleFastaFileMode && firstFile + u < fileNames.size()) x.name = fileNames[firstFile + u];
+        x.headers = B.unitHeaders[u]; x.lineLen = B.unitLineLen[u];
+        noteUnitArrived(std::move(x));
+    }
+}
+
 // files [f0, f1) of the list -> their contigs back to back in B.seqDev; contig c belongs to target targetBase + (file - f0)
 void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t afterF0, uint32_t afterF1) {
     openInputStage();
@@ -330,6 +364,7 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
     const int nf = (int) (f1 - f0);
     if (nf <= 0) {                                           // (a rank without targets in a short last round)
         B.offsets.assign(1, 0); B.targetOf.clear(); B.bytes = 0;
+        B.unitHeaders.clear(); B.unitLineLen.clear();
         return;
     }
     const double tWait0 = nowSeconds();
@@ -386,6 +421,7 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
         }
     }
     B.bytes = seqBase[nf];
+    if (keepsLayout()) keepHeaders(B, S->pin, fileOff.data(), recBase.data(), lineLen.data(), nf);   // (before the slot is read into again)
     g_tParse += nowSeconds() - tParse0;
 }
 
@@ -551,10 +587,12 @@ void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
             sf.nextElem = 1;
             totalFilesLength += g0Bytes;
         }
+        g0Headers.clear(); g0LineLen = hostLineLen;
         for (const Contig &c : contigs) {
             largestContigSize = std::max<uint64_t>(largestContigSize, c.seq.size());
             refStr.append(c.seq);
             processG0RefContig(c.seq.data(), c.seq.size());
+            g0Headers.append(c.header); g0Headers.push_back('\n');
         }
         refG0InitPos = refStr.size();
         const size_t basicRefLength = std::max<size_t>(refStr.size(), BLOCK);                  // :109-110
@@ -585,6 +623,7 @@ void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
 void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint32_t f1, RoundBatch &B) {
     const uint64_t BLOCK = MGMP_Params::MIN_BASIC_BLOCK_SIZE;
     B.offsets.assign(1, 0); B.targetOf.clear(); B.recCounts.clear(); B.bytes = 0; B.endOfInput = false;
+    B.unitHeaders.clear(); B.unitLineLen.clear();
     std::vector<uint64_t> fileOff(1, 0), ends;
     if (params->sequentialMatching) {
         uint64_t cut = 0;
@@ -645,6 +684,27 @@ void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint3
             B.recCounts.push_back((uint32_t) (recBase[f + 1] - recBase[f]));
         }
         B.bytes = seqBase[nf];
+        if (keepsLayout()) {
+            // the headers: the windows have left the staging buffers and the elements are in HBM — the header lines alone are packed
+            // there and come back (a few KB per batch, not the batch)
+            const uint64_t nrecs = recBase[nf];
+            std::vector<uint64_t> off(nrecs), len(nrecs);
+            uint64_t bytes = 0;
+            for (int f = 0; f < nf; f++)
+                for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) { off[k] = fileOff[f] + records[k].headerOff; len[k] = records[k].headerLen; bytes += len[k] + 1; }
+            sfBytes.resize(bytes);
+            uint64_t got = 0;
+            inputStageCheck(mbgc_fasta_gather_dev(fasta, sf.dev, n, off.data(), len.data(), nrecs, '\n', (uint8_t *) &sfBytes[0], bytes, &got));
+            B.unitHeaders.assign((size_t) nf, std::string());
+            B.unitLineLen.assign(lineLen.begin(), lineLen.end());
+            uint64_t at = 0;
+            for (int f = 0; f < nf; f++) {
+                uint64_t u = 0;
+                for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) u += len[k] + 1;
+                B.unitHeaders[f].assign(sfBytes, at, u);
+                at += u;
+            }
+        }
         g_tParse += nowSeconds() - tParse0;
         sfConsume(n);
         sf.nextElem += (uint32_t) nf;
@@ -711,10 +771,12 @@ void MultipleGenomeMatchingProcessor::loadG0Ref(const std::string &refName) {
     readG0(refName, contigs, &fileSize);
     std::string refStr;
     initStreamsForG0Ref();
+    g0LineLen = hostLineLen;
     for (const Contig &c : contigs) {                                                          // MGMP.cpp:82-105
         largestContigSize = std::max<uint64_t>(largestContigSize, c.seq.size());
         refStr.append(c.seq);
         processG0RefContig(c.seq.data(), c.seq.size());
+        g0Headers.append(c.header); g0Headers.push_back('\n');
         if (params->sequentialMatching) break;                                                 // :91-100: first contig only
     }
     refG0InitPos = refStr.size();
@@ -773,12 +835,18 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
     // single fasta file mode: the file is ONE target that arrives in batches of whole records, as many as it takes
     const bool single = singleFastaFileMode;
     if (single) seqsCounts.assign(1, 0);
+    LayoutUnit openUnit;
     size_t startPos = 0;
     for (uint32_t i = 0; single || i < filesCount; i++) {
         RoundBatch &B = three[i % 3];
         if (prev.valid && prev.buf == (i + 1) % 3) { matcher->emitEnd(); collectPrev(false); }  // (files without records in between: the arriving file would overwrite what that emission reads)
         loadRound(i, i + 1, B, i + 1, single ? i + 2 : std::min(filesCount, i + 2), &three[(i + 1) % 3]);   // MGMP.cpp:247-250
         if (single && !B.recCounts.empty()) seqsCounts[0] += B.recCounts[0];
+        if (!single) noteUnitsArrived(B, i);
+        else if (!B.unitHeaders.empty()) {                                                     // (the file is one unit, whatever its batches)
+            openUnit.headers += B.unitHeaders[0];
+            if (!openUnit.lineLen) openUnit.lineLen = B.unitLineLen[0];
+        }
         if (!single || i == 0) {
             startPos = matcher->getLoadedRefLength();                                          // :251
             unmatchedFractionFactors.push_back(params->currentUnmatchedFractionFactor < 256 ? params->currentUnmatchedFractionFactor : 0);
@@ -804,6 +872,7 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
             prev.valid = true; prev.buf = i % 3;
         }
         if (single && !B.endOfInput) continue;                                                  // (the target goes on in the next batch)
+        if (single && keepsLayout()) noteUnitArrived(std::move(openUnit));
         prev.fileSeps++;                                                                        // (behind the file's last contig)
         afterTargetWithParallelIO(startPos);                                                    // :306 without processAfterTarget
         if (single) break;
@@ -971,6 +1040,7 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
                 if (B.endOfInput) nRounds = r + 1;
                 if (!any) break;
             }
+            noteUnitsArrived(B, 1 + B.t0);
         } else if ((int) r == params->benchWarmup) {
             if (prev.valid) { matcher->emitEnd(); collect(prev, false); prev.valid = false; }
             matcher->synchronize();
@@ -1223,6 +1293,21 @@ void MBGC_Encoder::noteStreamOffsets() {
     for (const std::string *s : six) metaIndex.push_back(s->size());
 }
 void MBGC_Encoder::noteTargetAppended() {
+    if (keepsLayout()) {
+        // the unit whose bytes have just been appended is the oldest that waits: units arrive and are appended in target order
+        std::lock_guard<std::mutex> g(layoutMu);
+        const uint32_t target = (uint32_t) metaSeqCounts.size();
+        if (layoutPending.empty() || layoutPending.front().target != target) {
+            fprintf(stderr, "internal error: the streams of target %u were appended, and %s\n", target,
+                    layoutPending.empty() ? "no unit waits with its names and headers" : "the unit that waits is another target's");
+            exit(EXIT_FAILURE);
+        }
+        const LayoutUnit &u = layoutPending.front();
+        if (!singleFastaFileMode) { namesStream.append(u.name); namesStream.push_back('\n'); }
+        headersStream.append(u.headers);
+        lineLengthsStream.append((const char *) &u.lineLen, sizeof u.lineLen);
+        layoutPending.pop_front();
+    }
     metaSeqCounts.push_back(metaContigsInTarget);
     metaContigsInTarget = 0;
     noteStreamOffsets();
@@ -1440,6 +1525,8 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
     params->emit.enable40bitReference = params->enable40bitReference;
     if (params->lazyDecompressionSupport) refExtLoadedPosArr.emplace_back(matcher->getLoadingPosition());   // ENC.cpp:789-791
     noteStreamOffsets();                                                                        // (the first target starts behind G0's literals)
+    namesStream = fileNames[0] + "\n"; headersStream = g0Headers;
+    lineLengthsStream.assign((const char *) &g0LineLen, sizeof g0LineLen);
     performMatching();
     // prepareAndCompressStreams' first step on this path, ENC.cpp:636-638: the reverse-complement pass over the literals
     if (params->rcRedundancyRemoval && !params->benchMode && (!params->exchange || mbgc_xchg_rank(params->exchange) == 0))

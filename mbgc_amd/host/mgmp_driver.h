@@ -9,7 +9,9 @@
 // host exactly as in the reference; everything that touches sequence bytes runs through the C ABI.
 #pragma once
 #include <cstdint>
+#include <deque>
 #include <future>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -90,6 +92,10 @@ struct RoundBatch {
     // and whether the file ends with it
     std::vector<uint32_t> recCounts;
     bool endOfInput = false;
+    // the layout `mbgc-hip d --fasta` needs, per unit of the batch (a file of the list, an element of -i): its records' headers,
+    // each followed by '\n', and the line length the parser found — copied out of the staged file bytes while they are there
+    std::vector<std::string> unitHeaders;
+    std::vector<uint64_t> unitLineLen;
 };
 
 class MultipleGenomeMatchingProcessor {
@@ -142,6 +148,17 @@ protected:
     void extensionStrings(const RoundBatch &B, const std::vector<char> &ext, const std::vector<char> &rc, uint32_t ta, uint32_t tb,
                           std::vector<const uint8_t *> &extDev, std::vector<uint64_t> &extLen);
     std::vector<mbgc_fasta_record_t> records;
+    // The side files of the layout (<prefix>.names / .headers / .dnaLineLengths): the units whose matching has begun wait here, in
+    // target order, until their bytes are appended to the collection's streams — the thread that appends takes them from the front.
+    struct LayoutUnit { std::string name, headers; uint64_t lineLen = 0; uint32_t target = 0; };   // target: checked where it is taken
+    std::deque<LayoutUnit> layoutPending;
+    uint32_t layoutArrived = 0;
+    bool keepsLayout() const { return !params->benchMode && !params->exchange; }         // (not under --bench, not on the sharded host)
+    std::mutex layoutMu;
+    std::string g0Headers; uint64_t g0LineLen = 0, hostLineLen = 0;                      // the initial reference's; hostLineLen: of parseHostBytes' last file
+    void noteUnitsArrived(const RoundBatch &B, uint32_t firstFile);                     // the batch's units behind those that wait
+    void noteUnitArrived(LayoutUnit &&u);
+    void keepHeaders(RoundBatch &B, const uint8_t *fileBytes, const uint64_t *fileOff, const uint64_t *recBase, const uint64_t *lineLen, int nf);
     void openInputStage();
     void readG0(const std::string &path, std::vector<Contig> &out, uint64_t *fileSize);
     void parseHostBytes(const std::string &data, const std::string &name, std::vector<Contig> &out);
@@ -160,6 +177,7 @@ protected:
         uint32_t nextElem = 0;
         std::future<uint64_t> reading; int readSlot = 0; bool readActive = false;
     } sf;
+    std::string sfBytes;                                                                // a batch's header lines, gathered on the device
     void sfOpen(const std::string &path);
     void sfStartRead();
     bool sfExtend();                                                                    // one more window behind dev[have); false: the file has ended
@@ -242,6 +260,10 @@ public:
     // the streams the reference enrols at ENC.cpp:779-787 (+ the two it writes beside them)
     std::string literals, mapOff, mapOff5thByte, mapLen, gapDeltas, gapMismatchesFlags, locksPosStream, refExtSizeStream;
     std::string rcMapOff, rcMapLen;                                                     // ENC.cpp:636-638 (-m3)
+    // the layout beside the streams, for `mbgc-hip d --fasta`: a name per unit ('\n' each; G0's file first — under -t1 the first file
+    // is G0's and target 0's, and stands twice; -i: the one path), a header per contig ('\n' each), a u64 line length per unit.
+    // Empty on the sharded host and under --bench.
+    std::string namesStream, headersStream, lineLengthsStream;
     size_t extensionsMatchedCharsAll = 0, extensionsMismatchesAll = 0, removedGapBreakingMatchesAll = 0;
 
     explicit MBGC_Encoder(MBGC_Params *p) : MultipleGenomeMatchingProcessor(p), params(p) { device = p->device; }
@@ -251,7 +273,8 @@ public:
     // with the caller's leaf coders; what CompressionJob::writeCompressedCollectiveParallel would write for them
     // threads: the job pool of this call; numberOfThreads: what the reference's -t would be (it only decides LZMA's numThreads; 0: = threads).
     // The header-side streams (names, sequence counts, header templates, headers, line lengths) are the CLI's and go in empty:
-    // the section is what the reference's reader takes for the matcher-side streams, not a complete archive.
+    // the section is what the reference's reader takes for the matcher-side streams, not a complete archive. (Their facts are
+    // kept beside the streams in plain form — namesStream, headersStream, lineLengthsStream below; INTEGRATION.md §11 maps them.)
     std::string compressStreams(mbgc_leaf_compress_fn leaf, void *ctx, int threads, int blocksScale = 1, int numberOfThreads = 0);
     // The backend beside the matching (include/mbgc_backend.h, the incremental form): set before encode(), the encoder hands
     // over what its streams have grown by every few targets, so that the blocks of the split streams are coded while the rounds
