@@ -305,8 +305,12 @@ int swsem_profile_enable(swsem_t *h, int on);
 int swsem_profile_get(swsem_t *h, double ms[SWSEM_K_COUNT], uint64_t launches[SWSEM_K_COUNT]);
 /* counters of the last batch (after swsem_batch_counts): [0] query bases, [1] hash-table probes,
  * [2] verified hits, [3] matches, [4] sum of match lengths (after swsem_batch_fingerprint),
- * [5] resolve blocks whose speculation was rejected and that were replayed from the true state */
-int swsem_batch_stats(swsem_t *h, uint64_t stats[6]);
+ * [5] resolve blocks whose speculation was rejected and that were replayed from the true state,
+ * [6] of those, the blocks whose replay was taken from the launch that replays rejected blocks ahead of the stitch's walk
+ * (one wave each, from the state the predecessor's speculative chain ended in), [7] replays of that launch the walk did
+ * not use, [8] of those, the ones it met at a rejected block and refused (the assumed state was not the true one): such
+ * a block is replayed in place, as are the rejected blocks that launch did not have */
+int swsem_batch_stats(swsem_t *h, uint64_t stats[9]);
 
 #ifdef __cplusplus
 }

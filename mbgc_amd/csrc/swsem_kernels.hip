@@ -807,9 +807,18 @@ struct __attribute__((aligned(16))) FastRec {
     int32_t npush;         // rows the block adds
     int32_t popB;          // rows of the predecessor's it removes; -1: take the complete test
 };
+//
+// A block whose quick test FAILS — on the scan position or on a compared row — would, if its predecessor is accepted, be
+// replayed by k_stitch from the predecessor's final state, and that state is in the predecessor's record. Such blocks go
+// onto a compact list (one counter, at most `bound` of them in a batch; whatever comes after is no candidate) and
+// k_stitch_replay replays them all at once, one wave each, before the walk begins. A block the quick test cannot decide
+// (it looked deeper than the predecessor pushed or than a record holds, walked off the bottom of its stack, the
+// predecessor visited nothing or its chain jumped over the block) is no candidate: the walk's complete test has it.
+constexpr uint32_t NO_CAND = 0xFFFFFFFFu;
 __global__ void __launch_bounds__(256) k_stitch_pre(const Contig *__restrict__ contigs, const uint32_t *__restrict__ rbContig,
                                                     const BlockRec *__restrict__ recs, uint32_t rb, uint32_t nblocks,
-                                                    FastRec *__restrict__ fast) {
+                                                    FastRec *__restrict__ fast, uint32_t *__restrict__ candOf,
+                                                    uint32_t *__restrict__ candBlock, unsigned long long *__restrict__ candCount, uint32_t bound) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nblocks) return;
     const Contig cg = contigs[rbContig[g]];
@@ -818,6 +827,7 @@ __global__ void __launch_bounds__(256) k_stitch_pre(const Contig *__restrict__ c
     FastRec f;
     f.scanF = (int32_t) cur.scanF; f.minKeep = cur.minKeep; f.npush = cur.spF - cur.minKeep; f.popB = -1;
     const bool visited = cur.minTouched != 0x7fffffff;
+    uint32_t slot = NO_CAND;
     if (b == 0) {
         if (visited) f.popB = 0;                                      // started from the true (empty) state: spB = minKeep = 0
     } else if (visited && cur.minTouched >= 0) {
@@ -826,13 +836,174 @@ __global__ void __launch_bounds__(256) k_stitch_pre(const Contig *__restrict__ c
         const int32_t pScanF = (int32_t) prv.scanF;
         const int cmp = cur.spB - cur.minTouched;
         const int prevPush = prv.spF - prv.minKeep;
-        bool ok = prv.minTouched != 0x7fffffff && pScanF < w0 + span && (pScanF > w0 ? pScanF : w0) == (int32_t) cur.scanB &&
-                  cmp >= 0 && cmp <= SNAP && cmp <= prevPush;
+        const bool decidable = prv.minTouched != 0x7fffffff && pScanF < w0 + span && cmp >= 0 && cmp <= SNAP && cmp <= prevPush;
+        bool ok = decidable && (pScanF > w0 ? pScanF : w0) == (int32_t) cur.scanB;
         for (int j = 0; ok && j < cmp; j++)
             ok = cur.bTop[j].posSrc == prv.fTop[j].posSrc && cur.bTop[j].len == prv.fTop[j].len && cur.bTop[j].posDest == prv.fTop[j].posDest;
         if (ok) f.popB = cur.spB - cur.minKeep;                      // <= cmp <= prevPush: stays inside the predecessor's segment
+        else if (decidable) {
+            const unsigned long long s = atomicAdd(candCount, 1ull);
+            if (s < (unsigned long long) bound) { slot = (uint32_t) s; candBlock[slot] = g; }
+        }
     }
     fast[g] = f;
+    candOf[g] = slot;
+}
+
+// What k_stitch_replay leaves for k_stitch. A candidate's scratch is 2 * cap + SNAP rows: the replay's stack (the seeded
+// rows first), then, from row cap + SNAP on, the block's speculative rows [specFrom, spF) once the replay's rows have taken
+// their place in the block's region.
+struct __attribute__((aligned(16))) CandRec {
+    int32_t scan0;         // scan position the replay started from (>= the block's first position)
+    int32_t scanEnd;       // scan position after the block
+    int32_t n;             // the block's rows: region[0 .. n)
+    int32_t removed;       // seeded rows the replay removed (the newest ones)
+    int32_t examined;      // seeded rows it examined, counted from the newest (>= removed)
+    int32_t usable;        // 0: it looked beneath the seeded rows (or ran out of scratch): the region is as the block chain left it — replay in place
+    int32_t specFrom, specN; // the speculative rows saved in the scratch (usable only)
+};
+
+// ArrayStack that also keeps the row pushed last in registers (the stop rule compares it: no read-back from memory)
+struct SeedStack : ArrayStack<Row> {
+    uint64_t lastSrc, lastLen, lastDest;
+    __device__ __forceinline__ void truncate_push(int keep, const Match &m, int32_t scanAfter) {
+        lastSrc = m.posSrc; lastLen = m.len; lastDest = m.posDest;
+        ArrayStack<Row>::truncate_push(keep, m, scanAfter);
+    }
+};
+constexpr int SPECW = 256;             // speculative rows of a candidate held in LDS for the stop rule (the rest is read from memory)
+
+// One wave per candidate block: the replay k_stitch would run in place, started from the state the PREDECESSOR'S
+// speculative chain ended in — its final scan position and, as the stack, its newest rows (at most SNAP: what its record
+// holds). Same automaton, same stop rule (see k_stitch: the replay ends when it emits a row the block's own speculative
+// chain also kept, with the same scan position after it). A wave is alone with its chain and every step of it is a
+// round trip to memory, so the rows the stop rule looks at are fetched once, into LDS.
+//
+// A replay that did not look beneath the seeded rows is usable: its rows take the place of the speculative rows in the
+// block's region (those move to the scratch: k_stitch needs them if it has to replay the block in place after all) and
+// k_stitch takes them once it has seen that the true scan position and every seeded row the replay examined are what was
+// assumed here — a wrong assumption costs this wave's time, never a row. And where the assumption holds BY the walk's own
+// induction the block's FastRec is rewritten, so that the walk accepts the block inside a run like any other: the
+// predecessor is no candidate itself (a block accepted in a run after it ended in the state its record holds — scan
+// position, and as many newest rows as it pushed), and the replay examined no more rows than the predecessor pushed.
+// The block after it passed its quick test against THIS block's speculative record; it stays in the run only if the
+// replay synchronised and the rows that block compared all lie in the speculative continuation (which is then what the
+// list holds, and the final scan position is the record's); otherwise its FastRec is withdrawn and the walk tests it
+// completely. (No two waves write one FastRec: a candidate's is written by its own wave only, and only when the block
+// before it is no candidate; a successor's only when it is no candidate.)
+template <bool LAPS>
+__global__ void __launch_bounds__(WAVE) k_stitch_replay(RefView v, const uint8_t *__restrict__ qbuf,
+                                                        const Contig *__restrict__ contigs, const uint32_t *__restrict__ rbContig,
+                                                        Row *__restrict__ regions, Row *__restrict__ candArea,
+                                                        uint32_t cap, uint32_t rb, const BlockRec *__restrict__ recs,
+                                                        const uint32_t *__restrict__ candBlock, const unsigned long long *__restrict__ candCount,
+                                                        uint32_t bound, CandRec *__restrict__ cand,
+                                                        const uint32_t *__restrict__ candOf, FastRec *__restrict__ fast) {
+    __shared__ uint2 ring[RING];
+    __shared__ uint4 specA[SPECW];                                   // {posDest, len, posSrc lo, posSrc hi}
+    __shared__ int32_t specB[SPECW];                                 // scanAfter
+    const uint32_t slot = blockIdx.x;
+    if (slot >= bound || (unsigned long long) slot >= *candCount) return;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t g = rfl32(candBlock[slot]);
+    const Contig cg = contigs[rbContig[g]];
+    const uint32_t b = g - cg.rb0;                                   // >= 1 (k_stitch_pre)
+    const BlockRec *cur = recs + g, *prv = recs + g - 1;
+    const uint8_t *q = qbuf + cg.qoff;
+    const int32_t span = (int32_t) (rb * RBU), w0 = (int32_t) b * span;
+    const int32_t npos = cg.n >= (uint64_t) v.K ? (int32_t) (cg.n - v.K + 1) : 0;
+    const int32_t w1 = w0 + span < npos ? w0 + span : npos;
+    const int32_t room = (int32_t) cap + SNAP;                       // rows of the replay's stack
+    Row *scratch = candArea + (uint64_t) slot * (uint64_t) (room + (int32_t) cap);
+    Row *spec = regions + (uint64_t) g * cap;
+    const int spF = (int) rfl32((uint32_t) cur->spF), cMinKeep = (int) rfl32((uint32_t) cur->minKeep);
+    const int specFrom = cMinKeep < 0 ? 0 : cMinKeep;                // speculative rows pushed while the chain ran the own block: [specFrom, spF)
+    const int specN = spF > specFrom ? spF - specFrom : 0;
+    for (int k = (int) lane; k < specN && k < SPECW; k += WAVE) {
+        const Row x = spec[specFrom + k];
+        specA[k] = make_uint4((uint32_t) x.posDest, (uint32_t) x.len, (uint32_t) x.posSrc, (uint32_t) (x.posSrc >> 32));
+        specB[k] = (int32_t) x.scanAfter;
+    }
+    SeedStack stk;
+    stk.st = scratch; stk.ring = ring; stk.sp = 0; stk.ringLow = 0; stk.lastSrc = stk.lastLen = stk.lastDest = 0;
+    const int32_t pSpF = (int32_t) rfl32((uint32_t) prv->spF);
+    const int nSeed = pSpF < SNAP ? pSpF : SNAP;
+    for (int j = 0; j < nSeed; j++) {                                // oldest first
+        Match m;
+        m.posSrc = rfl64(prv->fTop[nSeed - 1 - j].posSrc); m.len = rfl64(prv->fTop[nSeed - 1 - j].len); m.posDest = rfl64(prv->fTop[nSeed - 1 - j].posDest);
+        stk.truncate_push(j, m, 0);
+    }
+    const int32_t pScanF = (int32_t) rfl32((uint32_t) prv->scanF);
+    Chain ch;
+    ch.scan = pScanF > w0 ? pScanF : w0; ch.minTouched = 0x7fffffff; ch.minKeep = 0x7fffffff; ch.visited = 0; ch.cands = 0; ch.emitted = false;
+    const int32_t scan0 = ch.scan;
+    int sp = specFrom;
+    int syncAt = -1;
+    bool full = false;
+    // row sp of the speculative chain (contigs stay below 2^31 bytes: posDest and len fit 32 bits)
+    auto spec_row = [&](int at, uint32_t &pos, uint32_t &len, uint64_t &src, int32_t &scanAfter) {
+        if (at - specFrom < SPECW) {
+            const uint4 a = specA[at - specFrom];
+            pos = rfl32(a.x); len = rfl32(a.y); src = ((uint64_t) rfl32(a.w) << 32) | rfl32(a.z); scanAfter = (int32_t) rfl32((uint32_t) specB[at - specFrom]);
+        } else {
+            pos = rfl32((uint32_t) spec[at].posDest); len = rfl32((uint32_t) spec[at].len); src = rfl64(spec[at].posSrc); scanAfter = (int32_t) rfl32((uint32_t) spec[at].scanAfter);
+        }
+    };
+    auto stop = [&]() -> bool {
+        if (stk.sp >= room - 1) { full = true; return true; }        // (cannot happen: cap bounds the rows of a chain over span + OVERLAP_MAX positions)
+        if (!ch.emitted) return false;
+        ch.emitted = false;
+        const uint32_t ePos = (uint32_t) stk.lastDest;               // the row just emitted
+        uint32_t pos = 0, len = 0; uint64_t src = 0; int32_t after = 0;
+        while (sp < spF) {
+            spec_row(sp, pos, len, src, after);
+            if (pos >= ePos) break;
+            sp++;
+        }
+        if (sp < spF && pos == ePos && len == (uint32_t) stk.lastLen && src == stk.lastSrc && after == ch.scan) { syncAt = sp; return true; }
+        return false;
+    };
+    chain_run<LAPS>(v, cg, q, w0, w1, stk, ch, stop);
+    __builtin_amdgcn_s_waitcnt(0);
+    CandRec r;
+    r.scan0 = scan0; r.specFrom = specFrom; r.specN = specN;
+    const int first = ch.minKeep < nSeed ? ch.minKeep : nSeed;       // seeded rows below it were not removed
+    r.removed = nSeed - first;
+    r.examined = !ch.visited || ch.minTouched >= nSeed ? 0 : nSeed - ch.minTouched;
+    int n = stk.sp - first;
+    bool usable = !full && !(ch.visited && ch.minTouched < 0) && r.removed <= r.examined && n >= 0;
+    r.scanEnd = ch.scan;
+    if (usable && syncAt >= 0) {                                     // append the speculative continuation
+        const int tail = spF - syncAt - 1;
+        if (stk.sp + tail > room) usable = false;
+        else {
+            for (int k = (int) lane; k < tail; k += WAVE) scratch[stk.sp + k] = spec[syncAt + 1 + k];
+            n += tail;
+            r.scanEnd = (int32_t) rfl32((uint32_t) cur->scanF);
+        }
+    }
+    if (n > (int) cap || specN > (int) cap) usable = false;          // (the block's region holds cap rows)
+    r.n = n; r.usable = usable ? 1 : 0;
+    if (lane == 0) cand[slot] = r;
+    if (!usable) return;
+    // the speculative rows to the scratch, the replay's rows to the region
+    Row *saved = scratch + room;
+    for (int k = (int) lane; k < specN; k += WAVE) saved[k] = spec[specFrom + k];
+    __builtin_amdgcn_s_waitcnt(0);
+    for (int k = (int) lane; k < n; k += WAVE) spec[k] = scratch[first + k];
+    // the walk's records (see above)
+    const int prevPush = pSpF - (int) rfl32((uint32_t) prv->minKeep);
+    if (rfl32(candOf[g - 1]) != NO_CAND || r.examined > prevPush) return;
+    if (lane == 0) {
+        FastRec f;
+        f.scanF = r.scanEnd; f.minKeep = 0; f.npush = n; f.popB = r.removed;
+        fast[g] = f;
+    }
+    if (b + 1 < cg.nrb && rfl32(candOf[g + 1]) == NO_CAND && (int32_t) rfl32((uint32_t) fast[g + 1].popB) >= 0) {
+        const BlockRec *nxt = recs + g + 1;
+        const int cmpNext = (int) rfl32((uint32_t) nxt->spB) - (int) rfl32((uint32_t) nxt->minTouched);
+        if (!(syncAt >= 0 && cmpNext <= spF - syncAt) && lane == 0) fast[g + 1].popB = -1;
+    }
 }
 
 // One wave per contig: walk the resolve blocks with the true state (see above). Outputs per block the
@@ -849,7 +1020,9 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
                                                  uint32_t *__restrict__ segStart, uint32_t *__restrict__ keepN,
                                                  int32_t *__restrict__ prev, uint32_t *__restrict__ dstOff,
                                                  uint32_t *__restrict__ matchCount,
-                                                 unsigned long long *__restrict__ stats) {
+                                                 unsigned long long *__restrict__ stats,
+                                                 const uint32_t *__restrict__ candOf, const CandRec *__restrict__ cand,
+                                                 const Row *__restrict__ candArea) {
     const Contig cg = contigs[blockIdx.x];
     const uint32_t lane = threadIdx.x;
     const uint8_t *q = qbuf + cg.qoff;
@@ -864,14 +1037,29 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
     __shared__ uint64_t ptop[TW];      // newest true rows, newest first, {posSrc, len, posDest} each
     int known = 0;                     // rows of ptop that are valid
     uint32_t replayed = 0, nFast = 0, nSlow = 0, nSkip = 0;   // (diagnostics: blocks accepted in runs / tested one by one / jumped over)
+    uint32_t nTaken = 0, nRefused = 0;                        // rejected blocks taken from k_stitch_replay / that had a replay there and were replayed in place
+    // the true newest rows (at most SNAP) from the list into ptop
+    auto refresh_top = [&]() {
+        __builtin_amdgcn_s_waitcnt(0);
+        const int n = vs.size_ < SNAP ? vs.size_ : SNAP;
+        for (int j = 0; j < n; j++) {
+            const Row *m = vs.at(vs.size_ - 1 - j);
+            if (lane < 3) ptop[3 * j + lane] = ((const uint64_t *) m)[lane];
+        }
+        known = n;
+    };
     const BlockRec *rc = recs + cg.rb0;
     const int32_t span = (int32_t) (rb * RBU);
     const int32_t npos = cg.n >= (uint64_t) v.K ? (int32_t) (cg.n - v.K + 1) : 0;
     __shared__ uint4 srec[sizeof(BlockRec) / 16];
     bool prevPlain = true;             // the block before was accepted as speculated (block 0: the empty state is what it assumed)
     uint4 fr = make_uint4(0, 0, 0, 0); // FastRec of block (b & ~63) + lane
+    uint32_t cf = NO_CAND;             // its slot in k_stitch_replay's list
     for (uint32_t b = 0; b < cg.nrb; b++) {
-        if ((b & (WAVE - 1)) == 0) fr = b + lane < cg.nrb ? ((const uint4 *) (fast + cg.rb0))[b + lane] : make_uint4(0, 0, 0, 0xFFFFFFFFu);
+        if ((b & (WAVE - 1)) == 0) {
+            fr = b + lane < cg.nrb ? ((const uint4 *) (fast + cg.rb0))[b + lane] : make_uint4(0, 0, 0, 0xFFFFFFFFu);
+            cf = b + lane < cg.nrb ? candOf[cg.rb0 + b + lane] : NO_CAND;
+        }
         const int32_t w0 = (int32_t) b * span;
         if (scanT >= w0 + span) { prevPlain = false; nSkip++; continue; }  // the sequential loop jumped over this block
         const int fl = (int) (b & (WAVE - 1));
@@ -916,14 +1104,22 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
             known = 0;                                          // the newest-rows window is rebuilt from the list if ever needed
             b += (uint32_t) (L - 1);
             nFast += (uint32_t) L;
+            // (a candidate with a FastRec that passes: k_stitch_replay wrote it — a rejected block, its replay taken)
+            const uint32_t nRep = (uint32_t) __popcll(__ballot(inRun && cf != NO_CAND));
+            replayed += nRep; nTaken += nRep;
             continue;
         }
         nSlow++;
+        const uint32_t ci = rl32(cf, fl);                       // the block's replay by k_stitch_replay, if it has one
         {                                                       // the complete test needs the whole record
             const uint4 *src = (const uint4 *) (rc + b);
             for (uint32_t i = lane; i < sizeof(BlockRec) / 16; i += WAVE) srec[i] = src[i];
             __builtin_amdgcn_s_waitcnt(0);
         }
+        // a usable replay has put its rows into the block's region; the speculative rows [specFrom, specFrom + specN) are in its scratch
+        const CandRec *cr = cand + (ci == NO_CAND ? 0u : ci);
+        const bool swapped = ci != NO_CAND && rfl32((uint32_t) cr->usable) != 0;
+        const Row *saved = candArea + (uint64_t) (ci == NO_CAND ? 0u : ci) * (uint64_t) (2 * cap + SNAP) + (cap + SNAP);
         const BlockRec *r = (const BlockRec *) srec;
         const int32_t rScanB = (int32_t) rfl32((uint32_t) r->scanB), rScanF = (int32_t) rfl32((uint32_t) r->scanF);
         const int spB = (int) rfl32((uint32_t) r->spB), spF = (int) rfl32((uint32_t) r->spF);
@@ -940,15 +1136,7 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
                 const int cmp = minTouched < 0 ? spB : spB - minTouched;
                 if (minTouched < 0) ok = vs.size_ == spB && spB <= SNAP;
                 else ok = cmp <= SNAP && cmp <= vs.size_;
-                if (ok && cmp > known) {                        // refresh the true newest rows from the list
-                    __builtin_amdgcn_s_waitcnt(0);
-                    const int n = vs.size_ < SNAP ? vs.size_ : SNAP;
-                    for (int j = 0; j < n; j++) {
-                        const Row *m = vs.at(vs.size_ - 1 - j);
-                        if (lane < 3) ptop[3 * j + lane] = ((const uint64_t *) m)[lane];
-                    }
-                    known = n;
-                }
+                if (ok && cmp > known) refresh_top();
                 if (ok) {
                     const bool diff = (int) lane < 3 * cmp && bw[lane < TW ? lane : 0] != ptop[lane < TW ? lane : 0];
                     ok = __ballot(diff) == 0;
@@ -956,6 +1144,12 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
             }
         }
         if (ok) {
+            if (swapped) {                                      // accepted as speculated after all (the predecessor was not): its own rows back
+                const int sFrom = (int) rfl32((uint32_t) cr->specFrom), sN = (int) rfl32((uint32_t) cr->specN);
+                Row *dst = vs.region + (uint64_t) b * cap + sFrom;
+                for (int k = (int) lane; k < sN; k += WAVE) dst[k] = saved[k];
+                __builtin_amdgcn_s_waitcnt(0);
+            }
             if (visited || b == 0) {
                 const int popB = spB - minKeep;
                 const int npush = spF - minKeep;
@@ -976,6 +1170,34 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
                 prevPlain = true;                               // its rows and final state are now known to be the true ones
             } else
                 prevPlain = false;
+        } else if ([&]() -> bool {
+            // The block is rejected. If k_stitch_replay has replayed it (from the state the predecessor's speculative chain
+            // ended in), that replay is the one that would run here — provided it started where the true chain stands and
+            // every row it looked at is a true row: the scan position, and the newest `examined` rows of the list against
+            // the predecessor's record, exactly as the complete test compares a block's boundary rows. (After a replay
+            // of the predecessor that synchronised late, or not at all, the rows its record holds need not be in the
+            // list: then this comparison fails and the block is replayed in place, below.) Its rows are in the region.
+            if (ci == NO_CAND) return false;
+            const int32_t cScan0 = (int32_t) rfl32((uint32_t) cr->scan0), cExam = (int32_t) rfl32((uint32_t) cr->examined);
+            bool good = swapped && (scanT > w0 ? scanT : w0) == cScan0 && cExam <= vs.size_;
+            if (good && cExam > 0) {
+                if (cExam > known) refresh_top();
+                const uint64_t *pf = (const uint64_t *) rc[b - 1].fTop;
+                const bool diff = (int) lane < 3 * cExam && pf[lane < TW ? lane : 0] != ptop[lane < TW ? lane : 0];
+                good = __ballot(diff) == 0;
+            }
+            if (!good) { nRefused++; return false; }
+            const int32_t cRem = (int32_t) rfl32((uint32_t) cr->removed), cN = (int32_t) rfl32((uint32_t) cr->n);
+            if (cRem > 0) vs.pop_segments(cRem);
+            vs.size_ -= cRem;
+            vs.push_segment((int) b, 0, (uint32_t) cN);
+            scanT = (int32_t) rfl32((uint32_t) cr->scanEnd);
+            known = 0;
+            nTaken++;
+            return true;
+        }()) {
+            prevPlain = false;
+            replayed++;
         } else {
             prevPlain = false;
             // Replay the block from the true state. The replay writes its rows to a scratch area and
@@ -987,7 +1209,7 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
             Chain ch;
             ch.scan = scanT; ch.minTouched = 0x7fffffff; ch.minKeep = 0x7fffffff; ch.visited = 0; ch.cands = 0; ch.emitted = false;
             Row *own = replayArea + (uint64_t) blockIdx.x * cap;
-            const Row *spec = vs.region + (uint64_t) b * cap;
+            const Row *spec = swapped ? saved - (int) rfl32((uint32_t) cr->specFrom) : vs.region + (uint64_t) b * cap;   // (rows [minKeep, spF) are read)
             vs.own = own; vs.ownN = 0;
             int sp = minKeep < 0 ? 0 : minKeep;                 // speculative rows pushed while replaying the own block
             int syncAt = -1;
@@ -1043,6 +1265,8 @@ __global__ void __launch_bounds__(WAVE) k_stitch(RefView v, const uint8_t *__res
         atomicAdd(&stats[5], (unsigned long long) nFast);
         atomicAdd(&stats[6], (unsigned long long) nSlow);
         atomicAdd(&stats[7], (unsigned long long) nSkip);
+        if (nTaken) atomicAdd(&stats[9], (unsigned long long) nTaken);
+        if (nRefused) atomicAdd(&stats[10], (unsigned long long) nRefused);
     }
 }
 

@@ -110,6 +110,7 @@ int swsem_create(swsem_t **out, uint64_t maxRefLength, int L, int k1, int k2, in
     h->device = device;
     if (g_eventsFailed) { swsem_destroy(h); return fail(SWSEM_EHIP, "hipEventCreate failed"); }
     h->sw = read_switches();                                // every environment switch of the library: see Switches
+    if (h->sw.overlapFixed >= 0) h->overlap = (uint32_t) h->sw.overlapFixed;
     h->maxRefLength = maxRefLength;
     h->L = L; h->k1 = k1; h->skipMargin = skipMargin;
     h->k1ord = __builtin_ctz((unsigned) k1);
@@ -162,6 +163,8 @@ void swsem_destroy(swsem_t *h) {
     if (h->sw.debugStats) {                                          // diagnostics: the stitch's and the pairing chain's counters of this handle
         fprintf(stderr, "swsem stitch: blocks replayed %llu, accepted in runs %llu, tested one by one %llu, jumped over %llu\n",
                 (unsigned long long) h->stitchDiag[0], (unsigned long long) h->stitchDiag[1], (unsigned long long) h->stitchDiag[2], (unsigned long long) h->stitchDiag[3]);
+        fprintf(stderr, "swsem stitch: replayed ahead of the walk %llu, taken %llu, refused and replayed in place %llu, most in one batch %llu, warm-up positions at the end %u\n",
+                (unsigned long long) h->stitchDiag[4], (unsigned long long) h->stitchDiag[5], (unsigned long long) h->stitchDiag[6], (unsigned long long) h->stitchDiag[7], h->overlap);
         uint64_t t[8];
         if (swsem_debug_emit_stats(h, t) == SWSEM_OK && (t[4] | t[5] | t[6] | t[7]))
             fprintf(stderr, "swsem pairing chain: foreign-boundary steps %llu, blocks not accepted %llu, groups replayed %llu, blocks given up %llu\n",
@@ -414,9 +417,9 @@ int swsem_profile_get(swsem_t *h, double ms[SWSEM_K_COUNT], uint64_t n[SWSEM_K_C
     return SWSEM_OK;
 }
 
-int swsem_batch_stats(swsem_t *h, uint64_t s[6]) { MATCHER_ONLY(h);
+int swsem_batch_stats(swsem_t *h, uint64_t s[9]) { MATCHER_ONLY(h);
     if (!h->batchValid) return fail(SWSEM_EINVAL, "no batch results");
-    for (int i = 0; i < 6; i++) s[i] = h->stats[i];
+    for (int i = 0; i < 9; i++) s[i] = h->stats[i];
     return SWSEM_OK;
 }
 

@@ -54,6 +54,7 @@ struct BatchShape {
     uint32_t rslots = 0;                   // waves of the resolve launch (batch_upload: the launch order's length)
     uint32_t cap = 0;                      // rows a block chain can hold: disjoint matches, each containing the K-mer of a distinct visited hit
     bool blocks = false;                   // resolve blocks, stitch and gather (not one wave per contig)
+    uint32_t cands = 0;                    // slots of the replays ahead of the walk (k_stitch_replay's grid)
 };
 
 // Step 1, host arithmetic only: the block length of this batch, h->contigs and the block -> contig table.
@@ -94,6 +95,7 @@ int batch_layout(swsem *h, const uint64_t *offsets, int n, uint32_t minLen, cons
     }
     B.blocks = !h->sw.seqResolve && B.rblocks != 0;
     B.cap = (uint32_t) ((h->rb * RBU + OVERLAP_MAX + h->K) / h->K + 8);
+    B.cands = (uint32_t) std::min<uint64_t>(std::min<uint64_t>(B.rblocks, CAND_MAX), std::max<uint64_t>(1, CAND_BYTES / ((2 * B.cap + SNAP) * sizeof(Row))));
     return SWSEM_OK;
 }
 
@@ -101,10 +103,11 @@ int batch_layout(swsem *h, const uint64_t *offsets, int n, uint32_t minLen, cons
 int batch_upload(swsem *h, int n, BatchShape &B) {
     const uint32_t rblocks = B.rblocks;
     int r;
-    if ((r = h->dContigs.reserve(n)) || (r = h->dMatchCount.reserve(n)) || (r = h->dStats.reserve(8)) || (r = h->dMatches.reserve(B.matchRows))) return r;
+    if ((r = h->dContigs.reserve(n)) || (r = h->dMatchCount.reserve(n)) || (r = h->dStats.reserve(NSTATS)) || (r = h->dMatches.reserve(B.matchRows))) return r;
     if (B.blocks && ((r = h->dRegions.reserve((size_t) rblocks * B.cap)) || (r = h->dReplay.reserve((size_t) n * B.cap)) || (r = h->dRecs.reserve(rblocks)) ||
                      (r = h->dFast.reserve(rblocks)) || (r = h->dSegStart.reserve(rblocks)) || (r = h->dKeepN.reserve(rblocks)) ||
-                     (r = h->dDstOff.reserve(rblocks)) || (r = h->dPrev.reserve(rblocks))))
+                     (r = h->dDstOff.reserve(rblocks)) || (r = h->dPrev.reserve(rblocks)) || (r = h->dCandOf.reserve(rblocks)) ||
+                     (r = h->dCandBlock.reserve(B.cands)) || (r = h->dCand.reserve(B.cands)) || (r = h->dCandArea.reserve((size_t) B.cands * (2 * B.cap + SNAP)))))
         return r;
     if ((r = upload(h, h->dContigs.p, h->contigs.data(), n * sizeof(Contig), h->stream))) return r;
     if ((r = h->dRbContig.reserve(std::max<uint32_t>(rblocks, 1)))) return r;
@@ -117,7 +120,7 @@ int batch_upload(swsem *h, int n, BatchShape &B) {
         if ((fresh || had != h->dRbOrder.p) && (r = upload(h, h->dRbOrder.p, h->rbOrderHost.data(), h->rbOrderHost.size() * sizeof(uint32_t), h->stream)))
             return r;
     }
-    if ((r = zero_dev(h, h->dStats.p, 8 * sizeof(unsigned long long), h->stream))) return r;
+    if ((r = zero_dev(h, h->dStats.p, NSTATS * sizeof(unsigned long long), h->stream))) return r;
     return flush_copies(h);
 }
 
@@ -139,7 +142,7 @@ int batch_launch(swsem *h, const uint8_t *qdev, int n, const BatchShape &B) {
         else k_resolve_seq<false><<<dim3(n), dim3(WAVE), 0, h->stream>>>(v, qdev, h->dContigs.p, h->dMatches.p, h->dMatchCount.p);
         h->mark(SWSEM_K_RESOLVE, false);
     } else {
-        h->batchBlocks = rblocks;
+        h->batchBlocks = rblocks; h->batchCands = B.cands;
         // An emission whose byte automata wait to be queued (run_phase2b): they are handed to the second stream AFTER the
         // resolve kernel has been handed to the first, behind an event recorded just before it — whatever hardware queues
         // the two streams share, the resolve is dealt its wave slots first.
@@ -161,11 +164,18 @@ int batch_launch(swsem *h, const uint8_t *qdev, int n, const BatchShape &B) {
             for (auto &E : h->slot) if ((r = run_phase2b(h, E, true))) return r;
         }
         h->mark(SWSEM_K_STITCH, true);
-        k_stitch_pre<<<dim3((rblocks + 255) / 256), dim3(256), 0, h->stream>>>(h->dContigs.p, h->dRbContig.p, h->dRecs.p, h->rb, rblocks, h->dFast.p);
+        unsigned long long *candCount = h->dStats.p + 8;
+        k_stitch_pre<<<dim3((rblocks + 255) / 256), dim3(256), 0, h->stream>>>(h->dContigs.p, h->dRbContig.p, h->dRecs.p, h->rb, rblocks, h->dFast.p,
+                                                                               h->dCandOf.p, h->dCandBlock.p, candCount, B.cands);
+        // the rejected blocks, all at once (a wave that finds no candidate in its slot ends at once), then the walk
+        if (wrapped) k_stitch_replay<true><<<dim3(B.cands), dim3(WAVE), 0, h->stream>>>(v, qdev, h->dContigs.p, h->dRbContig.p, h->dRegions.p, h->dCandArea.p, cap, h->rb, h->dRecs.p,
+                                                                                       h->dCandBlock.p, candCount, B.cands, h->dCand.p, h->dCandOf.p, h->dFast.p);
+        else k_stitch_replay<false><<<dim3(B.cands), dim3(WAVE), 0, h->stream>>>(v, qdev, h->dContigs.p, h->dRbContig.p, h->dRegions.p, h->dCandArea.p, cap, h->rb, h->dRecs.p,
+                                                                                 h->dCandBlock.p, candCount, B.cands, h->dCand.p, h->dCandOf.p, h->dFast.p);
         if (wrapped) k_stitch<true><<<dim3(n), dim3(WAVE), 0, h->stream>>>(v, qdev, h->dContigs.p, h->dRegions.p, h->dReplay.p, cap, h->rb, h->dRecs.p, h->dFast.p, h->dSegStart.p,
-                                                                          h->dKeepN.p, h->dPrev.p, h->dDstOff.p, h->dMatchCount.p, h->dStats.p);
+                                                                          h->dKeepN.p, h->dPrev.p, h->dDstOff.p, h->dMatchCount.p, h->dStats.p, h->dCandOf.p, h->dCand.p, h->dCandArea.p);
         else k_stitch<false><<<dim3(n), dim3(WAVE), 0, h->stream>>>(v, qdev, h->dContigs.p, h->dRegions.p, h->dReplay.p, cap, h->rb, h->dRecs.p, h->dFast.p, h->dSegStart.p,
-                                                                    h->dKeepN.p, h->dPrev.p, h->dDstOff.p, h->dMatchCount.p, h->dStats.p);
+                                                                    h->dKeepN.p, h->dPrev.p, h->dDstOff.p, h->dMatchCount.p, h->dStats.p, h->dCandOf.p, h->dCand.p, h->dCandArea.p);
         k_gather<<<dim3(rblocks), dim3(WAVE), 0, h->stream>>>(h->dContigs.p, h->dRbContig.p, h->dRegions.p, cap, h->dSegStart.p,
                                                             h->dKeepN.p, h->dDstOff.p, h->dMatches.p);
         h->mark(SWSEM_K_STITCH, false);
@@ -192,17 +202,17 @@ int run_batch(swsem *h, const uint8_t *qdev, const uint64_t *offsets, int n, uin
     return SWSEM_OK;
 }
 
-// Pinned landing zone for everything a batch hands back to the host: {stats[8] | match counts | emit results}:
+// Pinned landing zone for everything a batch hands back to the host: {stats[NSTATS] | match counts | emit results}:
 // the copies queue up back to back and one wait serves them all. Queues the copies of the match counts and
 // statistics (no wait; staged: the caller adds what it wants beside them and flushes).
 int queue_counts(swsem *h, size_t extraBytes, hipStream_t st = nullptr) {
     if (!st) st = h->stream;
     const size_t n = h->contigs.size();
-    const size_t countsAt = 64, extraAt = (countsAt + n * sizeof(uint32_t) + 63) & ~(size_t) 63;
+    const size_t countsAt = NSTATS * sizeof(unsigned long long), extraAt = (countsAt + n * sizeof(uint32_t) + 63) & ~(size_t) 63;
     const size_t bytes = extraAt + extraBytes;
     int r = h->pin.reserve(bytes, std::max<size_t>(2 * bytes, 1 << 20));       // see prepare_inserts: no regrowth in steady state
     if (r) return r;
-    if ((r = download(h, h->pin.p, h->dStats.p, 8 * sizeof(unsigned long long), st)) ||
+    if ((r = download(h, h->pin.p, h->dStats.p, NSTATS * sizeof(unsigned long long), st)) ||
         (r = download(h, h->pin.p + countsAt, h->dMatchCount.p, n * sizeof(uint32_t), st)))
         return r;
     h->pinExtraAt = extraAt;
@@ -213,13 +223,21 @@ int queue_counts(swsem *h, size_t extraBytes, hipStream_t st = nullptr) {
 void take_counts(swsem *h) {
     const size_t n = h->contigs.size();
     const unsigned long long *st = (const unsigned long long *) h->pin.p;
-    h->matchCount.assign((const uint32_t *) (h->pin.p + 64), (const uint32_t *) (h->pin.p + 64) + n);
+    const uint32_t *counts = (const uint32_t *) (h->pin.p + NSTATS * sizeof(unsigned long long));
+    h->matchCount.assign(counts, counts + n);
+    const uint64_t cands = std::min<uint64_t>(st[8], h->batchCands);   // replayed ahead of the walk (what the list had no room for was not)
     h->stats[1] = h->hostProbes; h->stats[2] = st[2]; h->stats[5] = st[3];
+    h->stats[6] = st[9]; h->stats[7] = cands - std::min<uint64_t>(cands, st[9]); h->stats[8] = st[10];
     h->stitchDiag[0] += st[3]; h->stitchDiag[1] += st[5]; h->stitchDiag[2] += st[6]; h->stitchDiag[3] += st[7];
-    if (h->batchBlocks >= 2048) {                                  // (a batch large enough for the share to mean something)
+    h->stitchDiag[4] += cands; h->stitchDiag[5] += st[9]; h->stitchDiag[6] += st[10]; h->stitchDiag[7] = std::max<uint64_t>(h->stitchDiag[7], st[8]);
+    if (h->batchBlocks >= 2048 && h->sw.overlapFixed < 0) {                                  // (a batch large enough for the share to mean something)
+        // Rejected blocks are replayed side by side (k_stitch_replay) and accepted inside the walk's runs, so what a shorter warm-up
+        // costs is that launch — as long as its slowest replay — while every block saves the positions it no longer scans twice. On
+        // configs[2] (MEASUREMENTS §0b): 768 / 640 / 512 / 384 / 256 positions reject 0.09 / 0.33 / 1.2 / 4.1 / 13.7 % of the blocks
+        // and 512 is the fastest; from 4 % on rejected blocks begin to follow each other, and those the walk replays itself.
         const uint64_t replayed = st[3];
-        if (replayed * 400 > h->batchBlocks) h->overlap = std::min<uint32_t>((uint32_t) OVERLAP_MAX, h->overlap + 128);         // > 0.25 %: longer
-        else if (replayed * 2000 < h->batchBlocks) h->overlap = std::max<uint32_t>(640u, h->overlap - 128);          // < 0.05 %: shorter
+        if (replayed * 40 > h->batchBlocks) h->overlap = std::min<uint32_t>((uint32_t) OVERLAP_MAX, h->overlap + 128);          // > 2.5 %: longer
+        else if (replayed * 160 < h->batchBlocks) h->overlap = std::max<uint32_t>(384u, h->overlap - 128);         // < 0.625 %: shorter
         h->batchBlocks = 0;                                          // (these counts are taken once per batch)
     }
     uint64_t tot = 0;

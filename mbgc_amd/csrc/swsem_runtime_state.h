@@ -21,6 +21,11 @@ constexpr uint64_t REF_SLACK = 256;
 constexpr uint64_t COPY_WGS = 2048;        // workgroups of the finalize's copies (a grid that is resident at once: k_copy_multi)
 constexpr uint32_t EMIT_THIN_MAX = 512;    // emissions of at most this many chunks of 256 gap tasks run their byte automata with 16 tasks per wave
 constexpr uint32_t RB_MIN = 2048 / RBU;    // shortest resolve block (units of RBU positions)
+constexpr uint32_t CAND_MAX = 4096;        // rejected blocks of a batch k_stitch_replay replays ahead of the walk, at most (and at most CAND_BYTES of scratch)
+constexpr uint64_t CAND_BYTES = 128ull << 20;
+// dStats, zeroed per batch: [2] hits, [3] blocks replayed, [5..7] the stitch's walk (runs / one by one / jumped over; k_fingerprint, a test
+// hook, later puts its three words at [4..6]), [8] candidates listed, [9] taken by the walk, [10] refused by it
+constexpr int NSTATS = 16;
 
 // The three kinds of resource a handle owns. Each frees what it holds when the handle is deleted (on the handle's
 // device: swsem_destroy) and none can be copied.
@@ -113,6 +118,7 @@ struct Switches {
     bool seqResolve = false;               // SWSEM_RESOLVE=seq: one wave per contig (cross-check path)
     bool simt = true;                      // four chains per wave (k_resolve_blocks4); SWSEM_CHAINS=1: one chain per wave (k_resolve_blocks)
     uint32_t rbFixed = 0;                  // SWSEM_RB=n: resolve blocks of n * 1024 positions instead of the length chosen per batch
+    int overlapFixed = -1;                 // SWSEM_OVERLAP=n: n warm-up positions in front of every resolve block, not adapted (-1: adapted, take_counts)
     uint32_t profMask = ~0u;               // families that get event brackets (SWSEM_PROF_FAMS: every bracket is two markers in the queue)
     int metaWarm = swk::MWARM;             // warm-up matches of the pairing chain's speculative blocks (SWSEM_META_WARM: fewer, so that blocks fail)
     bool lapTags = true;                   // SWSEM_LAP_TAGS=0: every stale entry is visited (the table image and the results are the same)
@@ -125,6 +131,7 @@ Switches read_switches() {
     if (const char *e = getenv("SWSEM_RESOLVE")) s.seqResolve = strcmp(e, "seq") == 0;
     if (const char *e = getenv("SWSEM_CHAINS")) s.simt = atoi(e) != 1;
     if (const char *e = getenv("SWSEM_RB")) { int x = atoi(e); if (x >= 1 && x <= 256) s.rbFixed = (uint32_t) x * (1024 / RBU); }
+    if (const char *e = getenv("SWSEM_OVERLAP")) { int x = atoi(e); if (x >= 0 && x <= swk::OVERLAP_MAX) s.overlapFixed = x; }
     if (const char *e = getenv("SWSEM_PROF_FAMS")) s.profMask = (uint32_t) strtoul(e, nullptr, 0);
     if (const char *e = getenv("SWSEM_META_WARM")) s.metaWarm = std::min(swk::MWARM, std::max(0, atoi(e)));
     if (const char *e = getenv("SWSEM_LAP_TAGS")) s.lapTags = atoi(e) != 0;
@@ -254,6 +261,11 @@ struct swsem {
     DevBuf<Row> dRegions, dReplay;
     DevBuf<BlockRec> dRecs;
     DevBuf<FastRec> dFast;
+    // the rejected blocks replayed ahead of the stitch's walk (k_stitch_pre lists them, k_stitch_replay runs them): block -> slot,
+    // slot -> block, every slot's result and its rows
+    DevBuf<uint32_t> dCandOf, dCandBlock;
+    DevBuf<CandRec> dCand;
+    DevBuf<Row> dCandArea;
     DevBuf<uint32_t> dSegStart, dKeepN, dDstOff;
     DevBuf<int32_t> dPrev;
     DevBuf<unsigned long long> dStats;
@@ -298,11 +310,14 @@ struct swsem {
     bool emitHostCopy = true;              // copy the streams to the host inside swsem_emit_batch
     // Warm-up positions of a speculative block chain (at most OVERLAP_MAX): a chain started from the empty state falls into step with the
     // true one after a few emissions, and how many positions that takes depends on the collection (on how far apart its matches
-    // lie). Too short and blocks are replayed by the stitch, one after the other; too long and every block scans positions twice.
-    // Adapted from the share of replayed blocks the last full batch reported (take_counts): the results never depend on it.
-    uint32_t overlap = 1024, batchBlocks = 0;
+    // lie). Too short and many blocks are rejected (replayed by k_stitch_replay, and by the stitch's walk itself where they follow each other);
+    // too long and every block scans positions twice. Adapted from the share of rejected blocks the last full batch reported
+    // (take_counts) unless SWSEM_OVERLAP fixes it: the results never depend on it.
+    uint32_t overlap = 1024, batchBlocks = 0, batchCands = 0;
     uint32_t rb = 8;                       // length of a resolve block in units of RBU positions: chosen per batch (batch_layout) unless SWSEM_RB fixes it
-    uint64_t stitchDiag[4] = {0, 0, 0, 0};  // over the handle's life: resolve blocks replayed / accepted in runs / tested one by one / jumped over (SWSEM_DEBUG_STATS)
+    // over the handle's life: resolve blocks replayed / accepted in runs / tested one by one / jumped over / replayed ahead of the walk
+    // (candidates) / of those taken by the walk / refused by it and replayed in place; [7] the most candidates one batch had (SWSEM_DEBUG_STATS)
+    uint64_t stitchDiag[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t slotPercent = 95;             // share of the wave slots a launch's blocks are sized for (80 %: +5 % on the 4.35e9-byte sizing, -3 % on configs[2]'s)
     uint32_t waveSlots = 256 * 4 * RESOLVE_WAVES_PER_SIMD;   // resolve waves the device holds at once (CUs x SIMDs x waves)
     std::vector<Contig> contigs;
@@ -311,7 +326,7 @@ struct swsem {
     const uint8_t *qdev = nullptr;         // query buffer of the last batch
     uint32_t minLen = 0;
     bool batchValid = false;
-    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // --- profiling
     bool prof = false;
     std::deque<ProfEvent> events;
