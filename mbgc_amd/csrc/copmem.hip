@@ -1,6 +1,6 @@
 // The `-m3` reverse-complement pass over the literal stream on an MI355X (include/mbgc_copmem.h):
 // SimpleSequenceMatcher::rcMatchSequence on CopMEMMatcher (matching/SimpleSequenceMatcher.cpp:165-176,
-// matching/copmem/CopMEMMatcher.cpp), single-thread semantics.
+// matching/copmem/CopMEMMatcher.cpp), single-thread semantics. Its inverse (restoreRCMatchedSequence, :178-211): copmem_restore.h.
 //
 //   index   every k1-th position is hashed (maRushPrime1HashSparsified<K>, utils/Hashes.h:47-68) into a bucket; a bucket keeps
 //           its first 13 positions in text order (genCumm / processRef, CopMEMMatcher.cpp:146-225). Here: one thread per sample
@@ -261,6 +261,8 @@ struct MaxOp { __device__ __host__ int32_t operator()(int32_t a, int32_t b) cons
 
 }  // namespace cm
 
+namespace cmr { struct State; }            // the inverse pass, copmem_restore.h
+
 struct mbgc_copmem {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -271,6 +273,7 @@ struct mbgc_copmem {
     cm::Buf<cm::Back> dIncoming, dLast;
     std::vector<mbgc_copmem_match_t> matches;
     std::vector<uint8_t> mapOff, mapLen;
+    cmr::State *restore = nullptr;         // made by the first mbgc_copmem_rc_restore_plan
 };
 
 namespace cm {
@@ -308,6 +311,8 @@ static void complements_lut(uint8_t *lut) {                              // PgHe
 
 }  // namespace cm
 
+#include "copmem_restore.h"
+
 extern "C" {
 
 const char *mbgc_copmem_last_error(void) { return cm::g_err.c_str(); }
@@ -333,6 +338,7 @@ void mbgc_copmem_destroy(mbgc_copmem_t *p) {
     p->dVals2.release(); p->dCounts.release(); p->dCapped.release(); p->dStartAll.release(); p->dCumm.release(); p->dSampled.release();
     p->dNpush.release(); p->dOff.release(); p->dDirty.release(); p->dNd.release(); p->dIdx.release(); p->dFrom.release();
     p->dRegions.release(); p->dTail.release(); p->dOut.release(); p->dIncoming.release(); p->dLast.release();
+    if (p->restore) { p->restore->release(); delete p->restore; }
     delete p;
 }
 
@@ -515,6 +521,19 @@ int mbgc_copmem_rc_match_sequence(mbgc_copmem_t *p, uint8_t *seq, uint64_t n, ui
     *mapOff = p->mapOff.data(); *mapOffLen = p->mapOff.size();
     *mapLen = p->mapLen.data(); *mapLenLen = p->mapLen.size();
     return 0;
+}
+
+int mbgc_copmem_rc_restore_plan(mbgc_copmem_t *p, const uint8_t *seq, uint64_t n, const uint8_t *mapOff, uint64_t mapOffLen, const uint8_t *mapLen,
+                                uint64_t mapLenLen, int offBytes, uint64_t *orgLen, uint64_t stats[4], double *kernel_ms) {
+    CCHK(hipSetDevice(p->device));
+    if (!p->restore) p->restore = new cmr::State();
+    return cmr::plan(*p->restore, p->stream, seq, n, mapOff, mapOffLen, mapLen, mapLenLen, offBytes, orgLen, stats, kernel_ms);
+}
+
+int mbgc_copmem_rc_restore_fill(mbgc_copmem_t *p, uint8_t *dst_dev, uint64_t cap, uint8_t *dst_host, double *kernel_ms, uint64_t *deepestChain) {
+    if (!p->restore) return cm::fail(-1, "no planned restore (mbgc_copmem_rc_restore_plan comes first)");
+    CCHK(hipSetDevice(p->device));
+    return cmr::fill(*p->restore, p->stream, p->device, dst_dev, cap, dst_host, kernel_ms, deepestChain);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
 #include "mbgc_decoder.h"
+#include "simple_sequence_matcher.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -282,13 +283,32 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     if (!readFile(prefix + ".meta", metaBytes)) return fail("cannot open " + prefix + ".meta (written by mbgc-hip c beside the streams)");
     MbgcMeta meta;
     { std::string e; if (!meta.parse(metaBytes, &e)) return fail(e); }
-    if (meta.rcRedundancyRemoval)
-        return fail("the streams were written with -m 3: its reverse-complement pass over the literal stream (rcMapOff / rcMapLen) is not inverted by mbgc-hip d");
+    if (meta.rcRedundancyRemoval && !opt.restoreRc)
+        return fail("the streams were written with -m 3: its reverse-complement pass over the literal stream (rcMapOff / rcMapLen) is not inverted by mbgc-hip d"
+                    " unless --restore-rc is given");
     static const char *NAMES[SWSEM_NSTREAMS] = {"literals", "mapOff", "mapOff5th", "mapLen", "gapDelta", "flags"};
     std::string stream[SWSEM_NSTREAMS], locksPos, refExtSize;
     for (int s = 0; s < SWSEM_NSTREAMS; s++)
         if (!readFile(prefix + "." + NAMES[s], stream[s])) return fail("cannot open " + prefix + "." + NAMES[s]);
     if (!readFile(prefix + ".locksPos", locksPos) || !readFile(prefix + ".refExtSize", refExtSize)) return fail("cannot open " + prefix + ".locksPos / .refExtSize");
+    // -m 3: the literals as they were before the reverse-complement pass cut them (MBGC_Decoder.cpp:1137), restored on the device
+    // before anything reads them; the meta's stream index holds offsets into the uncut literals
+    PgTools::SimpleSequenceMatcher::RestoreStats rcStats;
+    double rcRestoreMs = 0;
+    if (meta.rcRedundancyRemoval) {
+        std::string rcMapOff, rcMapLen;
+        if (!readFile(prefix + ".rcMapOff", rcMapOff) || !readFile(prefix + ".rcMapLen", rcMapLen)) return fail("cannot open " + prefix + ".rcMapOff / .rcMapLen");
+        const size_t uncut = meta.index.empty() ? PgTools::SimpleSequenceMatcher::UNKNOWN_LENGTH : (size_t) meta.index[meta.index.size() - SWSEM_NSTREAMS + SWSEM_LIT];
+        const std::string cutLiterals = opt.bench ? stream[SWSEM_LIT] : std::string();
+        for (int run = 0; run < (opt.bench ? 2 : 1); run++) {                                   // (bench: the second run is the timed one)
+            if (run) stream[SWSEM_LIT] = cutLiterals;
+            std::string e;
+            const double t0 = nowMs();
+            if (!PgTools::SimpleSequenceMatcher::restoreRCMatchedSequence(stream[SWSEM_LIT], rcMapOff, rcMapLen, uncut, opt.device, &e, &rcStats))
+                return fail("malformed stream set: " + e);
+            rcRestoreMs = nowMs() - t0;
+        }
+    }
     const size_t T = meta.targets.size();
     if (T == 0) return fail("malformed stream set: no target");
     if (locksPos.size() != T * sizeof(uint64_t)) return fail("malformed stream set: locksPos does not hold one position per target");
@@ -661,12 +681,17 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         }
     }
     if (opt.bench) {
-        const double ms = times.plan + times.fill + times.load;
+        // --restore-rc on -m 3 streams: the whole restore (upload of the cut literals, plan, fill, download) counts into the headline
+        char rcJson[160] = "";
+        if (meta.rcRedundancyRemoval)
+            snprintf(rcJson, sizeof rcJson, ", \"rc_restore_ms\": %.3f, \"rc_marks\": %llu, \"rc_max_chain\": %llu", rcRestoreMs,
+                     (unsigned long long) rcStats.marks, (unsigned long long) rcStats.maxChain);
+        const double ms = times.plan + times.fill + times.load + rcRestoreMs;
         printf("{\"metric\": \"output Gbases/s (decompress: streams in HBM to sequences in HBM)\", \"value\": %.4f, \"unit\": \"Gbases/s\", \"bases\": %llu, "
                "\"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, \"chain_starts\": %zu, \"plan_ms_per_target\": %.4f, \"waves\": %llu, "
-               "\"serial\": %s, \"index\": %s}\n",
+               "\"serial\": %s, \"index\": %s%s}\n",
                outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, starts.size(), times.plan / (double) T,
-               (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false");
+               (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false", rcJson);
     }
     if (opt.bench && wantFasta)
         printf("{\"metric\": \"FASTA text GB/s (format kernel)\", \"value\": %.4f, \"unit\": \"GB/s\", \"text_bytes\": %llu, \"batches\": %llu, "
@@ -687,17 +712,20 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         if (a == "--serial") opt.serial = true;
         else if (a == "--no-index") opt.noIndex = true;
         else if (a == "--bench") opt.bench = true;
+        else if (a == "--restore-rc") opt.restoreRc = true;
         else if (a == "--fasta" && i + 1 < argc) opt.fastaDir = argv[++i];
         else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
         else pos.push_back(a);
     }
     if (pos.size() != 2) {
-        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n"
+        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n"
                         "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
                         "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
                         "  --fasta dir: also the input FASTA files again, formatted on the device, as <dir>/<basename of each name of the list> (a .gz suffix\n"
                         "  is dropped: the text is written inflated; -i: the one file) from <streamsPrefix>.names / .headers / .dnaLineLengths\n"
-                        "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n");
+                        "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n"
+                        "  --restore-rc: streams of c -m 3 — the reverse-complement pass over the literals is inverted first, on the device, from\n"
+                        "  <streamsPrefix>.rcMapOff / .rcMapLen (without it such streams are refused; no effect on other streams)\n");
         return EXIT_FAILURE;
     }
     std::string error;

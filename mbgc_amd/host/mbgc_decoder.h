@@ -51,7 +51,8 @@ public:
         uint64_t loaded() const { return reachedRefLengthCount * (refTotalLength - 1) + (refPos - 1); }
     };
     struct ContigInfo { uint64_t length, unmatched; };
-    struct Options { bool serial = false, noIndex = false, bench = false; int device = 0; std::string fastaDir; };   // fastaDir: --fasta, empty = not asked for
+    // fastaDir: --fasta, empty = not asked for; restoreRc: --restore-rc, the -m 3 pass over the literals is inverted first
+    struct Options { bool serial = false, noIndex = false, bench = false, restoreRc = false; int device = 0; std::string fastaDir; };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
     static bool loadRef(RefState &st, int64_t contig, uint64_t textOffset, uint64_t seqLength, uint64_t refLockPos, bool loadRCRef,

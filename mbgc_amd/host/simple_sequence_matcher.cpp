@@ -2,6 +2,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "../../include/mbgc_copmem.h"
 
@@ -33,6 +34,32 @@ void SimpleSequenceMatcher::rcMatchSequence(std::string &sequence, std::string &
     rcMapOff.assign((const char *) off, nOff);
     rcMapLen.assign((const char *) len, nLen);
     mbgc_copmem_destroy(h);
+}
+
+bool SimpleSequenceMatcher::restoreRCMatchedSequence(std::string &sequence, std::string &rcMapOff, std::string &rcMapLen, size_t orgSrcLen,
+                                                     int device, std::string *error, RestoreStats *stats) {
+    mbgc_copmem_t *h = nullptr;
+    auto failed = [&](const std::string &m) {
+        if (h) mbgc_copmem_destroy(h);
+        if (!error) { fprintf(stderr, "%s\n\n", m.c_str()); exit(EXIT_FAILURE); }
+        *error = m;
+        return false;
+    };
+    if (mbgc_copmem_create(&h, device) != 0) return failed(mbgc_copmem_last_error());
+    const int offBytes = orgSrcLen == UNKNOWN_LENGTH ? 0 : (orgSrcLen <= UINT32_MAX ? 4 : 8);     // isSeqLengthStd, :183
+    uint64_t orgLen = 0, st[4] = {0, 0, 0, 0}, deepest = 0;
+    double planMs = 0, fillMs = 0;
+    if (mbgc_copmem_rc_restore_plan(h, (const uint8_t *) sequence.data(), sequence.size(), (const uint8_t *) rcMapOff.data(), rcMapOff.size(),
+                                    (const uint8_t *) rcMapLen.data(), rcMapLen.size(), offBytes, &orgLen, st, &planMs) != 0)
+        return failed(mbgc_copmem_last_error());
+    if (orgSrcLen != UNKNOWN_LENGTH && orgLen != orgSrcLen)
+        return failed("malformed rcMapOff / rcMapLen: they restore " + std::to_string(orgLen) + " bytes, " + std::to_string(orgSrcLen) + " were cut");
+    std::string restored(orgLen, '\0');
+    if (mbgc_copmem_rc_restore_fill(h, nullptr, orgLen, (uint8_t *) &restored[0], &fillMs, &deepest) != 0) return failed(mbgc_copmem_last_error());
+    mbgc_copmem_destroy(h);
+    sequence.swap(restored);
+    if (stats) { stats->marks = st[0]; stats->restoredFromMatches = st[1]; stats->maxChain = deepest; stats->minMatchLength = st[3]; stats->planMs = planMs; stats->fillMs = fillMs; }
+    return true;
 }
 
 }  // namespace PgTools

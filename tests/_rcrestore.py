@@ -1,0 +1,95 @@
+"""SimpleSequenceMatcher::restoreRCMatchedSequence (matching/SimpleSequenceMatcher.cpp:178-211) restated in Python, the whole of
+complementsLUT (utils/helper.cpp:312-361) included: the sequential loop — find a mark, read an offset (4 or 8 bytes) and a
+byte-frugal length, append the reverse complement of `substr(offset, length)` of what is restored so far. std::string::substr
+throws when the offset lies beyond the end and silently truncates a length that runs over it; so does this."""
+import numpy as np
+
+MARK = 0xA4                                              # MBGC_Params::RC_MATCH_MARK, '$' + 128
+
+
+def complements_lut():
+    """indexed by the byte; the constructor's loops stop before CHAR_MAX, so entry 127 stays 0"""
+    lut = np.arange(256, dtype=np.uint8)
+    lut[127] = 0
+    for a, b in zip(b"AaCcGgTtNnUuYyRrKkMmBbDdHhVvWwSs", b"TTGGCCAANNAARRYYMMKKVVHHDDBBSSWW"):
+        lut[a] = b
+    lut[ord("U")], lut[ord("u")] = ord("U"), ord("u")
+    for a, b in zip(b"acgtnyrkmbdhvws", b"tgcanrymkvhdbsw"):
+        lut[a] = b
+    return lut
+
+
+LUT = complements_lut()
+
+
+def put_byte_frugal(v):
+    """PgHelpers::writeUIntByteFrugal, utils/helper.cpp:217-225"""
+    out = bytearray()
+    while v >= 128:
+        out.append(128 + v % 128)
+        v //= 128
+    out.append(v)
+    return bytes(out)
+
+
+def read_byte_frugal(buf, at):
+    """PgHelpers::readUIntByteFrugal, utils/helper.h:232-241 -> (value, next position)"""
+    v, base = 0, 1
+    while True:
+        y = buf[at]
+        at += 1
+        v += base * (y % 128)
+        base *= 128
+        if y < 128:
+            return v, at
+
+
+def build_maps(min_len, matches, off_bytes=4):
+    """rcMapOff / rcMapLen for (source offset, length) pairs, as markAndRemoveExactMatches writes them"""
+    map_off = b"".join(int(s).to_bytes(off_bytes, "little") for s, _ in matches)
+    map_len = put_byte_frugal(min_len) + b"".join(put_byte_frugal(ln - min_len) for _, ln in matches)
+    return map_off, map_len
+
+
+def restore(cut, map_off, map_len, off_bytes=None):
+    """-> the restored bytes. off_bytes None: the reference's rule cannot be applied before the length is known — 4 is taken
+    (every test stream is far below 4 GiB); 8 reads the other layout."""
+    cut = bytes(cut)
+    w = off_bytes or 4
+    out = bytearray()
+    pos_dest = at_off = at_len = 0
+    min_len = 0
+    if map_len:
+        min_len, at_len = read_byte_frugal(map_len, 0)
+    while True:
+        mark = cut.find(MARK, pos_dest)
+        if mark < 0:
+            break
+        out += cut[pos_dest:mark]
+        pos_dest = mark + 1
+        src = int.from_bytes(map_off[at_off:at_off + w], "little")
+        at_off += w
+        ln, at_len = read_byte_frugal(map_len, at_len)
+        ln += min_len
+        if src > len(out):
+            raise IndexError("substr: the offset lies beyond the end")
+        piece = np.frombuffer(bytes(out[src:src + ln]), dtype=np.uint8)          # (a length over the end is truncated)
+        out += LUT[piece][::-1].tobytes()
+    out += cut[pos_dest:]
+    return bytes(out)
+
+
+CASES = ("planted", "long_copies", "manyfold", "short", "tiny")
+
+
+def inputs():
+    """the _rcdata cases the round trip runs on: the mark itself must not occur in an input of the forward pass, and 127 is the
+    one byte complementsLUT does not map back (both replaced by 'A'); lower case, N and the stream marks stay"""
+    import _rcdata
+    out = {}
+    for name, s in _rcdata.cases().items():
+        if name in CASES:
+            s = s.copy()
+            s[(s == MARK) | (s == 127)] = ord("A")
+            out[name] = s
+    return out
