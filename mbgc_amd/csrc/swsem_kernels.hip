@@ -601,7 +601,7 @@ __device__ __forceinline__ uint32_t window_hash(const RefView &v, const uint8_t 
     const uintptr_t A = (uintptr_t) (q + s);
     const uint32_t sh = (uint32_t) (A & 3);
     const uint32_t *A0 = (const uint32_t *) (A & ~(uintptr_t) 3);
-    const uint32_t ndw = (sh + (uint32_t) cnt + (uint32_t) v.K - 1u + 3u) >> 2;     // <= 64 (swsem_create checks K)
+    const uint32_t ndw = (sh + (uint32_t) cnt + (uint32_t) v.K - 1u + 3u) >> 2;     // <= 24 of the wave's 64 (K <= 56: init_params caps it, swsem_create does not check it)
     const uint32_t a = (uint32_t) lane < ndw ? A0[lane] : 0u;
     const uint32_t o = sh + (uint32_t) lane, wi = o >> 2, sft = o & 3u;
     const int nw = v.K / 4;

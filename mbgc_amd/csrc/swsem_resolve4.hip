@@ -38,6 +38,8 @@ constexpr int NL4 = SWSEM_VISIT_LANES; // lanes whose 16 reference bytes a visit
 #endif
 constexpr int RESOLVE4_WAVES_PER_SIMD = SWSEM_RESOLVE4_WAVES;   // the register budget the kernel is compiled for (80 vector registers at 6)
 constexpr int K_MAX4 = 40;             // window bytes GL + K - 1 (+3 of misalignment) must fit the group's 16 dwords
+// (init_params: a matching length L <= 62 gives K <= 40 and this kernel; L >= 63 gives K = 44, L > 110 K = 56, and those run
+// k_resolve_blocks, one chain per wave — which is also what SWSEM_CHAINS=1 selects at any K)
 
 __device__ __forceinline__ uint32_t gballot(bool p, uint32_t gbase) { return (uint32_t) (__ballot(p) >> gbase) & 0xFFFFu; }
 __device__ __forceinline__ uint32_t gread(uint32_t x, uint32_t srcLane) {

@@ -84,6 +84,10 @@ int main(int argc, char **argv) {
             params.k1 = atoi(argv[++i]);
             if (params.k1 <= 0) { fprintf(stderr, "s - reference sampling step - should be a positive integer.\n\n"); return EXIT_FAILURE; }
         }
+        else if (a == "-k" && i + 1 < argc) {                                    // matching k-mer length (MBGC_Params.h:583-591): the matcher's L, matchTexts' minimal length, .meta's k
+            params.k = atoi(argv[++i]);
+            if (params.k < 16 || params.k > 40) { fprintf(stderr, "k - matching kmer length - should be an integer between 16 and 40.\n\n"); return EXIT_FAILURE; }
+        }
         else if (a == "-i" && i + 1 < argc) params.inputFileName = argv[++i];      // single fasta file mode (MBGC_Params.h:793-803)
         else if (a == "--window-kib" && i + 1 < argc) params.singleFileWindow = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
@@ -107,7 +111,7 @@ int main(int argc, char **argv) {
     const bool single = !params.inputFileName.empty();
     if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
     if (pos.size() != 2 || (single && !pos[0].empty())) {
-        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
+        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
                         "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"

@@ -271,8 +271,11 @@ uint64_t orc_match_texts(orc_matcher *m, const uint8_t *q, uint64_t N2, uint32_t
                 p1++; p2++;
             }
             const int64_t lastDelta = p2 - (int64_t) lm->posDestText;          /* :264 */
+            /* lastDelta < 0: the last match was cut at its left end (:285-289) to begin BEHIND this hit's position, which is met when
+             * a skip margin above L sends the scan back inside it (:308-313). strcmplcp compares nothing for a length <= 0
+             * (utils/helper.cpp:559-580) and returns 0: the loop goes on, p1 / p2 move to the RIGHT by |lastDelta| */
             if (p1 - tmpStart1 < lastDelta || lm->length > OVERLAP_MATCH_MAX_LENGTH ||
-                memcmp(q + p2 - lastDelta, ref + p1 - lastDelta, (size_t) lastDelta) != 0) {   /* strcmplcp != 0 <=> differ */
+                (lastDelta > 0 && memcmp(q + p2 - lastDelta, ref + p1 - lastDelta, (size_t) lastDelta) != 0)) {   /* strcmplcp != 0 <=> differ */
                 p1--; p2--;
                 break;
             }

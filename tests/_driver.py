@@ -60,8 +60,9 @@ class Policy:
     def proper_for_rc_ext(self, n, unmatched): return unmatched * self.rc_factor > n
 
 
-def encode_sequential(matcher, emitter, files, policy=None, lazy=True):
-    """files: list of lists of contigs (uint8 arrays). Returns dict(locks=..., refExtSize=..., matches=[...])."""
+def encode_sequential(matcher, emitter, files, policy=None, lazy=True, min_len=32):
+    """files: list of lists of contigs (uint8 arrays). Returns dict(locks=..., refExtSize=..., matches=[...]).
+    min_len: matchTexts' minimal length, params->k (MGMP.cpp:274) — the matcher is built with the same value."""
     pol = policy or Policy()
     matcher.disable_sliding_window()                                   # MGMP.cpp:177-178
     matcher.load_ref(files[0][0], load_rc=True, add_sep=True, sep=0)   # :91-100 (first contig only), :183
@@ -70,7 +71,7 @@ def encode_sequential(matcher, emitter, files, policy=None, lazy=True):
     for fi, contigs in enumerate(files):
         start_pos = matcher.loaded_ref_length()
         for contig in contigs:
-            m = matcher.match(contig, 32, NO_LOCK)
+            m = matcher.match(contig, min_len, NO_LOCK)
             all_matches.append(m)
             unmatched = emitter.process(m, contig, NO_LOCK, pol.factor, 0, 0, loaded)
             if pol.proper_for_ext(contig.size, unmatched):
@@ -89,7 +90,7 @@ def encode_sequential(matcher, emitter, files, policy=None, lazy=True):
 
 
 def encode_rounds(matcher, make_emitter, g0, targets, round_size, policy=None, lazy=True, sw_factor=16, threads=1,
-                  keep_matches=True):
+                  keep_matches=True, min_len=32):
     """g0: list of contigs of the first file (reference only). targets: list of lists of contigs.
     make_emitter() -> fresh per-target emitter. Returns per-target streams merged in target order.
 
@@ -105,7 +106,7 @@ def encode_rounds(matcher, make_emitter, g0, targets, round_size, policy=None, l
     most targets hold a dissimilar contig, a pass over the rest of the round per stopped target.)
     threads > 1: the run-ahead part of a round goes to a thread pool (the reference is frozen meanwhile and the backends
     release the GIL: same results). keep_matches=False drops the match rows of finished targets (a 1000-genome run holds
-    48 M of them)."""
+    48 M of them). min_len: matchTexts' minimal length, params->k (MGMP.cpp:379)."""
     pol = policy or Policy()
     matcher.set_sliding_window_size(sw_factor)                         # MGMP.cpp:179-180
     g0cat = np.concatenate(g0)
@@ -142,7 +143,7 @@ def encode_rounds(matcher, make_emitter, g0, targets, round_size, policy=None, l
         out = []
         for ci in range(len(targets[t])):
             contig = targets[t][ci]
-            m = matcher.match(contig, 32, lock[t])
+            m = matcher.match(contig, min_len, lock[t])
             unmatched = em.process(m, contig, lock[t], pol.factor, processed, t, loaded_now)
             if unmatched == SKIPPED:
                 return out, ci

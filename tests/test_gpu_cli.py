@@ -415,3 +415,40 @@ def test_an_odd_sampling_step_through_the_cpp_host(tmp_path, k1, args, rs):
     for k in ("mapOff", "mapLen", "gapDelta", "flags"):
         assert got[k] == streams[k], k
     assert got["locksPos"] == res["locks"] and got["refExtSize"] == res["refExtSize"]
+
+
+def test_listeria_t1_with_another_kmer_length_equals_the_oracle_driver(tmp_path):
+    """`mbgc-hip c -t1 -k 24` (K = 20) on the three Listeria genomes: the streams the oracle writes when it is driven through the
+    reference's sequential target loop with L = 24 (tests/test_oracle_vs_ref.py pins that drive on the reference's own dumps at the
+    default length, and the oracle's matcher on the reference at this one)"""
+    exp = json.load(open(os.path.join(LIST, "expected_t1.json")))
+    paths = []
+    for f in exp["files"]:
+        (tmp_path / f).write_bytes(lzma.open(os.path.join(LIST, f + ".xz")).read())
+        paths.append(str(tmp_path / f))
+    (tmp_path / "seqlist.txt").write_text("\n".join(paths) + "\n")
+    out = run_tool(["c", "-t1", "-k", "24", "seqlist.txt", "lm"], str(tmp_path))
+    files = [_driver.parse_fasta(p) for p in paths]
+    lim, _ = _driver.ref_length_limit(len(files), os.path.getsize(paths[0]))
+    o = _orc.OracleMatcher(lim, L=24)
+    assert o.K() == 20
+    oe = _orc.OracleEmitter(o)
+    res = _driver.encode_sequential(o, oe, files, min_len=24)
+    streams = oe.streams()
+    nrows = sum(len(m) for m in res["matches"])
+    assert nrows > 29731 and any((np.asarray(m)[:, 1] == 24).any() for m in res["matches"] if len(m))     # (more than at the default length)
+    assert ("exact matches total: %d" % nrows) in out
+    got = {k: (tmp_path / ("lm." + k)).read_bytes() for k in ("literals", "mapOff", "mapLen", "gapDelta", "flags", "locksPos", "refExtSize")}
+    assert got["literals"] == files[0][0].tobytes() + b"\xa2" + streams["literals"]
+    for k in ("mapOff", "mapLen", "gapDelta", "flags"):
+        assert got[k] == streams[k], k
+    assert got["locksPos"] == res["locks"] and got["refExtSize"] == res["refExtSize"]
+    o.close()
+
+
+@pytest.mark.parametrize("k", ["15", "41"])
+def test_a_kmer_length_out_of_range_is_refused(tmp_path, k):
+    """setKmerLength (MBGC_Params.h:583-591): the reference's message and exit code, before anything is read"""
+    r = subprocess.run([TOOL, "c", "-k", k, "nowhere.txt", "o"], cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and "k - matching kmer length - should be an integer between 16 and 40." in r.stderr, r.stderr
+    assert not os.listdir(str(tmp_path))

@@ -89,6 +89,8 @@ CASES = [
     (["-L", "-R", "3"], 7), (["-L", "-t1"], 5),
     (["-s", "15", "-R", "3"], 6), (["-s", "15", "-t1"], 5),
     (["-U", "-R", "4"], 9),
+    # other matching lengths (-k: the matcher's L, matchTexts' minimal length and .meta's k): K = 12, 20, 28 (L = 40) and 16
+    (["-k", "16", "-R", "3"], 7), (["-k", "24", "-t1"], 5), (["-k", "40", "-R", "3"], 7), (["-k", "20", "-m", "2", "-R", "3"], 7),
 ]
 
 
@@ -98,6 +100,8 @@ def test_collection_comes_back(tmp_path, args, n):
     paths = write_collection(tmp, n, 100_000 + 2000 * n)
     tool(["c"] + args + ["list.txt", "out"], tmp)
     assert os.path.exists(os.path.join(tmp, "out.meta"))
+    if "-k" in args:
+        assert _meta.parse(open(os.path.join(tmp, "out.meta"), "rb").read())["k"] == int(args[args.index("-k") + 1])
     out = decode_three_ways(tmp, "out")
     check_outputs(tmp, "d0", expected(paths, "-U" in args))
     m = re.search(r"waves: (\d+) for (\d+) targets", out)

@@ -422,3 +422,111 @@ def test_an_odd_sampling_step_takes_the_identity_encoded_matcher(refh, k1, L, se
             r.release_lock(lock); assert o.release_lock(lock) == 0
         assert_same_state(r, o)
     assert o.loaded_ref_length() > 89_999 + 40_000 and nm > 500      # wrapped (with locks the window clips what a round loads)
+
+
+# ---- the k-mer length axis: one matching length L per K the reference instantiates its hash for (.cpp:57-66, 74-87). The
+# reference build makes a matcher at every one of these L (refm_create builds it as MGMP.cpp:170-176 does), so none is left out.
+import _kmer
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("L", _kmer.LS)
+def test_params_and_table_image_at_every_kmer_length(refh, L):
+    """K() and hash_size() for a small and a large buffer, and — the hash itself, maRushPrime1HashSimplified<K> — the table image
+    and loader state after G0 and its reverse complement"""
+    for lim in (1 << 20, 300_000_000):
+        r, o = both(refh, lim, L=L)
+        assert r.K() == o.K() == _kmer.K_OF_L[L] and r.hash_size() == o.hash_size()
+        r.close(); o.close()
+    g0 = _kmer.related(1, 80_000, 300 + L)[0]
+    r, o = both(refh, 1 << 20, L=L)
+    for m in (r, o):
+        m.load_ref(g0, load_rc=True, add_sep=True)
+    assert_same_state(r, o)
+    assert int((o.ht() != 0).sum()) > 9_000                            # (160 000 bytes sampled every 16th)
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("L,k1", [(L, 16) for L in _kmer.LS] + [(16, 5), (64, 15)])
+def test_match_rows_through_a_wrap_at_every_kmer_length(refh, L, k1):
+    """the schedule of test_an_odd_sampling_step_takes_the_identity_encoded_matcher (a 90 000-byte buffer, 12 steps, locks,
+    separators, reverse-complement loads) at every K with the default step, and with an odd one at K = 12 and K = 44: match
+    rows, table image and loader state equal the reference's. Oracle rows over the 12 steps (all / of length exactly L), k1 = 16:
+    L=16 3032/18, L=20 2163/9, L=24 4142/32, L=28 1801/19, L=32 2838/21, L=44 1638/36, L=48 2191/33, L=56 1034/23, L=64 2276/59,
+    L=120 436/9; L=16 k1=5 3692/72, L=64 k1=15 1510/53."""
+    r, o = refh.RefMatcher(90_000, L=L, k1=k1), _orc.OracleMatcher(90_000, L=L, k1=k1)
+    assert r.K() == o.K() == _kmer.K_OF_L[L] and r.hash_size() == o.hash_size()
+    rows = []
+    for step, (g, rc, sep) in enumerate(_kmer.wrap_steps(L, 900 + L + k1, steps=12)):
+        lr, lo = r.acquire_lock(), o.acquire_lock()
+        assert lr == lo
+        mr, mo = r.match(g, L, lr), o.match(g, L, lo)
+        assert np.array_equal(mr, mo), step
+        rows.append(mo)
+        for m in (r, o):
+            m.load_ref(g, load_rc=rc, add_sep=True)
+            if sep:
+                m.load_separator(0)
+        r.release_lock(lr); assert o.release_lock(lo) == 0
+        assert_same_state(r, o)
+    assert o.loaded_ref_length() > 89_999 + 40_000                    # wrapped
+    print("L=%d k1=%d: %d rows, %d of length L" % ((L, k1) + _kmer.assert_covered(rows, L, "wrap")))
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("L", [16, 32, 64])
+def test_the_length_filter_of_match_texts(refh, L):
+    """matchTexts keeps what is at least minMatchLength long (.cpp:283-286): exact copies of L - 1, L and L + 1 bases, each between
+    two mismatches (_kmer.planted) — the reference's rows and the oracle's are the same, copies of L bases are among them and none
+    of L - 1 (that the shorter copies reach the filter at all: they hold sampled K-mers as the longer ones do, L - K of 16 phases).
+    Oracle rows (all / of length exactly L): L=16 82/35, L=32 88/40, L=64 256/128."""
+    ref, q = _kmer.planted(L)
+    r, o = both(refh, 1 << 20, L=L)
+    for m in (r, o):
+        m.load_ref(ref, load_rc=True, add_sep=True)
+    mr, mo = r.match(q, L), o.match(q, L)
+    assert np.array_equal(mr, mo)
+    n, exact = _kmer.assert_covered([mo], L, "planted")
+    print("L=%d: %d rows, %d of length L" % (L, n, exact))
+    assert not (mo[:, 1] == L - 1).any() and (mo[:, 1] == L + 1).any()
+    # the same query with a shorter minimal length: the copies of L - 1 bases ARE found (the filter, not the hash, drops them above)
+    if L - 1 >= _kmer.K_OF_L[L] and L > 16:
+        assert (o.match(q, L - 1)[:, 1] == L - 1).any()
+
+
+class _Both:
+    """a matcher for tests/_driver.py that drives the reference and the oracle together and compares every call's rows"""
+
+    def __init__(self, r, o):
+        self.r, self.o, self.rows = r, o, []
+
+    def __getattr__(self, name):
+        def call(*a, **k):
+            getattr(self.r, name)(*a, **k)
+            return getattr(self.o, name)(*a, **k)
+        return call
+
+    def match(self, q, min_len, lock):
+        mr, mo = self.r.match(q, min_len, lock), self.o.match(q, min_len, lock)
+        assert np.array_equal(mr, mo), "contig %d: %d rows from the reference, %d from the oracle" % (len(self.rows), len(mr), len(mo))
+        self.rows.append(mo)
+        return mo
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("L,margin,mode", [(16, 24, 2), (20, 24, 2), (16, 20, 1), (16, 40, 2), (32, 48, 1)])
+def test_a_skip_margin_above_the_matching_length(refh, L, margin, mode):
+    """`-k 16 -m 2` (skip margin 24) and its like: a match shorter than the margin sends the scan on by ONE position (.cpp:308-313),
+    back inside a match whose left end was cut behind that position (:285-289); the next hit there meets a NEGATIVE lastDelta
+    (:264), for which strcmplcp compares nothing and returns 0 (utils/helper.cpp:559-580) — the loop goes on and p1 / p2 move to
+    the right. The restatement took such a hit for a failed comparison: on these contigs (the sequential drive, five genomes
+    2 % apart) its rows differed from the reference's from the eighth contig on (L = 16, margin 24: 316 / 440 rows against the
+    reference's 317 / 437) while the device path had them right. Rows and state through the whole drive."""
+    gs = _kmer.related(5, 70_000, 500 + L)[:5]
+    files = [[g[:30_000], g[30_000:]] for g in gs]
+    lim, _ = _driver.ref_length_limit(len(files), 70_000)
+    r, o = both(refh, lim, L=L, skip_margin=margin)
+    m = _Both(r, o)
+    _driver.encode_sequential(m, _orc.OracleEmitter(o, _orc.emit_params(mode)), files, _driver.Policy(mode), min_len=L)
+    assert_same_state(r, o)
+    print("L=%d margin=%d: %d rows, %d of length L" % ((L, margin) + _kmer.assert_covered(m.rows, L, "margin")))
