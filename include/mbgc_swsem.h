@@ -268,9 +268,24 @@ int swsem_decode_plan_chain_dev(swsem_t *h, const swsem_emit_params_t *p, const 
                                 const uint32_t *seqCount, const uint64_t *lockPos, uint64_t ncontigs, swsem_chain_contig_t *out,
                                 int *firstBadChain);
 /* The bytes of planned contigs [c0, c1): contig c to dest_dev + destOff[c] (destOff: host, one entry per planned contig + 1),
- * against the reference buffer as it stands, one launch for the range, queued on the handle's stream. *nbad (may be NULL; then
+ * against the reference buffer as it stands, one launch for the range, queued on the handle's stream. Only the contigs of the
+ * range need a place: destOff[c + 1] - destOff[c] may be 0 for a contig that is never filled. *nbad (may be NULL; then
  * nothing is waited for) = contigs of the range whose bytes did not come out as planned. */
 int swsem_decode_fill_range_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *dest_dev, const uint64_t *destOff, uint64_t *nbad);
+/* The dependency closure of a set of planned contigs (`mbgc-hip d --select`), after swsem_decode_plan_chain_dev and before any
+ * fill: which contigs must be filled and loaded so that the chosen ones come out right. The loader only moves forward, so a
+ * load has a virtual position lap x refTotalLength + refPos; rows: the load schedule as a table sorted by it, without
+ * overlaps — the load at [vstart, vstart + len) wrote bytes of planned contig `owner` (-1: nobody's, the initial reference
+ * or a separator). timeOf[c]: the loader's virtual position just before contig c's own first load in serial order, the state
+ * it is filled against. units: the fill units in the order they run (a unit's contigs read nothing the unit itself loads).
+ * need: one bit per planned contig (bit c & 31 of word c >> 5), in: the chosen contigs, out: those and every contig whose loads
+ * wrote a byte that a record of a needed contig reads — a superset of what is read (the records' ranges are the read hull's,
+ * a byte wider at a right extension's ends), never a subset. One upload, the units swept in reverse order with one launch
+ * each and nothing waited for between them, one download. The records stay as the plan left them. */
+typedef struct { uint64_t vstart, len; int64_t owner; } swsem_prov_row_t;
+typedef struct { uint64_t c0, c1; } swsem_fill_unit_t;
+int swsem_decode_closure_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_t *rows, uint64_t ncontigs,
+                             const uint64_t *timeOf, uint64_t nunits, const swsem_fill_unit_t *units, uint32_t *need);
 /* MBGC_Decoder::loadRef as a schedule: segments applied to the reference buffer in order. src: offset into src_dev (the decoded
  * contigs), or a reference position (FROM_REF: the per-target reverse complement of :608-616); dst: reference position;
  * RC: upperReverseComplement of the len source bytes; BYTE: the single byte `src & 0xFF` (a region separator). */

@@ -19,6 +19,8 @@
 //                   (MBGC_Decoder::decodeTarget :535-634) and carries the six cursors from one to the next — per target with the
 //                   stream index of <prefix>.meta, one chain for everything without; no reference byte is read;
 //   k_decode_load   MBGC_Decoder::loadRef (:651-675) as the host scheduled it: copies, reverse complements, separator bytes;
+//   k_decode_closure  (`d --select`) the contigs whose loads wrote what a needed contig's records read, from the plan's records
+//                   and the load schedule alone, before a base exists;
 // k_decode_fill then fills a wave of planned contigs against the decoder's reference buffer (swsem_create_decoder: no table).
 // The contigs of a round are independent (each stands against the reference as its lock position froze it) and are decoded
 // side by side. Used as the device-side check of an emission (swsem_emit_verify: what was just emitted must decode to the
@@ -344,6 +346,24 @@ __device__ uint32_t plan_next_len(Plan &d, bool frugal) {
 // what the records of a contig read of the reference buffer: matches and both extensions (a little wider at the right
 // extension's ends, never narrower)
 struct DecHull { uint64_t minSrc, maxSrcEnd; };
+// The reference bytes one record reads, as up to three ranges [lo, hi): the match, the left extension (dec_left_write reads
+// leftLen bytes downwards from leftSrcMatch - 1) and the right extension (dec_extend_right reads from the contig position +
+// offsetDelta on; a byte wider at either end, never narrower). The one place this arithmetic lives: plan_contig folds the
+// ranges into the contig's hull, which the wave test trusts, and k_decode_closure follows every one of them to the contigs
+// whose loads wrote the bytes — so the closure is never narrower than the hull.
+struct DecRange { uint64_t lo, hi; };
+__device__ __forceinline__ int rec_read_ranges(const DecRec &r, DecRange out[3]) {
+    if (r.flags & REC_TAIL) return 0;
+    int n = 0;
+    out[n].lo = r.src; out[n].hi = r.src + r.len; n++;
+    if (r.leftLen) { out[n].lo = (uint64_t) (r.leftSrcMatch - (int64_t) r.leftLen); out[n].hi = (uint64_t) r.leftSrcMatch; n++; }
+    if (r.rightLen) {
+        const uint64_t plain = (r.mark - r.litFrom) - r.leftCodes;
+        const int64_t lo = (int64_t) (r.destAt + plain + r.leftLen + r.len) + r.offsetDelta - 1;
+        out[n].lo = lo < 0 ? 0 : (uint64_t) lo; out[n].hi = out[n].lo + r.rightLen + 2; n++;
+    }
+    return n;
+}
 // The automaton over one contig: d stands at the contig's start in every stream (its windows loaded anywhere), the contig's
 // literals end at seqEnd; the other streams go on as far as the contig reads them. Leaves the records in out[0, *nrec) and
 // d at the contig's end (d.bad set: malformed, nothing else valid).
@@ -409,13 +429,6 @@ __device__ void plan_contig(const swsem_emit_params_t &p, Plan &d, const uint64_
         if (matchSrcPos > refBytes || matchLength > refBytes - matchSrcPos) d.bad = 1;   // (a match outside the reference buffer: malformed)
         if (d.bad) break;
         rec.src = matchSrcPos; rec.len = matchLength;
-        if (matchSrcPos < hull.minSrc) hull.minSrc = matchSrcPos;
-        if (matchSrcPos + matchLength > hull.maxSrcEnd) hull.maxSrcEnd = matchSrcPos + matchLength;
-        if (rec.leftLen) {                                                    // (dec_left_write reads leftLen bytes downwards from leftSrcMatch - 1)
-            const uint64_t lo = (uint64_t) (rec.leftSrcMatch - (int64_t) rec.leftLen);
-            if (lo < hull.minSrc) hull.minSrc = lo;
-            if ((uint64_t) rec.leftSrcMatch > hull.maxSrcEnd) hull.maxSrcEnd = (uint64_t) rec.leftSrcMatch;
-        }
         markPos = plan_find_mark(d, d.litPos);
         uint32_t gapDelta = 0;
         if (p.gapDepthOffsetEncoding && markPos != DEC_NPOS && markPos < seqEnd) {
@@ -457,11 +470,13 @@ __device__ void plan_contig(const swsem_emit_params_t &p, Plan &d, const uint64_
             rec.flags |= REC_RIGHT; rec.offsetDelta = offsetDelta; rec.guardLit = guardLit;
             extRightLen = plan_extend_right(d, isGap, gapStart, gapMiddle, gapEnd, guardLit);
             rec.rightLen = (uint32_t) extRightLen;
-            if (extRightLen) {                                                // (dec_extend_right reads from the contig position + offsetDelta on)
-                const int64_t lo = (int64_t) (d.destLen - extRightLen) + offsetDelta - 1;
-                if (lo < 0) hull.minSrc = 0; else if ((uint64_t) lo < hull.minSrc) hull.minSrc = (uint64_t) lo;
-                const uint64_t hi = (uint64_t) (lo < 0 ? 0 : lo) + extRightLen + 2;
-                if (hi > hull.maxSrcEnd) hull.maxSrcEnd = hi;
+        }
+        {   // what the record reads of the reference buffer, into the contig's hull
+            DecRange rg[3];
+            const int nr = rec_read_ranges(rec, rg);
+            for (int q = 0; q < nr; q++) {
+                if (rg[q].lo < hull.minSrc) hull.minSrc = rg[q].lo;
+                if (rg[q].hi > hull.maxSrcEnd) hull.maxSrcEnd = rg[q].hi;
             }
         }
         if (l0) out[j] = rec;
@@ -740,6 +755,58 @@ __global__ void __launch_bounds__(256) k_decode_fill(const uint8_t *__restrict__
         if (bad && (int) lane == l) d.bad = 1;
     }
     if (d.bad) atomicOr(&badFlags[c], 1u);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the dependency closure of a selection (`mbgc-hip d --select`): which contigs' loads wrote the bytes a contig reads
+// ------------------------------------------------------------------------------------------------------------------
+// The loader only moves forward, so every load has a virtual position lap x refTotalLength + refPos, and the schedule is a
+// table sorted by it: rows {vstart, len, owner}, owner = the planned contig whose bytes the load wrote (PROV_NONE: the
+// initial reference, a separator). A contig stands against the buffer as the loader left it just before the contig's own
+// first load in serial order: its time, the loader's virtual position then. A physical position p maps to the largest
+// virtual position below that time that lies at p: this lap below the loader's position, the lap before from it on (nothing
+// before the first lap). One thread per record of a contig whose need bit is set: its read ranges (rec_read_ranges), mapped,
+// a binary search, a walk over the rows the range overlaps, the owners' need bits set. The units run in reverse order, one
+// launch each: a contig reads only what units in front of its own loaded (firstOfUnit: an owner from it on is never read,
+// its bit stays as it is), so the bit of a block's own contig is final when the block reads it, and one pass is the fixpoint.
+// A superset, never a subset: the ranges are the hull's (a byte wider at the right extension's ends), and a separator that
+// overwrote a byte of a segment is not in the table.
+struct ProvRow { uint64_t vstart, len; int64_t owner; };           // == swsem_prov_row_t
+constexpr int64_t PROV_NONE = -1;
+__device__ __forceinline__ void closure_mark(const ProvRow *__restrict__ rows, uint64_t nrows, uint64_t va, uint64_t vb, uint32_t *need, uint32_t firstOfUnit) {
+    uint64_t lo = 0, hi = nrows;                                              // the first row that ends behind va
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (rows[mid].vstart + rows[mid].len > va) hi = mid; else lo = mid + 1;
+    }
+    for (; lo < nrows && rows[lo].vstart < vb; lo++) {
+        const int64_t o = rows[lo].owner;
+        if (o < 0 || o >= (int64_t) firstOfUnit) continue;
+        const uint32_t bit = 1u << ((uint32_t) o & 31u);
+        if (!(need[o >> 5] & bit)) atomicOr(&need[o >> 5], bit);              // (a plain read first: most owners are marked already)
+    }
+}
+__global__ void __launch_bounds__(256) k_decode_closure(const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase, const DecPlanOut *__restrict__ plans,
+                                                        const ProvRow *__restrict__ rows, uint64_t nrows, const uint64_t *__restrict__ timeOf, uint32_t *need,
+                                                        uint64_t refTotalLength, uint32_t c0, uint32_t firstOfUnit) {
+    const uint32_t c = c0 + blockIdx.y;                                     // (grid.y holds at most 65 535: slices, as k_decode_fill)
+    if (!((need[c >> 5] >> (c & 31u)) & 1u)) return;                          // nobody asked for this contig
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (plans[c].unmatched < 0 || i >= plans[c].nrec) return;
+    const DecRec r = recs[recBase[c] + i];
+    DecRange rg[3];
+    const int nr = rec_read_ranges(r, rg);
+    const uint64_t tv = timeOf[c], lap = tv / refTotalLength, refPos = tv % refTotalLength;
+    for (int q = 0; q < nr; q++) {
+        const uint64_t a = rg[q].lo, b = rg[q].hi < refTotalLength ? rg[q].hi : refTotalLength;   // (nothing is loaded beyond the buffer)
+        if (a >= b) continue;
+        // a range that straddles the loader's position is split there
+        if (a < refPos) closure_mark(rows, nrows, lap * refTotalLength + a, lap * refTotalLength + (b < refPos ? b : refPos), need, firstOfUnit);
+        if (b > refPos && lap) {
+            const uint64_t base = (lap - 1) * refTotalLength;
+            closure_mark(rows, nrows, base + (a > refPos ? a : refPos), base + b, need, firstOfUnit);
+        }
+    }
 }
 
 // the contig the streams gave back against the one that was encoded: first differing byte per contig (DEC_NPOS: equal)

@@ -622,6 +622,14 @@ int swsem_decode_fill_range_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *d
     return SWSEM_OK;
 }
 
+int swsem_decode_closure_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_t *rows, uint64_t ncontigs, const uint64_t *timeOf,
+                             uint64_t nunits, const swsem_fill_unit_t *units, uint32_t *need) {
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->decoder) return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: the handle is no decoder's (swsem_create_decoder)");
+    if (!timeOf || !need || (nrows && !rows) || (nunits && !units)) return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: a table is missing");
+    return decode_closure(h, refTotalLength, nrows, rows, ncontigs, timeOf, nunits, units, need);
+}
+
 int swsem_decode_load_dev(swsem_t *h, const uint8_t *src_dev, int n, const swsem_load_seg_t *segs) {
     HIPCHK(hipSetDevice(h->device));
     return decode_load(h, src_dev, n, segs);

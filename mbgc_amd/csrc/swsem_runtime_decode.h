@@ -119,13 +119,15 @@ int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const u
             for (int st = 0; st < SWSEM_NSTREAMS; st++) { j.stream[st] = C.streams.p[st]; j.size[st] = C.streams.n[st]; }
             j.size[SWSEM_LIT] = C.litEnd[c];                                  // (the fill reads literals up to the contig's separator, flags as far as the plan said)
             j.refLockPos = C.lock[c]; j.dest = dest + destOff[c]; j.destCap = destOff[c + 1] - destOff[c]; j.expect = nullptr;
-            if (j.destCap < C.destLen[c]) return fail(SWSEM_EINVAL, "swsem_decode_fill_range_dev: contig %llu does not fit its place", (unsigned long long) c);
         }
         if ((r = h->dJobs.reserve(C.n))) return r;
         HIPCHK(hipMemcpyAsync(h->dJobs.p, jobs.data(), C.n * sizeof(DecodeJob), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));                               // (the table is pageable host memory)
         C.jobsDest = dest;
     }
+    // (a contig that is never filled needs no place: a selection's buffer holds the contigs of its closure only)
+    for (uint64_t c = c0; c < c1; c++)
+        if (destOff[c + 1] - destOff[c] < C.destLen[c]) return fail(SWSEM_EINVAL, "swsem_decode_fill_range_dev: contig %llu does not fit its place", (unsigned long long) c);
     constexpr uint64_t YMAX = 65535;
     for (uint64_t a = c0; a < c1; a += YMAX) {
         const uint64_t cn = std::min<uint64_t>(YMAX, c1 - a);
@@ -135,6 +137,43 @@ int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const u
         if (maxRec) k_decode_fill<<<dim3((unsigned) ((maxRec + 255) / 256), (unsigned) cn), dim3(256), 0, h->stream>>>(h->ref, C.params, h->dJobs.p, h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dBad.p, h->maxRefLength + REF_SLACK, (uint32_t) a);
     }
     HIPCHK(hipGetLastError());
+    return SWSEM_OK;
+}
+
+// The dependency closure of the contigs whose need bits are set (k_decode_closure): table, times and bitmap go up once, the
+// fill units are swept in reverse order, one launch each (slices of 65 535 contigs), back to back on the handle's stream with
+// nothing waited for between them; then the bitmap comes down.
+int decode_closure(swsem *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_t *rows, uint64_t ncontigs, const uint64_t *timeOf,
+                   uint64_t nunits, const swsem_fill_unit_t *units, uint32_t *need) {
+    static_assert(sizeof(ProvRow) == sizeof(swsem_prov_row_t) && sizeof(ProvRow) == 24, "swsem_prov_row_t");
+    auto &C = h->chain;
+    if (ncontigs != C.n || ncontigs == 0 || ncontigs > 0xFFFFFFFFull) return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: %llu contigs, %llu planned", (unsigned long long) ncontigs, (unsigned long long) C.n);
+    if (refTotalLength == 0) return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: reference length");
+    for (uint64_t k = 0; k < nrows; k++) {
+        if (rows[k].owner >= (int64_t) ncontigs || (k && rows[k].vstart < rows[k - 1].vstart + rows[k - 1].len))
+            return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: row %llu of the provenance table is out of order or names no planned contig", (unsigned long long) k);
+    }
+    for (uint64_t u = 0; u < nunits; u++)
+        if (units[u].c0 > units[u].c1 || units[u].c1 > ncontigs) return fail(SWSEM_EINVAL, "swsem_decode_closure_dev: unit %llu leaves the plan", (unsigned long long) u);
+    const size_t words = (size_t) ((ncontigs + 31) / 32);
+    int r;
+    if ((r = C.dProv.reserve(nrows + 1)) || (r = C.dTime.reserve(ncontigs)) || (r = C.dNeed.reserve(words))) return r;
+    if (nrows) HIPCHK(hipMemcpyAsync(C.dProv.p, rows, nrows * sizeof(ProvRow), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dTime.p, timeOf, ncontigs * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dNeed.p, need, words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    constexpr uint64_t YMAX = 65535;
+    for (uint64_t u = nunits; u-- > 0;) {
+        for (uint64_t a = units[u].c0; a < units[u].c1; a += YMAX) {
+            const uint64_t cn = std::min<uint64_t>(YMAX, units[u].c1 - a);
+            uint64_t maxRec = 0;
+            for (uint64_t c = a; c < a + cn; c++) maxRec = std::max(maxRec, C.nrec[c]);
+            if ((maxRec + 255) / 256 > 0x7FFFFFFFull) return fail(SWSEM_EINVAL, "swsem decode: a contig too long for one launch");
+            if (maxRec) k_decode_closure<<<dim3((unsigned) ((maxRec + 255) / 256), (unsigned) cn), dim3(256), 0, h->stream>>>(h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dProv.p, nrows, C.dTime.p, C.dNeed.p, refTotalLength, (uint32_t) a, (uint32_t) units[u].c0);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(need, C.dNeed.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SWSEM_OK;
 }
 

@@ -282,6 +282,9 @@ struct swsem {
         DevBuf<uint32_t> dSeqCount, dChainBad, dBad;
         DevBuf<uint64_t> dLock, dRecBase;
         DevBuf<LoadSeg> dSegs;
+        DevBuf<ProvRow> dProv;               // the closure of a selection: provenance table, per-contig times, need bitmap
+        DevBuf<uint64_t> dTime;
+        DevBuf<uint32_t> dNeed;
         ChainStreams streams = {};
         swsem_emit_params_t params = {};
         uint64_t n = 0;                      // contigs planned

@@ -191,7 +191,124 @@ struct DevFree {
     ~DevFree() { for (void *p : ptrs) if (p) swsem_dev_free(h, p); if (h) swsem_destroy(h); }
 };
 struct Interval { uint64_t from, to; };
-struct PassTimes { double plan = 0, fill = 0, load = 0; uint64_t waves = 0, widest = 0; };
+struct PassTimes { double plan = 0, closure = 0, fill = 0, load = 0; uint64_t waves = 0, widest = 0; };
+
+// ---- the provenance table: whose bytes lie where in the reference buffer, at every moment
+// The loader only moves forward, so a load has a virtual position lap x refTotalLength + refPos and the schedule is a table
+// sorted by it. Only loads of planned contigs have rows: the initial reference and the separators are nobody's (they cost
+// nothing: G0 is literals). A FROM_REF segment (the per-target reverse complement of :608-616) is resolved at once into the
+// contigs whose loads wrote its source range, mirrored. THE SUPERSET RULE: a separator that later overwrote one byte of a
+// segment (the lazy mode's mark at the lock position) is ignored — the byte keeps its owner; with the read ranges of the
+// records, which are the read hull's, the closure that follows from this table may hold more than what is read, never less.
+struct Provenance {
+    uint64_t L = 0, cur = REF_SHIFT;                               // the loader's virtual position (refPos == L: (lap + 1) x L)
+    std::vector<swsem_prov_row_t> rows;
+
+    // the owned pieces of physical range [p0, p1) as the loader left the buffer at virtual position tv: f(physFrom, physTo, owner).
+    // Below the loader's position the bytes are this lap's, from it on the lap before's (before the first lap: never written);
+    // a range that straddles the position is split there. (k_decode_closure: the same on the device.)
+    template <class F> void query(uint64_t tv, uint64_t p0, uint64_t p1, F f) const {
+        if (p1 > L) p1 = L;
+        if (p0 >= p1) return;
+        const uint64_t lap = tv / L, rp = tv % L;
+        auto part = [&](uint64_t a, uint64_t b, uint64_t base) {
+            const uint64_t va = base + a, vb = base + b;
+            size_t i = (size_t) (std::partition_point(rows.begin(), rows.end(), [&](const swsem_prov_row_t &r) { return r.vstart + r.len <= va; }) - rows.begin());
+            for (; i < rows.size() && rows[i].vstart < vb; i++)
+                f(std::max(va, rows[i].vstart) - base, std::min(vb, rows[i].vstart + rows[i].len) - base, rows[i].owner);
+        };
+        if (p0 < rp) part(p0, std::min(p1, rp), lap * L);
+        if (p1 > rp && lap) part(std::max(p0, rp), p1, (lap - 1) * L);
+    }
+    // the next segment of the schedule, in serial order; contigs from firstPlanned on are the planned ones (owner = contig - firstPlanned)
+    void add(const LoadSegment &s, uint64_t firstPlanned) {
+        if (s.length == 0) return;
+        if (s.contig == LoadSegment::SEPARATOR && s.length == 1 && (s.refPos + 1) % L == cur % L) return;   // written over the last loaded byte: the superset rule
+        const uint64_t v = cur + (s.refPos + L - cur % L) % L;      // the next virtual position that lies at refPos
+        if (s.contig == LoadSegment::FROM_REF) {
+            std::vector<swsem_prov_row_t> got;
+            query(cur, s.offset, s.offset + s.length, [&](uint64_t a, uint64_t b, int64_t owner) {
+                const uint64_t at = s.reverseComplement ? s.length - (b - s.offset) : a - s.offset;
+                got.push_back({v + at, b - a, owner});
+            });
+            std::sort(got.begin(), got.end(), [](const swsem_prov_row_t &x, const swsem_prov_row_t &y) { return x.vstart < y.vstart; });
+            rows.insert(rows.end(), got.begin(), got.end());
+        } else if (s.contig >= 0 && (uint64_t) s.contig >= firstPlanned)
+            rows.push_back({v, s.length, (int64_t) ((uint64_t) s.contig - firstPlanned)});
+        cur = v + s.length;
+    }
+};
+
+// ---- the fill units: what is filled by one launch, and the loads that follow it. A wave — targets [t0, t1) whose contigs
+// stand against the same frozen buffer, all their segments behind the fill — or one contig of a target that goes alone with
+// segments [sA, sB) of that target (c0 == c1: a target without a contig, only its segments). counted: the targets the unit
+// adds to the `waves:` line (a target that goes alone counts once, on its first unit).
+struct FillUnit { uint64_t c0, c1; size_t t0, t1, sA, sB; uint64_t counted; bool wave; };
+
+// The partition of the targets into fill units, from the plan's read hulls and the load schedule alone.
+// segAt[t][i]: segments [segAt[t][i], segAt[t][i + 1]) of target t belong to its contig i; what follows its last contig goes
+// with that one — a separator written at the lock position goes with the contig whose load reached it.
+static std::vector<FillUnit> partitionUnits(const std::vector<uint32_t> &seqCount, const std::vector<uint64_t> &lock, const std::vector<std::vector<LoadSegment>> &tSegs,
+                                            const std::vector<swsem_chain_contig_t> &cc, uint64_t g0n, bool everyContigAlone, std::vector<std::vector<size_t>> &segAt) {
+    const size_t T = seqCount.size();
+    std::vector<FillUnit> units;
+    segAt.assign(T, std::vector<size_t>());
+    std::vector<Interval> written;                                                              // what the current wave's loads will write
+    auto addWrites = [&](std::vector<Interval> &w, const std::vector<LoadSegment> &segs, size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) {
+            if (!w.empty() && w.back().to == segs[i].refPos) w.back().to += segs[i].length;
+            else w.push_back({segs[i].refPos, segs[i].refPos + segs[i].length});
+        }
+    };
+    auto reads = [&](const std::vector<Interval> &w, uint64_t c) {
+        if (cc[c].minSrc >= cc[c].maxSrcEnd) return false;
+        for (const Interval &i : w) if (cc[c].minSrc < i.to && i.from < cc[c].maxSrcEnd) return true;
+        return false;
+    };
+    FillUnit wave = {};
+    uint64_t waveLock = 0;
+    auto closeWave = [&]() { if (wave.counted) units.push_back(wave); wave = FillUnit(); written.clear(); };
+    uint64_t c = 0;
+    for (size_t t = 0; t < T; t++) {
+        const uint64_t c1 = c + seqCount[t];
+        const std::vector<LoadSegment> &segs = tSegs[t];
+        std::vector<size_t> &at = segAt[t];
+        at.assign(seqCount[t] + 1, segs.size());
+        {
+            size_t lastOwn = 0;                                                                 // behind the last segment that is a contig's
+            for (size_t i = 0; i < segs.size(); i++) if (segs[i].contig >= 0) lastOwn = i + 1;
+            size_t i = 0;
+            for (uint32_t s = 0; s < seqCount[t]; s++) {
+                at[s] = i;
+                if (s + 1 == seqCount[t]) break;
+                while (i < lastOwn && (segs[i].contig < 0 || segs[i].contig <= (int64_t) (g0n + c + s))) i++;
+            }
+        }
+        // Every target of an encoder round holds one lock position and was matched against the buffer the round found: it may be
+        // filled beside the targets in front of it as long as nothing it reads is written by their loads. -t1 streams carry the
+        // window's end 0 (no window): contig c + 1 may match contig c, the target goes alone, contig by contig.
+        bool side = !everyContigAlone && lock[t] != 0;
+        std::vector<Interval> own;
+        for (uint32_t s = 0; side && s < seqCount[t]; s++) {
+            if (reads(own, c + s)) side = false;
+            addWrites(own, segs, at[s], at[s + 1]);
+        }
+        bool join = side && wave.counted && lock[t] == waveLock;
+        for (uint64_t k = c; join && k < c1; k++) if (reads(written, k)) join = false;
+        if (!join) closeWave();
+        if (side) {
+            if (!wave.counted) { wave.c0 = c; wave.t0 = t; wave.wave = true; waveLock = lock[t]; }
+            wave.c1 = c1; wave.t1 = t + 1; wave.counted++;
+            addWrites(written, segs, 0, segs.size());
+        } else {
+            for (uint32_t s = 0; s < seqCount[t]; s++) units.push_back({c + s, c + s + 1, t, t + 1, at[s], at[s + 1], s == 0 ? 1u : 0u, false});
+            if (seqCount[t] == 0) units.push_back({c, c, t, t + 1, 0, segs.size(), 1, false});
+        }
+        c = c1;
+    }
+    closeWave();
+    return units;
+}
 
 // ---- --fasta: the layout beside the streams (<prefix>.names / .headers / .dnaLineLengths, written by mbgc-hip c)
 static const uint64_t FASTA_BATCH_TEXT = 256ull << 20;            // text bytes of a batch of whole units (a larger unit is a batch of its own)
@@ -232,6 +349,18 @@ static std::string outputName(const std::string &name) {
 }
 }
 
+// the lines of <prefix>.names, held to the meta: one per unit (G0, then every target), one for a single-FASTA collection
+static bool parseNames(const std::string &names, const MbgcMeta &meta, std::vector<std::string> &out, std::string &msg) {
+    const size_t T = meta.targets.size();
+    if (!names.empty() && names.back() != '\n') { msg = "malformed .names: the last line does not end"; return false; }
+    for (size_t at = 0; at < names.size();) { const size_t e = names.find('\n', at); out.push_back(names.substr(at, e - at)); at = e + 1; }
+    if (out.size() != (meta.singleFastaFile ? 1 : T + 1)) {
+        msg = "malformed .names: " + std::to_string(out.size()) + " names for " + std::to_string(meta.singleFastaFile ? 1 : T + 1) + " units";
+        return false;
+    }
+    return true;
+}
+
 // reads and checks the three side files against the meta: false and a message, or the layout
 static bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t contigs, FastaLayout &L, std::string &msg) {
     std::string names, lens;
@@ -241,12 +370,7 @@ static bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uin
             return false;
         }
     const size_t T = meta.targets.size();
-    if (!names.empty() && names.back() != '\n') { msg = "malformed .names: the last line does not end"; return false; }
-    for (size_t at = 0; at < names.size();) { const size_t e = names.find('\n', at); L.names.push_back(names.substr(at, e - at)); at = e + 1; }
-    if (L.names.size() != (meta.singleFastaFile ? 1 : T + 1)) {
-        msg = "malformed .names: " + std::to_string(L.names.size()) + " names for " + std::to_string(meta.singleFastaFile ? 1 : T + 1) + " units";
-        return false;
-    }
+    if (!parseNames(names, meta, L.names, msg)) return false;
     if (!L.headers.empty() && L.headers.back() != '\n') { msg = "malformed .headers: the last header does not end"; return false; }
     for (size_t at = 0; at < L.headers.size();) {
         const char *e = (const char *) memchr(L.headers.data() + at, '\n', L.headers.size() - at);
@@ -367,8 +491,31 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         starts.push_back(c);
     }
 
+    // ---- --select: the units to bring back (G0, then every target), by the names mbgc-hip c wrote beside the streams
+    const bool selecting = !opt.select.empty();
+    std::vector<char> unitSel(T + 1, 1);
+    uint64_t selectedFiles = 0;
+    if (selecting) {
+        if (meta.singleFastaFile) return fail("--select: the streams hold one FASTA file (mbgc-hip c -i): it has one name, there is nothing to select");
+        std::vector<std::string> own;
+        if (!wantFasta) {
+            std::string bytes, m;
+            if (!readFile(prefix + ".names", bytes)) return fail("malformed stream set: cannot open " + prefix + ".names (--select needs the names mbgc-hip c writes beside the streams)");
+            if (!parseNames(bytes, meta, own, m)) return fail(m);
+        }
+        const std::vector<std::string> &names = wantFasta ? layout.names : own;
+        // (-t1: the first file is G0's unit and target 0; the selection is over output files, and G0's unit is none of them)
+        for (size_t u = 0; u <= T; u++) {
+            unitSel[u] = 0;
+            if (u == 0 && meta.sequentialMatching) continue;
+            for (const std::string &pat : opt.select) if (names[u].find(pat) != std::string::npos) unitSel[u] = 1;   // MBGC_Decoder.cpp:1022-1025
+            selectedFiles += unitSel[u];
+        }
+        if (!selectedFiles) return fail("--select: no file of the collection matches (" + std::to_string(opt.select.size()) + " patterns against " + prefix + ".names)");
+    }
+
     PassTimes times;
-    uint64_t totalBases = 0, outBases = 0;
+    uint64_t outBases = 0, outContigs = 0, plannedBases = 0, closureContigs = 0, closureBases = 0, dependencyTargets = 0;
     const int passes = opt.bench ? 2 : 1;                                                        // (bench: the second pass is the timed one)
     for (int pass = 0; pass < passes; pass++) {
         times = PassTimes();
@@ -398,20 +545,6 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         contigLen.resize(g0n);
         for (uint64_t c = 0; c < planned; c++) contigLen.push_back(cc[c].destLen);
         const uint64_t N = g0n + planned;
-        std::vector<uint64_t> seqOff(N + 1, 0);
-        for (uint64_t c = 0; c < N; c++) seqOff[c + 1] = seqOff[c] + contigLen[c];
-        totalBases = seqOff[N];
-        void *seqp = nullptr;
-        if (swsem_dev_malloc(h, totalBases + 64, &seqp)) return hipFail("sequences");
-        dev.ptrs.push_back(seqp);
-        uint8_t *seqDev = (uint8_t *) seqp;
-        {   // G0's bytes are literals
-            uint64_t at = 0;
-            for (uint64_t g = 0; g < g0n; g++) {
-                if (swsem_dev_copy(h, seqDev + seqOff[g], sdev[SWSEM_LIT] + at, contigLen[g])) return hipFail("initial reference");
-                at += contigLen[g] + 1;
-            }
-        }
         // ---- the load schedule: complete before a base exists
         RefState st;
         st.refTotalLength = meta.maxRefLength; st.lazyDecompressionSupport = lazy;
@@ -433,14 +566,78 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 c += seqCount[t];
             }
         }
-        auto toAbi = [&](const std::vector<LoadSegment> &in, size_t a, size_t b, std::vector<swsem_load_seg_t> &out) {
+        if (st.reachedRefLengthCount != meta.reachedRefLengthCount || (meta.finalRefLength && (st.reachedRefLengthCount ? st.refTotalLength : st.refPos) != meta.finalRefLength))
+            return fail("malformed stream set: the rebuilt reference ends at " + std::to_string(st.refPos) + " after " + std::to_string(st.reachedRefLengthCount) +
+                        " laps, the encoder's at " + std::to_string(meta.finalRefLength) + " after " + std::to_string(meta.reachedRefLengthCount));
+        // ---- waves (DESIGN.md): targets whose contigs stand against the same frozen buffer are filled by one launch
+        std::vector<std::vector<size_t>> segAt;
+        const std::vector<FillUnit> units = partitionUnits(seqCount, lock, tSegs, cc, g0n, opt.serial || meta.sequentialMatching, segAt);
+        // ---- --select: the closure, before a base exists. mark[c]: 0 = not filled, 1 = filled as a dependency, 2 = filled because selected
+        std::vector<uint8_t> mark(planned, selecting ? 0 : 2);
+        std::vector<char> targetRuns(T, 1);
+        if (selecting) {
+            std::vector<uint32_t> need((planned + 31) / 32, 0);
+            std::vector<uint64_t> timeOf(planned, 0);
+            t0 = nowMs();
+            Provenance prov;
+            prov.L = meta.maxRefLength;
+            for (const LoadSegment &s : g0Segs) prov.add(s, g0n);
+            uint64_t c = 0;
+            for (size_t t = 0; t < T; t++) {
+                // a contig's time: the loader's position just before its own first load in serial order — the state --serial fills it against
+                uint32_t s = 0;
+                for (size_t i = 0; i <= tSegs[t].size(); i++) {
+                    for (; s < seqCount[t] && segAt[t][s] == i; s++) timeOf[c + s] = prov.cur;
+                    if (i < tSegs[t].size()) prov.add(tSegs[t][i], g0n);
+                }
+                if (unitSel[t + 1]) for (uint32_t k = 0; k < seqCount[t]; k++) { mark[c + k] = 2; need[(c + k) >> 5] |= 1u << ((c + k) & 31); }
+                c += seqCount[t];
+            }
+            std::vector<swsem_fill_unit_t> sweep;
+            for (const FillUnit &u : units) if (u.c1 > u.c0) sweep.push_back({u.c0, u.c1});
+            if (planned && swsem_decode_closure_dev(h, prov.L, prov.rows.size(), prov.rows.data(), planned, timeOf.data(), sweep.size(), sweep.data(), need.data()))
+                return hipFail("closure");
+            times.closure = nowMs() - t0;
+            closureContigs = closureBases = dependencyTargets = 0;
+            c = 0;
+            for (size_t t = 0; t < T; t++) {
+                bool any = false;
+                for (uint32_t k = 0; k < seqCount[t]; k++, c++) {
+                    if (!mark[c] && ((need[c >> 5] >> (c & 31)) & 1u)) mark[c] = 1;
+                    if (mark[c]) { any = true; closureContigs++; closureBases += contigLen[g0n + c]; }
+                }
+                targetRuns[t] = any;
+                if (any && !unitSel[t + 1]) dependencyTargets++;
+            }
+        }
+        // the sequence buffer: G0, then the contigs that are filled — HBM and the download scale with the closure
+        std::vector<uint64_t> seqOff(N + 1, 0);
+        for (uint64_t c = 0; c < N; c++) seqOff[c + 1] = seqOff[c] + (c < g0n || mark[c - g0n] ? contigLen[c] : 0);
+        const uint64_t totalBases = seqOff[N];
+        void *seqp = nullptr;
+        if (swsem_dev_malloc(h, totalBases + 64, &seqp)) return hipFail("sequences");
+        dev.ptrs.push_back(seqp);
+        uint8_t *seqDev = (uint8_t *) seqp;
+        {   // G0's bytes are literals
+            uint64_t at = 0;
+            for (uint64_t g = 0; g < g0n; g++) {
+                if (swsem_dev_copy(h, seqDev + seqOff[g], sdev[SWSEM_LIT] + at, contigLen[g])) return hipFail("initial reference");
+                at += contigLen[g] + 1;
+            }
+        }
+        // (a selection: only the segments whose contig is filled are loaded — separators and G0 always, a target's own reverse
+        // complement when any of its contigs is filled; what is left out is read by nothing that is filled)
+        auto toAbi = [&](const std::vector<LoadSegment> &in, size_t a, size_t b, bool targetRuns, std::vector<swsem_load_seg_t> &out) {
             for (size_t i = a; i < b; i++) {
                 const LoadSegment &s = in[i];
                 swsem_load_seg_t g = {};
                 g.dst = s.refPos; g.len = s.length;
                 if (s.contig == LoadSegment::SEPARATOR) { g.flags = SWSEM_SEG_BYTE; g.src = REF_REGION_SEPARATOR; }
-                else if (s.contig == LoadSegment::FROM_REF) { g.flags = SWSEM_SEG_FROM_REF | (s.reverseComplement ? SWSEM_SEG_RC : 0); g.src = s.offset; }
-                else { g.flags = s.reverseComplement ? SWSEM_SEG_RC : 0; g.src = seqOff[s.contig] + s.offset; }
+                else if (s.contig == LoadSegment::FROM_REF) { if (!targetRuns) continue; g.flags = SWSEM_SEG_FROM_REF | (s.reverseComplement ? SWSEM_SEG_RC : 0); g.src = s.offset; }
+                else {
+                    if ((uint64_t) s.contig >= g0n && !mark[s.contig - g0n]) continue;
+                    g.flags = s.reverseComplement ? SWSEM_SEG_RC : 0; g.src = seqOff[s.contig] + s.offset;
+                }
                 out.push_back(g);
             }
         };
@@ -461,91 +658,45 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             return r ? 1 : (nbad ? 2 : 0);
         };
         std::vector<swsem_load_seg_t> abi;
-        toAbi(g0Segs, 0, g0Segs.size(), abi);
+        toAbi(g0Segs, 0, g0Segs.size(), true, abi);
         if (!load(abi)) return hipFail("initial reference");
-        // ---- waves (DESIGN.md): targets whose contigs stand against the same frozen buffer are filled by one launch
-        std::vector<Interval> written;                                                          // what the current wave's loads will write
-        auto addWrites = [&](std::vector<Interval> &w, const std::vector<LoadSegment> &segs, size_t a, size_t b) {
-            for (size_t i = a; i < b; i++) {
-                if (!w.empty() && w.back().to == segs[i].refPos) w.back().to += segs[i].length;
-                else w.push_back({segs[i].refPos, segs[i].refPos + segs[i].length});
-            }
-        };
-        auto reads = [&](const std::vector<Interval> &w, uint64_t c) {
-            if (cc[c].minSrc >= cc[c].maxSrcEnd) return false;
-            for (const Interval &i : w) if (cc[c].minSrc < i.to && i.from < cc[c].maxSrcEnd) return true;
-            return false;
-        };
-        uint64_t waveC0 = 0, waveC1 = 0, waveLock = 0, waveTargets = 0;
-        std::vector<swsem_load_seg_t> waveSegs;
-        auto closeWave = [&]() -> int {
-            if (!waveTargets) return 0;
-            const int r = fill(waveC0, waveC1);
-            if (r) return r;
-            if (!load(waveSegs)) return 1;
-            times.waves++; times.widest = std::max(times.widest, waveTargets);
-            waveTargets = 0; written.clear();
-            return 0;
-        };
-        uint64_t c = 0;
-        for (size_t t = 0; t < T; t++) {
-            const uint64_t c1 = c + seqCount[t];
-            const std::vector<LoadSegment> &segs = tSegs[t];
-            // segments [segAt[i], segAt[i + 1]) belong to contig i of the target; what follows its last contig goes with that one
-            // — a separator written at the lock position goes with the contig whose load reached it
-            std::vector<size_t> segAt(seqCount[t] + 1, segs.size());
-            {
-                size_t lastOwn = 0;                                                             // behind the last segment that is a contig's
-                for (size_t i = 0; i < segs.size(); i++) if (segs[i].contig >= 0) lastOwn = i + 1;
-                size_t i = 0;
-                for (uint32_t s = 0; s < seqCount[t]; s++) {
-                    segAt[s] = i;
-                    if (s + 1 == seqCount[t]) break;
-                    while (i < lastOwn && (segs[i].contig < 0 || segs[i].contig <= (int64_t) (g0n + c + s))) i++;
-                }
-            }
-            // Every target of an encoder round holds one lock position and was matched against the buffer the round found: it may be
-            // filled beside the targets in front of it as long as nothing it reads is written by their loads. -t1 streams carry the
-            // window's end 0 (no window): contig c + 1 may match contig c, the target goes alone, contig by contig.
-            bool side = !opt.serial && !meta.sequentialMatching && lock[t] != 0;
-            std::vector<Interval> own;
-            for (uint32_t s = 0; side && s < seqCount[t]; s++) {
-                if (reads(own, c + s)) side = false;
-                addWrites(own, segs, segAt[s], segAt[s + 1]);
-            }
-            bool join = side && waveTargets && lock[t] == waveLock;
-            for (uint64_t k = c; join && k < c1; k++) if (reads(written, k)) join = false;
-            if (!join) {
-                const int r = closeWave();
+        // ---- the forward run: every unit's fill, then its loads (a selection: the runs of filled contigs inside the unit, one launch each)
+        for (const FillUnit &u : units) {
+            for (uint64_t c = u.c0; c < u.c1;) {
+                if (!mark[c]) { c++; continue; }
+                uint64_t e = c;
+                while (e < u.c1 && mark[e]) e++;
+                const int r = fill(c, e);
                 if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
+                c = e;
             }
-            if (side) {
-                if (!waveTargets) { waveC0 = c; waveLock = lock[t]; }
-                waveC1 = c1; waveTargets++;
-                addWrites(written, segs, 0, segs.size());
-                toAbi(segs, 0, segs.size(), waveSegs);
-            } else {
-                for (uint32_t s = 0; s < seqCount[t]; s++) {
-                    const int r = fill(c + s, c + s + 1);
-                    if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
-                    toAbi(segs, segAt[s], segAt[s + 1], abi);
-                    if (!load(abi)) return hipFail("load");
-                }
-                if (seqCount[t] == 0) { toAbi(segs, 0, segs.size(), abi); if (!load(abi)) return hipFail("load"); }
-                times.waves++; times.widest = std::max<uint64_t>(times.widest, 1);
+            uint64_t width = 0;
+            for (size_t t = u.t0; t < u.t1; t++) {
+                toAbi(tSegs[t], u.wave ? 0 : u.sA, u.wave ? tSegs[t].size() : u.sB, targetRuns[t], abi);
+                width += targetRuns[t] ? 1 : 0;
             }
-            c = c1;
-        }
-        {
-            const int r = closeWave();
-            if (r) return r == 2 ? fail("malformed stream set: the bytes of a contig do not come out as planned") : hipFail("fill");
+            if (!load(abi)) return hipFail("load");
+            if (!selecting) width = u.counted;
+            if (u.counted && width) { times.waves++; times.widest = std::max(times.widest, width); }
         }
         if (swsem_synchronize(h)) return hipFail("decode");
-        if (st.reachedRefLengthCount != meta.reachedRefLengthCount || (meta.finalRefLength && (st.reachedRefLengthCount ? st.refTotalLength : st.refPos) != meta.finalRefLength))
-            return fail("malformed stream set: the rebuilt reference ends at " + std::to_string(st.refPos) + " after " + std::to_string(st.reachedRefLengthCount) +
-                        " laps, the encoder's at " + std::to_string(meta.finalRefLength) + " after " + std::to_string(meta.reachedRefLengthCount));
         const uint64_t outFrom = meta.sequentialMatching ? g0n : 0;                               // (-t1: the initial reference is the first contig of target 0 again)
-        outBases = totalBases - seqOff[outFrom];
+        // what is written: the chosen units' contigs, in collection order, as ranges [from, to) of the collection's contigs
+        std::vector<Interval> outRanges;
+        outBases = outContigs = plannedBases = 0;
+        {
+            uint64_t c = 0;
+            for (size_t u = 0; u <= T; u++) {
+                const uint64_t n = u == 0 ? g0n : seqCount[u - 1];
+                if (unitSel[u] && c + n > outFrom && n) {
+                    const uint64_t from = std::max(c, outFrom);
+                    if (!outRanges.empty() && outRanges.back().to == from) outRanges.back().to = c + n; else outRanges.push_back({from, c + n});
+                }
+                c += n;
+            }
+            for (const Interval &r : outRanges) for (uint64_t k = r.from; k < r.to; k++) { outBases += contigLen[k]; outContigs++; }
+            for (uint64_t k = g0n; k < N; k++) plannedBases += contigLen[k];
+        }
         if (wantFasta) {
             // ---- the FASTA files again: units in order, batches of whole units of at most FASTA_BATCH_TEXT bytes of
             // text; a batch is formatted on the device, downloaded into one of two page-locked buffers, and written by a thread of
@@ -553,6 +704,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             ftimes = FastaTimes();
             auto faFail = [&](const char *what) { return fail(std::string(what) + ": " + mbgc_fasta_last_error()); };
             std::vector<FastaUnit> units;
+            std::vector<char> fileWanted(layout.outNames.size(), 0);
             {
                 uint64_t c = 0;
                 for (size_t u = 0; u <= T; u++) {
@@ -560,7 +712,9 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                     FastaUnit x = {c, c + n, layout.lineLen[u], 0, 0};
                     c += n;
                     if (u == 0 && meta.sequentialMatching) continue;
+                    if (!unitSel[u]) continue;                                                  // (--select: no other file is made, empty ones included)
                     x.file = meta.singleFastaFile ? 0 : u - (meta.sequentialMatching ? 1 : 0);
+                    fileWanted[x.file] = 1;
                     for (uint64_t k = x.c0; k < x.c1; k++) x.text += recordText(layout.hdrLen[k], contigLen[k], x.lineLen);
                     units.push_back(x);
                 }
@@ -665,17 +819,27 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             // (files of units without a record exist too, empty)
             if (writeFiles)
                 for (size_t f = 0; f < opened.size(); f++)
-                    if (!opened[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f], "", 0)) return fail("cannot write under " + opt.fastaDir);
+                    if (!opened[f] && fileWanted[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f], "", 0)) return fail("cannot write under " + opt.fastaDir);
         }
 
         if (pass + 1 == passes && !opt.bench) {
             std::string seq(outBases, '\0');
-            if (outBases && swsem_dev_download(h, &seq[0], seqDev + seqOff[outFrom], outBases)) return hipFail("download");
+            std::vector<uint64_t> outLens;
+            {
+                uint64_t at = 0;
+                for (const Interval &r : outRanges) {                                           // (a unit's contigs lie back to back in the buffer)
+                    const uint64_t n = seqOff[r.to] - seqOff[r.from];
+                    if (n && swsem_dev_download(h, &seq[at], seqDev + seqOff[r.from], n)) return hipFail("download");
+                    at += n;
+                    outLens.insert(outLens.end(), contigLen.begin() + r.from, contigLen.begin() + r.to);
+                }
+            }
             std::vector<uint32_t> counts;
-            if (!meta.sequentialMatching) counts.push_back(meta.g0Contigs);
-            for (size_t t = 0; t < T; t++) counts.push_back(seqCount[t]);
+            if (!meta.sequentialMatching && unitSel[0]) counts.push_back(meta.g0Contigs);
+            for (size_t t = 0; t < T; t++) if (unitSel[t + 1]) counts.push_back(seqCount[t]);
+            if (!opt.closureOut.empty() && !writeFile(opt.closureOut, mark.data(), mark.size())) return fail("cannot write " + opt.closureOut);
             if (!writeFile(outPrefix + ".seq", seq.data(), seq.size()) ||
-                !writeFile(outPrefix + ".contigLens", contigLen.data() + outFrom, (contigLen.size() - outFrom) * sizeof(uint64_t)) ||
+                !writeFile(outPrefix + ".contigLens", outLens.data(), outLens.size() * sizeof(uint64_t)) ||
                 !writeFile(outPrefix + ".seqCounts", counts.data(), counts.size() * sizeof(uint32_t)))
                 return fail("cannot write " + outPrefix + ".seq / .contigLens / .seqCounts");
         }
@@ -686,27 +850,35 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         if (meta.rcRedundancyRemoval)
             snprintf(rcJson, sizeof rcJson, ", \"rc_restore_ms\": %.3f, \"rc_marks\": %llu, \"rc_max_chain\": %llu", rcRestoreMs,
                      (unsigned long long) rcStats.marks, (unsigned long long) rcStats.maxChain);
-        const double ms = times.plan + times.fill + times.load + rcRestoreMs;
+        char selJson[256] = "";
+        if (selecting)
+            snprintf(selJson, sizeof selJson, ", \"closure_ms\": %.3f, \"closure_contigs\": %llu, \"closure_bases\": %llu, \"selected_targets\": %llu, \"dependency_targets\": %llu",
+                     times.closure, (unsigned long long) closureContigs, (unsigned long long) closureBases, (unsigned long long) selectedFiles, (unsigned long long) dependencyTargets);
+        const double ms = times.plan + times.closure + times.fill + times.load + rcRestoreMs;
         printf("{\"metric\": \"output Gbases/s (decompress: streams in HBM to sequences in HBM)\", \"value\": %.4f, \"unit\": \"Gbases/s\", \"bases\": %llu, "
                "\"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, \"chain_starts\": %zu, \"plan_ms_per_target\": %.4f, \"waves\": %llu, "
-               "\"serial\": %s, \"index\": %s%s}\n",
+               "\"serial\": %s, \"index\": %s%s%s}\n",
                outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, starts.size(), times.plan / (double) T,
-               (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false", rcJson);
+               (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false", rcJson, selJson);
     }
     if (opt.bench && wantFasta)
         printf("{\"metric\": \"FASTA text GB/s (format kernel)\", \"value\": %.4f, \"unit\": \"GB/s\", \"text_bytes\": %llu, \"batches\": %llu, "
                "\"format_kernel_ms\": %.3f, \"download_ms\": %.3f, \"write_ms\": %.3f}\n",
                ftimes.format > 0 ? ftimes.text / (ftimes.format * 1e-3) / 1e9 : 0.0, (unsigned long long) ftimes.text, (unsigned long long) ftimes.batches,
                ftimes.format, ftimes.download, ftimes.write);
+    if (selecting)
+        printf("closure: %llu of %llu contigs, %llu of %llu bases, %llu selected, %llu dependency targets\n", (unsigned long long) closureContigs, (unsigned long long) planned,
+               (unsigned long long) closureBases, (unsigned long long) plannedBases, (unsigned long long) selectedFiles, (unsigned long long) dependencyTargets);
     printf("waves: %llu for %zu targets\n", (unsigned long long) times.waves, T);
     printf("widest wave: %llu targets\n", (unsigned long long) times.widest);
-    printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) (contigLen.size() - (meta.sequentialMatching ? g0n : 0)), (unsigned long long) outBases);
+    printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) outContigs, (unsigned long long) outBases);
     return 0;
 }
 
 int mbgc_hip_decompress_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     std::vector<std::string> pos;
+    bool selectAsked = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--serial") opt.serial = true;
@@ -714,20 +886,38 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--bench") opt.bench = true;
         else if (a == "--restore-rc") opt.restoreRc = true;
         else if (a == "--fasta" && i + 1 < argc) opt.fastaDir = argv[++i];
+        else if (a == "--select" && i + 1 < argc) { opt.select.push_back(argv[++i]); selectAsked = true; }
+        else if (a == "--select-list" && i + 1 < argc) {
+            std::ifstream f(argv[++i]);
+            if (!f) { fprintf(stderr, "mbgc-hip d: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
+            for (std::string line; std::getline(f, line);) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                if (!line.empty()) opt.select.push_back(line);
+            }
+            selectAsked = true;
+        }
+        else if (a == "--closure-out" && i + 1 < argc) opt.closureOut = argv[++i];
         else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
         else pos.push_back(a);
     }
     if (pos.size() != 2) {
-        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n"
+        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir] [--select pattern]... [--select-list file]\n"
+                        "                  [--closure-out file] [-d device] <streamsPrefix> <outputPrefix>\n"
                         "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
                         "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
                         "  --fasta dir: also the input FASTA files again, formatted on the device, as <dir>/<basename of each name of the list> (a .gz suffix\n"
                         "  is dropped: the text is written inflated; -i: the one file) from <streamsPrefix>.names / .headers / .dnaLineLengths\n"
                         "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n"
                         "  --restore-rc: streams of c -m 3 — the reverse-complement pass over the literals is inverted first, on the device, from\n"
-                        "  <streamsPrefix>.rcMapOff / .rcMapLen (without it such streams are refused; no effect on other streams)\n");
+                        "  <streamsPrefix>.rcMapOff / .rcMapLen (without it such streams are refused; no effect on other streams)\n"
+                        "  --select pattern (repeatable) / --select-list file (a pattern per line): only the files whose line in <streamsPrefix>.names\n"
+                        "  contains a pattern, and the contigs they depend on, are decoded; the outputs and --fasta hold the chosen files only\n"
+                        "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n");
         return EXIT_FAILURE;
     }
+    if (selectAsked) for (const std::string &pat : opt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip d: --select: an empty pattern\n"); return EXIT_FAILURE; }
+    if (selectAsked && opt.select.empty()) { fprintf(stderr, "mbgc-hip d: --select-list: the list of patterns is empty\n"); return EXIT_FAILURE; }
+    if (!selectAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
     std::string error;
     if (MBGC_Decoder::decode(pos[0], pos[1], opt, &error) != 0) {
         fprintf(stderr, "mbgc-hip d: %s\n", error.c_str());
@@ -757,6 +947,31 @@ int mbgc_decoder_schedule(uint64_t *refPos, uint64_t *reachedRefLengthCount, uin
     }
     *refPos = st.refPos; *reachedRefLengthCount = st.reachedRefLengthCount;
     return 0;
+}
+
+// The provenance table over a schedule (segs: rows of {contig, offset, length, refPos, rc} in serial order, as mbgc_decoder_schedule
+// writes them; contigs from firstPlanned on are owners, the loader starts at refPos 1 before the first lap), asked as the loader
+// stood just before segment nBefore (nsegs: behind them all): the owned pieces of physical range [p0, p1) as rows of
+// {physFrom, physTo, owner = contig - firstPlanned}. 0, or -2 (cap too small; *nout = the rows needed).
+int mbgc_decoder_provenance(const int64_t *segs, uint64_t nsegs, uint64_t refTotalLength, uint64_t firstPlanned, uint64_t nBefore, uint64_t p0, uint64_t p1,
+                            int64_t *out, uint64_t cap, uint64_t *nout) {
+    if (refTotalLength < 2 || nBefore > nsegs) return -1;
+    Provenance prov;
+    prov.L = refTotalLength;
+    uint64_t tv = prov.cur;
+    for (uint64_t i = 0; i < nsegs; i++) {
+        const LoadSegment s = {segs[5 * i], (uint64_t) segs[5 * i + 1], (uint64_t) segs[5 * i + 2], (uint64_t) segs[5 * i + 3], segs[5 * i + 4] != 0};
+        if (i == nBefore) tv = prov.cur;
+        prov.add(s, firstPlanned);
+    }
+    if (nBefore == nsegs) tv = prov.cur;
+    uint64_t n = 0;
+    prov.query(tv, p0, p1, [&](uint64_t a, uint64_t b, int64_t owner) {
+        if (n < cap) { out[3 * n] = (int64_t) a; out[3 * n + 1] = (int64_t) b; out[3 * n + 2] = owner; }
+        n++;
+    });
+    *nout = n;
+    return n > cap ? -2 : 0;
 }
 
 // parse + serialize: 0 and the bytes again, or -1 (malformed; the message in err)

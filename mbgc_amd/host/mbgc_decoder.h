@@ -52,7 +52,12 @@ public:
     };
     struct ContigInfo { uint64_t length, unmatched; };
     // fastaDir: --fasta, empty = not asked for; restoreRc: --restore-rc, the -m 3 pass over the literals is inverted first
-    struct Options { bool serial = false, noIndex = false, bench = false, restoreRc = false; int device = 0; std::string fastaDir; };
+    // select: --select / --select-list, the files to bring back (a unit is chosen when its line of <prefix>.names contains one of the
+    // patterns; empty = the whole collection); closureOut: --closure-out, one byte per planned contig
+    struct Options {
+        bool serial = false, noIndex = false, bench = false, restoreRc = false; int device = 0; std::string fastaDir;
+        std::vector<std::string> select; std::string closureOut;
+    };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
     static bool loadRef(RefState &st, int64_t contig, uint64_t textOffset, uint64_t seqLength, uint64_t refLockPos, bool loadRCRef,
