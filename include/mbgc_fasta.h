@@ -30,6 +30,11 @@ typedef struct {
 #define MBGC_FASTA_OK 0
 #define MBGC_FASTA_ENOTFASTA (-3)    /* kseq status -3: the file does not start with '>'                     */
 #define MBGC_FASTA_ELINES (-4)       /* kseq status -4: empty line / inconsistent line lengths (kseq.h:251-265) */
+#define MBGC_FASTA_EFASTQ (-16)      /* lossy rule only, no kseq status: a '+' where a sequence line could start — FASTQ, not read here */
+
+/* flags of the *2 entry points */
+#define MBGC_FASTA_UPPERCASE 1u      /* params->uppercaseDNA */
+#define MBGC_FASTA_LOSSY 2u          /* the rule of `mbgc c -L`: kseq_read_lossy instead of kseq_read_lossless_fasta */
 
 int mbgc_fasta_create(mbgc_fasta_t **out, int device);
 void mbgc_fasta_destroy(mbgc_fasta_t *p);
@@ -55,6 +60,27 @@ int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const 
 int mbgc_fasta_parse_host(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n, int uppercaseDNA, uint8_t *seq_out_host,
                           uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
                           uint64_t *dnaLineLen, int *status);
+
+/* The two calls above with flags in place of uppercaseDNA; flags = uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0 is the call above.
+ * MBGC_FASTA_LOSSY reads by the FASTA part of kseq_read_lossy (utils/kseq.h:282-333, selected by allowLossyParsing,
+ * MultipleGenomeMatchingProcessor.cpp:9-14), one kseq_t per file:
+ *   - every byte in front of the file's first '>' or '@' is skipped, wherever in a line that byte stands; a file without one has
+ *     no records; afterwards a record starts at every line whose first byte is '>' or '@' (not at one that is the file's last byte);
+ *   - the header is the line without its marker and '\n', and without one trailing '\r' when it is longer than one byte;
+ *   - the sequence is the lines up to the next record start; empty lines are skipped; a line's trailing '\r' is dropped when the
+ *     record's sequence, that line appended, is longer than one byte (ks_getuntil2, :147) — so a line that is one '\r' keeps it only
+ *     as the record's first sequence byte, or as the file's last byte with no '\n' behind it (:143 returns before the strip);
+ *   - dnaLineLen[f] = maxLastDnaLineLen: the longest sequence line of the file after that strip, 0 when there is none;
+ *   - status[f] is 0, or MBGC_FASTA_EFASTQ when a line that could be a sequence line starts with '+' (the reference goes on to
+ *     read quality strings there, :320-332; this stage does not). Never -3 or -4.
+ * headerOff stays an offset in the whole file. */
+int mbgc_fasta_parse_batch_dev2(mbgc_fasta_t *p, const uint8_t *files_dev, const uint64_t *fileOff, int nf, uint32_t flags,
+                                uint8_t *seq_out_dev, uint64_t outCap, uint64_t *seqBase,
+                                mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *recBase,
+                                uint64_t *dnaLineLen, int *status);
+int mbgc_fasta_parse_host2(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n, uint32_t flags, uint8_t *seq_out_host,
+                           uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
+                           uint64_t *dnaLineLen, int *status);
 
 /* Single-FASTA input (`mbgc c -i`): the rule by which the reference cuts one multi-FASTA byte stream into the initial reference
  * and the targets, mgmpInSplit_next(iter, minSplitSize, '>') (matching/input_with_libdeflate_wrapper.cpp:150-171), on a window of

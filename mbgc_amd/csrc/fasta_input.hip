@@ -7,6 +7,15 @@
 // on), (3) every chunk, now knowing the state it starts in and how many bytes / records precede it, writes its
 // sequence bytes and its records and votes on the line-length rule. Streaming work: the file is read twice,
 // the sequences are written once.
+//
+// The lossy rule (kseq_read_lossy, utils/kseq.h:282-333; MBGC_FASTA_LOSSY) is a compile-time variant of the same three
+// passes. What it adds to the state: the file starts at its first '>' or '@' (k_fa_first_marker moves the file's start
+// there, so that byte 0 is a header line's marker as in a well-formed file); a line's last CR goes (ks_getuntil2, :147)
+// unless it is the record's first sequence byte — a CR alone on its line stays exactly when only empty lines lie between
+// it and the record's header line, so the scan also carries "the record has no sequence byte yet" across chunks that are
+// nothing but newlines; the line-length vote is one maximum over the stripped lines. At most one CR per chunk cannot be
+// decided inside the chunk (the one behind the chunk's leading run of newlines): the summary names what it depends on,
+// the scan counts it, the emit pass keeps or drops it by the same two flags.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,20 +47,20 @@ struct ChunkSum {             // what a chunk knows on its own
     uint8_t fresh;            // the chunk's first byte starts a line (file start, or the byte before it is '\n')
     uint8_t firstGt;          // the chunk's first byte is '>'
     uint8_t openHdr;          // the line open at the chunk's end is a header line (valid when lastNL >= 0 and it is not the last byte)
-    uint8_t pad;
+    uint8_t aux;              // lossy rule only (AUX_*), else 0
 };
 
 struct ChunkIn {              // what the scan adds
     uint64_t lineStart;       // file offset where the line open at the chunk's first byte started
     uint64_t keptBefore;      // sequence bytes of the file before the chunk
     uint32_t recBefore;       // records of the file before the chunk
-    uint32_t inHdr;           // that open line is a header line
+    uint32_t inHdr;           // that open line is a header line (lossy rule: bit 0; bit 1: the record has no sequence byte where that line starts)
 };
 
 struct FileOut {              // per file, written by the scan and the emit kernels
     uint64_t kept, recs;
     unsigned long long minLine, maxLine, maxLast;   // lengths of the non-last lines of all records / of their last lines
-    uint32_t emptyLine, firstNotGt;
+    uint32_t emptyLine, firstNotGt;                 // (lossy rule: maxLine = the longest stripped line, firstNotGt = a '+' starts a line)
 };
 
 __device__ __forceinline__ uint8_t up(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t) (c - 32) : c; }
@@ -70,6 +79,54 @@ __device__ __forceinline__ uint32_t stage(const uint8_t *__restrict__ f, const F
         for (uint32_t k = o; k < len && k < o + PER; k++) lds[k] = src[k];
     __syncthreads();
     return len;
+}
+
+// ---- lossy rule
+__device__ __forceinline__ bool marker(uint8_t c) { return c == '>' || c == '@'; }
+
+// ChunkSum::aux. A verdict of two bits: 0 no, 1 yes, 2 = yes iff the record has no sequence byte where the chunk's open line
+// starts (ChunkIn bit 1), 3 = yes iff the chunk's open line is a header line (ChunkIn bit 0).
+constexpr uint32_t AUX_COND = 3;          // verdict on the chunk's one lone CR that the chunk cannot decide (2, 3), 0: there is none
+constexpr uint32_t AUX_PREFIX_CR = 4;     // the open line's last byte lies in the chunk and is a CR that goes if that line is sequence
+constexpr uint32_t AUX_PLUS = 8;          // a '+' starts a line: FASTQ
+constexpr int AUX_TAIL = 4;               // verdict "the record has no sequence byte behind the chunk" (read when the chunk ends with '\n')
+constexpr uint32_t NO_MARKER = 0xffffffffu;
+
+// the lossy chunk: an empty one when the file, cut at its first marker, ends before it; ch[len] = the byte behind the chunk,
+// '\n' at the end of the file (a line's last byte is the one in front of either)
+__device__ __forceinline__ uint32_t stage_lossy(const uint8_t *__restrict__ f, const FileDesc &fd, uint32_t c, uint8_t *lds) {
+    const uint64_t cs = (uint64_t) c * CHUNK;
+    const uint32_t len = cs < fd.n ? (uint32_t) (fd.n - cs < CHUNK ? fd.n - cs : CHUNK) : 0u;
+    const uint8_t *src = f + fd.off + cs;
+    const uint32_t o = threadIdx.x * PER;
+    if (o + PER <= len) {
+        uint4 t;
+        memcpy(&t, src + o, PER);
+        *(uint4 *) (lds + o) = t;
+    } else
+        for (uint32_t k = o; k < len && k < o + PER; k++) lds[k] = src[k];
+    if (threadIdx.x == THREADS - 1) lds[len] = cs + len < fd.n ? src[len] : (uint8_t) '\n';
+    __syncthreads();
+    return len;
+}
+
+// Is the line that holds ch[j] a header line? nl: what prev_newline() leaves behind (thread t: the last '\n' at or before its
+// segment's end). -> verdict 0, 1 or 3.
+__device__ __forceinline__ uint32_t line_is_header(const uint8_t *ch, const int32_t *nl, int32_t j, bool fresh) {
+    const int32_t t0 = j / PER * PER;
+    int32_t q = j - 1;
+    while (q >= t0 && ch[q] != '\n') q--;
+    if (q < t0) q = t0 ? nl[t0 / PER - 1] : -1;
+    if (q < 0) return fresh ? (marker(ch[0]) ? 1u : 0u) : 3u;        // the chunk's open line
+    return marker(ch[q + 1]) ? 1u : 0u;
+}
+
+// ch[k] is a CR alone on its line and a '\n' follows: does the byte stay (kseq.h:147 with seq.l == 1)? -> verdict
+__device__ __forceinline__ uint32_t lone_cr_stays(const uint8_t *ch, const int32_t *nl, int32_t k, bool fresh) {
+    int32_t j = k - 2;                                              // (ch[k - 1] is the '\n' that makes k a line start)
+    while (j >= 0 && ch[j] == '\n') j--;
+    if (j < 0) return fresh ? 2u : 3u;                               // empty lines back to the chunk's first byte
+    return line_is_header(ch, nl, j, fresh);
 }
 
 // last '\n' at or before every thread's segment start (exclusive of the segment), as an offset in the chunk, -1: none.
@@ -112,17 +169,19 @@ __device__ uint32_t block_sum_scan(uint32_t x, uint32_t *lds, uint32_t *total) {
 }
 
 // (1) per chunk
+template <bool LOSSY>
 __global__ void __launch_bounds__(THREADS) k_fa_summary(const uint8_t *__restrict__ f, const FileDesc *__restrict__ files,
                                                         const uint32_t *__restrict__ owner, ChunkSum *__restrict__ sums) {
     __shared__ uint8_t ch[CHUNK + 16];
     __shared__ int32_t nl[THREADS];
     __shared__ uint32_t red[THREADS / WAVE + 2];
     __shared__ int32_t firstNL, lastNL;
+    __shared__ uint32_t sAux;
     const FileDesc fd = files[owner[blockIdx.x]];
     const uint32_t c = blockIdx.x - fd.chunk0;
-    const uint32_t len = stage(f, fd, c, ch);
+    const uint32_t len = LOSSY ? stage_lossy(f, fd, c, ch) : stage(f, fd, c, ch);
     const uint64_t cs = (uint64_t) c * CHUNK;
-    if (threadIdx.x == 0) { firstNL = 0x7fffffff; lastNL = -1; }
+    if (threadIdx.x == 0) { firstNL = 0x7fffffff; lastNL = -1; if (LOSSY) sAux = 0; }
     __syncthreads();
     const uint32_t o = threadIdx.x * PER;
     int32_t myFirst = 0x7fffffff, myLast = -1;
@@ -135,6 +194,44 @@ __global__ void __launch_bounds__(THREADS) k_fa_summary(const uint8_t *__restric
     // walk the segment: bytes after the chunk's first newline know their line start
     uint32_t keep = 0, hdr = 0;
     int32_t ls = prevNL >= 0 ? prevNL + 1 : -1;                       // start of the open line if it lies in the chunk
+    if constexpr (LOSSY) {
+        bool isHdr = ls >= 0 && ls < (int32_t) len && marker(ch[ls]);
+        const bool fresh = len && (cs == 0 || f[fd.off + cs - 1] == '\n');
+        uint32_t aux = 0;
+        for (uint32_t k = o; k < o + PER && k < len; k++) {
+            const uint8_t b = ch[k];
+            const bool lineStart = k == 0 ? fresh : ch[k - 1] == '\n';
+            if (lineStart) { isHdr = marker(b); if (isHdr && cs + k + 1 < fd.n) hdr++; if (b == '+') aux |= AUX_PLUS; }
+            const bool after = fNL >= 0 && (int32_t) k > fNL;
+            bool stays = b != '\n';
+            if (b == '\r' && ch[k + 1] == '\n') {                    // the line's last byte (ch[len]: the byte behind the chunk)
+                uint32_t v = 0;
+                if (lineStart) v = cs + k + 1 == fd.n ? 1u : lone_cr_stays(ch, nl, (int32_t) k, fresh);   // (nothing behind it: -1 at kseq.h:143, before the strip)
+                if (v >= 2) { aux |= v; v = 0; }                     // the scan decides, and counts it
+                stays = v == 1;
+                if (!after && !stays) aux |= AUX_PREFIX_CR;
+            }
+            if (after && !isHdr && stays) keep++;
+        }
+        if (aux) atomicOr(&sAux, aux);
+        uint32_t tk, th;
+        block_sum_scan<THREADS>(keep, red, &tk);
+        block_sum_scan<THREADS>(hdr, red, &th);
+        if (threadIdx.x == 0) {
+            uint32_t tail = 0;
+            if (len && lastNL == (int32_t) len - 1) {                // what a chunk that starts a line behind this one needs to know
+                int32_t j = (int32_t) len - 2;
+                while (j >= 0 && ch[j] == '\n') j--;
+                tail = j < 0 ? (fresh ? 2u : 3u) : line_is_header(ch, nl, j, fresh);
+            }
+            ChunkSum s;
+            s.firstNL = fNL; s.lastNL = lastNL; s.keepAfter = tk; s.hdrStarts = th;
+            s.fresh = fresh; s.firstGt = len && marker(ch[0]);
+            s.openHdr = lastNL >= 0 && lastNL + 1 < (int32_t) len && marker(ch[lastNL + 1]);
+            s.aux = (uint8_t) (sAux | (tail << AUX_TAIL));
+            sums[blockIdx.x] = s;
+        }
+    } else {
     bool isHdr = ls >= 0 && ls < (int32_t) len && ch[ls] == '>';
     const bool fresh = cs == 0 || f[fd.off + cs - 1] == '\n';
     for (uint32_t k = o; k < o + PER && k < len; k++) {
@@ -151,28 +248,32 @@ __global__ void __launch_bounds__(THREADS) k_fa_summary(const uint8_t *__restric
         s.firstNL = fNL; s.lastNL = lastNL; s.keepAfter = tk; s.hdrStarts = th;
         s.fresh = fresh; s.firstGt = len && ch[0] == '>';
         s.openHdr = lastNL >= 0 && lastNL + 1 < (int32_t) len && ch[lastNL + 1] == '>';
-        s.pad = 0;
+        s.aux = 0;
         sums[blockIdx.x] = s;
+    }
     }
 }
 
 // (2) one wave per file
+template <bool LOSSY>
 __global__ void __launch_bounds__(WAVE) k_fa_scan(const uint8_t *__restrict__ f, const FileDesc *__restrict__ files,
                                                   const ChunkSum *__restrict__ sums, ChunkIn *__restrict__ ins, FileOut *__restrict__ fout) {
     const FileDesc fd = files[blockIdx.x];
     const int lane = threadIdx.x;
     // state carried across groups of 64 chunks
-    bool carryHdr = fd.n && f[fd.off] == '>';                         // the file's first line (no newline seen yet)
+    bool carryHdr = fd.n && (LOSSY ? marker(f[fd.off]) : f[fd.off] == '>');   // the file's first line (no newline seen yet)
     uint64_t carryLS = 0, kept = 0;
     uint32_t recs = 0;
+    int carryE = 0;                                                   // lossy: the record has no sequence byte behind the chunks so far
+    bool plus = false;
     for (uint32_t g0 = 0; g0 < fd.nchunks; g0 += WAVE) {
         const uint32_t c = g0 + lane;
         const bool live = c < fd.nchunks;
         ChunkSum s;
-        s.firstNL = -1; s.lastNL = -1; s.keepAfter = 0; s.hdrStarts = 0; s.fresh = 0; s.firstGt = 0; s.openHdr = 0; s.pad = 0;
+        s.firstNL = -1; s.lastNL = -1; s.keepAfter = 0; s.hdrStarts = 0; s.fresh = 0; s.firstGt = 0; s.openHdr = 0; s.aux = 0;
         if (live) s = sums[fd.chunk0 + c];
         const uint64_t cs = (uint64_t) c * CHUNK;
-        const uint32_t len = live ? (uint32_t) (fd.n - cs < CHUNK ? fd.n - cs : CHUNK) : 0;
+        const uint32_t len = live && (!LOSSY || cs < fd.n) ? (uint32_t) (fd.n - cs < CHUNK ? fd.n - cs : CHUNK) : 0;
         // nearest earlier chunk of the group that fixes the state of what follows: one with a newline (the line open
         // at its end), or one whose first byte starts a line and that has no newline (that very line)
         int idx = (live && (s.lastNL >= 0 || s.fresh)) ? lane : -1;
@@ -195,7 +296,29 @@ __global__ void __launch_bounds__(WAVE) k_fa_scan(const uint8_t *__restrict__ f,
         else if (pidx >= 0) { inHdr = pHdr; inLS = pLS; }
         else { inHdr = carryHdr; inLS = carryLS; }
         const uint32_t prefix = s.firstNL >= 0 ? (uint32_t) s.firstNL : len;        // bytes of the open line inside the chunk (no newline among them)
-        const uint32_t mine = live ? s.keepAfter + (inHdr ? 0u : prefix) : 0u;
+        uint32_t mine = live ? s.keepAfter + (inHdr ? 0u : prefix) : 0u;
+        int inE = 0;
+        if constexpr (LOSSY) {
+            // "no sequence byte yet" behind every chunk: its own verdict, or what it starts with when it is nothing but newlines
+            const uint32_t tail = (s.aux >> AUX_TAIL) & 3u;
+            const int ev = tail == 2 ? -1 : tail == 3 ? (int) inHdr : (int) tail;
+            int eidx = ev >= 0 ? lane : -1;
+            for (int d = 1; d < WAVE; d <<= 1) {
+                const int y = __shfl_up(eidx, d);
+                if (lane >= d && y > eidx) eidx = y;
+            }
+            const int evAt = __shfl(ev, eidx >= 0 ? eidx : 0);
+            const int outE = eidx >= 0 ? evAt : carryE;
+            const int before = __shfl_up(outE, 1);
+            inE = lane ? before : carryE;
+            carryE = __shfl(outE, WAVE - 1);
+            const uint32_t cond = s.aux & AUX_COND;
+            if (live) {
+                if (!inHdr && (s.aux & AUX_PREFIX_CR)) mine -= 1;
+                if ((cond == 2 && inE) || (cond == 3 && inHdr)) mine += 1;
+            }
+            plus = plus || __ballot(live && (s.aux & AUX_PLUS)) != 0;
+        }
         uint32_t incK = mine, incR = live ? s.hdrStarts : 0u;
         for (int d = 1; d < WAVE; d <<= 1) {
             const uint32_t a = (uint32_t) __shfl_up((int) incK, d), b = (uint32_t) __shfl_up((int) incR, d);
@@ -203,7 +326,7 @@ __global__ void __launch_bounds__(WAVE) k_fa_scan(const uint8_t *__restrict__ f,
         }
         if (live) {
             ChunkIn in;
-            in.lineStart = inLS; in.keptBefore = kept + incK - mine; in.recBefore = recs + incR - s.hdrStarts; in.inHdr = inHdr;
+            in.lineStart = inLS; in.keptBefore = kept + incK - mine; in.recBefore = recs + incR - s.hdrStarts; in.inHdr = (uint32_t) inHdr | (uint32_t) (inE << 1);
             ins[fd.chunk0 + c] = in;
         }
         // carry out of the group: the last chunk with a newline (or the old carry), totals
@@ -219,24 +342,26 @@ __global__ void __launch_bounds__(WAVE) k_fa_scan(const uint8_t *__restrict__ f,
     if (lane == 0) {
         FileOut o;
         o.kept = kept; o.recs = recs; o.minLine = ~0ull; o.maxLine = 0; o.maxLast = 0; o.emptyLine = 0;
-        o.firstNotGt = fd.n && f[fd.off] != '>';
+        o.firstNotGt = LOSSY ? (uint32_t) plus : (uint32_t) (fd.n && f[fd.off] != '>');
         fout[blockIdx.x] = o;
     }
 }
 
-// (3) per chunk again
+// (3) per chunk again. shift (lossy rule): what k_fa_first_marker cut off every file's front — record headers are offsets in the whole file
+template <bool LOSSY>
 __global__ void __launch_bounds__(THREADS) k_fa_emit(const uint8_t *__restrict__ f, const FileDesc *__restrict__ files,
                                                      const uint32_t *__restrict__ owner, const ChunkSum *__restrict__ sums,
                                                      const ChunkIn *__restrict__ ins, const uint64_t *__restrict__ seqBase,
                                                      const uint64_t *__restrict__ recBase, int uppercase, uint8_t *__restrict__ out,
-                                                     mbgc_fasta_record_t *__restrict__ recs, FileOut *__restrict__ fout) {
+                                                     mbgc_fasta_record_t *__restrict__ recs, FileOut *__restrict__ fout,
+                                                     const uint64_t *__restrict__ shift) {
     __shared__ uint8_t ch[CHUNK + 16];
     __shared__ int32_t nl[THREADS];
     __shared__ uint32_t red[THREADS / WAVE + 2];
     const uint32_t fi = owner[blockIdx.x];
     const FileDesc fd = files[fi];
     const uint32_t c = blockIdx.x - fd.chunk0;
-    const uint32_t len = stage(f, fd, c, ch);
+    const uint32_t len = LOSSY ? stage_lossy(f, fd, c, ch) : stage(f, fd, c, ch);
     const uint64_t cs = (uint64_t) c * CHUNK;
     const ChunkIn in = ins[blockIdx.x];
     const ChunkSum sm = sums[blockIdx.x];
@@ -246,6 +371,76 @@ __global__ void __launch_bounds__(THREADS) k_fa_emit(const uint8_t *__restrict__
     const int32_t prevNL = prev_newline(myLast, nl);
     // state at the thread's first byte
     uint64_t ls = prevNL >= 0 ? cs + (uint64_t) prevNL + 1 : in.lineStart;        // file offset of the open line's start
+    if constexpr (LOSSY) {
+        const bool inHdr = in.inHdr & 1u, inE = in.inHdr & 2u;
+        bool isHdr = prevNL >= 0 ? (prevNL + 1 < (int32_t) len ? marker(ch[prevNL + 1]) : false) : inHdr;
+        // pass A: the CRs that go (bit i: byte o + i), what the thread keeps, its header starts
+        uint32_t keep = 0, hdr = 0, goes = 0;
+        {
+            bool h2 = isHdr;
+            for (uint32_t k = o; k < o + PER && k < len; k++) {
+                const uint8_t b = ch[k];
+                const bool lineStart = k == 0 ? sm.fresh : ch[k - 1] == '\n';
+                if (lineStart) { h2 = marker(b); if (h2 && cs + k + 1 < fd.n) hdr++; }
+                if (b == '\r' && ch[k + 1] == '\n') {                // the line's last byte: as in k_fa_summary
+                    uint32_t v = 0;
+                    if (lineStart) v = cs + k + 1 == fd.n ? 1u : lone_cr_stays(ch, nl, (int32_t) k, sm.fresh);
+                    const bool stays = v == 1 || (v == 2 && inE) || (v == 3 && inHdr);
+                    if (!stays) goes |= 1u << (k - o);
+                }
+                if (!h2 && b != '\n' && !((goes >> (k - o)) & 1u)) keep++;
+            }
+        }
+        uint32_t tk, th;
+        const uint32_t keepEx = block_sum_scan<THREADS>(keep, red, &tk);
+        const uint32_t hdrEx = block_sum_scan<THREADS>(hdr, red, &th);
+        __shared__ uint8_t packed[CHUNK];
+        __shared__ unsigned long long sMax;
+        if (threadIdx.x == 0) sMax = 0;
+        __syncthreads();
+        uint8_t *dst = packed + keepEx;
+        mbgc_fasta_record_t *R = recs + recBase[fi];
+        const uint64_t cut = shift[fi];
+        uint32_t kk = 0, hh = in.recBefore + hdrEx;                 // hh: records started before the current byte
+        unsigned long long mx = 0;
+        for (uint32_t k = o; k < o + PER && k < len; k++) {
+            const uint8_t b = ch[k];
+            const uint64_t p = cs + k;
+            const bool lineStart = k == 0 ? sm.fresh : ch[k - 1] == '\n';
+            if (lineStart) {
+                ls = p; isHdr = marker(b);
+                if (isHdr && p + 1 < fd.n) {                        // a record starts here
+                    R[hh].headerOff = cut + p + 1;
+                    R[hh].seqOff = in.keptBefore + keepEx + kk;
+                    hh++;
+                }
+            }
+            const bool gone = (goes >> (k - o)) & 1u;
+            if (b != '\n' && ch[k + 1] == '\n') {                    // the line's last byte ('\n' or the file's end follows)
+                if (isHdr) {
+                    if (ls + 1 < fd.n && hh > 0) {                  // the record whose header line ends here; its CR goes when more than the CR is there (:147)
+                        const uint64_t hl = p - ls;
+                        R[hh - 1].headerLen = hl > 1 && b == '\r' ? hl - 1 : hl;
+                    }
+                } else {
+                    const unsigned long long d = p + 1 - ls - (gone ? 1 : 0);       // maxLastDnaLineLen (:301-312) counts what the strip left
+                    if (d > mx) mx = d;
+                }
+            }
+            if (!isHdr && b != '\n' && !gone) dst[kk++] = uppercase ? up(b) : b;
+        }
+        if (mx) atomicMax(&sMax, mx);
+        __syncthreads();
+        if (threadIdx.x == 0 && sMax) atomicMax(&fout[fi].maxLine, sMax);
+        uint8_t *g = out + seqBase[fi] + in.keptBefore;
+        for (uint32_t k = threadIdx.x * 16; k < tk; k += THREADS * 16) {
+            if (k + 16 <= tk) {
+                uint4 t = *(const uint4 *) (packed + k);
+                memcpy(g + k, &t, 16);
+            } else
+                for (uint32_t j = k; j < tk; j++) g[j] = packed[j];
+        }
+    } else {
     bool isHdr = prevNL >= 0 ? (prevNL + 1 < (int32_t) len ? ch[prevNL + 1] == '>' : false) : in.inHdr != 0;
     // pass A: count what the thread keeps and the header starts before each byte
     uint32_t keep = 0, hdr = 0;
@@ -317,6 +512,38 @@ __global__ void __launch_bounds__(THREADS) k_fa_emit(const uint8_t *__restrict__
             memcpy(g + k, &t, 16);
         } else
             for (uint32_t j = k; j < tk; j++) g[j] = packed[j];
+    }
+    }
+}
+
+// the lossy rule's first step (kseq.h:288): everything in front of the file's first '>' or '@' is skipped, wherever in a line that
+// byte stands. One workgroup per file reads chunks until it meets one (the first chunk, in a file that is not damaged) and moves
+// the file's start there; a file without one becomes empty. shift: how far.
+__global__ void __launch_bounds__(THREADS) k_fa_first_marker(const uint8_t *__restrict__ f, FileDesc *__restrict__ files, uint64_t *__restrict__ shift) {
+    __shared__ uint32_t first;
+    const FileDesc fd = files[blockIdx.x];
+    const uint32_t o = threadIdx.x * PER;
+    uint64_t at = fd.n;
+    for (uint64_t cs = 0; cs < fd.n; cs += CHUNK) {                  // (every branch on `first` is taken by the whole workgroup)
+        if (threadIdx.x == 0) first = NO_MARKER;
+        __syncthreads();
+        const uint32_t len = (uint32_t) (fd.n - cs < CHUNK ? fd.n - cs : CHUNK);
+        const uint8_t *src = f + fd.off + cs;
+        uint8_t t[PER];
+        if (o + PER <= len) memcpy(t, src + o, PER);
+        else for (uint32_t k = 0; k < PER; k++) t[k] = o + k < len ? src[o + k] : 0;
+        uint32_t mine = NO_MARKER;
+#pragma unroll
+        for (int k = PER - 1; k >= 0; k--) if (marker(t[k])) mine = o + (uint32_t) k;
+        if (mine != NO_MARKER) atomicMin(&first, mine);
+        __syncthreads();
+        const uint32_t r = first;
+        __syncthreads();
+        if (r != NO_MARKER) { at = cs + r; break; }
+    }
+    if (threadIdx.x == 0) {
+        files[blockIdx.x].off = fd.off + at; files[blockIdx.x].n = fd.n - at;
+        shift[blockIdx.x] = at;
     }
 }
 
@@ -470,6 +697,7 @@ struct mbgc_fasta {
     fa::Buf<fa::FileOut> dOut;
     fa::Buf<uint64_t> dBases;
     fa::Buf<mbgc_fasta_record_t> dRecs;
+    fa::Buf<uint64_t> dShift;                   // lossy rule: every file's bytes in front of its first marker
     fa::Buf<uint8_t> dHostIn, dHostOut;         // mbgc_fasta_parse_host: the file and its sequences on the device
     fa::Buf<uint32_t> dTileFirst;               // mbgc_fasta_split_dev: first '>' of every tile, and its result
     fa::Buf<uint64_t> dSplit;
@@ -504,7 +732,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     if (!p) return;
     (void) hipSetDevice(p->device);
     if (p->stream) { (void) hipStreamSynchronize(p->stream); (void) hipStreamDestroy(p->stream); }
-    p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dHostIn.release(); p->dHostOut.release();
+    p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dShift.release(); p->dHostIn.release(); p->dHostOut.release();
     p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
@@ -512,12 +740,15 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     delete p;
 }
 
-int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const uint64_t *fileOff, int nf, int uppercaseDNA,
-                               uint8_t *seq_out_dev, uint64_t outCap, uint64_t *seqBase,
-                               mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *recBase,
-                               uint64_t *dnaLineLen, int *status) {
+int mbgc_fasta_parse_batch_dev2(mbgc_fasta_t *p, const uint8_t *files_dev, const uint64_t *fileOff, int nf, uint32_t flags,
+                                uint8_t *seq_out_dev, uint64_t outCap, uint64_t *seqBase,
+                                mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *recBase,
+                                uint64_t *dnaLineLen, int *status) {
     using namespace fa;
     if (nf <= 0) return fail(-103, "empty batch");
+    if (flags & ~(uint32_t) (MBGC_FASTA_UPPERCASE | MBGC_FASTA_LOSSY)) return fail(-103, "unknown parse flags %#x", flags);
+    const bool lossy = flags & MBGC_FASTA_LOSSY;
+    const int uppercaseDNA = (flags & MBGC_FASTA_UPPERCASE) != 0;
     FCHK(hipSetDevice(p->device));
     std::vector<FileDesc> files(nf);
     std::vector<uint32_t> owner;
@@ -532,12 +763,20 @@ int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const 
     }
     int r;
     if ((r = p->dFiles.reserve(nf)) || (r = p->dOwner.reserve(std::max<uint32_t>(chunks, 1))) || (r = p->dSums.reserve(std::max<uint32_t>(chunks, 1))) ||
-        (r = p->dIns.reserve(std::max<uint32_t>(chunks, 1))) || (r = p->dOut.reserve(nf)) || (r = p->dBases.reserve(2 * (size_t) nf + 2)))
+        (r = p->dIns.reserve(std::max<uint32_t>(chunks, 1))) || (r = p->dOut.reserve(nf)) || (r = p->dBases.reserve(2 * (size_t) nf + 2)) ||
+        (lossy && (r = p->dShift.reserve(nf))))
         return r;
     FCHK(hipMemcpyAsync(p->dFiles.p, files.data(), nf * sizeof(FileDesc), hipMemcpyHostToDevice, p->stream));
     if (chunks) FCHK(hipMemcpyAsync(p->dOwner.p, owner.data(), chunks * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-    if (chunks) k_fa_summary<<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p);
-    k_fa_scan<<<dim3(nf), dim3(WAVE), 0, p->stream>>>(files_dev, p->dFiles.p, p->dSums.p, p->dIns.p, p->dOut.p);
+    if (lossy) {
+        // (the files' chunks are counted from their whole sizes: those behind a file's cut end are empty)
+        k_fa_first_marker<<<dim3(nf), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dShift.p);
+        if (chunks) k_fa_summary<true><<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p);
+        k_fa_scan<true><<<dim3(nf), dim3(WAVE), 0, p->stream>>>(files_dev, p->dFiles.p, p->dSums.p, p->dIns.p, p->dOut.p);
+    } else {
+        if (chunks) k_fa_summary<false><<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p);
+        k_fa_scan<false><<<dim3(nf), dim3(WAVE), 0, p->stream>>>(files_dev, p->dFiles.p, p->dSums.p, p->dIns.p, p->dOut.p);
+    }
     FCHK(hipGetLastError());
     std::vector<FileOut> fo(nf);
     FCHK(hipMemcpyAsync(fo.data(), p->dOut.p, nf * sizeof(FileOut), hipMemcpyDeviceToHost, p->stream));
@@ -550,8 +789,12 @@ int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const 
     if (rb[nf] > recCap) { recBase[nf] = rb[nf]; return fail(-104, "record table needs %llu entries, capacity %llu", (unsigned long long) rb[nf], (unsigned long long) recCap); }
     if ((r = p->dRecs.reserve(std::max<uint64_t>(rb[nf], 1)))) return r;
     FCHK(hipMemcpyAsync(p->dBases.p, bases.data(), bases.size() * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
-    if (chunks) k_fa_emit<<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p, p->dIns.p, p->dBases.p,
-                                                                         p->dBases.p + nf + 1, uppercaseDNA, seq_out_dev, p->dRecs.p, p->dOut.p);
+    if (chunks && lossy)
+        k_fa_emit<true><<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p, p->dIns.p, p->dBases.p,
+                                                                       p->dBases.p + nf + 1, uppercaseDNA, seq_out_dev, p->dRecs.p, p->dOut.p, p->dShift.p);
+    else if (chunks)
+        k_fa_emit<false><<<dim3(chunks), dim3(THREADS), 0, p->stream>>>(files_dev, p->dFiles.p, p->dOwner.p, p->dSums.p, p->dIns.p, p->dBases.p,
+                                                                        p->dBases.p + nf + 1, uppercaseDNA, seq_out_dev, p->dRecs.p, p->dOut.p, nullptr);
     FCHK(hipGetLastError());
     if (rb[nf]) FCHK(hipMemcpyAsync(records, p->dRecs.p, rb[nf] * sizeof(mbgc_fasta_record_t), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipMemcpyAsync(fo.data(), p->dOut.p, nf * sizeof(FileOut), hipMemcpyDeviceToHost, p->stream));
@@ -565,6 +808,11 @@ int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const 
         // kseq status and KSEQ_DNA_LINE_LENGTH (kseq.h:251-265, MGMP.cpp:12-14)
         const bool haveLine = fo[i].minLine != ~0ull;
         const unsigned long long L = haveLine ? fo[i].minLine : 0;
+        if (lossy) {                                                 // never -3 or -4; the longest line (kseq.h:301-312)
+            status[i] = fo[i].firstNotGt ? MBGC_FASTA_EFASTQ : MBGC_FASTA_OK;
+            dnaLineLen[i] = status[i] == MBGC_FASTA_OK ? fo[i].maxLine : 0;
+            continue;
+        }
         int st = MBGC_FASTA_OK;
         if (fo[i].firstNotGt) st = MBGC_FASTA_ENOTFASTA;
         else if (fo[i].emptyLine || (haveLine && fo[i].minLine != fo[i].maxLine) || (haveLine && fo[i].maxLast > L)) st = MBGC_FASTA_ELINES;
@@ -575,9 +823,24 @@ int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const 
     return 0;
 }
 
+int mbgc_fasta_parse_batch_dev(mbgc_fasta_t *p, const uint8_t *files_dev, const uint64_t *fileOff, int nf, int uppercaseDNA,
+                               uint8_t *seq_out_dev, uint64_t outCap, uint64_t *seqBase,
+                               mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *recBase,
+                               uint64_t *dnaLineLen, int *status) {
+    return mbgc_fasta_parse_batch_dev2(p, files_dev, fileOff, nf, uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u, seq_out_dev, outCap, seqBase,
+                                       records, recCap, recBase, dnaLineLen, status);
+}
+
 int mbgc_fasta_parse_host(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n, int uppercaseDNA, uint8_t *seq_out_host,
                           uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
                           uint64_t *dnaLineLen, int *status) {
+    return mbgc_fasta_parse_host2(p, file_host, n, uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u, seq_out_host, seqBytes, records, recCap, nrec,
+                                  dnaLineLen, status);
+}
+
+int mbgc_fasta_parse_host2(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n, uint32_t flags, uint8_t *seq_out_host,
+                           uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
+                           uint64_t *dnaLineLen, int *status) {
     using namespace fa;
     FCHK(hipSetDevice(p->device));
     int r;
@@ -587,7 +850,7 @@ int mbgc_fasta_parse_host(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n,
     uint64_t sb[2] = {0, 0}, rb[2] = {0, 0};
     *nrec = 0; *seqBytes = 0;
     if (n == 0) { *status = MBGC_FASTA_OK; *dnaLineLen = 0; return 0; }
-    r = mbgc_fasta_parse_batch_dev(p, p->dHostIn.p, off, 1, uppercaseDNA, p->dHostOut.p, n, sb, records, recCap, rb, dnaLineLen, status);
+    r = mbgc_fasta_parse_batch_dev2(p, p->dHostIn.p, off, 1, flags, p->dHostOut.p, n, sb, records, recCap, rb, dnaLineLen, status);
     if (r) { *nrec = rb[1]; return r; }
     *nrec = rb[1]; *seqBytes = sb[1];
     if (sb[1]) FCHK(hipMemcpy(seq_out_host, p->dHostOut.p, sb[1], hipMemcpyDeviceToHost));

@@ -1,12 +1,16 @@
-"""ctypes view of include/mbgc_fasta.h — the input stage (kseq_read_lossless_fasta for whole files in HBM)."""
+"""ctypes view of include/mbgc_fasta.h — the input stage (kseq_read_lossless_fasta, or kseq_read_lossy, for whole files in HBM)."""
 import ctypes as C
 
 import numpy as np
 
 from . import binding
 
-EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
+EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download""".split()
+
+
+UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
+EFASTQ = -16                         # MBGC_FASTA_EFASTQ
 
 
 class Record(C.Structure):
@@ -33,6 +37,12 @@ def _lib():
         L.mbgc_fasta_parse_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64), C.POINTER(Record), C.c_uint64, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mbgc_fasta_parse_batch_dev2.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                  C.POINTER(C.c_uint64), C.POINTER(Record), C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        for name, second in (("mbgc_fasta_parse_host", C.c_int), ("mbgc_fasta_parse_host2", C.c_uint32)):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, second, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(Record), C.c_uint64,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mbgc_fasta_split_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mbgc_fasta_split_buf_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
@@ -63,9 +73,13 @@ class FastaParser:
         except Exception:
             pass
 
-    def parse_batch_dev(self, files_ptr, file_offsets, out_ptr, out_cap, uppercase=False):
+    def parse_batch_dev(self, files_ptr, file_offsets, out_ptr, out_cap, uppercase=False, lossy=False, flags=None):
         """files_ptr: device buffer holding the files back to back, file f at [file_offsets[f], file_offsets[f+1]).
+        lossy: the rule of `mbgc c -L` (mbgc_fasta_parse_batch_dev2 with MBGC_FASTA_LOSSY); flags: that entry point with these
+        flags as they are (0: the lossless rule through it).
         -> dict(seq_base [nf+1], rec_base [nf+1], records (structured array), dna_line_len [nf], status [nf])"""
+        if flags is None and lossy:
+            flags = LOSSY | (UPPERCASE if uppercase else 0)
         offs = np.ascontiguousarray(file_offsets, dtype=np.uint64)
         nf = offs.size - 1
         P = C.POINTER(C.c_uint64)
@@ -74,9 +88,10 @@ class FastaParser:
         rec_cap = max(self._rec_cap, nf)
         while True:
             recs = (Record * rec_cap)()
-            r = _lib().mbgc_fasta_parse_batch_dev(self.h, files_ptr, offs.ctypes.data_as(P), nf, int(uppercase), out_ptr, out_cap,
-                                                  seq_base.ctypes.data_as(P), recs, rec_cap, rec_base.ctypes.data_as(P),
-                                                  line.ctypes.data_as(P), status.ctypes.data_as(C.POINTER(C.c_int)))
+            call = _lib().mbgc_fasta_parse_batch_dev if flags is None else _lib().mbgc_fasta_parse_batch_dev2
+            r = call(self.h, files_ptr, offs.ctypes.data_as(P), nf, int(uppercase) if flags is None else int(flags), out_ptr, out_cap,
+                     seq_base.ctypes.data_as(P), recs, rec_cap, rec_base.ctypes.data_as(P),
+                     line.ctypes.data_as(P), status.ctypes.data_as(C.POINTER(C.c_int)))
             if r == -104 and int(rec_base[-1]) > rec_cap:              # the table was too small: the call says how many it needs
                 rec_cap = self._rec_cap = int(rec_base[-1])
                 continue
@@ -86,6 +101,32 @@ class FastaParser:
         n = int(rec_base[-1])
         arr = np.frombuffer(recs, dtype=[("headerOff", "<u8"), ("headerLen", "<u8"), ("seqOff", "<u8"), ("seqLen", "<u8")], count=n).copy()
         return dict(seq_base=seq_base, rec_base=rec_base, records=arr, dna_line_len=line, status=status)
+
+    def parse_host(self, data, uppercase=False, lossy=False):
+        """one file in host memory (mbgc_fasta_parse_host, or _host2 with MBGC_FASTA_LOSSY): uploaded, parsed, its sequences downloaded
+        -> dict(status, records=[(header bytes, sequence bytes)], dna_line_len, seq=the sequences back to back)"""
+        data = bytes(data)
+        src = np.frombuffer(data + b"\0", dtype=np.uint8)
+        out = np.zeros(max(len(data), 1), dtype=np.uint8)
+        nb, nrec, line, status = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        rec_cap = self._rec_cap
+        while True:
+            recs = (Record * rec_cap)()
+            args = (src.ctypes.data_as(C.c_void_p), len(data))
+            rest = (out.ctypes.data_as(C.c_void_p), C.byref(nb), recs, rec_cap, C.byref(nrec), C.byref(line), C.byref(status))
+            if lossy:
+                r = _lib().mbgc_fasta_parse_host2(self.h, *args, LOSSY | (UPPERCASE if uppercase else 0), *rest)
+            else:
+                r = _lib().mbgc_fasta_parse_host(self.h, *args, int(uppercase), *rest)
+            if r == -104 and nrec.value > rec_cap:
+                rec_cap = self._rec_cap = int(nrec.value)
+                continue
+            if r:
+                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+            break
+        seq = out[: nb.value].tobytes()
+        records = [(data[x.headerOff: x.headerOff + x.headerLen], seq[x.seqOff: x.seqOff + x.seqLen]) for x in recs[: nrec.value]]
+        return dict(status=status.value, records=records, dna_line_len=line.value, seq=seq)
 
     def split_dev(self, bytes_ptr, n, is_file_end, first_min, next_min, max_elems):
         """mgmpInSplit_next over the window bytes_ptr[0..n) in HBM (it starts at an element start): the end offsets of the

@@ -93,6 +93,7 @@ int main(int argc, char **argv) {
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "-L") params.lazyDecompressionSupport = false;             // disable lazy decompression support
         else if (a == "-U") params.uppercaseDNA = true;                          // MBGC_Params.h: converts bases to uppercase
+        else if (a == "--lossy") params.allowLossyParsing = true;                 // the reference's -L (MGMP_Params.h:213): ragged lines, CRLF, leading junk are read, not refused
         else if (a == "--bench") params.benchMode = true;                        // rounds timed with every contig resident in HBM (no streams written)
         else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
         else if (a == "--verify") params.verifyEmissions = true;                  // every emission decoded again on the device before the reference moves on
@@ -111,13 +112,15 @@ int main(int argc, char **argv) {
     const bool single = !params.inputFileName.empty();
     if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
     if (pos.size() != 2 || (single && !pos[0].empty())) {
-        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
+        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--lossy] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
                         "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
                         "  2 MiB at '>' bytes, on the device, while it travels to the GPU in windows of K KiB (default 32768; host memory is bounded by two\n"
                         "  windows, except for a gzip file, which is inflated on the host and held whole in memory); also prints `single-file elements: <n>`\n"
                         "  and writes <outputPrefix>.seqCounts (one little-endian u32 per target: its records)\n"
+                        "  --lossy: the files of the list are read as `mbgc c -L` reads them (any line lengths, empty lines, CRLF, bytes in front of the first\n"
+                        "  '>'; the longest line becomes the file's line length); FASTQ files are refused; not with -i\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
         fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n");
@@ -129,6 +132,10 @@ int main(int argc, char **argv) {
     }
     if (single && (gpus > 1 || transport == "hostmem")) {
         fprintf(stderr, "-i (single fasta file mode) runs on one GPU: the rounds sharded over --gpus N take a file list\n");
+        return EXIT_FAILURE;
+    }
+    if (single && params.allowLossyParsing) {
+        fprintf(stderr, "--lossy reads the files of a list: single fasta file mode (-i) cuts its elements by the lossless rule only\n");
         return EXIT_FAILURE;
     }
     if (gpus > 1 && params.verifyEmissions) {

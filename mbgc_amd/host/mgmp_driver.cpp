@@ -123,11 +123,17 @@ static bool readWholeFile(const std::string &path, std::string &dest) {
     return true;
 }
 
+// the parser's flags for the files of a list (kseq_read_lossy under allowLossyParsing, MultipleGenomeMatchingProcessor.cpp:9-14)
+static uint32_t listParseFlags(const MGMP_Params *params) {
+    return (params->uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u) | (params->allowLossyParsing ? MBGC_FASTA_LOSSY : 0u);
+}
+
 static void validate_kseq_status(const std::string &fileName, int status) {
     if (status == MBGC_FASTA_OK) return;
     fprintf(stderr, "Error parsing file %s", fileName.c_str());
     if (status == MBGC_FASTA_ENOTFASTA) fprintf(stderr, " - expected FASTA format.\n");
-    else if (status == MBGC_FASTA_ELINES) fprintf(stderr, "\nDetected inconsistent line length in sequences.\n");
+    else if (status == MBGC_FASTA_ELINES) fprintf(stderr, "\nDetected inconsistent line length in sequences.\nConsider the lossy mode (--lossy).\n");
+    else if (status == MBGC_FASTA_EFASTQ) fprintf(stderr, " - FASTQ input is not supported.\n");
     else fprintf(stderr, " - unknown error (code %d).\n", status);
     exit(EXIT_FAILURE);
 }
@@ -170,12 +176,13 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
     // (the record table starts small and grows to what the parser asks for: one entry per two input bytes, the bound,
     // is gigabytes of zeroed memory for a round's files)
     if (records.size() < 4096) records.resize(4096);
-    int rc = mbgc_fasta_parse_host(fasta, (const uint8_t *) data.data(), data.size(), params->uppercaseDNA, (uint8_t *) &seq[0], &seqBytes,
-                                   records.data(), records.size(), &nrec, &lineLen, &status);
+    const uint32_t flags = singleFastaFileMode ? (params->uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u) : listParseFlags(params);
+    int rc = mbgc_fasta_parse_host2(fasta, (const uint8_t *) data.data(), data.size(), flags, (uint8_t *) &seq[0], &seqBytes,
+                                    records.data(), records.size(), &nrec, &lineLen, &status);
     if (rc == -104) {
         records.resize(nrec + nrec / 4 + 16);
-        rc = mbgc_fasta_parse_host(fasta, (const uint8_t *) data.data(), data.size(), params->uppercaseDNA, (uint8_t *) &seq[0], &seqBytes,
-                                   records.data(), records.size(), &nrec, &lineLen, &status);
+        rc = mbgc_fasta_parse_host2(fasta, (const uint8_t *) data.data(), data.size(), flags, (uint8_t *) &seq[0], &seqBytes,
+                                    records.data(), records.size(), &nrec, &lineLen, &status);
     }
     if (rc != 0) {
         fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error());
@@ -398,12 +405,12 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
     std::vector<uint64_t> seqBase(nf + 1), recBase(nf + 1), lineLen(nf);
     std::vector<int> status(nf);
     if (records.size() < 4096) records.resize(4096);
-    int rc = mbgc_fasta_parse_batch_dev(fasta, rawDev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
-                                        records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+    int rc = mbgc_fasta_parse_batch_dev2(fasta, rawDev, fileOff.data(), nf, listParseFlags(params), B.seqDev, B.seqCap, seqBase.data(),
+                                         records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
     if (rc == -104) {                                        // the table was too small: the parser said how many records there are
         records.resize(recBase[nf] + recBase[nf] / 4 + 16);
-        rc = mbgc_fasta_parse_batch_dev(fasta, rawDev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
-                                        records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+        rc = mbgc_fasta_parse_batch_dev2(fasta, rawDev, fileOff.data(), nf, listParseFlags(params), B.seqDev, B.seqCap, seqBase.data(),
+                                         records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
     }
     if (rc != 0) {
         fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error());

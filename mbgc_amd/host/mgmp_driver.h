@@ -41,6 +41,7 @@ struct MGMP_Params {                                   // matching/MGMP_Params.h
     int roundSize = 0;
     static constexpr int MAX_TARGETS_IN_FLIGHT = 64;
     bool uppercaseDNA = false;                         // :196 (-U)
+    bool allowLossyParsing = false;                    // :213 (the reference's -L; mbgc-hip c --lossy): the files of a list are read by kseq_read_lossy
     // mbgc-hip c --bench: every round's contigs are put into HBM first, the rounds after `benchWarmup` are timed and the
     // emitted streams stay packed in HBM (what bench.py measures, from the C++ host)
     bool benchMode = false;
