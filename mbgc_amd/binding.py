@@ -337,6 +337,7 @@ class SlidingWindowSparseEMMatcher:
         pe, prc = np.ascontiguousarray(pred_ext, dtype=np.uint8), np.ascontiguousarray(pred_rc, dtype=np.uint8)
         sp = SpecFinalize(nt, C.cast(ptrs, C.c_void_p), lens.ctypes.data_as(P), int(add_sep), sep, int(lazy), tl.ctypes.data_as(P),
                           after.ctypes.data_as(P), pe.ctypes.data_as(C.c_void_p), prc.ctypes.data_as(C.c_void_p), int(factor), int(rc_factor))
+        sp.veto = int(veto)                           # (also without an exchange: a single replica may decline as well)
         failure = []
         if reduce is not None:
             def _cb(ctx, phase, gate_dev, stream):
@@ -349,7 +350,7 @@ class SlidingWindowSparseEMMatcher:
                     failure.append(e)
                     return -1
             cb = SPEC_EXCHANGE(_cb)
-            sp.gate_dev, sp.exchange, sp.veto = int(gate), C.cast(cb, C.c_void_p), int(veto)
+            sp.gate_dev, sp.exchange = int(gate), C.cast(cb, C.c_void_p)
         applied = C.c_int()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         rc = lib().swsem_emit_batch_begin_spec(self.h, C.byref(params), n, None, vp(lk), vp(fa), vp(pr), vp(ti), vp(ld), ld.size,

@@ -94,6 +94,20 @@ class OracleDeviceMatcher:
     def emit_batch_end(self):
         pass
 
+    def synchronize(self):
+        pass
+
+    def batch_fingerprint(self):
+        rows = [m for m in self._matches if len(m)]
+        allm = np.concatenate(rows) if rows else np.zeros((0, 3), dtype=np.uint64)
+        return _orc.fingerprint(allm), len(allm), int(allm[:, 1].sum())
+
+    def emit_result(self, k):
+        """(unmatchedChars, the six streams by name, None) of result k of the selected emission; no bytes for a contig given up"""
+        un, em = self._selected()[k]
+        streams = em.streams() if un != _orc.SKIPPED else {name: b"" for name in _orc.STREAM_NAMES}
+        return int(un), streams, None
+
     def emit_select(self, previous):
         self._sel_prev = bool(previous)
 
