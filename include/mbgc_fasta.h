@@ -82,6 +82,38 @@ int mbgc_fasta_parse_host2(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n
                            uint64_t *seqBytes, mbgc_fasta_record_t *records, uint64_t recCap, uint64_t *nrec,
                            uint64_t *dnaLineLen, int *status);
 
+/* The protein-profile probe (MGMP_Params::probeProteinsProfile, matching/MGMP_Params.h:86-127, called for the records of the
+ * initial reference by loadG0Ref, MultipleGenomeMatchingProcessor.cpp:82-105), on contigs that lie in HBM.
+ * seq_dev[0..seqBytes) holds the parsed contigs; record r is seq_dev[recOff[r] .. recOff[r] + recLen[r]) (host arrays of nrec
+ * entries, any offsets and alignments). k = the matching k-mer length as it stands (MGMP_Params::k). state_inout is the pair
+ * the reference carries from call to call: probe_remaining starts at MBGC_FASTA_PROBE_MAX_LEN, probe_non_std_count at 0.
+ * For each record in order, while probe_remaining > 0:
+ *     len = min(recLen, probe_remaining); probe_remaining -= len;
+ *     probe_non_std_count += the bytes among the first len that are none of a c g t u A C G T U N (a lowercase n counts);
+ *     probe_len = MBGC_FASTA_PROBE_MAX_LEN - probe_remaining;
+ *     pct = probe_non_std_count * 100 / len      (integers; the RUNNING count over this record's clipped length, as the reference has it)
+ *     fires when probe_len >= MBGC_FASTA_PROBE_MIN_LEN && k != 16 && pct > 10, and then sets probe_remaining = 0 for good.
+ * One deviation: a record whose clipped length is 0 makes the reference divide by zero; here an empty record leaves the state
+ * untouched and does not fire.
+ * result_out: whether the probe fired, at which record (index into recOff; 0 when it did not), and the state afterwards, which
+ * is also written back to state_inout. Every record is walked, so a caller that takes only some records' verdicts (the
+ * sequential schedule takes the first one's) compares `record`. At most MBGC_FASTA_PROBE_MAX_LEN bytes are read. Synchronous. */
+#define MBGC_FASTA_PROBE_MIN_LEN 256
+#define MBGC_FASTA_PROBE_MAX_LEN 65536
+typedef struct { int32_t probe_remaining, probe_non_std_count; } mbgc_fasta_probe_state_t;
+typedef struct {
+    int32_t fired, reserved;
+    uint64_t record;
+    mbgc_fasta_probe_state_t state;
+} mbgc_fasta_probe_result_t;
+int mbgc_fasta_probe_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const uint64_t *recOff, const uint64_t *recLen,
+                         uint64_t nrec, int k, mbgc_fasta_probe_state_t *state_inout, mbgc_fasta_probe_result_t *result_out);
+/* The same for the file that mbgc_fasta_parse_host2 (or _host) parsed last on this handle: its contigs are still in the handle's
+ * device buffer, and records[0..nrec) are the first nrec entries of the table that call returned (seqOff / seqLen are read). The
+ * bytes are probed where they were parsed, as they are after MBGC_FASTA_UPPERCASE. */
+int mbgc_fasta_probe_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, uint64_t nrec, int k,
+                          mbgc_fasta_probe_state_t *state_inout, mbgc_fasta_probe_result_t *result_out);
+
 /* Single-FASTA input (`mbgc c -i`): the rule by which the reference cuts one multi-FASTA byte stream into the initial reference
  * and the targets, mgmpInSplit_next(iter, minSplitSize, '>') (matching/input_with_libdeflate_wrapper.cpp:150-171), on a window of
  * the file in HBM. bytes_dev[0..n) starts at an element start. Element j starts where element j - 1 ended (element 0 at 0) and

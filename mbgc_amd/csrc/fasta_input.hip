@@ -658,6 +658,70 @@ __global__ void __launch_bounds__(THREADS) k_fa_gather(const uint8_t *__restrict
     if (threadIdx.x == 0) dst[to + len] = sep;
 }
 
+// ---- the protein-profile probe (MGMP_Params::probeProteinsProfile, matching/MGMP_Params.h:86-127; rule in mbgc_fasta.h)
+// The host clips the records to what the probe still takes (index arithmetic on the record table, which it holds) and leaves out
+// the empty ones; the bytes are counted and the rule's predicate is evaluated here, where the contigs lie.
+struct ProbeRec { uint64_t off; uint32_t len, index; };          // where the record lies, its clipped length (> 0), its number in the caller's table
+struct ProbeOut { int32_t fired, remaining, nonStd, pad; uint64_t record; };
+
+constexpr uint64_t probe_bit(char c) { return 1ull << (c - 64); }      // the standard symbols all lie in 64..127
+constexpr uint64_t PROBE_STD = probe_bit('a') | probe_bit('c') | probe_bit('g') | probe_bit('t') | probe_bit('u') | probe_bit('A') |
+                               probe_bit('C') | probe_bit('G') | probe_bit('T') | probe_bit('U') | probe_bit('N');
+__device__ __forceinline__ uint32_t probe_non_std(uint32_t c) { return (c >> 6) != 1u || !((PROBE_STD >> (c & 63u)) & 1u) ? 1u : 0u; }
+
+// one wave per record: 16 bytes per lane and step, the record's non-standard bytes counted by ballots
+__global__ void __launch_bounds__(THREADS) k_fa_probe_count(const uint8_t *__restrict__ seq, const ProbeRec *__restrict__ recs, uint32_t nrec,
+                                                            uint32_t *__restrict__ counts) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1), wavesPerBlock = THREADS / WAVE;
+    for (uint32_t r = blockIdx.x * wavesPerBlock + threadIdx.x / WAVE; r < nrec; r += gridDim.x * wavesPerBlock) {   // (the same r for a whole wave)
+        const uint8_t *src = seq + recs[r].off;
+        const uint32_t len = recs[r].len;
+        uint32_t cnt = 0;
+        for (uint32_t base = 0; base < len; base += WAVE * PER) {
+            const uint32_t o = base + lane * PER;
+            uint32_t bad = 0;                                            // bit j: byte o + j is non-standard
+            if (o + PER <= len) {
+                uint4 t;
+                memcpy(&t, src + o, PER);
+                const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+                for (int j = 0; j < PER; j++) bad |= probe_non_std((w[j >> 2] >> (8 * (j & 3))) & 0xffu) << j;
+            } else
+                for (uint32_t q = o; q < len && q < o + PER; q++) bad |= probe_non_std(src[q]) << (q - o);
+            for (int j = 0; j < PER; j++) cnt += (uint32_t) __popcll(__ballot((bad >> j) & 1u));
+        }
+        if (lane == 0) counts[r] = cnt;
+    }
+}
+
+// one wave walks the records in order, 64 at a time: prefix sums of the clipped lengths and the counts give every record the
+// state the reference has behind it; the first record whose predicate holds fires
+__global__ void __launch_bounds__(WAVE) k_fa_probe_walk(const ProbeRec *__restrict__ recs, const uint32_t *__restrict__ counts, uint32_t nrec,
+                                                        int32_t remaining, int32_t nonStd, int32_t k, ProbeOut *__restrict__ out) {
+    const uint32_t lane = threadIdx.x;
+    int32_t fired = 0, record = 0;
+    for (uint32_t base = 0; base < nrec && !fired; base += WAVE) {
+        const uint32_t r = base + lane;
+        const int32_t len = r < nrec ? (int32_t) recs[r].len : 0, cnt = r < nrec ? (int32_t) counts[r] : 0;
+        const int32_t index = r < nrec ? (int32_t) recs[r].index : 0;
+        int32_t sumLen = len, sumCnt = cnt;                             // inclusive
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const int32_t y = __shfl_up(sumLen, d), z = __shfl_up(sumCnt, d);
+            if ((int) lane >= d) { sumLen += y; sumCnt += z; }
+        }
+        const int32_t probeLen = MBGC_FASTA_PROBE_MAX_LEN - (remaining - sumLen), running = nonStd + sumCnt;
+        const bool fire = len > 0 && probeLen >= MBGC_FASTA_PROBE_MIN_LEN && k != 16 && running * 100 / (len > 0 ? len : 1) > 10;
+        const unsigned long long m = __ballot(fire);
+        if (m) {
+            const int f = __ffsll(m) - 1;
+            fired = 1; record = __shfl(index, f);
+            remaining = 0; nonStd = __shfl(running, f);
+        } else {
+            remaining -= __shfl(sumLen, WAVE - 1); nonStd += __shfl(sumCnt, WAVE - 1);
+        }
+    }
+    if (lane == 0) { out->fired = fired; out->remaining = remaining; out->nonStd = nonStd; out->pad = 0; out->record = (uint64_t) (uint32_t) record; }
+}
+
 std::string g_err;
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -709,6 +773,10 @@ struct mbgc_fasta {
     bool copyPending = false;
     fa::Buf<uint64_t> dGatherTab;               // mbgc_fasta_gather_dev
     fa::Buf<uint8_t> dGatherOut;
+    fa::Buf<fa::ProbeRec> dProbeRecs;           // mbgc_fasta_probe_dev: the clipped records, their counts, the result
+    fa::Buf<uint32_t> dProbeCounts;
+    fa::Buf<fa::ProbeOut> dProbeOut;
+    uint64_t hostParsedBytes = 0;               // sequence bytes mbgc_fasta_parse_host2 left in dHostOut (mbgc_fasta_probe_host)
 };
 
 extern "C" {
@@ -734,6 +802,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     if (p->stream) { (void) hipStreamSynchronize(p->stream); (void) hipStreamDestroy(p->stream); }
     p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dShift.release(); p->dHostIn.release(); p->dHostOut.release();
     p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
+    p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
@@ -844,6 +913,7 @@ int mbgc_fasta_parse_host2(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n
     using namespace fa;
     FCHK(hipSetDevice(p->device));
     int r;
+    p->hostParsedBytes = 0;
     if ((r = p->dHostIn.reserve(std::max<uint64_t>(n, 1))) || (r = p->dHostOut.reserve(std::max<uint64_t>(n, 1)))) return r;
     if (n) FCHK(hipMemcpy(p->dHostIn.p, file_host, n, hipMemcpyHostToDevice));
     const uint64_t off[2] = {0, n};
@@ -853,8 +923,53 @@ int mbgc_fasta_parse_host2(mbgc_fasta_t *p, const uint8_t *file_host, uint64_t n
     r = mbgc_fasta_parse_batch_dev2(p, p->dHostIn.p, off, 1, flags, p->dHostOut.p, n, sb, records, recCap, rb, dnaLineLen, status);
     if (r) { *nrec = rb[1]; return r; }
     *nrec = rb[1]; *seqBytes = sb[1];
+    p->hostParsedBytes = sb[1];
     if (sb[1]) FCHK(hipMemcpy(seq_out_host, p->dHostOut.p, sb[1], hipMemcpyDeviceToHost));
     return 0;
+}
+
+int mbgc_fasta_probe_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const uint64_t *recOff, const uint64_t *recLen,
+                         uint64_t nrec, int k, mbgc_fasta_probe_state_t *state_inout, mbgc_fasta_probe_result_t *result_out) {
+    using namespace fa;
+    const int32_t remaining0 = state_inout->probe_remaining, nonStd0 = state_inout->probe_non_std_count;
+    if (remaining0 < 0 || remaining0 > MBGC_FASTA_PROBE_MAX_LEN || nonStd0 < 0 || nonStd0 > MBGC_FASTA_PROBE_MAX_LEN)
+        return fail(-103, "probe: state (%d, %d) is none the rule can reach", remaining0, nonStd0);
+    if (nrec > UINT32_MAX) return fail(-103, "probe: %llu records", (unsigned long long) nrec);
+    // the records the probe still reaches, clipped (an empty one changes nothing: left out)
+    std::vector<ProbeRec> tab;
+    uint64_t left = (uint64_t) remaining0;
+    for (uint64_t r = 0; r < nrec && left; r++) {
+        if (recOff[r] > seqBytes || recLen[r] > seqBytes - recOff[r]) return fail(-103, "probe: record %llu lies outside the sequence bytes", (unsigned long long) r);
+        const uint64_t len = std::min<uint64_t>(recLen[r], left);
+        if (!len) continue;
+        tab.push_back(ProbeRec{recOff[r], (uint32_t) len, (uint32_t) r});
+        left -= len;
+    }
+    *result_out = mbgc_fasta_probe_result_t{0, 0, 0, *state_inout};
+    if (tab.empty()) return 0;
+    FCHK(hipSetDevice(p->device));
+    const uint32_t n = (uint32_t) tab.size();
+    int rc;
+    if ((rc = p->dProbeRecs.reserve(n)) || (rc = p->dProbeCounts.reserve(n)) || (rc = p->dProbeOut.reserve(1))) return rc;
+    FCHK(hipMemcpyAsync(p->dProbeRecs.p, tab.data(), n * sizeof(ProbeRec), hipMemcpyHostToDevice, p->stream));
+    const uint32_t wavesPerBlock = THREADS / WAVE;
+    k_fa_probe_count<<<dim3(std::min<uint32_t>((n + wavesPerBlock - 1) / wavesPerBlock, 1024)), dim3(THREADS), 0, p->stream>>>(seq_dev, p->dProbeRecs.p, n, p->dProbeCounts.p);
+    k_fa_probe_walk<<<dim3(1), dim3(WAVE), 0, p->stream>>>(p->dProbeRecs.p, p->dProbeCounts.p, n, remaining0, nonStd0, k, p->dProbeOut.p);
+    FCHK(hipGetLastError());
+    ProbeOut out;
+    FCHK(hipMemcpyAsync(&out, p->dProbeOut.p, sizeof out, hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    result_out->fired = out.fired; result_out->record = out.fired ? out.record : 0;
+    result_out->state.probe_remaining = out.remaining; result_out->state.probe_non_std_count = out.nonStd;
+    *state_inout = result_out->state;
+    return 0;
+}
+
+int mbgc_fasta_probe_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, uint64_t nrec, int k,
+                          mbgc_fasta_probe_state_t *state_inout, mbgc_fasta_probe_result_t *result_out) {
+    std::vector<uint64_t> off(nrec), len(nrec);
+    for (uint64_t r = 0; r < nrec; r++) { off[r] = records[r].seqOff; len[r] = records[r].seqLen; }
+    return mbgc_fasta_probe_dev(p, p->dHostOut.p, p->hostParsedBytes, off.data(), len.data(), nrec, k, state_inout, result_out);
 }
 
 int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,

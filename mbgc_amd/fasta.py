@@ -6,7 +6,8 @@ import numpy as np
 from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
-           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download""".split()
+           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -19,6 +20,17 @@ class Record(C.Structure):
 
 class FormatRecord(C.Structure):
     _fields_ = [("seqOff", C.c_uint64), ("seqLen", C.c_uint64), ("headerOff", C.c_uint64), ("headerLen", C.c_uint64), ("lineLen", C.c_uint64)]
+
+
+PROBE_MIN_LEN, PROBE_MAX_LEN = 256, 65536      # MBGC_FASTA_PROBE_MIN_LEN, MBGC_FASTA_PROBE_MAX_LEN
+
+
+class ProbeState(C.Structure):
+    _fields_ = [("probe_remaining", C.c_int32), ("probe_non_std_count", C.c_int32)]
+
+
+class ProbeResult(C.Structure):
+    _fields_ = [("fired", C.c_int32), ("reserved", C.c_int32), ("record", C.c_uint64), ("state", ProbeState)]
 
 
 class TextTooSmall(binding.SwsemError):
@@ -51,6 +63,9 @@ def _lib():
                                             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_gather_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint8,
                                             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.mbgc_fasta_probe_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_int,
+                                           C.POINTER(ProbeState), C.POINTER(ProbeResult)]
+        L.mbgc_fasta_probe_host.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, C.c_int, C.POINTER(ProbeState), C.POINTER(ProbeResult)]
         L._fasta_ready = True
     return L
 
@@ -127,6 +142,38 @@ class FastaParser:
         seq = out[: nb.value].tobytes()
         records = [(data[x.headerOff: x.headerOff + x.headerLen], seq[x.seqOff: x.seqOff + x.seqLen]) for x in recs[: nrec.value]]
         return dict(status=status.value, records=records, dna_line_len=line.value, seq=seq)
+
+    def probe_dev(self, seq_ptr, seq_bytes, offsets, lengths, k=32, state=(PROBE_MAX_LEN, 0)):
+        """probeProteinsProfile over the records seq_ptr[offsets[r] .. + lengths[r]) of a device buffer of seq_bytes bytes, from
+        state = (probe_remaining, probe_non_std_count) -> (fired, record index, state afterwards)"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        assert off.size == ln.size
+        st, res = ProbeState(int(state[0]), int(state[1])), ProbeResult()
+        P = C.POINTER(C.c_uint64)
+        if _lib().mbgc_fasta_probe_dev(self.h, seq_ptr, int(seq_bytes), off.ctypes.data_as(P), ln.ctypes.data_as(P), off.size, int(k),
+                                       C.byref(st), C.byref(res)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        assert (st.probe_remaining, st.probe_non_std_count) == (res.state.probe_remaining, res.state.probe_non_std_count)
+        return bool(res.fired), int(res.record), (st.probe_remaining, st.probe_non_std_count)
+
+    def probe_host(self, data, k=32, state=(PROBE_MAX_LEN, 0), uppercase=False, records=None):
+        """one file in host memory: parsed (mbgc_fasta_parse_host2), then its first `records` records (all: None) probed where the
+        parse left them on the device (mbgc_fasta_probe_host) -> as probe_dev"""
+        data = bytes(data)
+        src = np.frombuffer(data + b"\0", dtype=np.uint8)
+        out = np.zeros(max(len(data), 1), dtype=np.uint8)
+        nb, nrec, line, status = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        rec_cap = max(self._rec_cap, len(data) // 2 + 1)
+        recs = (Record * rec_cap)()
+        if _lib().mbgc_fasta_parse_host2(self.h, src.ctypes.data_as(C.c_void_p), len(data), UPPERCASE if uppercase else 0, out.ctypes.data_as(C.c_void_p),
+                                         C.byref(nb), recs, rec_cap, C.byref(nrec), C.byref(line), C.byref(status)) or status.value:
+            raise binding.SwsemError("parse: status %d %s" % (status.value, _lib().mbgc_fasta_last_error().decode()))
+        n = nrec.value if records is None else min(int(records), nrec.value)
+        st, res = ProbeState(int(state[0]), int(state[1])), ProbeResult()
+        if _lib().mbgc_fasta_probe_host(self.h, recs, n, int(k), C.byref(st), C.byref(res)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return bool(res.fired), int(res.record), (st.probe_remaining, st.probe_non_std_count)
 
     def split_dev(self, bytes_ptr, n, is_file_end, first_min, next_min, max_elems):
         """mgmpInSplit_next over the window bytes_ptr[0..n) in HBM (it starts at an element start): the end offsets of the

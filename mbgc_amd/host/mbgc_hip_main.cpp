@@ -85,7 +85,7 @@ int main(int argc, char **argv) {
             if (params.k1 <= 0) { fprintf(stderr, "s - reference sampling step - should be a positive integer.\n\n"); return EXIT_FAILURE; }
         }
         else if (a == "-k" && i + 1 < argc) {                                    // matching k-mer length (MBGC_Params.h:583-591): the matcher's L, matchTexts' minimal length, .meta's k
-            params.k = atoi(argv[++i]);
+            params.setKmerLength(atoi(argv[++i]));                                // (fixed: the protein profile then leaves it alone)
             if (params.k < 16 || params.k > 40) { fprintf(stderr, "k - matching kmer length - should be an integer between 16 and 40.\n\n"); return EXIT_FAILURE; }
         }
         else if (a == "-i" && i + 1 < argc) params.inputFileName = argv[++i];      // single fasta file mode (MBGC_Params.h:793-803)
@@ -93,6 +93,7 @@ int main(int argc, char **argv) {
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "-L") params.lazyDecompressionSupport = false;             // disable lazy decompression support
         else if (a == "-U") params.uppercaseDNA = true;                          // MBGC_Params.h: converts bases to uppercase
+        else if (a == "--proteins") params.setProteinsCompressionProfile();       // the reference's developer option -P (main.cpp:332-334); where it stands among the options matters as it does there
         else if (a == "--lossy") params.allowLossyParsing = true;                 // the reference's -L (MGMP_Params.h:213): ragged lines, CRLF, leading junk are read, not refused
         else if (a == "--bench") params.benchMode = true;                        // rounds timed with every contig resident in HBM (no streams written)
         else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
@@ -112,13 +113,18 @@ int main(int argc, char **argv) {
     const bool single = !params.inputFileName.empty();
     if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
     if (pos.size() != 2 || (single && !pos[0].empty())) {
-        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--lossy] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
+        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
                         "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
                         "  2 MiB at '>' bytes, on the device, while it travels to the GPU in windows of K KiB (default 32768; host memory is bounded by two\n"
                         "  windows, except for a gzip file, which is inflated on the host and held whole in memory); also prints `single-file elements: <n>`\n"
                         "  and writes <outputPrefix>.seqCounts (one little-endian u32 per target: its records)\n"
+                        "  --proteins: the protein profile (the reference's developer option -P): k = 16 unless -k is given, mismatches coded without\n"
+                        "  exclusion, no reverse-complement pass under -m 3. Without the option the first 65536 bases of the initial reference are probed on\n"
+                        "  the device, as `mbgc c` probes them: record by record, the profile is switched (\"Switching to protein profile.\") at the first\n"
+                        "  record behind which at least 256 bases have been seen, k is not 16 and (symbols so far outside acgtuACGTUN) * 100 / (the record's\n"
+                        "  probed length) > 10; -t1 / -m 3 take only the first record's verdict. An empty record is skipped (the reference divides by zero)\n"
                         "  --lossy: the files of the list are read as `mbgc c -L` reads them (any line lengths, empty lines, CRLF, bytes in front of the first\n"
                         "  '>'; the longest line becomes the file's line length); FASTQ files are refused; not with -i\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
@@ -214,12 +220,13 @@ int main(int argc, char **argv) {
         void *lib = dlopen(backend.c_str(), RTLD_NOW | RTLD_LOCAL);
         leaf = lib ? (mbgc_leaf_compress_fn) dlsym(lib, "mbgc_leaf_compress") : nullptr;
         if (!leaf) { fprintf(stderr, "cannot load the leaf coders from %s: %s\n", backend.c_str(), dlerror()); return finish(EXIT_FAILURE); }
-        if (backendOverlapBlock) {
-            mbgc_backend_params_t bp;
-            enc.backendParams(bp, 1, coderThreads > 0 ? coderThreads : backendThreads);
-            enc.backendStream = mbgc_backend_stream_open(&bp, leaf, nullptr, backendThreads, backendOverlapBlock);
-            if (!enc.backendStream) { fprintf(stderr, "%s\n", mbgc_backend_last_error()); return finish(EXIT_FAILURE); }
-        }
+        if (backendOverlapBlock)
+            enc.afterG0Loaded = [&] {                                            // (the probe of the initial reference may have changed k and the exclusion flag: the coders follow them)
+                mbgc_backend_params_t bp;
+                enc.backendParams(bp, 1, coderThreads > 0 ? coderThreads : backendThreads);
+                enc.backendStream = mbgc_backend_stream_open(&bp, leaf, nullptr, backendThreads, backendOverlapBlock);
+                if (!enc.backendStream) { fprintf(stderr, "%s\n", mbgc_backend_last_error()); exit(EXIT_FAILURE); }
+            };
     }
     struct timespec tEnc0, tEnc1;
     clock_gettime(CLOCK_MONOTONIC, &tEnc0);

@@ -31,12 +31,24 @@ void MBGC_Params::setCompressionMode(int mode) {                // MBGC_Params.h
     }
     coderMode = (uint8_t) mode;
     swsem_emit_params_default(&emit, mode);
+    if (mismatchesWithExclusionDisabled) emit.mismatchesWithExclusion = 0;
     if (mode >= 2) {
         bigReferenceCompressorRatio = 4;
         skipMargin = 24;
         unmatchedFractionRCFactor = 128;
     }
-    if (mode == 3) { sequentialMatching = true; rcMatchMinLength = 55; rcRedundancyRemoval = true; }   // :915-920, DEFAULT_RC_MATCH_MINIMUM_LENGTH :61
+    if (mode == 3) {                                                                           // :915-920, DEFAULT_RC_MATCH_MINIMUM_LENGTH :61
+        sequentialMatching = true;
+        if (!rcMatchMinLengthFixed) { rcMatchMinLength = 55; rcRedundancyRemoval = true; }
+    }
+}
+
+void MBGC_Params::setProteinsCompressionProfile() {             // MBGC_Params.h:924-936
+    if (!exchange || mbgc_xchg_rank(exchange) == 0) fprintf(stderr, "Switching to protein profile.\n");   // (every rank decides; one reports)
+    if (!kmerLengthFixed) k = PROTEINS_PROFILE_KMER_LENGTH;
+    mismatchesWithExclusionDisabled = true;
+    emit.mismatchesWithExclusion = 0;
+    if (!rcMatchMinLengthFixed) { rcMatchMinLength = 0; rcRedundancyRemoval = false; }
 }
 
 // PgHelpers::writeUInt64Frugal, utils/helper.cpp:237-246
@@ -165,10 +177,28 @@ void MultipleGenomeMatchingProcessor::readG0(const std::string &path, std::vecto
     std::string data;
     if (!readWholeFile(path, data)) { fprintf(stderr, "cannot open file %s\n", path.c_str()); exit(EXIT_FAILURE); }
     if (fileSize) *fileSize = data.size();
-    parseHostBytes(data, path, out);
+    parseHostBytes(data, path, out, true);
 }
 
-void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, const std::string &path, std::vector<Contig> &out) {
+// The protein-profile probe over the initial reference's records, which the parser has left in HBM (after -U): MGMP.cpp:85-87.
+// Round schedule: every record is probed and the first that fires switches the profile. Sequential schedule (:91-98): only the
+// first record's verdict switches; the records behind it are still probed while fewer than MIN_PROBE_LEN bases have been seen, their
+// verdicts discarded (what they do to the state is kept, as there).
+void MultipleGenomeMatchingProcessor::probeG0Records(uint64_t nrec) {
+    if (params->sequentialMatching && nrec) {
+        uint64_t m = 1, probed = records[0].seqLen;
+        while (probed < MBGC_FASTA_PROBE_MIN_LEN && m < nrec) probed += records[m++].seqLen;
+        nrec = m;
+    }
+    mbgc_fasta_probe_result_t res;
+    if (mbgc_fasta_probe_host(fasta, records.data(), nrec, params->k, &params->probe, &res) != 0) {
+        fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error());
+        exit(EXIT_FAILURE);
+    }
+    if (res.fired && (!params->sequentialMatching || res.record == 0)) setProteinsProfile();
+}
+
+void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, const std::string &path, std::vector<Contig> &out, bool probeG0) {
     openInputStage();
     std::string seq(data.size(), '\0');
     uint64_t seqBytes = 0, nrec = 0, lineLen = 0;
@@ -189,6 +219,7 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
         exit(EXIT_FAILURE);
     }
     validate_kseq_status(path, status);
+    if (probeG0) probeG0Records(nrec);
     hostLineLen = lineLen;
     out.clear();
     for (uint64_t k = 0; k < nrec; k++) {
@@ -580,7 +611,7 @@ void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
         initStreamsForG0Ref();
         largestContigSize = 0;
         if (params->sequentialMatching) {                                                      // MGMP.cpp:91-100: the first contig; the file is target 0
-            parseHostBytes(sfFirstRecord(), name, contigs);
+            parseHostBytes(sfFirstRecord(), name, contigs, true);
             if (contigs.empty()) validate_kseq_status(name, MBGC_FASTA_ENOTFASTA);
             contigs.resize(1);
         } else {                                                                               // :73-76: element 0
@@ -589,7 +620,7 @@ void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
             g0Bytes = ends.empty() ? 0 : ends[0];
             std::string data(g0Bytes, '\0');
             if (g0Bytes) inputStageCheck(mbgc_fasta_download(fasta, &data[0], sf.dev, g0Bytes));
-            parseHostBytes(data, name, contigs);
+            parseHostBytes(data, name, contigs, true);
             sfConsume(g0Bytes);
             sf.nextElem = 1;
             totalFilesLength += g0Bytes;
@@ -1525,6 +1556,7 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
         startReadAhead(1, std::min<uint32_t>(filesCount, 1 + (uint32_t) std::max(1, params->roundSize)), 1, readBesideUpload());
     const double tG0 = nowSeconds();
     loadG0Ref(fileNames[0]);
+    if (afterG0Loaded) afterG0Loaded();
     if (getenv("MBGC_HIP_TIMES")) fprintf(stderr, "  loadG0Ref (the matcher's buffers and table, the first file): %.0f ms\n", (nowSeconds() - tG0) * 1e3);
     const int guessed = params->roundSize;
     if (autoRound) params->roundSize = (int) windowRoundSize(matcher->getSlidingWindowSize(), gpus);   // (the window as the matcher has it)

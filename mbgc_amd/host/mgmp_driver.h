@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <future>
 #include <mutex>
 #include <string>
@@ -22,6 +23,10 @@
 
 struct MGMP_Params {                                   // matching/MGMP_Params.h (only what this path reads)
     int k = 32, k1 = 16, k2 = 1;                       // :199-202
+    static constexpr int PROTEINS_PROFILE_KMER_LENGTH = 16;               // :27
+    // probeProteinsProfile's state (:90-91), carried from one load of the initial reference to the next (the -i path that falls
+    // back to the sequential schedule loads it twice); the probe itself runs on the device (mbgc_fasta_probe_dev)
+    mbgc_fasta_probe_state_t probe = {MBGC_FASTA_PROBE_MAX_LEN, 0};
     uint8_t skipMargin = 16;                           // :203 (24 in -m2/-m3, MBGC_Params.h:908-909)
     int referenceFactor = -1;                          // ADJUSTED_REFERENCE_FACTOR_FLAG, :24,:205
     int referenceSlidingWindowFactor = 16;             // :206
@@ -73,11 +78,18 @@ struct MBGC_Params : MGMP_Params {                     // mbgccoder/MBGC_Params.
     uint8_t coderMode = 1;
     bool lazyDecompressionSupport = true;              // :38
     uint64_t rcMatchMinLength = 0;                     // :99 (55 in -m3, :61,:917-918)
+    bool rcMatchMinLengthFixed = false;                // :100 (set by the reference's -r, which this tool does not have)
     bool rcRedundancyRemoval = false;                  // :101
+    bool kmerLengthFixed = false;                      // :71 (-k)
+    bool mismatchesWithExclusionDisabled = false;      // disableMismatchesEncodingWithExclusion, :731-738: outlives a later -m
     swsem_emit_params_t emit;
     int device = 0;
     MBGC_Params() { setCompressionMode(1); }
     void setCompressionMode(int mode);                 // :886-922
+    void setKmerLength(int kmerLength) { k = kmerLength; kmerLengthFixed = true; }   // :583-591
+    // :924-936, on --proteins and when the probe of the initial reference fires: k = 16 unless -k was given, mismatches coded
+    // without exclusion, no reverse-complement pass over the literals; "Switching to protein profile." on stderr
+    void setProteinsCompressionProfile();
 };
 
 struct Contig { std::string header, seq; };
@@ -162,7 +174,9 @@ protected:
     void keepHeaders(RoundBatch &B, const uint8_t *fileBytes, const uint64_t *fileOff, const uint64_t *recBase, const uint64_t *lineLen, int nf);
     void openInputStage();
     void readG0(const std::string &path, std::vector<Contig> &out, uint64_t *fileSize);
-    void parseHostBytes(const std::string &data, const std::string &name, std::vector<Contig> &out);
+    // probeG0: the file is the initial reference, and its parsed records are probed for the protein profile before they come down
+    void parseHostBytes(const std::string &data, const std::string &name, std::vector<Contig> &out, bool probeG0 = false);
+    void probeG0Records(uint64_t nrec);                                                 // MGMP.cpp:85-87,91-98 over records[0, nrec) of the last parseHostBytes
     // Single fasta file mode: the file travels through the two staging buffers in windows of params->singleFileWindow bytes (the
     // next one is read while this one is uploaded and split) into a device buffer that starts at an element start; what a batch
     // leaves behind its last element is moved to the front of a second buffer and the two change places. Host memory is bounded
@@ -193,6 +207,7 @@ protected:
     void loadRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t nextF0 = 0, uint32_t nextF1 = 0, RoundBatch *nextB = nullptr);
 
     // hooks, MGMP.h:79-115
+    virtual void setProteinsProfile() = 0;
     virtual void initStreamsForG0Ref() = 0;
     virtual void processG0RefContig(const char *seq, size_t len) = 0;
     virtual size_t processMatches(size_t destLen, int targetIdx, size_t matchingLockPos) = 0;   // consumes the handle's last match
@@ -239,6 +254,7 @@ class MBGC_Encoder : public MultipleGenomeMatchingProcessor {
     void noteTargetAppended();
     size_t backendFed[MBGC_ST_COUNT] = {};                                              // bytes of every stream the backend has been handed
 
+    void setProteinsProfile() override { params->setProteinsCompressionProfile(); }     // ENC.cpp:20-23
     void initStreamsForG0Ref() override;                                                // ENC.cpp:25-32
     void processG0RefContig(const char *seq, size_t len) override;                      // :34-37
     size_t processMatches(size_t destLen, int targetIdx, size_t matchingLockPos) override;      // :143-308 on the device
@@ -282,6 +298,9 @@ public:
     // go on; finishBackendStream() hands over the rest and returns the section. The literals wait for the end under -m3 (the
     // reverse-complement pass rewrites them, ENC.cpp:636-638).
     mbgc_backend_stream_t *backendStream = nullptr;
+    // called once the initial reference is loaded: the profile (k, exclusion, the RC pass) is decided by then, and a backend that
+    // runs beside the matching is opened here, with the coders of the parameters as they now stand
+    std::function<void()> afterG0Loaded;
     void feedBackendStream(bool everything);
     std::string finishBackendStream(uint64_t *blocksCodedEarly);
     void backendParams(mbgc_backend_params_t &bp, int blocksScale, int numberOfThreads) const;
