@@ -316,6 +316,11 @@ enum { SWSEM_K_LOAD = 0, SWSEM_K_INSERT = 1, SWSEM_K_PROBE = 2 /* unused: the ch
    the true state, out[7] = blocks given up because they carried too many such boundaries (diagnostics; synchronises the device) */
 int swsem_debug_emit_stats(swsem_t *h, uint64_t out[8]);
 int swsem_debug_block_times(swsem_t *h, uint64_t *out /* [cap][3]: ticks, candidates visited, stack rows */, uint64_t cap, uint64_t *nblocks);
+/* the lap tags (one uint16 per sampling slot of k1 bytes) and their summary (one uint16 per 2^*shift slots: the tag every slot of
+   the block holds, or 0xFFFF = mixed, look at the tags) as the device holds them behind everything queued on the handle's stream;
+   at most cap entries are copied, *n says how many there are (0: the handle keeps none) */
+int swsem_debug_tags(swsem_t *h, uint16_t *out, uint64_t cap, uint64_t *n);
+int swsem_debug_tag_summary(swsem_t *h, uint16_t *out, uint64_t cap, uint64_t *n, int *shift);
 int swsem_profile_enable(swsem_t *h, int on);
 int swsem_profile_get(swsem_t *h, double ms[SWSEM_K_COUNT], uint64_t launches[SWSEM_K_COUNT]);
 /* counters of the last batch (after swsem_batch_counts): [0] query bases, [1] hash-table probes,

@@ -21,7 +21,7 @@ swsem_disable_sliding_window swsem_set_sliding_window_size swsem_disable_circula
 swsem_get_loading_position swsem_get_loaded_ref_length swsem_get_max_ref_length swsem_get_sliding_window_size swsem_get_dropped_bytes swsem_set_position
 swsem_acquire_lock swsem_release_lock swsem_get_K swsem_get_hash_size swsem_load_ref swsem_load_ref_dev
 swsem_load_separator swsem_finalize_targets swsem_revcomp_dev swsem_match swsem_match_batch_dev swsem_batch_counts swsem_batch_matches
-swsem_batch_fingerprint swsem_emit_params_default swsem_emit swsem_emit_batch swsem_emit_batch_begin swsem_emit_batch_begin_spec swsem_emit_batch_end swsem_emit_select swsem_emit_result swsem_emit_set_host_copy swsem_emit_unmatched swsem_emit_pack_dev swsem_emit_pack_dev_on swsem_emit_counters swsem_debug_copy_ref swsem_debug_write_ref swsem_debug_copy_ht swsem_debug_emit_stats
+swsem_batch_fingerprint swsem_emit_params_default swsem_emit swsem_emit_batch swsem_emit_batch_begin swsem_emit_batch_begin_spec swsem_emit_batch_end swsem_emit_select swsem_emit_result swsem_emit_set_host_copy swsem_emit_unmatched swsem_emit_pack_dev swsem_emit_pack_dev_on swsem_emit_counters swsem_debug_copy_ref swsem_debug_write_ref swsem_debug_copy_ht swsem_debug_emit_stats swsem_debug_tags swsem_debug_tag_summary
 swsem_profile_enable swsem_profile_get swsem_batch_stats swsem_dev_malloc swsem_dev_free swsem_dev_upload swsem_dev_download swsem_dev_copy swsem_decode_contigs_dev swsem_emit_verify
 swsem_create_decoder swsem_decode_plan_chain_dev swsem_decode_fill_range_dev swsem_decode_load_dev""".split()
 
@@ -153,6 +153,9 @@ def lib():
         L.swsem_debug_copy_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_write_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_copy_ht.argtypes = [vp, vp]
+        if hasattr(L, "swsem_debug_tag_summary"):        # (an older library loaded through MBGC_HIP_LIB for an A/B run has neither)
+            L.swsem_debug_tags.argtypes = [vp, vp, u64, pu64]
+            L.swsem_debug_tag_summary.argtypes = [vp, vp, u64, pu64, C.POINTER(ci)]
         L.swsem_profile_enable.argtypes = [vp, ci]
         L.swsem_profile_get.argtypes = [vp, C.POINTER(C.c_double), pu64]
         L.swsem_batch_stats.argtypes = [vp, pu64]
@@ -430,6 +433,23 @@ class SlidingWindowSparseEMMatcher:
         out = np.zeros(self.hash_size(), dtype=np.uint32)
         _chk(lib().swsem_debug_copy_ht(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def tags(self):
+        """the lap tag of every sampling slot (uint16; empty when the handle keeps none)"""
+        n = C.c_uint64()
+        _chk(lib().swsem_debug_tags(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint16)
+        _chk(lib().swsem_debug_tags(self.h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out
+
+    def tag_summary(self):
+        """-> (the device's summary of the lap tags: one uint16 per 2**shift sampling slots, 0xFFFF = mixed; shift). Without a
+        summary (SWSEM_TAGSUM_SHIFT=0): an empty array and 0."""
+        n, shift = C.c_uint64(), C.c_int()
+        _chk(lib().swsem_debug_tag_summary(self.h, None, 0, C.byref(n), C.byref(shift)))
+        out = np.zeros(n.value, dtype=np.uint16)
+        _chk(lib().swsem_debug_tag_summary(self.h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n), C.byref(shift)))
+        return out, shift.value
 
     def profile_enable(self, on=True): _chk(lib().swsem_profile_enable(self.h, int(on)))
 

@@ -46,6 +46,11 @@ struct RefView {
     // its K-mer's bytes changed afterwards. tagCur / tagPrev: the tags of the current / previous lap (0: there is none).
     const uint16_t *tags;
     uint32_t tagCur, tagPrev;
+    // one entry per 2^tagSumShift sampling slots: the tag EVERY slot of that coarse block holds in tags[], or TAGSUM_MIXED: look at
+    // tags[]. The loader writes a piece as one run of on-grid samples, so nearly every block is uniform; the summary (78 KB for the
+    // 320 MB of tags at a 2.56e9-byte buffer) stays in every XCD's L2, where tags[] is a scattered 2-byte read beyond it. Null: none.
+    const uint16_t *tagSum;
+    int tagSumShift;
     int K, k1ord, skipMargin;
     uint32_t minLen;
 };
@@ -123,8 +128,11 @@ __device__ __forceinline__ uint32_t ht_value(const RefView &v, ht_entry e, uint3
 // hashes here, and memcmp (.cpp:298) fails without any other effect. lap_want gives the tag such a sampling left: the
 // current lap's for slots wholly below the loading position, the previous lap's for slots at or above it, none for a slot
 // that straddles it. (After many laps about 40 % of the buckets hold stale entries: each costs one 2-byte lookup here
-// instead of a 256-byte visit.)
+// instead of a 256-byte visit — and where the slot's coarse block is uniform, a lookup in the summary, which stays in L2.)
 __host__ __device__ __forceinline__ uint32_t lap_tag(int lap) { return 1u + (uint32_t) lap % 65535u; }
+// lap_tag takes every value from 1 to 0xFFFF, so no 16-bit value is free for "mixed": an entry that holds 0xFFFF is read as mixed
+// whatever it was meant to say (always safe: tags[] decides), and the loader never writes lap_tag(lap) == 0xFFFF into the summary.
+constexpr uint32_t TAGSUM_MIXED = 0xFFFFu;
 __device__ __forceinline__ uint32_t lap_want(const RefView &v, uint32_t val) {
     return val <= v.curMax ? v.tagCur : (val >= v.prevMin ? v.tagPrev : 0u);
 }
@@ -136,7 +144,9 @@ __device__ __forceinline__ bool stale_settled(const RefView &v, ht_entry hte, ui
     const uint32_t ep = (uint32_t) (hte >> (32 + v.fpBits));
     if (ep == 0 || (e <= v.curMax ? ep >= v.eCur : (e >= v.prevMin && ep >= v.ePrev))) return false;   // marked by k_mark_stale / as young as the text
     const uint32_t want = lap_want(v, e);
-    return want != 0 && v.tags[e] == want;
+    if (want == 0) return false;
+    const uint32_t s = v.tagSum ? (uint32_t) v.tagSum[e >> v.tagSumShift] : TAGSUM_MIXED;
+    return s != TAGSUM_MIXED ? s == want : v.tags[e] == want;
 }
 
 // window test of SlidingWindowSparseEMMatcher.cpp:212-222. Returns false when the entry is rejected.

@@ -97,6 +97,19 @@ __global__ void k_set_bytes(uint8_t *__restrict__ ref, const BytePiece *__restri
     if (gate && *gate == 0) return;
     for (int i = 0; i < n; i++) ref[b[i].off] = (uint8_t) b[i].val;
 }
+// The lap-tag summary's entries a finalize changes (RefView::tagSum), behind the same gate as the tag writes they describe:
+// entries [first, first + count) of run i become val. The host lists runs that do not overlap (plan_tag_summary), so the
+// order in which the threads arrive does not matter; nEntries bounds every index.
+struct SumRun { uint32_t first, count, val, pad; };
+__global__ void __launch_bounds__(256) k_set_tagsum(uint16_t *__restrict__ tagSum, uint32_t nEntries, const SumRun *__restrict__ runs, int n,
+                                                    const uint32_t *__restrict__ gate) {
+    if (gate && *gate == 0) return;
+    for (int i = 0; i < n; i++) {
+        const SumRun r = runs[i];
+        for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < r.count; k += gridDim.x * blockDim.x)
+            if ((uint64_t) r.first + k < nEntries) tagSum[r.first + k] = (uint16_t) r.val;
+    }
+}
 
 
 // A table entry stores its sample's position in units of k1 (htEncodePos, .h:132), so a lookup is sent to the slot's FIRST

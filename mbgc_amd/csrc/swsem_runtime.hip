@@ -130,8 +130,12 @@ int swsem_create(swsem_t **out, uint64_t maxRefLength, int L, int k1, int k2, in
     { int d = deal_streams(h); if (d) { swsem_destroy(h); return d; } }
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) h->waveSlots = (uint32_t) pr.multiProcessorCount * 4u * RESOLVE_WAVES_PER_SIMD; }
     const size_t nSlots = (size_t) ((maxRefLength + REF_SLACK) >> h->k1ord) + 2;
+    // the summary of the tags (RefView::tagSum); its kernels take k1 for a slot's length, so only where k1 is a power of two
+    h->tagSumShift = h->useTags && k1 == (1 << h->k1ord) ? h->sw.tagSumShift : 0;
+    h->tagSumEntries = h->tagSumShift ? (uint32_t) (((nSlots - 1) >> h->tagSumShift) + 1) : 0u;
     if (hipMalloc((void **) &h->ref, maxRefLength + REF_SLACK) != hipSuccess ||
         (h->useTags && hipMalloc((void **) &h->tags, nSlots * sizeof(uint16_t)) != hipSuccess) ||
+        (h->tagSumEntries && hipMalloc((void **) &h->tagSum, (size_t) h->tagSumEntries * sizeof(uint16_t)) != hipSuccess) ||
         hipMalloc((void **) &h->ht, (size_t) h->hash_size * sizeof(ht_entry)) != hipSuccess ||
         hipMalloc((void **) &h->lut, 256) != hipSuccess) {
         swsem_destroy(h);
@@ -143,6 +147,7 @@ int swsem_create(swsem_t **out, uint64_t maxRefLength, int L, int k1, int k2, in
     HIPCHK(hipMemcpy(h->lut, lut, 256, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(h->ht, 0, (size_t) h->hash_size * sizeof(ht_entry), h->stream));
     if (h->tags) HIPCHK(hipMemsetAsync(h->tags, 0, nSlots * sizeof(uint16_t), h->stream));
+    if (h->tagSum) HIPCHK(hipMemsetAsync(h->tagSum, 0xFF, (size_t) h->tagSumEntries * sizeof(uint16_t), h->stream));   // TAGSUM_MIXED: nothing is claimed yet
     // start1[0] = 0 (.cpp:335); the rest of the buffer is written before it is ever read, the slack
     // past the end is zeroed because the reference's own reads run a few bytes over (:224, ENC:337)
     // the whole buffer starts out as zeros (the reference reads — harmlessly — bytes it has not loaded yet, e.g. the one at the
@@ -350,6 +355,10 @@ int swsem_debug_write_ref(swsem_t *h, uint64_t from, uint64_t n, const uint8_t *
     {   // the bytes of these slots changed without a sample: their tags say so
         const uint64_t s0 = from >= (uint64_t) h->K ? (from - h->K + 1) >> h->k1ord : 0, s1 = (from + n + ((1ull << h->k1ord) - 1)) >> h->k1ord;
         if (h->tags && s1 > s0) HIPCHK(hipMemset(h->tags + s0, 0, (s1 - s0) * sizeof(uint16_t)));
+        if (h->tagSum && s1 > s0) {
+            const uint64_t b0 = s0 >> h->tagSumShift, b1 = std::min<uint64_t>(((s1 - 1) >> h->tagSumShift) + 1, h->tagSumEntries);
+            if (b1 > b0) HIPCHK(hipMemset(h->tagSum + b0, 0xFF, (b1 - b0) * sizeof(uint16_t)));
+        }
     }
     return SWSEM_OK;
 }
@@ -361,6 +370,25 @@ int swsem_debug_copy_ht(swsem_t *h, uint32_t *out) { MATCHER_ONLY(h);
     k_ht_low_words<<<dim3((h->hash_size + 255) / 256), dim3(256), 0, h->stream>>>(h->ht, tmp.p, h->hash_size, h->fpBits);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, tmp.p, (size_t) h->hash_size * 4, hipMemcpyDeviceToHost));
+    return SWSEM_OK;
+}
+
+// diagnostics: the lap tags (one per sampling slot) and their summary (one entry per 2^shift slots, 0xFFFF: mixed) as the device
+// holds them behind everything queued on the main stream. *n: how many there are (cap of them are copied at most); a handle
+// without tags, or without a summary, reports 0.
+int swsem_debug_tags(swsem_t *h, uint16_t *out, uint64_t cap, uint64_t *n) { MATCHER_ONLY(h);
+    HIPCHK(hipSetDevice(h->device));
+    *n = h->tags ? ((h->maxRefLength + REF_SLACK) >> h->k1ord) + 2 : 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (std::min(cap, *n)) HIPCHK(hipMemcpy(out, h->tags, std::min(cap, *n) * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return SWSEM_OK;
+}
+int swsem_debug_tag_summary(swsem_t *h, uint16_t *out, uint64_t cap, uint64_t *n, int *shift) { MATCHER_ONLY(h);
+    HIPCHK(hipSetDevice(h->device));
+    *n = h->tagSum ? h->tagSumEntries : 0;
+    *shift = h->tagSum ? h->tagSumShift : 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (std::min(cap, *n)) HIPCHK(hipMemcpy(out, h->tagSum, std::min(cap, *n) * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return SWSEM_OK;
 }
 

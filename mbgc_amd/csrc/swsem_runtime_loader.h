@@ -124,7 +124,76 @@ int ref_write_guard(swsem *h, uint64_t firstByte, uint64_t lastByte) {
     return SWSEM_OK;
 }
 
-// processIgnoreCollisionsRef (.cpp:146-171): derive the two sample sets and launch one insertion.
+// The lap-tag summary (RefView::tagSum) is kept from the loader's own arithmetic. A step that writes text [lo, hi) and samples
+// S + t k1 (t < nMain), T + u k1 (u < nTail) touches the slots whose K-mer reaches into the text and the slots whose tag it
+// writes (on-grid samples only: k_insert, k_insert_multi). Of the coarse blocks that hold a touched slot, those whose every slot
+// lies in the on-grid main run end up with the lap's tag in all of tags[]: they become uniform. Every other one — the piece's
+// edges, its tail samples, a main run off the grid (the stretch after a wrap, which writes no tag at all) — becomes mixed. The
+// spans only collect here; plan_tag_summary turns the spans of one flush into the runs k_set_tagsum writes.
+void note_piece(swsem *h, uint64_t lo, uint64_t hi, uint64_t S, uint64_t nMain, uint64_t T, uint64_t nTail, uint32_t tag) {
+    if (!h->tagSum) return;
+    const int ord = h->k1ord, sh = h->tagSumShift;
+    const uint64_t grid = (1ull << ord) - 1;
+    uint64_t s0 = UINT64_MAX, s1 = 0;                                 // touched slots [s0, s1]
+    auto touch = [&](uint64_t a, uint64_t b) { s0 = std::min(s0, a); s1 = std::max(s1, b); };
+    if (hi > lo) touch((lo >= (uint64_t) h->K ? lo - h->K + 1 : 0) >> ord, (hi - 1) >> ord);
+    const bool mainOnGrid = nMain && (S & grid) == 0;
+    if (mainOnGrid) touch(S >> ord, (S >> ord) + nMain - 1);
+    if (nTail && (T & grid) == 0) touch(T >> ord, (T >> ord) + nTail - 1);
+    if (s0 > s1) return;
+    const uint64_t b0 = s0 >> sh, b1 = (s1 >> sh) + 1;                // touched blocks [b0, b1)
+    uint64_t u0 = b1, u1 = b1;                                        // of them uniform: [u0, u1)
+    if (mainOnGrid && tag != swk::TAGSUM_MIXED) {
+        const uint64_t a = S >> ord, b = a + nMain;
+        u0 = (a + (1ull << sh) - 1) >> sh; u1 = b >> sh;
+        if (u1 <= u0) u0 = u1 = b1;
+    }
+    if (u0 > b0) h->sumMixed.push_back({b0, u0, swk::TAGSUM_MIXED});
+    if (u1 > u0) h->sumUniform.push_back({u0, u1, tag});
+    if (b1 > u1) h->sumMixed.push_back({u1, b1, swk::TAGSUM_MIXED});
+}
+// one byte at `at` changes without a sample (a separator; k_mark_stale clears the tag of the slot whose K-mer ends there)
+void note_byte(swsem *h, uint64_t at) {
+    if (!h->tagSum) return;
+    const uint64_t s0 = (at >= (uint64_t) h->K ? at - h->K + 1 : 0) >> h->k1ord, s1 = at >> h->k1ord;
+    h->sumMixed.push_back({s0 >> h->tagSumShift, (s1 >> h->tagSumShift) + 1, swk::TAGSUM_MIXED});
+}
+// The spans of one flush as runs that do not overlap: a block that two steps of the flush touch is mixed, whatever either
+// says (the one case that could be uniform — a later step's main run covering all of it — is given up: mixed is always safe).
+void plan_tag_summary(swsem *h, std::vector<SumRun> &runs) {
+    runs.clear();
+    auto &U = h->sumUniform, &M = h->sumMixed;
+    for (size_t i = 0; i < U.size(); i++)
+        for (size_t j = i + 1; j < U.size(); j++)
+            if (U[i].a < U[j].b && U[j].a < U[i].b) M.push_back({std::max(U[i].a, U[j].a), std::min(U[i].b, U[j].b), swk::TAGSUM_MIXED});
+    std::sort(M.begin(), M.end(), [](const swsem::SumSpan &x, const swsem::SumSpan &y) { return x.a < y.a; });
+    size_t nm = 0;                                                    // merged in place
+    for (size_t i = 0; i < M.size(); i++) {
+        if (nm && M[i].a <= M[nm - 1].b) M[nm - 1].b = std::max(M[nm - 1].b, M[i].b);
+        else M[nm++] = M[i];
+    }
+    M.resize(nm);
+    const uint64_t end = h->tagSumEntries;
+    auto push = [&](uint64_t a, uint64_t b, uint32_t val) {
+        b = std::min(b, end);
+        if (a < b) runs.push_back({(uint32_t) a, (uint32_t) (b - a), val, 0u});
+    };
+    for (auto &u : U) {
+        uint64_t cur = u.a;
+        for (auto &m : M) {
+            if (m.b <= cur) continue;
+            if (m.a >= u.b) break;
+            push(cur, std::min(m.a, u.b), u.val);                     // (nothing when m.a <= cur)
+            cur = std::max(cur, m.b);
+        }
+        push(cur, u.b, u.val);
+    }
+    for (auto &m : M) push(m.a, m.b, swk::TAGSUM_MIXED);
+    U.clear(); M.clear();
+}
+
+// processIgnoreCollisionsRef (.cpp:146-171): derive the two sample sets and launch one insertion. [lo, hi): the text the
+// step has just written (src: where its bytes come from, when the insertion may hash them from there).
 int insert_samples(swsem *h, const uint8_t *src = nullptr, uint64_t lo = 0, uint64_t hi = 0) {
     LoaderState &ld = h->ld;
     const int64_t STEP = (int64_t) h->k1 * 128;
@@ -139,6 +208,7 @@ int insert_samples(swsem *h, const uint8_t *src = nullptr, uint64_t lo = 0, uint
     uint64_t nTail = 0;
     if (T < E + 1) nTail = (uint64_t) ((E - T) / h->k1 + 1);
     const uint64_t total = nMain + nTail;
+    note_piece(h, lo, hi, (uint64_t) S, nMain, (uint64_t) T, nTail, swk::lap_tag(ld.laps));
     if (total && h->deferInserts) {
         InsertPiece pc;
         pc.S = (uint64_t) S; pc.nMain = nMain; pc.T = (uint64_t) T; pc.nTail = nTail; pc.epoch = ld.epoch; pc.tag = swk::lap_tag(ld.laps);
@@ -158,6 +228,7 @@ int insert_samples(swsem *h, const uint8_t *src = nullptr, uint64_t lo = 0, uint
 }
 
 // private loadRef, .cpp:402-437, on a device-resident text
+int flush_tag_summary(swsem *h);
 int load_pieces(swsem *h, const uint8_t *text, uint64_t len, bool rc, bool addSep, int sep) {
     LoaderState &ld = h->ld;
     while (len != 0) {
@@ -195,19 +266,20 @@ int load_pieces(swsem *h, const uint8_t *text, uint64_t len, bool rc, bool addSe
             // (with the window full every target of a round comes by here and through loadSeparator's same case: once is enough)
             if (h->deferInserts) { BytePiece bp; bp.off = ld.swEnd - 1; bp.val = (uint64_t) (uint8_t) sep; h->pendingBytes.push_back(bp); }
             else k_set_byte<<<1, 1, 0, h->stream>>>(h->ref + ld.swEnd - 1, (uint8_t) sep);
+            note_byte(h, ld.swEnd - 1);
             ld.sep_end_set((int64_t) ld.swEnd, sep);
         }
         const bool viaTable = tmpLength && !rc && h->deferInserts;
         const uint64_t copiedTo = (uint64_t) ld.pos1;
         ld.pos1 += (int64_t) tmpLength;
-        int r = viaTable ? insert_samples(h, text, copiedTo, copiedTo + tmpLength) : insert_samples(h);
+        int r = insert_samples(h, viaTable ? text : nullptr, copiedTo, copiedTo + tmpLength);
         if (r) return r;
         text += rc ? 0 : tmpLength;
         if ((uint64_t) ld.pos1 == tmpEnd) ld.droppedBytes += len - tmpLength;
         len = (uint64_t) ld.pos1 == tmpEnd ? 0 : len - tmpLength;
     }
     HIPCHK(hipGetLastError());
-    return SWSEM_OK;
+    return h->deferInserts ? SWSEM_OK : flush_tag_summary(h);
 }
 
 // Everything collected while deferInserts was set: all copies in one launch, the separator bytes in one (in program
@@ -221,8 +293,10 @@ int prepare_inserts(swsem *h, hipStream_t upStream) {
     PreparedInserts &P = h->prep;
     P = PreparedInserts();
     const size_t np = h->pendingPieces.size(), nc = h->pendingCopies.size(), nb = h->pendingBytes.size();
-    P.np = np; P.nc = nc; P.nb = nb;
-    if (!np && !nc && !nb) return SWSEM_OK;
+    plan_tag_summary(h, h->sumRuns);
+    const size_t ns = h->sumRuns.size();
+    P.np = np; P.nc = nc; P.nb = nb; P.ns = ns;
+    if (!np && !nc && !nb && !ns) return SWSEM_OK;
     // (every copy and byte collected here went through ref_write_guard when it was collected — load_pieces,
     // load_separator — with the lap count of that moment; one test of the whole span would take the two halves of a
     // round that wraps for a write across the whole buffer and give the speculative finalize up once per lap)
@@ -266,16 +340,17 @@ int prepare_inserts(swsem *h, hipStream_t upStream) {
     } else
         for (auto &pc : h->pendingPieces) pc.src = nullptr;
     const size_t ne = edge.size();
-    const size_t wPieces = np * (sizeof(InsertPiece) / 8), wCopies = nc * (sizeof(CopyPiece) / 8), wBytes = nb * (sizeof(BytePiece) / 8), wEdge = ne * (sizeof(InsertPiece) / 8);
+    const size_t wPieces = np * (sizeof(InsertPiece) / 8), wCopies = nc * (sizeof(CopyPiece) / 8), wBytes = nb * (sizeof(BytePiece) / 8), wEdge = ne * (sizeof(InsertPiece) / 8),
+                 wSums = ns * (sizeof(SumRun) / 8);
     // host table: a member (two alternating ones), so the upload needs no wait before returning
     swsem::HostTab &ht = h->hostTables[h->hostTableSel ^= 1];
-    const size_t words = wPieces + (np + 1) + wCopies + (nc + 1) + wBytes + wEdge + (ne + 1);
+    const size_t words = wPieces + (np + 1) + wCopies + (nc + 1) + wBytes + wEdge + (ne + 1) + wSums;
     if (ht.pending) { HIPCHK(hipEventSynchronize(ht.ev)); ht.pending = false; }
     int r;
     if ((r = ht.buf.reserve(words * 8, std::max<size_t>(2 * words, 1 << 16) * 8))) return r;
     uint64_t *const tab = (uint64_t *) ht.buf.p;
     uint64_t *tPieces = tab, *tFirst = tPieces + wPieces, *tCopies = tFirst + np + 1, *tCFirst = tCopies + wCopies, *tBytes = tCFirst + nc + 1,
-             *tEdge = tBytes + wBytes, *tEFirst = tEdge + wEdge;
+             *tEdge = tBytes + wBytes, *tEFirst = tEdge + wEdge, *tSums = tEFirst + ne + 1;
     if (np) memcpy(tPieces, h->pendingPieces.data(), np * sizeof(InsertPiece));
     tFirst[0] = 0;
     for (size_t i = 0; i < np; i++) tFirst[i + 1] = tFirst[i] + h->pendingPieces[i].nMain + h->pendingPieces[i].nTail;
@@ -286,6 +361,7 @@ int prepare_inserts(swsem *h, hipStream_t upStream) {
     if (ne) memcpy(tEdge, edge.data(), ne * sizeof(InsertPiece));
     tEFirst[0] = 0;
     for (size_t i = 0; i < ne; i++) tEFirst[i + 1] = tEFirst[i] + edge[i].nMain;
+    if (ns) memcpy(tSums, h->sumRuns.data(), ns * sizeof(SumRun));
     if ((r = h->dTables.reserve(std::max<size_t>(2 * words, 1 << 16)))) return r;   // regrowing = hipFree = a device-wide wait
     // (a kernel reading the pinned table: a runtime copy here costs an engine switch in the middle of the main stream)
     k_upload<<<dim3((unsigned) ((words * 8 + 4095) / 4096)), dim3(256), 0, upStream>>>((uint8_t *) h->dTables.p, (const uint8_t *) tab, words * 8);
@@ -298,6 +374,7 @@ int prepare_inserts(swsem *h, hipStream_t upStream) {
     P.dCopies = (const CopyPiece *) (d + (tCopies - tab)); P.dCFirst = d + (tCFirst - tab);
     P.dBytes = (const BytePiece *) (d + (tBytes - tab));
     P.dEdge = (const InsertPiece *) (d + (tEdge - tab)); P.dEFirst = d + (tEFirst - tab);
+    P.dSums = (const SumRun *) (d + (tSums - tab));
     h->pendingPieces.clear(); h->pendingCopies.clear(); h->pendingBytes.clear();
     HIPCHK(hipGetLastError());
     return SWSEM_OK;
@@ -306,8 +383,8 @@ int prepare_inserts(swsem *h, hipStream_t upStream) {
 int launch_inserts(swsem *h, const uint32_t *gate) {
     hipStream_t sV = h->stream;
     PreparedInserts &P = h->prep;
-    const size_t np = P.np, nc = P.nc, nb = P.nb, ne = P.ne;
-    if (!np && !nc && !nb) return SWSEM_OK;
+    const size_t np = P.np, nc = P.nc, nb = P.nb, ne = P.ne, ns = P.ns;
+    if (!np && !nc && !nb && !ns) return SWSEM_OK;
     hipStream_t cs = sV;                                           // the copies' stream
     if (P.beside) {
         // (its own priority class: the runtime deals the streams of one class over a handful of hardware queues, and a copy
@@ -322,6 +399,8 @@ int launch_inserts(swsem *h, const uint32_t *gate) {
         h->mark(SWSEM_K_LOAD, false, cs);
     }
     if (nb) k_set_bytes<<<1, 1, 0, cs>>>(h->ref, P.dBytes, (int) nb, gate);
+    // (the summary's entries beside the bytes: behind the same gate, and in front of the next resolve like the insertion itself)
+    if (ns) k_set_tagsum<<<dim3(16), dim3(256), 0, cs>>>(h->tagSum, h->tagSumEntries, P.dSums, (int) ns, gate);
     if (P.beside) HIPCHK(hipEventRecord(h->evLoadDone, cs));
     if (np && P.nSamples) {
         h->mark(SWSEM_K_INSERT, true);
@@ -344,6 +423,11 @@ int flush_inserts(swsem *h, const uint32_t *gate = nullptr) {
     int r = prepare_inserts(h, h->stream);
     return r ? r : launch_inserts(h, gate);
 }
+// a loader step outside a finalize (loadRef, loadSeparator called on their own) has launched its kernels itself: its summary runs follow
+int flush_tag_summary(swsem *h) {
+    if (h->sumUniform.empty() && h->sumMixed.empty()) return SWSEM_OK;
+    return flush_inserts(h);
+}
 
 // loadSeparator, .cpp:439-451
 int load_separator(swsem *h, int sep) {
@@ -360,14 +444,18 @@ int load_separator(swsem *h, int sep) {
         if (ld.pos1 >= (int64_t) h->K + REF_SHIFT)
             k_mark_stale<<<1, 1, 0, h->stream>>>(h->ref, h->ht, (uint64_t) (ld.pos1 - h->K), h->K, h->k1ord, h->mask, h->fpBits, h->tags);
         k_set_byte<<<1, 1, 0, h->stream>>>(h->ref + ld.pos1 - 1, (uint8_t) sep);
+        note_byte(h, (uint64_t) ld.pos1 - 1);
         ld.sep_end_set(ld.pos1, sep);
     } else if (h->deferInserts) {
+        note_byte(h, (uint64_t) ld.pos1);
         BytePiece bp; bp.off = (uint64_t) ld.pos1++; bp.val = (uint64_t) (uint8_t) sep;
         h->pendingBytes.push_back(bp);
-    } else
+    } else {
+        note_byte(h, (uint64_t) ld.pos1);
         k_set_byte<<<1, 1, 0, h->stream>>>(h->ref + ld.pos1++, (uint8_t) sep);
+    }
     HIPCHK(hipGetLastError());
-    return SWSEM_OK;
+    return h->deferInserts ? SWSEM_OK : flush_tag_summary(h);
 }
 
 // getLoadedRefLength, .h:108
@@ -409,7 +497,7 @@ int finalize_impl(swsem *h, int n, const uint8_t *const *ext_dev, const uint64_t
         if (!r && lockPos) r = release_lock(h, lockPos[i]);
     }
     h->deferInserts = false;
-    if (r == SWSEM_ESPEC) { h->pendingPieces.clear(); h->pendingCopies.clear(); h->pendingBytes.clear(); return r; }
+    if (r == SWSEM_ESPEC) { h->pendingPieces.clear(); h->pendingCopies.clear(); h->pendingBytes.clear(); h->sumUniform.clear(); h->sumMixed.clear(); return r; }
     // planOnly (the speculative finalize): the host's bookkeeping is done and the launches are listed; the caller queues them
     // (prepare_inserts, launch_inserts) once every replica's verdict has been reduced into the gate — and knows by now whether
     // THIS replica can

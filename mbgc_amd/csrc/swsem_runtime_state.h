@@ -122,6 +122,7 @@ struct Switches {
     uint32_t profMask = ~0u;               // families that get event brackets (SWSEM_PROF_FAMS: every bracket is two markers in the queue)
     int metaWarm = swk::MWARM;             // warm-up matches of the pairing chain's speculative blocks (SWSEM_META_WARM: fewer, so that blocks fail)
     bool lapTags = true;                   // SWSEM_LAP_TAGS=0: every stale entry is visited (the table image and the results are the same)
+    int tagSumShift = 12;                  // SWSEM_TAGSUM_SHIFT=n: one summary entry per 2^n sampling slots (RefView::tagSum); 0: no summary
     bool streamCalib = true;               // SWSEM_STREAM_CALIB=0: no measurement, the side streams in the order they were made
     bool streamDebug = false;              // SWSEM_STREAM_DEBUG: prints the deal of the side streams
     bool debugStats = false;               // SWSEM_DEBUG_STATS: the stitch's and the pairing chain's counters at swsem_destroy
@@ -135,6 +136,7 @@ Switches read_switches() {
     if (const char *e = getenv("SWSEM_PROF_FAMS")) s.profMask = (uint32_t) strtoul(e, nullptr, 0);
     if (const char *e = getenv("SWSEM_META_WARM")) s.metaWarm = std::min(swk::MWARM, std::max(0, atoi(e)));
     if (const char *e = getenv("SWSEM_LAP_TAGS")) s.lapTags = atoi(e) != 0;
+    if (const char *e = getenv("SWSEM_TAGSUM_SHIFT")) { int x = atoi(e); if (x >= 0 && x <= 24) s.tagSumShift = x; }
     if (const char *e = getenv("SWSEM_STREAM_CALIB")) s.streamCalib = atoi(e) != 0;
     s.streamDebug = getenv("SWSEM_STREAM_DEBUG") != nullptr;
     s.debugStats = getenv("SWSEM_DEBUG_STATS") != nullptr;
@@ -143,7 +145,8 @@ Switches read_switches() {
 
 // what prepare_inserts has uploaded for the launches that follow (launch_inserts)
 struct PreparedInserts {
-    size_t np = 0, nc = 0, nb = 0, ne = 0;
+    size_t np = 0, nc = 0, nb = 0, ne = 0, ns = 0;
+    const SumRun *dSums = nullptr;
     bool beside = false;
     uint64_t nSamples = 0, nEdge = 0, copyBlocks = 0;
     const InsertPiece *dPieces = nullptr, *dEdge = nullptr;
@@ -215,6 +218,16 @@ struct swsem {
     uint8_t *lut = nullptr;                // upper-complement LUT, utils/helper.cpp:312-338
     uint16_t *tags = nullptr;              // per sampling slot: lap_tag of its last on-grid sampling (swsem_device.h, lap_want)
     bool useTags = true;                   // (not with an odd k1, not with SWSEM_LAP_TAGS=0)
+    // The summary of tags[] (RefView::tagSum): tagSumEntries entries, one per 2^tagSumShift sampling slots; null: none. Only the
+    // device holds it. The host never needs an entry's old value: whatever a loader step touches gets a new one from the step's
+    // own piece arithmetic (note_piece, note_bytes), and the runs collected here leave with the step's tables (prepare_inserts)
+    // to be written behind the same gate as the tag writes they describe (k_set_tagsum).
+    uint16_t *tagSum = nullptr;
+    int tagSumShift = 0;
+    uint32_t tagSumEntries = 0;
+    struct SumSpan { uint64_t a, b; uint32_t val; };   // coarse blocks [a, b) -> val
+    std::vector<SumSpan> sumUniform, sumMixed;
+    std::vector<SumRun> sumRuns;           // plan_tag_summary's result for the flush being prepared
     LoaderState ld;
     uint64_t maxRefLength = 0;
     int L = 0, K = 0, k1 = 0, skipMargin = 0, k1ord = 0;
@@ -347,6 +360,7 @@ struct swsem {
         // (position << k1ord) + K + 1 <= pos1  <=>  value <= curMax;   (position << k1ord) >= pos1  <=>  value >= prevMin
         v.curMax = ld.pos1 >= (int64_t) K + 1 ? (uint32_t) (((uint64_t) ld.pos1 - K - 1) >> k1ord) : 0u;
         v.prevMin = (uint32_t) ((((uint64_t) ld.pos1) + (1ull << k1ord) - 1) >> k1ord); v.K = K; v.k1ord = k1ord; v.skipMargin = skipMargin; v.minLen = minLen;
+        v.tagSum = useTags ? tagSum : nullptr; v.tagSumShift = tagSumShift;
         v.tags = useTags ? tags : nullptr; v.tagCur = swk::lap_tag(ld.laps); v.tagPrev = ld.laps ? swk::lap_tag(ld.laps - 1) : 0u;
         return v;
     }
@@ -385,7 +399,7 @@ struct swsem {
     }
     // (the buffers and events above free themselves; what is left are the four exact-size allocations and the timing pairs)
     ~swsem() {
-        for (void *p : {(void *) ref, (void *) tags, (void *) ht, (void *) lut}) if (p) (void) hipFree(p);
+        for (void *p : {(void *) ref, (void *) tags, (void *) tagSum, (void *) ht, (void *) lut}) if (p) (void) hipFree(p);
         drain_events();
         for (auto &e : idle) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
     }
