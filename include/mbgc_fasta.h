@@ -150,6 +150,19 @@ int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
                           const mbgc_fasta_format_rec_t *recs, uint64_t nrec, uint8_t *text_dev, uint64_t textCap, uint64_t *textOff,
                           double *kernelMs);
 
+/* The comparison of `mbgc-hip v`: text that was formatted on the device against the originals that were uploaded beside it. Piece k
+ * compares a_dev[aOff, aOff + len) with b_dev[bOff, bOff + len) (buffers of aBytes and bBytes bytes). firstDiff (host, nslots
+ * entries) receives for every slot the smallest offset WITHIN ITS PIECE at which the bytes of a piece of that slot differ, taken over
+ * all pieces that name the slot — the caller adds its own base — and UINT64_MAX when none differ (also for a slot no piece names).
+ * Pieces of no bytes are legal. Any alignment of either side; the two sides of a piece may stand at different offsets modulo 16.
+ * A piece that does not lie inside both buffers, or names a slot >= nslots, is refused (-103, message in mbgc_fasta_last_error): nothing
+ * is launched and firstDiff is left as it was. kernelMs (may be NULL): the kernel's time from events on the stream. Equal bytes
+ * cost no atomic: a wave that finds a difference issues one 64-bit atomicMin per piece it touches. Runs on the input stage's
+ * stream; synchronous. */
+typedef struct { uint64_t aOff, bOff, len; uint32_t slot; } mbgc_fasta_compare_piece_t;
+int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aBytes, const uint8_t *b_dev, uint64_t bBytes,
+                           const mbgc_fasta_compare_piece_t *pieces, uint64_t npieces, uint64_t *firstDiff, uint32_t nslots, double *kernelMs);
+
 /* A download that runs beside the kernels of the input stage's stream (the decoder's text batches: batch b travels while batch b + 1
  * is formatted): begin queues the copy on a stream of its own and returns; wait returns when it has arrived, with the copy's time
  * from events on that stream in *copyMs (may be NULL). One download at a time: begin before the last one's wait is refused (-103).

@@ -646,6 +646,27 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
 }
 
 #include "fasta_format.h"
+#include "fasta_compare.h"
+
+// mbgc_fasta_compare_dev: a wave's steps, then — only when a lane found a difference — one 64-bit atomicMin per piece the wave
+// touches, from the lowest differing lane of that piece (its offset is the smallest: the steps of a piece ascend with the lanes).
+// Equal data issues no atomic.
+__global__ void __launch_bounds__(THREADS) k_fa_compare(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const CmpPiece *__restrict__ P,
+                                                        const uint32_t *__restrict__ owner, uint32_t tile0, uint32_t ntiles, uint64_t total,
+                                                        unsigned long long *__restrict__ firstDiff) {
+    const uint32_t tile = tile0 + blockIdx.x;
+    if (tile >= ntiles) return;
+    uint32_t piece = 0;
+    const uint64_t d = cmp_lane_step(a, b, P, owner, tile, threadIdx.x, total, &piece);
+    unsigned long long m = __ballot(d != CMP_NONE);
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    while (m) {                                                      // (uniform over the wave)
+        const int leader = __ffsll(m) - 1;
+        const uint32_t leaderPiece = (uint32_t) __shfl((int) piece, leader);
+        if (lane == (uint32_t) leader) atomicMin(firstDiff + P[piece].slot, (unsigned long long) d);
+        m &= ~__ballot(piece == leaderPiece);
+    }
+}
 
 // pieces of a device buffer packed back to back, each followed by one separator byte (the headers of a -i batch: only they travel
 // back to the host, not the elements): one workgroup per piece
@@ -768,6 +789,9 @@ struct mbgc_fasta {
     fa::Buf<fa::FmtRec> dFmtRecs;               // mbgc_fasta_format_dev: the record table and the tiles' owners
     fa::Buf<uint32_t> dFmtOwner;
     hipEvent_t fmtEv[2] = {nullptr, nullptr};   // around the format launches (made at the first call that asks for the time)
+    fa::Buf<fa::CmpPiece> dCmpPieces;           // mbgc_fasta_compare_dev: the piece table, the tiles' owners, the slots' results
+    fa::Buf<uint32_t> dCmpOwner;
+    fa::Buf<unsigned long long> dCmpOut;
     hipStream_t copyStream = nullptr;           // mbgc_fasta_download_begin / _wait: a download beside the kernels of `stream`
     hipEvent_t copyEv[2] = {nullptr, nullptr};
     bool copyPending = false;
@@ -803,6 +827,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dShift.release(); p->dHostIn.release(); p->dHostOut.release();
     p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
     p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
+    p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
@@ -1050,6 +1075,50 @@ int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
     if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    return 0;
+}
+
+int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aBytes, const uint8_t *b_dev, uint64_t bBytes,
+                           const mbgc_fasta_compare_piece_t *pieces, uint64_t npieces, uint64_t *firstDiff, uint32_t nslots, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(CmpIn) == sizeof(mbgc_fasta_compare_piece_t), "the table builder reads the ABI's pieces");
+    if (kernelMs) *kernelMs = 0;
+    if (npieces >= 0xffffffffull) return fail(-103, "compare: %llu pieces in one call", (unsigned long long) npieces);
+    for (uint64_t k = 0; k < npieces; k++) {
+        const mbgc_fasta_compare_piece_t &x = pieces[k];
+        if (x.aOff > aBytes || x.len > aBytes - x.aOff || x.bOff > bBytes || x.len > bBytes - x.bOff)
+            return fail(-103, "compare: piece %llu lies outside the buffers", (unsigned long long) k);
+        if (x.slot >= nslots) return fail(-103, "compare: piece %llu names slot %u of %u", (unsigned long long) k, x.slot, nslots);
+    }
+    std::vector<CmpPiece> table;
+    const uint64_t total = cmp_build_table((const CmpIn *) pieces, npieces, (uint64_t) (uintptr_t) a_dev, table);
+    const uint64_t nt64 = (total + CHUNK - 1) / CHUNK;
+    if (nt64 >= 0xffffffffull) return fail(-103, "compare: %llu bytes in one call", (unsigned long long) total);
+    if (total == 0 || nslots == 0) {
+        for (uint32_t s = 0; s < nslots; s++) firstDiff[s] = UINT64_MAX;
+        return 0;
+    }
+    FCHK(hipSetDevice(p->device));
+    const uint32_t ntiles = (uint32_t) nt64;
+    std::vector<uint32_t> owner;
+    cmp_build_owner(table, ntiles, owner);
+    int rc;
+    if ((rc = p->dCmpPieces.reserve(table.size())) || (rc = p->dCmpOwner.reserve((size_t) ntiles + 1)) || (rc = p->dCmpOut.reserve(nslots))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dCmpPieces.p, table.data(), table.size() * sizeof(CmpPiece), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dCmpOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemsetAsync(p->dCmpOut.p, 0xff, (size_t) nslots * sizeof(unsigned long long), p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
+        k_fa_compare<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(a_dev, b_dev, p->dCmpPieces.p, p->dCmpOwner.p, t0, ntiles, total,
+                                                                                             p->dCmpOut.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    std::vector<unsigned long long> out(nslots);                     // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(out.data(), p->dCmpOut.p, (size_t) nslots * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    for (uint32_t s = 0; s < nslots; s++) firstDiff[s] = out[s];
     return 0;
 }
 

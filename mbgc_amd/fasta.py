@@ -7,7 +7,7 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -20,6 +20,13 @@ class Record(C.Structure):
 
 class FormatRecord(C.Structure):
     _fields_ = [("seqOff", C.c_uint64), ("seqLen", C.c_uint64), ("headerOff", C.c_uint64), ("headerLen", C.c_uint64), ("lineLen", C.c_uint64)]
+
+
+class ComparePiece(C.Structure):
+    _fields_ = [("aOff", C.c_uint64), ("bOff", C.c_uint64), ("len", C.c_uint64), ("slot", C.c_uint32)]
+
+
+NO_DIFFERENCE = 2 ** 64 - 1          # UINT64_MAX: what compare_dev leaves in a slot whose pieces are equal
 
 
 PROBE_MIN_LEN, PROBE_MAX_LEN = 256, 65536      # MBGC_FASTA_PROBE_MIN_LEN, MBGC_FASTA_PROBE_MAX_LEN
@@ -66,6 +73,8 @@ def _lib():
         L.mbgc_fasta_probe_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_int,
                                            C.POINTER(ProbeState), C.POINTER(ProbeResult)]
         L.mbgc_fasta_probe_host.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, C.c_int, C.POINTER(ProbeState), C.POINTER(ProbeResult)]
+        L.mbgc_fasta_compare_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(ComparePiece), C.c_uint64,
+                                             C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_double)]
         L._fasta_ready = True
     return L
 
@@ -211,6 +220,20 @@ class FastaParser:
         if r:
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return offs, ms.value
+
+    def compare_dev(self, a_ptr, a_bytes, b_ptr, b_bytes, pieces, nslots, first_diff=None):
+        """pieces = rows of (aOff, bOff, len, slot): a[aOff, aOff + len) against b[bOff, bOff + len) on the device -> (first differing
+        offset within its piece per slot, the smallest over the slot's pieces, NO_DIFFERENCE when none differ [nslots]; the kernel's
+        ms). first_diff: the uint64 array to fill (a refused call leaves it untouched and raises)."""
+        rows = [tuple(int(v) for v in r) for r in pieces]
+        arr = (ComparePiece * max(len(rows), 1))(*rows)
+        out = np.zeros(int(nslots), dtype=np.uint64) if first_diff is None else first_diff
+        assert out.dtype == np.uint64 and out.size >= int(nslots) and out.flags.c_contiguous
+        ms = C.c_double(0)
+        if _lib().mbgc_fasta_compare_dev(self.h, a_ptr, int(a_bytes), b_ptr, int(b_bytes), arr, len(rows), out.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         int(nslots), C.byref(ms)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return out, ms.value
 
     def gather_dev(self, src_ptr, src_bytes, offsets, lengths, sep=10):
         """pieces of a device buffer, each followed by the byte sep, packed on the device and downloaded -> bytes"""

@@ -1,5 +1,6 @@
 #include "mbgc_decoder.h"
 #include "simple_sequence_matcher.h"
+#include "gzip_inflate.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -9,7 +10,9 @@
 #include <fstream>
 #include <future>
 #include <set>
+#include <fcntl.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <time.h>
 
 static const uint64_t REF_SHIFT = 1;                           // SlidingWindowSparseEMMatcher.h:14
@@ -347,6 +350,89 @@ static std::string outputName(const std::string &name) {
     if (b.size() >= 3 && b.compare(b.size() - 3, 3, ".gz") == 0) b.resize(b.size() - 3);
     return b;
 }
+
+// the directory, with the ones above it; false: *failed = the one that could not be made
+static bool makeDirs(const std::string &dir, std::string *failed) {
+    for (size_t at = 1; at <= dir.size(); at++)
+        if (at == dir.size() || dir[at] == '/')
+            if (mkdir(dir.substr(0, at).c_str(), 0777) != 0 && errno != EEXIST) { *failed = dir.substr(0, at); return false; }
+    return true;
+}
+
+// ---- `mbgc-hip v`: the originals of a batch as the read-ahead thread leaves them in a page-locked buffer
+static const uint64_t VALIDATION_LOG_LIMIT = 100, VALIDATION_DUMP_LIMIT = 3;   // MBGC_Params.h:121-122
+struct Original {
+    std::string path;                                              // as it is named in the report (without the .gz that was tried)
+    bool found = false;
+    std::string unreadable;                                        // found, but its gzip stream does not inflate: why
+    uint64_t size = 0;                                             // of the file, inflated
+    uint64_t off = 0, n = 0;                                       // its bytes that are compared: buffer[off, off + n)
+};
+struct OriginalsBatch { std::vector<Original> files; double ms = 0; uint64_t bytes = 0; std::string error; };
+struct ValidateTimes { double read = 0, upload = 0, compare = 0; uint64_t compared = 0; };
+
+// where a unit's original lies: its line of <prefix>.names; --flat: the basename `d --fasta` writes it under; --root before relative names
+static std::string originalPath(const std::string &name, const std::string &root, bool flat) {
+    std::string n = flat ? outputName(name) : name;
+    if (!root.empty() && (n.empty() || n[0] != '/')) n = root + "/" + n;
+    return n;
+}
+
+// an original opened for reading: the path, or <path>.gz when the path does not exist (MBGC_Decoder.cpp:120-129); a file that starts
+// with the gzip magic is inflated whole (mgmpInOpen)
+struct OpenOriginal {
+    int fd = -1; bool gz = false; uint64_t size = 0; std::string inflated;
+    std::string broken;                                            // a gzip file that does not inflate (corrupt, truncated): the inflate's message; size = 0
+    ~OpenOriginal() { if (fd >= 0) close(fd); }
+    bool open(const std::string &path, std::string &error) {
+        fd = ::open(path.c_str(), O_RDONLY);
+        if (fd < 0) fd = ::open((path + ".gz").c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        if (fstat(fd, &st) != 0) { error = "cannot read " + path; return true; }
+        size = (uint64_t) st.st_size;
+        uint8_t head[18];
+        if (size >= 18 && pread(fd, head, 18, 0) == 18 && isGzip(head, 18)) {
+            std::string bytes(size, '\0');
+            if (!readAt(&bytes[0], 0, size)) { error = "cannot read " + path; return true; }
+            gz = true;
+            if (!tryInflateGzip(bytes, inflated, broken)) inflated.clear();                    // (reported as an invalid file, not the end of the run)
+            size = inflated.size();
+        }
+        return true;
+    }
+    bool readAt(void *dst, uint64_t at, uint64_t n) const {
+        if (gz) { memcpy(dst, inflated.data() + at, n); return true; }
+        for (uint64_t got = 0; got < n;) {
+            const ssize_t r = pread(fd, (char *) dst + got, n - got, (off_t) (at + got));
+            if (r <= 0) return false;
+            got += (uint64_t) r;
+        }
+        return true;
+    }
+};
+
+// where the first difference lies (MBGC_Decoder.cpp:157-170 on the text's records instead of its '>' bytes): `at` bytes into the text
+// of record `rec` of the file's records [first, ...). A difference at a record's first byte belongs to the record in front (the equal
+// part ends behind it); at the file's first byte there is no record in the equal part.
+struct ErrorLocation { enum Kind { NONE, NO_SEQUENCE, HEADER, SEQUENCE } kind = NONE; uint64_t seqIdx = 0, seqPos = 0; };
+static ErrorLocation locateError(uint64_t first, uint64_t rec, uint64_t at, const std::vector<uint64_t> &hdrLen, const std::vector<uint64_t> &seqLen, uint64_t lineLen) {
+    ErrorLocation loc;
+    if (at == 0) {
+        if (rec == first) { loc.kind = ErrorLocation::NO_SEQUENCE; return loc; }
+        loc.kind = ErrorLocation::SEQUENCE; loc.seqIdx = rec - 1 - first; loc.seqPos = seqLen[rec - 1];
+        return loc;
+    }
+    loc.seqIdx = rec - first;
+    const uint64_t zs = hdrLen[rec] + 2;
+    if (at < zs) { loc.kind = ErrorLocation::HEADER; return loc; }
+    uint64_t line = (lineLen == 0 || lineLen > seqLen[rec]) ? seqLen[rec] : lineLen;
+    if (line == 0) line = 1;
+    const uint64_t p = at - zs;                                    // the newlines in front of zone offset p: one per full line
+    loc.kind = ErrorLocation::SEQUENCE;
+    loc.seqPos = std::min(seqLen[rec], p - p / (line + 1));
+    return loc;
+}
 }
 
 // the lines of <prefix>.names, held to the meta: one per unit (G0, then every target), one for a single-FASTA collection
@@ -463,10 +549,12 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     if (planned > stream[SWSEM_LIT].size()) return fail("malformed .meta: more sequences than literal bytes");
     uint64_t sizes[SWSEM_NSTREAMS];
     for (int s = 0; s < SWSEM_NSTREAMS; s++) sizes[s] = stream[s].size();
-    const bool wantFasta = !opt.fastaDir.empty();
+    const bool wantFasta = !opt.fastaDir.empty() || opt.validate;   // (`v` builds the units and batches of --fasta, and formats them)
     FastaLayout layout;
     if (wantFasta) { std::string m; if (!readFastaLayout(prefix, meta, g0n + planned, layout, m)) return fail(m); }
     FastaTimes ftimes;
+    ValidateTimes vtimes;
+    uint64_t validFiles = 0, invalidFiles = 0, validatedFiles = 0;
     // chain starts
     const bool useIndex = !opt.noIndex && !meta.index.empty();
     std::vector<swsem_chain_start_t> starts;
@@ -724,17 +812,13 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             {
                 uint64_t cur = 0;
                 for (size_t u = 0; u < units.size(); u++) {
-                    if (cur && cur + units[u].text > FASTA_BATCH_TEXT) { batchEnd.push_back(u); maxBatch = std::max(maxBatch, cur); cur = 0; }
+                    if (cur && cur + units[u].text > (opt.batchText ? opt.batchText : FASTA_BATCH_TEXT)) { batchEnd.push_back(u); maxBatch = std::max(maxBatch, cur); cur = 0; }
                     cur += units[u].text;
                 }
                 batchEnd.push_back(units.size()); maxBatch = std::max(maxBatch, cur);
             }
-            const bool writeFiles = !opt.bench || pass == 0;                                    // (bench: the timed pass formats and downloads only)
-            if (writeFiles) {                                                                   // the directory, with the ones above it
-                for (size_t at = 1; at <= opt.fastaDir.size(); at++)
-                    if (at == opt.fastaDir.size() || opt.fastaDir[at] == '/')
-                        if (mkdir(opt.fastaDir.substr(0, at).c_str(), 0777) != 0 && errno != EEXIST) return fail("cannot create the directory " + opt.fastaDir.substr(0, at));
-            }
+            const bool writeFiles = !opt.validate && (!opt.bench || pass == 0);                  // (bench: the timed pass formats and downloads only)
+            if (std::string failed; writeFiles && !makeDirs(opt.fastaDir, &failed)) return fail("cannot create the directory " + failed);
             FastaBuffers fb;
             if (mbgc_fasta_create(&fb.fa, opt.device)) return faFail("--fasta");
             if (mbgc_fasta_dev_alloc(fb.fa, layout.headers.size() + 64, &fb.hdrDev)) return faFail("--fasta");
@@ -783,20 +867,213 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 return 0;
             };
             auto settleFail = [&](int r) { return r == 1 ? faFail("download") : fail("cannot write under " + opt.fastaDir); };
-            size_t u0 = 0;
-            for (size_t b = 0; b < batchEnd.size(); b++) {
-                const size_t u1 = batchEnd[b];
+            // units [u0, u1) formatted into dst: recs and textOff hold the batch's record table afterwards; false: the device call failed
+            auto formatBatch = [&](size_t u0, size_t u1, uint8_t *dst, uint64_t &bytes) -> bool {
                 recs.clear();
                 for (size_t u = u0; u < u1; u++)
                     for (uint64_t k = units[u].c0; k < units[u].c1; k++)
                         recs.push_back({seqOff[k], contigLen[k], layout.hdrOff[k], layout.hdrLen[k], units[u].lineLen});
                 textOff.assign(recs.size() + 1, 0);
                 double kms = 0;
-                if (mbgc_fasta_format_dev(fb.fa, seqDev, totalBases, fb.hdrDev, layout.headers.size(), recs.data(), recs.size(), fb.textDev[b & 1], maxBatch,
-                                          textOff.data(), &kms)) return faFail("format");
+                if (mbgc_fasta_format_dev(fb.fa, seqDev, totalBases, fb.hdrDev, layout.headers.size(), recs.data(), recs.size(), dst, maxBatch, textOff.data(), &kms))
+                    return false;
                 ftimes.format += kms;
-                const uint64_t bytes = textOff[recs.size()];
+                bytes = textOff[recs.size()];
                 ftimes.text += bytes; ftimes.batches++;
+                return true;
+            };
+            size_t u0 = 0;
+            if (opt.validate) {
+                // ---- `mbgc-hip v`: the text stays on the device. Batch b is formatted into the first text buffer while a
+                // thread reads (and inflates) the originals of batch b + 1 into the page-locked buffer that batch b - 1 left; the
+                // originals of b go up into the second text buffer, one compare call runs over the batch with a slot per file, and a
+                // word per file comes back. A single-FASTA collection is one file over all batches: one piece per batch at the
+                // file's running offset, only that slice of the original is read and uploaded.
+                const bool report = pass + 1 == passes;                                         // (bench: the first pass warms up and stays quiet)
+                const bool single = meta.singleFastaFile;
+                const size_t nb = batchEnd.size();
+                vtimes = ValidateTimes();
+                validFiles = invalidFiles = 0;
+                validatedFiles = single ? 1 : units.size();
+                uint64_t dumped = 0;
+                auto nameOf = [&](const FastaUnit &x) { return originalPath(layout.names[single ? 0 : x.file + (meta.sequentialMatching ? 1 : 0)], opt.root, opt.flat); };
+                if (report && !opt.skipCompare && meta.uppercaseDNA)
+                    printf("the streams were written with -U: the text is upper case, originals that hold lower-case bases differ from it\n");
+                std::vector<uint64_t> batchAt(nb + 1, 0);                                        // text in front of every batch
+                for (size_t b = 0, u = 0; b < nb; b++) { batchAt[b + 1] = batchAt[b]; for (; u < batchEnd[b]; u++) batchAt[b + 1] += units[u].text; }
+                const uint64_t totalText = batchAt[nb];
+                OpenOriginal one;                                                               // the single file, open over all batches
+                bool oneFound = false, oneDiffers = false;
+                ErrorLocation oneLoc;
+                const std::string onePath = single && !units.empty() ? nameOf(units[0]) : std::string();
+                if (single && !opt.skipCompare) {
+                    const double r0 = nowMs();
+                    std::string e;
+                    oneFound = one.open(onePath, e);
+                    if (!e.empty()) return fail(e);
+                    vtimes.read += nowMs() - r0;
+                }
+                auto readBatch = [&](size_t b) {
+                    OriginalsBatch R;
+                    const double r0 = nowMs();
+                    uint8_t *dst = (uint8_t *) fb.pin[b & 1];
+                    const size_t ua = b ? batchEnd[b - 1] : 0, ub = batchEnd[b];
+                    if (single) {
+                        Original o;
+                        o.path = onePath; o.found = oneFound; o.size = one.size; o.unreadable = one.broken;
+                        if (oneFound && batchAt[b] < one.size) {
+                            o.n = std::min(batchAt[b + 1] - batchAt[b], one.size - batchAt[b]);
+                            if (!one.readAt(dst, batchAt[b], o.n)) R.error = "cannot read " + onePath;
+                        }
+                        R.bytes = o.n;
+                        R.files.push_back(o);
+                    } else {
+                        for (size_t u = ua; u < ub && R.error.empty(); u++) {
+                            Original o;
+                            OpenOriginal f;
+                            o.path = nameOf(units[u]);
+                            o.found = f.open(o.path, R.error);
+                            if (o.found && R.error.empty()) {
+                                o.unreadable = f.broken;
+                                o.size = f.size; o.off = R.bytes; o.n = std::min(f.size, units[u].text);
+                                if (!f.readAt(dst + o.off, 0, o.n)) R.error = "cannot read " + o.path;
+                                R.bytes += o.n;
+                            }
+                            R.files.push_back(o);
+                        }
+                    }
+                    R.ms = nowMs() - r0;
+                    return R;
+                };
+                auto reportInvalid = [&](const std::string &path, bool sizeDiffer, uint64_t ours, uint64_t theirs, const ErrorLocation &loc) {
+                    if (!report || invalidFiles >= VALIDATION_LOG_LIMIT) return;
+                    const unsigned long long n = validFiles + invalidFiles;
+                    if (sizeDiffer) printf("Validation ERROR: ~%llu. %s size differ (%llu instead of %llu)\n", n, path.c_str(), (unsigned long long) ours, (unsigned long long) theirs);
+                    else printf("Validation ERROR: ~%llu. %s contents differ.\n", n, path.c_str());
+                    if (loc.kind == ErrorLocation::SEQUENCE) printf("Error location:\t\tseqIdx = %llu\tseqPos = %llu\n", (unsigned long long) loc.seqIdx, (unsigned long long) loc.seqPos);
+                    else if (loc.kind == ErrorLocation::HEADER) printf("Error in header:\t\tseqIdx = %llu\n", (unsigned long long) loc.seqIdx);
+                    else if (loc.kind == ErrorLocation::NO_SEQUENCE) printf("Error in FASTA format - no sequences found in equal part.\n");
+                };
+                // the record of unit x (its text starts at `at` in the batch, its records at row `rec` of the batch's table) that holds text offset pos of the unit
+                auto locate = [&](const FastaUnit &x, uint64_t at, size_t rec, uint64_t pos, uint64_t firstContig) {
+                    const size_t nrec = (size_t) (x.c1 - x.c0);
+                    if (nrec == 0) return locateError(firstContig, firstContig, 0, layout.hdrLen, contigLen, x.lineLen);
+                    const size_t j = (size_t) (std::upper_bound(textOff.begin() + rec, textOff.begin() + rec + nrec, at + pos) - (textOff.begin() + rec)) - 1;
+                    return locateError(firstContig, x.c0 + j, at + pos - textOff[rec + j], layout.hdrLen, contigLen, x.lineLen);
+                };
+                auto dumpText = [&](const std::string &name, const uint8_t *src, uint64_t n, bool append) -> int {     // 0 ok, 1 device, 2 write
+                    std::string text(n, '\0');
+                    if (n && mbgc_fasta_download(fb.fa, &text[0], src, n)) return 1;
+                    if (std::string failed; !makeDirs(opt.dumpDir, &failed)) return 2;
+                    std::ofstream f(opt.dumpDir + "/" + name, std::ios::binary | (append ? std::ios::app : std::ios::trunc));
+                    f.write(text.data(), (std::streamsize) n);
+                    f.close();
+                    return f ? 0 : 2;
+                };
+                auto dumpFail = [&](int r) { return r == 1 ? faFail("--dump") : fail("cannot write under " + opt.dumpDir); };
+                std::vector<mbgc_fasta_compare_piece_t> pieces;
+                std::vector<uint64_t> firstDiff;
+                std::future<OriginalsBatch> reading;
+                if (!opt.skipCompare && nb) reading = std::async(std::launch::async, readBatch, (size_t) 0);
+                for (size_t b = 0; b < nb; b++) {
+                    const size_t u1 = batchEnd[b];
+                    OriginalsBatch R;
+                    if (!opt.skipCompare) {
+                        R = reading.get();
+                        if (b + 1 < nb) reading = std::async(std::launch::async, readBatch, b + 1);
+                        if (!R.error.empty()) return fail(R.error);
+                        vtimes.read += R.ms;
+                    }
+                    uint64_t bytes = 0;
+                    if (!formatBatch(u0, u1, fb.textDev[0], bytes)) return faFail("format");
+                    if (bytes != batchAt[b + 1] - batchAt[b]) return fail("internal error: the text of a batch is not the sum of its units");
+                    if (opt.skipCompare) { u0 = u1; continue; }
+                    const double up0 = nowMs();
+                    if (mbgc_fasta_upload(fb.fa, fb.textDev[1], fb.pin[b & 1], R.bytes)) return faFail("upload");
+                    vtimes.upload += nowMs() - up0;
+                    pieces.clear();
+                    if (single) pieces.push_back({0, 0, R.files[0].n, 0});
+                    else {
+                        uint64_t at = 0;
+                        for (size_t u = u0; u < u1; u++) { pieces.push_back({at, R.files[u - u0].off, R.files[u - u0].n, (uint32_t) (u - u0)}); at += units[u].text; }
+                    }
+                    firstDiff.assign(R.files.size(), UINT64_MAX);
+                    double kms = 0;
+                    if (mbgc_fasta_compare_dev(fb.fa, fb.textDev[0], bytes, fb.textDev[1], R.bytes, pieces.data(), pieces.size(), firstDiff.data(), (uint32_t) firstDiff.size(), &kms))
+                        return faFail("compare");
+                    vtimes.compare += kms;
+                    for (const mbgc_fasta_compare_piece_t &pc : pieces) vtimes.compared += pc.len;
+                    if (single) {
+                        // the first difference, or — sizes differ, bytes do not — the end of the shorter of the two, in the batch that holds it
+                        uint64_t pos = UINT64_MAX;
+                        const uint64_t commonEnd = std::min(totalText, one.size);
+                        if (oneFound && oneLoc.kind == ErrorLocation::NONE) {
+                            if (firstDiff[0] != UINT64_MAX) { pos = firstDiff[0]; oneDiffers = true; }
+                            else if (one.size != totalText && commonEnd >= batchAt[b] && (commonEnd < batchAt[b + 1] || b + 1 == nb)) pos = commonEnd - batchAt[b];
+                        }
+                        uint64_t at = 0;
+                        size_t rec = 0;
+                        for (size_t u = u0; u < u1 && pos != UINT64_MAX; u++) {
+                            if (pos < at + units[u].text || u + 1 == u1) { oneLoc = locate(units[u], at, rec, pos - at, units[0].c0); break; }
+                            at += units[u].text; rec += (size_t) (units[u].c1 - units[u].c0);
+                        }
+                    } else {
+                        uint64_t at = 0;
+                        size_t rec = 0;
+                        for (size_t u = u0; u < u1; u++) {
+                            const FastaUnit &x = units[u];
+                            const Original &o = R.files[u - u0];
+                            if (!o.found) {
+                                if (report && invalidFiles < VALIDATION_LOG_LIMIT) fprintf(stderr, "Cannot find %s for validation.\n", o.path.c_str());
+                                invalidFiles++;
+                            } else if (!o.unreadable.empty()) {
+                                if (report && invalidFiles < VALIDATION_LOG_LIMIT) fprintf(stderr, "Cannot read %s for validation: %s\n", o.path.c_str(), o.unreadable.c_str());
+                                invalidFiles++;
+                            } else if (o.size == x.text && firstDiff[u - u0] == UINT64_MAX) validFiles++;
+                            else {
+                                const uint64_t pos = firstDiff[u - u0] != UINT64_MAX ? firstDiff[u - u0] : std::min(x.text, o.size);
+                                reportInvalid(o.path, o.size != x.text, x.text, o.size, locate(x, at, rec, pos, x.c0));
+                                invalidFiles++;
+                                if (report && !opt.dumpDir.empty() && dumped++ < VALIDATION_DUMP_LIMIT)
+                                    if (const int r = dumpText(layout.outNames[x.file], fb.textDev[0] + at, x.text, false)) return dumpFail(r);
+                            }
+                            at += x.text; rec += (size_t) (x.c1 - x.c0);
+                        }
+                    }
+                    u0 = u1;
+                }
+                if (single && !opt.skipCompare) {                                               // one file: its verdict, and its size, after the last batch
+                    if (!oneFound) {
+                        if (report) fprintf(stderr, "Cannot find %s for validation.\n", onePath.c_str());
+                        invalidFiles++;
+                    } else if (!one.broken.empty()) {
+                        if (report) fprintf(stderr, "Cannot read %s for validation: %s\n", onePath.c_str(), one.broken.c_str());
+                        invalidFiles++;
+                    } else if (one.size == totalText && !oneDiffers) validFiles++;
+                    else {
+                        reportInvalid(onePath, one.size != totalText, totalText, one.size, oneLoc);
+                        invalidFiles++;
+                        if (report && !opt.dumpDir.empty()) {                                   // (the text of the earlier batches is gone: formatted once more)
+                            const FastaTimes keep = ftimes;
+                            size_t a = 0;
+                            for (size_t b = 0; b < nb; a = batchEnd[b], b++) {
+                                uint64_t bytes = 0;
+                                if (!formatBatch(a, batchEnd[b], fb.textDev[0], bytes)) return faFail("format");
+                                if (const int r = dumpText(layout.outNames[0], fb.textDev[0], bytes, b != 0)) return dumpFail(r);
+                            }
+                            ftimes = keep;
+                        }
+                    }
+                }
+                if (report && !opt.skipCompare) {
+                    printf("Validation%s: correctly decoded %llu out of %llu files.\n", invalidFiles ? " ERROR" : "", (unsigned long long) validFiles, (unsigned long long) validatedFiles);
+                    if (invalidFiles) fprintf(stderr, "Validation ERROR: errors in contents of %llu decoded files.\n", (unsigned long long) invalidFiles);
+                }
+            } else
+            for (size_t b = 0; b < batchEnd.size(); b++) {
+                const size_t u1 = batchEnd[b];
+                uint64_t bytes = 0;
+                if (!formatBatch(u0, u1, fb.textDev[b & 1], bytes)) return faFail("format");
                 if (const int r = settle()) return settleFail(r);                               // batch b - 1: it travelled beside this batch's format
                 // (the writer of b - 2, which read page-locked buffer b & 1, was waited for by that settle or the one before)
                 inFlight.clear();
@@ -822,7 +1099,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                     if (!opened[f] && fileWanted[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f], "", 0)) return fail("cannot write under " + opt.fastaDir);
         }
 
-        if (pass + 1 == passes && !opt.bench) {
+        if (pass + 1 == passes && !opt.bench && !opt.validate) {
             std::string seq(outBases, '\0');
             std::vector<uint64_t> outLens;
             {
@@ -844,7 +1121,19 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 return fail("cannot write " + outPrefix + ".seq / .contigLens / .seqCounts");
         }
     }
-    if (opt.bench) {
+    if (opt.bench && opt.validate) {
+        // one line: the comparison, and the headline fields of `d --bench` (the restore of -m 3 counts into the decode's time as it does there)
+        const double ms = times.plan + times.closure + times.fill + times.load + rcRestoreMs;
+        printf("{\"metric\": \"compared GB/s (validate: compare kernel, text and originals in HBM)\", \"value\": %.4f, \"unit\": \"GB/s\", \"compared_bytes\": %llu, "
+               "\"compare_kernel_ms\": %.3f, \"upload_ms\": %.3f, \"read_inflate_ms\": %.3f, \"files\": %llu, \"valid\": %llu, \"text_bytes\": %llu, \"batches\": %llu, "
+               "\"format_kernel_ms\": %.3f, \"decode_gbases_per_s\": %.4f, \"bases\": %llu, \"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, "
+               "\"waves\": %llu, \"serial\": %s, \"index\": %s}\n",
+               vtimes.compare > 0 ? vtimes.compared / (vtimes.compare * 1e-3) / 1e9 : 0.0, (unsigned long long) vtimes.compared, vtimes.compare, vtimes.upload, vtimes.read,
+               (unsigned long long) validatedFiles, (unsigned long long) validFiles, (unsigned long long) ftimes.text, (unsigned long long) ftimes.batches, ftimes.format,
+               outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, (unsigned long long) times.waves,
+               opt.serial ? "true" : "false", useIndex ? "true" : "false");
+    }
+    if (opt.bench && !opt.validate) {
         // --restore-rc on -m 3 streams: the whole restore (upload of the cut literals, plan, fill, download) counts into the headline
         char rcJson[160] = "";
         if (meta.rcRedundancyRemoval)
@@ -861,7 +1150,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                outBases / (ms * 1e-3) / 1e9, (unsigned long long) outBases, times.plan, times.fill, times.load, T, starts.size(), times.plan / (double) T,
                (unsigned long long) times.waves, opt.serial ? "true" : "false", useIndex ? "true" : "false", rcJson, selJson);
     }
-    if (opt.bench && wantFasta)
+    if (opt.bench && wantFasta && !opt.validate)
         printf("{\"metric\": \"FASTA text GB/s (format kernel)\", \"value\": %.4f, \"unit\": \"GB/s\", \"text_bytes\": %llu, \"batches\": %llu, "
                "\"format_kernel_ms\": %.3f, \"download_ms\": %.3f, \"write_ms\": %.3f}\n",
                ftimes.format > 0 ? ftimes.text / (ftimes.format * 1e-3) / 1e9 : 0.0, (unsigned long long) ftimes.text, (unsigned long long) ftimes.batches,
@@ -872,7 +1161,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     printf("waves: %llu for %zu targets\n", (unsigned long long) times.waves, T);
     printf("widest wave: %llu targets\n", (unsigned long long) times.widest);
     printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) outContigs, (unsigned long long) outBases);
-    return 0;
+    return opt.validate && invalidFiles ? 2 : 0;
 }
 
 int mbgc_hip_decompress_main(int argc, char **argv) {
@@ -924,6 +1213,59 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     return EXIT_SUCCESS;
+}
+
+// `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device
+int mbgc_hip_validate_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.validate = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--serial") opt.serial = true;
+        else if (a == "--no-index") opt.noIndex = true;
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "--restore-rc") opt.restoreRc = true;
+        else if (a == "--flat") opt.flat = true;
+        else if (a == "--skip-compare") opt.skipCompare = true;
+        else if (a == "--root" && i + 1 < argc) opt.root = argv[++i];
+        else if (a == "--dump" && i + 1 < argc) opt.dumpDir = argv[++i];
+        else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
+        else if (a == "--select" && i + 1 < argc) { opt.select.push_back(argv[++i]); selectAsked = true; }
+        else if (a == "--select-list" && i + 1 < argc) {
+            std::ifstream f(argv[++i]);
+            if (!f) { fprintf(stderr, "mbgc-hip v: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
+            for (std::string line; std::getline(f, line);) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                if (!line.empty()) opt.select.push_back(line);
+            }
+            selectAsked = true;
+        }
+        else if (a == "--gpus") { fprintf(stderr, "mbgc-hip v: validation runs on one GPU (--gpus is an option of mbgc-hip c)\n"); return EXIT_FAILURE; }
+        else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
+        else pos.push_back(a);
+    }
+    if (pos.size() != 1) {
+        fprintf(stderr, "usage: mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat]\n"
+                        "                  [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n"
+                        "  validates the stream set against its FASTA files: every file is decoded and formatted on the device as d --fasta does, its original\n"
+                        "  (its line of <streamsPrefix>.names, or that path with .gz; gzip files are inflated on the host) is uploaded beside it and the two are\n"
+                        "  compared there. Nothing is downloaded, nothing is written. Exit status 0: every file is valid; 2: a file differs or is missing\n"
+                        "  --root dir: put before relative names; --flat: the basename d --fasta writes a file under (d --fasta back; v --flat --root back)\n"
+                        "  --serial, --no-index, --restore-rc, --select, --select-list: as in mbgc-hip d (streams of c -m 3 need --restore-rc)\n"
+                        "  --skip-compare: decode and format only, no verdict; --dump dir: the decoded text of the first 3 invalid files is written under dir\n"
+                        "  --bench: two passes, the second one timed; one JSON line behind the verdict\n"
+                        "  --batch-kib K: KiB of text per batch (default 262144; a knob of the tests: several batches on a small collection)\n"
+                        "  streams of c -U or c --lossy are compared as they are: originals that were not upper case, or not strict FASTA, differ\n");
+        return EXIT_FAILURE;
+    }
+    if (selectAsked) for (const std::string &pat : opt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip v: --select: an empty pattern\n"); return EXIT_FAILURE; }
+    if (selectAsked && opt.select.empty()) { fprintf(stderr, "mbgc-hip v: --select-list: the list of patterns is empty\n"); return EXIT_FAILURE; }
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r == 1) { fprintf(stderr, "mbgc-hip v: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return r;
 }
 
 // ---------------------------------------------------------------- C exports for tests (host only, no device)

@@ -1,4 +1,5 @@
-// `mbgc-hip d`: a collection back from the raw streams `mbgc-hip c` wrote, on the device.
+// `mbgc-hip d`: a collection back from the raw streams `mbgc-hip c` wrote, on the device; `mbgc-hip v`: the same, compared there
+// with the FASTA files on disk (the reference's `mbgc v`, main.cpp:420-445).
 //   MbgcMeta       <prefix>.meta: what a decoder needs beyond the streams (the reference CLI keeps the same facts in its
 //                  archive header and header-side streams: MBGC_Decoder::readParams / readStats, MBGC_Decoder.cpp:1291-1323)
 //   MBGC_Decoder   mbgccoder/MBGC_Decoder.{h,cpp}: decodeTarget (:535-634) and loadRef (:651-675) restated as a load
@@ -57,6 +58,11 @@ public:
     struct Options {
         bool serial = false, noIndex = false, bench = false, restoreRc = false; int device = 0; std::string fastaDir;
         std::vector<std::string> select; std::string closureOut;
+        // `mbgc-hip v`: validate — the units are formatted as for --fasta and compared on the device with the originals named by
+        // <prefix>.names, nothing is downloaded or written; root / flat: where the originals lie (--root is put before relative names,
+        // --flat keeps the basename `d --fasta` writes); skipCompare: decode and format only; dumpDir: the text of the first invalid
+        // files is written there; batchText: text bytes per batch, 0 = the default of --fasta
+        bool validate = false, flat = false, skipCompare = false; std::string root, dumpDir; uint64_t batchText = 0;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -73,7 +79,10 @@ public:
     // streams under streamsPrefix -> outputPrefix.{seq,contigLens,seqCounts}; the message of a failure in *error.
     // opt.fastaDir: also the input FASTA files again, under that directory, from <streamsPrefix>.names / .headers / .dnaLineLengths
     // (formatted on the device: mbgc_fasta_format_dev, include/mbgc_fasta.h)
+    // opt.validate: nothing is written; 0 = every file equals its original, 2 = a file differs or is missing (reported on stdout /
+    // stderr in the reference's words, MBGC_Decoder.cpp:112-183, :1194-1200), 1 = a failure as above
     static int decode(const std::string &streamsPrefix, const std::string &outputPrefix, const Options &opt, std::string *error);
 };
 
 int mbgc_hip_decompress_main(int argc, char **argv);
+int mbgc_hip_validate_main(int argc, char **argv);

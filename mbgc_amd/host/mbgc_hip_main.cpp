@@ -66,6 +66,7 @@ static void dump(const std::string &prefix, const char *name, const std::string 
 
 int main(int argc, char **argv) {
     if (argc > 1 && std::string(argv[1]) == "d") return mbgc_hip_decompress_main(argc, argv);   // the streams back to the collection (mbgc_decoder.cpp)
+    if (argc > 1 && std::string(argv[1]) == "v") return mbgc_hip_validate_main(argc, argv);     // ... and compared with the files on disk, on the device
     MBGC_Params params;
     std::vector<std::string> pos;
     int gpus = 1;
@@ -130,6 +131,7 @@ int main(int argc, char **argv) {
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
         fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n");
+        fprintf(stderr, "       mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat] [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n");
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
