@@ -11,7 +11,8 @@
  * memory and are copied up by the caller). One call strips the headers and the newlines of all of them and
  * leaves every file's contigs back to back in HBM — exactly the layout swsem_match_batch_dev takes — plus the
  * record table (header bytes, contig offsets), the detected DNA line length and the kseq status per file.
- * gzip inflate (input_with_libdeflate_wrapper.cpp) stays on the host. No CPU fallback. */
+ * gzip inflate (input_with_libdeflate_wrapper.cpp) runs where the caller puts it: zlib on the host, or mbgc_fasta_inflate_dev on
+ * files that were uploaded compressed. No CPU fallback. */
 #ifndef MBGC_FASTA_H
 #define MBGC_FASTA_H
 #include <stdint.h>
@@ -162,6 +163,27 @@ int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
 typedef struct { uint64_t aOff, bOff, len; uint32_t slot; } mbgc_fasta_compare_piece_t;
 int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aBytes, const uint8_t *b_dev, uint64_t bBytes,
                            const mbgc_fasta_compare_piece_t *pieces, uint64_t npieces, uint64_t *firstDiff, uint32_t nslots, double *kernelMs);
+
+/* gzip files that lie compressed in HBM, inflated there (mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
+ * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
+ * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three
+ * block types) — and writes the text to out_dev[outOff, outOff + outCap). One wave per job; no byte outside either range is touched,
+ * whatever the input holds, and every input ends its job. results[k] (host, njobs entries):
+ *   status   MBGC_INFLATE_OK, or what stopped the job; a job's failure is its own, the others of the call complete
+ *   members  members that were decoded and checked
+ *   outLen   the text's length (valid for OK only; what a failed job left in its range is unspecified)
+ *   inUsed   input bytes consumed (inLen for OK)
+ * Each member's CRC-32 and ISIZE are checked as zlib checks them. A job that does not lie inside both buffers, or whose output range
+ * overlaps another job's, is refused before anything is launched (-103, message in mbgc_fasta_last_error; results untouched).
+ * kernelMs (may be NULL): the kernel's time from events on the stream. Runs on the input stage's stream; synchronous. */
+#define MBGC_INFLATE_OK      0
+#define MBGC_INFLATE_ESHORT  1   /* the text does not fit outCap; nothing past the cap was written */
+#define MBGC_INFLATE_EDATA   2   /* not gzip / malformed DEFLATE / input ends early */
+#define MBGC_INFLATE_ECHECK  3   /* a member's CRC-32 or ISIZE does not match */
+typedef struct { uint64_t inOff, inLen, outOff, outCap; } mbgc_fasta_inflate_job_t;
+typedef struct { int32_t status; uint32_t members; uint64_t outLen, inUsed; } mbgc_fasta_inflate_result_t;
+int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBytes, uint8_t *out_dev, uint64_t outBytes,
+                           const mbgc_fasta_inflate_job_t *jobs, uint64_t njobs, mbgc_fasta_inflate_result_t *results, double *kernelMs);
 
 /* A download that runs beside the kernels of the input stage's stream (the decoder's text batches: batch b travels while batch b + 1
  * is formatted): begin queues the copy on a stream of its own and returns; wait returns when it has arrived, with the copy's time

@@ -648,6 +648,26 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
 #include "fasta_format.h"
 #include "fasta_compare.h"
 
+#define INF_CONST static __device__
+#define INF_LANES_DO(lane) for (uint32_t lane = threadIdx.x, once_ = 1; once_; once_ = 0)
+#define INF_LANE0 (threadIdx.x == 0)
+#define INF_SYNC() __syncthreads()
+#define INF_UNI(x) ((uint32_t) __builtin_amdgcn_readfirstlane((int) (x)))
+#include "fasta_inflate.h"
+
+// mbgc_fasta_inflate_dev: one gzip file per block of one wave (the decoder, the ring and the tables: fasta_inflate.h). gz and out may
+// be one buffer (the round's file buffer holds both): no restrict on them; a job's input that another job's output runs over is refused
+__global__ void __launch_bounds__(INF_WAVE) k_fa_inflate(const uint8_t *gz, uint8_t *out, const InfJob *__restrict__ jobs,
+                                                         uint32_t job0, uint32_t njobs, InfResult *__restrict__ results) {
+    __shared__ InfShared S;
+    const uint32_t j = job0 + blockIdx.x;
+    if (j >= njobs) return;
+    const InfJob job = jobs[j];
+    Inf I(S, gz + job.inOff, job.inLen, out + job.outOff, job.outCap);
+    const InfResult r = I.run();
+    if (threadIdx.x == 0) results[j] = r;
+}
+
 // mbgc_fasta_compare_dev: a wave's steps, then — only when a lane found a difference — one 64-bit atomicMin per piece the wave
 // touches, from the lowest differing lane of that piece (its offset is the smallest: the steps of a piece ascend with the lanes).
 // Equal data issues no atomic.
@@ -792,6 +812,8 @@ struct mbgc_fasta {
     fa::Buf<fa::CmpPiece> dCmpPieces;           // mbgc_fasta_compare_dev: the piece table, the tiles' owners, the slots' results
     fa::Buf<uint32_t> dCmpOwner;
     fa::Buf<unsigned long long> dCmpOut;
+    fa::Buf<fa::InfJob> dInfJobs;               // mbgc_fasta_inflate_dev: the jobs and their results
+    fa::Buf<fa::InfResult> dInfResults;
     hipStream_t copyStream = nullptr;           // mbgc_fasta_download_begin / _wait: a download beside the kernels of `stream`
     hipEvent_t copyEv[2] = {nullptr, nullptr};
     bool copyPending = false;
@@ -828,6 +850,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
     p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
+    p->dInfJobs.release(); p->dInfResults.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
@@ -1119,6 +1142,54 @@ int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aByte
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
     for (uint32_t s = 0; s < nslots; s++) firstDiff[s] = out[s];
+    return 0;
+}
+
+int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBytes, uint8_t *out_dev, uint64_t outBytes,
+                           const mbgc_fasta_inflate_job_t *jobs, uint64_t njobs, mbgc_fasta_inflate_result_t *results, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(InfJob) == sizeof(mbgc_fasta_inflate_job_t) && sizeof(InfResult) == sizeof(mbgc_fasta_inflate_result_t), "the kernel reads the ABI's jobs");
+    static_assert(INF_OK == MBGC_INFLATE_OK && INF_ESHORT == MBGC_INFLATE_ESHORT && INF_EDATA == MBGC_INFLATE_EDATA && INF_ECHECK == MBGC_INFLATE_ECHECK, "status codes");
+    if (kernelMs) *kernelMs = 0;
+    if (njobs >= 0xffffffffull) return fail(-103, "inflate: %llu jobs in one call", (unsigned long long) njobs);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;               // the output ranges that hold bytes
+    for (uint64_t k = 0; k < njobs; k++) {
+        const mbgc_fasta_inflate_job_t &x = jobs[k];
+        if (x.inOff > gzBytes || x.inLen > gzBytes - x.inOff || x.outOff > outBytes || x.outCap > outBytes - x.outOff)
+            return fail(-103, "inflate: job %llu lies outside the buffers", (unsigned long long) k);
+        if (x.outCap) ranges.emplace_back(x.outOff, x.outOff + x.outCap);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+        if (ranges[k].first < ranges[k - 1].second) return fail(-103, "inflate: the output ranges of two jobs overlap at byte %llu", (unsigned long long) ranges[k].first);
+    // the two buffers may be one, or overlap: no job's input may lie where a job's output is written (the output ranges are
+    // sorted and apart, so the last one that starts in front of the input's end is the one that can reach into it)
+    const uint64_t gzA = (uint64_t) (uintptr_t) gz_dev, outA = (uint64_t) (uintptr_t) out_dev;
+    if (gzA < outA + outBytes && outA < gzA + gzBytes)
+        for (uint64_t k = 0; k < njobs; k++) {
+            const uint64_t a = gzA + jobs[k].inOff, e = a + jobs[k].inLen;
+            if (a == e || e <= outA) continue;
+            auto it = std::lower_bound(ranges.begin(), ranges.end(), std::make_pair(e - outA, (uint64_t) 0));   // the first range that starts at or behind the input's end
+            if (it != ranges.begin() && outA + std::prev(it)->second > a)
+                return fail(-103, "inflate: the input of job %llu overlaps a job's output range", (unsigned long long) k);
+        }
+    if (njobs == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dInfJobs.reserve(njobs)) || (rc = p->dInfResults.reserve(njobs))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dInfJobs.p, jobs, njobs * sizeof(InfJob), hipMemcpyHostToDevice, p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint64_t k0 = 0; k0 < njobs; k0 += FMT_SLICE)
+        k_fa_inflate<<<dim3((uint32_t) std::min<uint64_t>(FMT_SLICE, njobs - k0)), dim3(INF_WAVE), 0, p->stream>>>(gz_dev, out_dev, p->dInfJobs.p, (uint32_t) k0, (uint32_t) njobs,
+                                                                                                                  p->dInfResults.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    std::vector<InfResult> got(njobs);                               // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(got.data(), p->dInfResults.p, njobs * sizeof(InfResult), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    memcpy(results, got.data(), njobs * sizeof(InfResult));
     return 0;
 }
 

@@ -7,7 +7,7 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -27,6 +27,17 @@ class ComparePiece(C.Structure):
 
 
 NO_DIFFERENCE = 2 ** 64 - 1          # UINT64_MAX: what compare_dev leaves in a slot whose pieces are equal
+
+
+INFLATE_OK, INFLATE_ESHORT, INFLATE_EDATA, INFLATE_ECHECK = 0, 1, 2, 3      # MBGC_INFLATE_*
+
+
+class InflateJob(C.Structure):
+    _fields_ = [("inOff", C.c_uint64), ("inLen", C.c_uint64), ("outOff", C.c_uint64), ("outCap", C.c_uint64)]
+
+
+class InflateResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("members", C.c_uint32), ("outLen", C.c_uint64), ("inUsed", C.c_uint64)]
 
 
 PROBE_MIN_LEN, PROBE_MAX_LEN = 256, 65536      # MBGC_FASTA_PROBE_MIN_LEN, MBGC_FASTA_PROBE_MAX_LEN
@@ -75,6 +86,8 @@ def _lib():
         L.mbgc_fasta_probe_host.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, C.c_int, C.POINTER(ProbeState), C.POINTER(ProbeResult)]
         L.mbgc_fasta_compare_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(ComparePiece), C.c_uint64,
                                              C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_double)]
+        L.mbgc_fasta_inflate_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(InflateJob), C.c_uint64,
+                                             C.POINTER(InflateResult), C.POINTER(C.c_double)]
         L._fasta_ready = True
     return L
 
@@ -234,6 +247,18 @@ class FastaParser:
                                          int(nslots), C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out, ms.value
+
+    def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
+        """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into
+        out[outOff, outOff + outCap) -> ([(status, members, outLen, inUsed)] per job, the kernel's ms). A refused call (a job outside
+        the buffers, overlapping output ranges) raises and launches nothing."""
+        rows = [tuple(int(v) for v in r) for r in jobs]
+        arr = (InflateJob * max(len(rows), 1))(*rows)
+        res = (InflateResult * max(len(rows), 1))()
+        ms = C.c_double(0)
+        if _lib().mbgc_fasta_inflate_dev(self.h, gz_ptr, int(gz_bytes), out_ptr, int(out_bytes), arr, len(rows), res, C.byref(ms)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return [(r.status, r.members, r.outLen, r.inUsed) for r in res[: len(rows)]], ms.value
 
     def gather_dev(self, src_ptr, src_bytes, offsets, lengths, sep=10):
         """pieces of a device buffer, each followed by the byte sep, packed on the device and downloaded -> bytes"""

@@ -7,13 +7,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unistd.h>
 #include <zlib.h>
 
 // mgmpInOpen (matching/input_with_libdeflate_wrapper.cpp:51-124): the whole file, and when it starts with the gzip magic,
 // its members inflated one after the other (the reference: libdeflate_gzip_decompress_ex in a loop until the input is
-// used up, output buffer sized by the ISIZE trailer and doubled when short; here: zlib on the host — DEFLATE's bit-serial
-// Huffman decoding has no place on the device, and a round's files inflate on the host while the GPU matches the round
-// before)
+// used up, output buffer sized by the ISIZE trailer and doubled when short; here: zlib on the host, where a round's files
+// inflate while the GPU matches the round before. `mbgc-hip c --inflate device` and `mbgc-hip v --inflate device` inflate the
+// files of a list, and the originals, in HBM instead (mbgc_fasta_inflate_dev) and come here only for a file that does not
+// inflate to its ISIZE there)
 // false, the message in error and dest as it was: the inflate failed (a corrupt or truncated file)
 static bool tryInflateGzip(const std::string &gz, std::string &dest, std::string &error) {
     const size_t at = dest.size();
@@ -50,10 +52,14 @@ static bool tryInflateGzip(const std::string &gz, std::string &dest, std::string
     return true;
 }
 
-// the input stage's way (the reference's: message and exit)
+// the input stage's way (the reference's: message and exit). The callers stand on reader threads and on the input thread, beside
+// threads that are reading files and a main thread that has kernels in flight: exit() there runs the exit handlers and the
+// destructors of static objects (the HIP runtime's among them) while those threads still use them, which the C++ standard leaves
+// undefined and which has ended such a run with SIGSEGV behind its message. So: the message, the streams flushed, and _exit —
+// the same status, no handlers run beside working threads.
 [[maybe_unused]] static void inflateGzip(const std::string &gz, std::string &dest) {
     std::string error;
-    if (!tryInflateGzip(gz, dest, error)) { fprintf(stderr, "%s\n", error.c_str()); exit(EXIT_FAILURE); }
+    if (!tryInflateGzip(gz, dest, error)) { fprintf(stderr, "%s\n", error.c_str()); fflush(nullptr); _exit(EXIT_FAILURE); }
 }
 
 static bool isGzip(const uint8_t *p, size_t n) { return n >= 18 && p[0] == 0x1f && p[1] == 0x8b; }     // GZIP_ID1, GZIP_ID2

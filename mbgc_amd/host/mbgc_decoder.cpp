@@ -367,9 +367,10 @@ struct Original {
     std::string unreadable;                                        // found, but its gzip stream does not inflate: why
     uint64_t size = 0;                                             // of the file, inflated
     uint64_t off = 0, n = 0;                                       // its bytes that are compared: buffer[off, off + n)
+    uint64_t gzOff = 0, gzLen = 0;                                 // --inflate device: its place [off, off + n) is empty, its gzip bytes are gz[gzOff, gzOff + gzLen) of the batch
 };
-struct OriginalsBatch { std::vector<Original> files; double ms = 0; uint64_t bytes = 0; std::string error; };
-struct ValidateTimes { double read = 0, upload = 0, compare = 0; uint64_t compared = 0; };
+struct OriginalsBatch { std::vector<Original> files; double ms = 0; uint64_t bytes = 0; std::string error; std::string gz; };
+struct ValidateTimes { double read = 0, upload = 0, compare = 0, inflate = 0; uint64_t compared = 0, inflatedOnDevice = 0, inflatedAgainOnHost = 0; };
 
 // where a unit's original lies: its line of <prefix>.names; --flat: the basename `d --fasta` writes it under; --root before relative names
 static std::string originalPath(const std::string &name, const std::string &root, bool flat) {
@@ -382,9 +383,15 @@ static std::string originalPath(const std::string &name, const std::string &root
 // with the gzip magic is inflated whole (mgmpInOpen)
 struct OpenOriginal {
     int fd = -1; bool gz = false; uint64_t size = 0; std::string inflated;
+    std::string compressed; bool deferred = false;                 // deferGz: a gzip file is left compressed, size = its ISIZE trailer, until inflateNow()
     std::string broken;                                            // a gzip file that does not inflate (corrupt, truncated): the inflate's message; size = 0
     ~OpenOriginal() { if (fd >= 0) close(fd); }
-    bool open(const std::string &path, std::string &error) {
+    void inflateNow() {
+        deferred = false;
+        if (!tryInflateGzip(compressed, inflated, broken)) inflated.clear();                       // (reported as an invalid file, not the end of the run)
+        size = inflated.size();
+    }
+    bool open(const std::string &path, std::string &error, bool deferGz = false) {
         fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) fd = ::open((path + ".gz").c_str(), O_RDONLY);
         if (fd < 0) return false;
@@ -393,11 +400,17 @@ struct OpenOriginal {
         size = (uint64_t) st.st_size;
         uint8_t head[18];
         if (size >= 18 && pread(fd, head, 18, 0) == 18 && isGzip(head, 18)) {
-            std::string bytes(size, '\0');
-            if (!readAt(&bytes[0], 0, size)) { error = "cannot read " + path; return true; }
+            compressed.assign(size, '\0');
+            if (!readAt(&compressed[0], 0, size)) { error = "cannot read " + path; return true; }
             gz = true;
-            if (!tryInflateGzip(bytes, inflated, broken)) inflated.clear();                    // (reported as an invalid file, not the end of the run)
-            size = inflated.size();
+            if (deferGz) {
+                uint32_t isize;
+                memcpy(&isize, compressed.data() + compressed.size() - 4, 4);
+                size = isize; deferred = true;
+            } else {
+                inflateNow();
+                std::string().swap(compressed);
+            }
         }
         return true;
     }
@@ -932,7 +945,20 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                             Original o;
                             OpenOriginal f;
                             o.path = nameOf(units[u]);
-                            o.found = f.open(o.path, R.error);
+                            o.found = f.open(o.path, R.error, opt.inflateOnDevice);
+                            if (o.found && R.error.empty() && f.deferred) {
+                                // a gzip original whose trailer states the length of our text goes up compressed and is inflated into its
+                                // place beside the batch; any other one differs in size already and is inflated here, for its size
+                                if (f.size == units[u].text) {
+                                    o.size = o.n = f.size; o.off = R.bytes; R.bytes += o.n;
+                                    o.gzOff = R.gz.size(); o.gzLen = f.compressed.size();
+                                    R.gz += f.compressed;
+                                    R.gz.resize((R.gz.size() + 15) & ~(size_t) 15);
+                                    R.files.push_back(o);
+                                    continue;
+                                }
+                                f.inflateNow();
+                            }
                             if (o.found && R.error.empty()) {
                                 o.unreadable = f.broken;
                                 o.size = f.size; o.off = R.bytes; o.n = std::min(f.size, units[u].text);
@@ -973,6 +999,8 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 auto dumpFail = [&](int r) { return r == 1 ? faFail("--dump") : fail("cannot write under " + opt.dumpDir); };
                 std::vector<mbgc_fasta_compare_piece_t> pieces;
                 std::vector<uint64_t> firstDiff;
+                uint8_t *gzDev = nullptr; uint64_t gzDevCap = 0;                                    // --inflate device: a batch's gzip bytes in HBM
+                struct FreeGz { mbgc_fasta_t *fa; uint8_t *&p; ~FreeGz() { if (p) mbgc_fasta_dev_free(fa, p); } } freeGz{fb.fa, gzDev};
                 std::future<OriginalsBatch> reading;
                 if (!opt.skipCompare && nb) reading = std::async(std::launch::async, readBatch, (size_t) 0);
                 for (size_t b = 0; b < nb; b++) {
@@ -989,7 +1017,46 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                     if (bytes != batchAt[b + 1] - batchAt[b]) return fail("internal error: the text of a batch is not the sum of its units");
                     if (opt.skipCompare) { u0 = u1; continue; }
                     const double up0 = nowMs();
-                    if (mbgc_fasta_upload(fb.fa, fb.textDev[1], fb.pin[b & 1], R.bytes)) return faFail("upload");
+                    if (R.gz.empty()) { if (mbgc_fasta_upload(fb.fa, fb.textDev[1], fb.pin[b & 1], R.bytes)) return faFail("upload"); }
+                    else {
+                        // --inflate device: the plain originals go up run by run, the gzip ones compressed, and those are inflated into their
+                        // places. A job that does not end with exactly the text's length is done again by tryInflateGzip, as --inflate
+                        // host does it: its verdict, its size and its message are the ones reported.
+                        for (size_t i = 0; i < R.files.size();) {
+                            size_t j = i;
+                            while (j < R.files.size() && !R.files[j].gzLen) j++;
+                            if (j > i) {
+                                const uint64_t a = R.files[i].off, e = R.files[j - 1].off + R.files[j - 1].n;
+                                if (e > a && mbgc_fasta_upload(fb.fa, fb.textDev[1] + a, (const uint8_t *) fb.pin[b & 1] + a, e - a)) return faFail("upload");
+                            }
+                            while (j < R.files.size() && R.files[j].gzLen) j++;
+                            i = j;
+                        }
+                        if (R.gz.size() + 64 > gzDevCap) {
+                            if (gzDev && mbgc_fasta_dev_free(fb.fa, gzDev)) return faFail("upload");
+                            gzDev = nullptr; gzDevCap = R.gz.size() + R.gz.size() / 4 + 64;
+                            if (mbgc_fasta_dev_alloc(fb.fa, gzDevCap, &gzDev)) return faFail("upload");
+                        }
+                        if (mbgc_fasta_upload(fb.fa, gzDev, R.gz.data(), R.gz.size())) return faFail("upload");
+                        std::vector<mbgc_fasta_inflate_job_t> jobs;
+                        std::vector<size_t> jobFile;
+                        for (size_t i = 0; i < R.files.size(); i++)
+                            if (R.files[i].gzLen) { jobs.push_back({R.files[i].gzOff, R.files[i].gzLen, R.files[i].off, R.files[i].n}); jobFile.push_back(i); }
+                        std::vector<mbgc_fasta_inflate_result_t> res(jobs.size());
+                        double ims = 0;
+                        if (mbgc_fasta_inflate_dev(fb.fa, gzDev, R.gz.size(), fb.textDev[1], R.bytes, jobs.data(), jobs.size(), res.data(), &ims)) return faFail("inflate");
+                        vtimes.inflate += ims;
+                        for (size_t k = 0; k < jobs.size(); k++) {
+                            Original &o = R.files[jobFile[k]];
+                            if (res[k].status == MBGC_INFLATE_OK && res[k].outLen == o.n) { vtimes.inflatedOnDevice++; continue; }
+                            vtimes.inflatedAgainOnHost++;
+                            std::string text;
+                            if (!tryInflateGzip(R.gz.substr(o.gzOff, o.gzLen), text, o.unreadable)) text.clear();
+                            o.size = text.size();
+                            o.n = std::min<uint64_t>(o.size, o.n);                                  // (its place is as long as our text)
+                            if (o.n && mbgc_fasta_upload(fb.fa, fb.textDev[1] + o.off, text.data(), o.n)) return faFail("upload");
+                        }
+                    }
                     vtimes.upload += nowMs() - up0;
                     pieces.clear();
                     if (single) pieces.push_back({0, 0, R.files[0].n, 0});
@@ -1121,6 +1188,9 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 return fail("cannot write " + outPrefix + ".seq / .contigLens / .seqCounts");
         }
     }
+    if (opt.bench && opt.validate && opt.inflateOnDevice)
+        printf("{\"inflate_kernel_ms\": %.3f, \"inflated_on_device\": %llu, \"inflated_again_on_host\": %llu}\n", vtimes.inflate, (unsigned long long) vtimes.inflatedOnDevice,
+               (unsigned long long) vtimes.inflatedAgainOnHost);
     if (opt.bench && opt.validate) {
         // one line: the comparison, and the headline fields of `d --bench` (the restore of -m 3 counts into the decode's time as it does there)
         const double ms = times.plan + times.closure + times.fill + times.load + rcRestoreMs;
@@ -1229,6 +1299,11 @@ int mbgc_hip_validate_main(int argc, char **argv) {
         else if (a == "--restore-rc") opt.restoreRc = true;
         else if (a == "--flat") opt.flat = true;
         else if (a == "--skip-compare") opt.skipCompare = true;
+        else if (a == "--inflate" && i + 1 < argc) {                                            // where gzip originals are inflated
+            const std::string w = argv[++i];
+            if (w != "host" && w != "device") { fprintf(stderr, "mbgc-hip v: --inflate takes host or device\n"); return EXIT_FAILURE; }
+            opt.inflateOnDevice = w == "device";
+        }
         else if (a == "--root" && i + 1 < argc) opt.root = argv[++i];
         else if (a == "--dump" && i + 1 < argc) opt.dumpDir = argv[++i];
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
@@ -1248,15 +1323,18 @@ int mbgc_hip_validate_main(int argc, char **argv) {
     }
     if (pos.size() != 1) {
         fprintf(stderr, "usage: mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat]\n"
-                        "                  [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n"
+                        "                  [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [--inflate host|device] [-d device] <streamsPrefix>\n"
                         "  validates the stream set against its FASTA files: every file is decoded and formatted on the device as d --fasta does, its original\n"
-                        "  (its line of <streamsPrefix>.names, or that path with .gz; gzip files are inflated on the host) is uploaded beside it and the two are\n"
+                        "  (its line of <streamsPrefix>.names, or that path with .gz; gzip files are inflated where --inflate says) is uploaded beside it and the two are\n"
                         "  compared there. Nothing is downloaded, nothing is written. Exit status 0: every file is valid; 2: a file differs or is missing\n"
                         "  --root dir: put before relative names; --flat: the basename d --fasta writes a file under (d --fasta back; v --flat --root back)\n"
                         "  --serial, --no-index, --restore-rc, --select, --select-list: as in mbgc-hip d (streams of c -m 3 need --restore-rc)\n"
                         "  --skip-compare: decode and format only, no verdict; --dump dir: the decoded text of the first 3 invalid files is written under dir\n"
                         "  --bench: two passes, the second one timed; one JSON line behind the verdict\n"
                         "  --batch-kib K: KiB of text per batch (default 262144; a knob of the tests: several batches on a small collection)\n"
+                        "  --inflate device: a gzip original whose trailer states our text's length is uploaded compressed and inflated on the device beside\n"
+                        "  its batch, CRC-32 and length checked there; one that does not inflate to that length there is inflated by the host, so the report is\n"
+                        "  that of --inflate host (the default: zlib on the read-ahead thread). The one file of a single-FASTA collection inflates on the host\n"
                         "  streams of c -U or c --lossy are compared as they are: originals that were not upper case, or not strict FASTA, differ\n");
         return EXIT_FAILURE;
     }

@@ -62,7 +62,7 @@ public:
         // <prefix>.names, nothing is downloaded or written; root / flat: where the originals lie (--root is put before relative names,
         // --flat keeps the basename `d --fasta` writes); skipCompare: decode and format only; dumpDir: the text of the first invalid
         // files is written there; batchText: text bytes per batch, 0 = the default of --fasta
-        bool validate = false, flat = false, skipCompare = false; std::string root, dumpDir; uint64_t batchText = 0;
+        bool validate = false, flat = false, skipCompare = false, inflateOnDevice = false; std::string root, dumpDir; uint64_t batchText = 0;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).

@@ -96,6 +96,11 @@ int main(int argc, char **argv) {
         else if (a == "-U") params.uppercaseDNA = true;                          // MBGC_Params.h: converts bases to uppercase
         else if (a == "--proteins") params.setProteinsCompressionProfile();       // the reference's developer option -P (main.cpp:332-334); where it stands among the options matters as it does there
         else if (a == "--lossy") params.allowLossyParsing = true;                 // the reference's -L (MGMP_Params.h:213): ragged lines, CRLF, leading junk are read, not refused
+        else if (a == "--inflate" && i + 1 < argc) {                             // where the gzip files of a list are inflated
+            const std::string w = argv[++i];
+            if (w != "host" && w != "device") { fprintf(stderr, "--inflate takes host or device\n"); return EXIT_FAILURE; }
+            params.inflateOnDevice = w == "device";
+        }
         else if (a == "--bench") params.benchMode = true;                        // rounds timed with every contig resident in HBM (no streams written)
         else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
         else if (a == "--verify") params.verifyEmissions = true;                  // every emission decoded again on the device before the reference moves on
@@ -114,7 +119,7 @@ int main(int argc, char **argv) {
     const bool single = !params.inputFileName.empty();
     if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
     if (pos.size() != 2 || (single && !pos[0].empty())) {
-        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
+        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--inflate host|device] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
                         "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
@@ -128,6 +133,10 @@ int main(int argc, char **argv) {
                         "  probed length) > 10; -t1 / -m 3 take only the first record's verdict. An empty record is skipped (the reference divides by zero)\n"
                         "  --lossy: the files of the list are read as `mbgc c -L` reads them (any line lengths, empty lines, CRLF, bytes in front of the first\n"
                         "  '>'; the longest line becomes the file's line length); FASTQ files are refused; not with -i\n"
+                        "  --inflate device: the gzip files of the list are uploaded compressed and inflated on the device, one wave per file, with their\n"
+                        "  CRC-32 and length checked there; a file that does not inflate to the length its trailer states there (several members, a corrupt\n"
+                        "  stream) is inflated by the host. The streams are the same either way. host (the default): zlib on the reader threads. The first\n"
+                        "  file of the list and a gzip file given with -i are always inflated by the host\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
         fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n");

@@ -66,6 +66,7 @@ static double nowSeconds() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, 
 // where the host's wall time goes (MBGC_HIP_TIMES=1 prints it with "matching finished"): reading + inflating files,
 // upload + device parse, taking the streams over
 static uint64_t g_retryPasses = 0, g_retryContigs = 0;          // rounds whose first pass gave contigs up, and the contigs of the targets matched again in units
+static double g_tInflateKernel = 0;                            // --inflate device: the inflate kernel's time, from events
 static double g_tRead = 0, g_tParse = 0, g_tCollect = 0, g_tWait = 0, g_tCollectWait = 0, g_tAppend = 0, g_tAppendWait = 0, g_tPrepareSync = 0, g_tReadWait = 0, g_tMatch = 0, g_tEmit = 0, g_tFinalize = 0;
 
 // ---------------------------------------------------------------- input stage
@@ -74,9 +75,9 @@ static double g_tRead = 0, g_tParse = 0, g_tCollect = 0, g_tWait = 0, g_tCollect
 // validate_kseq_status (MGMP.cpp:16-35).
 // mgmpInOpen (matching/input_with_libdeflate_wrapper.cpp:51-124): the whole file, and when it starts with the gzip magic,
 // its members inflated one after the other (the reference: libdeflate_gzip_decompress_ex in a loop until the input is
-// used up, output buffer sized by the ISIZE trailer and doubled when short; here: zlib on the host — DEFLATE's bit-serial
-// Huffman decoding has no place on the device, and a round's files inflate on the host while the GPU matches the round
-// before)
+// used up, output buffer sized by the ISIZE trailer and doubled when short; here: zlib on the host, while the GPU matches
+// the round before — or, for the files of a list under --inflate device, mbgc_fasta_inflate_dev on the compressed bytes
+// in HBM, one wave per file, with zlib taking over the file that does not inflate to its ISIZE there)
 static bool readWholeFile(const std::string &path, std::string &dest) {
     std::ifstream f(path, std::ios::binary | std::ios::ate);
     if (!f) return false;
@@ -189,7 +190,9 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
 }
 
 // files [f0, f1) of the list, each whole (inflated when gzip), back to back in page-locked memory: the sizes first (a
-// gzip file's is known once it is inflated), then every plain file read straight to its place, by up to 8 threads
+// gzip file's is known once it is inflated), then every plain file read straight to its place, by up to 8 threads.
+// --inflate device: a gzip file's size is its ISIZE trailer, its place stays empty and its compressed bytes are read
+// behind the last file's place
 void MultipleGenomeMatchingProcessor::readFiles(StagedFiles &S, uint32_t f0, uint32_t f1) {
     const double tRead0 = nowSeconds();
     S.error.clear();
@@ -198,6 +201,7 @@ void MultipleGenomeMatchingProcessor::readFiles(StagedFiles &S, uint32_t f0, uin
     std::vector<uint64_t> size(nf, 0);
     std::vector<std::string> inflated(nf);
     std::vector<std::string> errors(nf);
+    S.gzOff.assign(nf, 0); S.gzLen.assign(nf, 0);
     auto parallel = [&](const std::function<void(size_t)> &body) {
         std::atomic<size_t> next{0};
         auto work = [&] { for (size_t i; (i = next.fetch_add(1)) < nf;) body(i); };
@@ -215,6 +219,12 @@ void MultipleGenomeMatchingProcessor::readFiles(StagedFiles &S, uint32_t f0, uin
         size[i] = (uint64_t) st.st_size;
         uint8_t head[18];
         if (size[i] >= 18 && pread(fd[i], head, 18, 0) == 18 && isGzip(head, 18)) {
+            uint32_t isize;
+            if (params->inflateOnDevice && pread(fd[i], &isize, 4, (off_t) (size[i] - 4)) == 4) {
+                S.gzLen[i] = size[i];
+                size[i] = isize;
+                return;
+            }
             std::string gz(size[i], '\0');
             size_t got = 0;
             while (got < gz.size()) { const ssize_t k = pread(fd[i], &gz[got], gz.size() - got, (off_t) got); if (k <= 0) break; got += (size_t) k; }
@@ -227,7 +237,8 @@ void MultipleGenomeMatchingProcessor::readFiles(StagedFiles &S, uint32_t f0, uin
     for (size_t i = 0; i < nf; i++) if (!errors[i].empty()) { S.error = errors[i]; break; }
     S.fileOff.assign(1, 0);
     for (size_t i = 0; i < nf; i++) S.fileOff.push_back(S.fileOff.back() + size[i]);
-    const size_t n = S.fileOff.back();
+    size_t n = S.fileOff.back();
+    for (size_t i = 0; i < nf; i++) if (S.gzLen[i]) { S.gzOff[i] = n = (n + 15) & ~(size_t) 15; n += S.gzLen[i]; }
     if (S.error.empty() && n + 64 > S.cap) {                 // grow-only
         if (S.pin) mbgc_fasta_host_free(fasta, S.pin);
         S.pin = nullptr;
@@ -238,11 +249,12 @@ void MultipleGenomeMatchingProcessor::readFiles(StagedFiles &S, uint32_t f0, uin
     }
     if (S.error.empty())
         parallel([&](size_t i) {
-            uint8_t *dst = S.pin + S.fileOff[i];
+            uint8_t *dst = S.gzLen[i] ? S.pin + S.gzOff[i] : S.pin + S.fileOff[i];
             if (fd[i] < 0) { memcpy(dst, inflated[i].data(), inflated[i].size()); return; }
+            const size_t want = S.gzLen[i] ? S.gzLen[i] : size[i];
             size_t got = 0;
-            while (got < size[i]) { const ssize_t k = pread(fd[i], dst + got, size[i] - got, (off_t) got); if (k <= 0) break; got += (size_t) k; }
-            if (got != size[i]) errors[i] = "Problem reading from file: " + fileNames[f0 + i];
+            while (got < want) { const ssize_t k = pread(fd[i], dst + got, want - got, (off_t) got); if (k <= 0) break; got += (size_t) k; }
+            if (got != want) errors[i] = "Problem reading from file: " + fileNames[f0 + i];
         });
     for (size_t i = 0; i < nf; i++) {
         if (fd[i] >= 0) close(fd[i]);
@@ -376,8 +388,14 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
     if (readBesideUpload() && afterF1 > afterF0 && afterF0 >= f1) {  // the files after these, into the other staging buffer, meanwhile
         startReadAhead(afterF0, afterF1, S == &staged[0] ? 1 : 0);
     }
-    const std::vector<uint64_t> &fileOff = S->fileOff;
     const double tParse0 = nowSeconds();
+    bool onDevice = false;                                   // some of the round's files were inflated in HBM: the host does not hold their text
+    for (int f = 0; f < nf; f++) onDevice = onDevice || S->gzLen[f] != 0;
+    std::string redo;                                        // ... unless one of them had to go the host's way
+    std::vector<uint64_t> redoOff;
+    if (onDevice && !uploadAndInflate(*S, nf, redo, redoOff)) onDevice = false;
+    const std::vector<uint64_t> &fileOff = redoOff.empty() ? S->fileOff : redoOff;
+    const uint8_t *hostBytes = redoOff.empty() ? S->pin : (const uint8_t *) redo.data();
     const size_t n = fileOff[nf];                            // (the staged files may be more than this round's)
     totalFilesLength += n;
     if (n + 64 > rawCap) {                                   // grow-only: freeing device memory waits for the whole device
@@ -390,7 +408,7 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
         B.seqCap = n + n / 4 + 64;
         B.seqDev = matcher->devAlloc(B.seqCap);
     }
-    if (mbgc_fasta_upload(fasta, rawDev, S->pin, n) != 0) { fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error()); exit(EXIT_FAILURE); }
+    if (!onDevice && mbgc_fasta_upload(fasta, rawDev, hostBytes, n) != 0) { fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error()); exit(EXIT_FAILURE); }
     std::vector<uint64_t> seqBase(nf + 1), recBase(nf + 1), lineLen(nf);
     std::vector<int> status(nf);
     if (records.size() < 4096) records.resize(4096);
@@ -417,8 +435,92 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
         }
     }
     B.bytes = seqBase[nf];
-    if (keepsLayout()) keepHeaders(B, S->pin, fileOff.data(), recBase.data(), lineLen.data(), nf);   // (before the slot is read into again)
+    if (keepsLayout()) {
+        if (onDevice) keepHeadersFromDevice(B, rawDev, n, fileOff.data(), recBase.data(), lineLen.data(), nf);
+        else keepHeaders(B, hostBytes, fileOff.data(), recBase.data(), lineLen.data(), nf);   // (before the slot is read into again)
+    }
     g_tParse += nowSeconds() - tParse0;
+}
+
+// --inflate device. The round's bytes in rawDev: every file at its place fileOff[f] — the plain ones uploaded there, run by run,
+// the gzip ones inflated there from their compressed bytes, which are uploaded behind the last file's place. A gzip file whose
+// job does not end with MBGC_INFLATE_OK and exactly the length its ISIZE trailer promised (several members, a wrong trailer, a
+// corrupt stream) is inflated again by zlib, which prints what it prints today and exits as it does today; when zlib accepts it,
+// the round is laid out again in host memory — the other files' text comes back from HBM — and goes the host's way from there.
+bool MultipleGenomeMatchingProcessor::uploadAndInflate(StagedFiles &S, int nf, std::string &redo, std::vector<uint64_t> &redoOff) {
+    auto check = [](int rc) { if (rc != 0) { fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error()); exit(EXIT_FAILURE); } };
+    uint64_t end = S.fileOff[nf];
+    for (int f = 0; f < nf; f++) if (S.gzLen[f]) end = S.gzOff[f] + S.gzLen[f];
+    if (end + 64 > rawCap) {
+        if (rawDev) matcher->devFree(rawDev);
+        rawCap = end + end / 4 + 64;
+        rawDev = matcher->devAlloc(rawCap);
+    }
+    std::vector<mbgc_fasta_inflate_job_t> jobs;
+    std::vector<int> jobFile;
+    for (int f = 0; f < nf;) {
+        int g = f;
+        if (S.gzLen[f]) {                                    // (the compressed bytes of neighbours are neighbours but for the padding)
+            while (g < nf && S.gzLen[g]) { jobs.push_back(mbgc_fasta_inflate_job_t{S.gzOff[g], S.gzLen[g], S.fileOff[g], S.fileOff[g + 1] - S.fileOff[g]}); jobFile.push_back(g); g++; }
+            check(mbgc_fasta_upload(fasta, rawDev + S.gzOff[f], S.pin + S.gzOff[f], S.gzOff[g - 1] + S.gzLen[g - 1] - S.gzOff[f]));
+        } else {
+            while (g < nf && !S.gzLen[g]) g++;
+            check(mbgc_fasta_upload(fasta, rawDev + S.fileOff[f], S.pin + S.fileOff[f], S.fileOff[g] - S.fileOff[f]));
+        }
+        f = g;
+    }
+    std::vector<mbgc_fasta_inflate_result_t> res(jobs.size());
+    double ms = 0;
+    check(mbgc_fasta_inflate_dev(fasta, rawDev, rawCap, rawDev, rawCap, jobs.data(), jobs.size(), res.data(), &ms));
+    g_tInflateKernel += ms * 1e-3;
+    bool good = true;
+    for (size_t j = 0; j < jobs.size(); j++) good = good && res[j].status == MBGC_INFLATE_OK && res[j].outLen == jobs[j].outCap;
+    if (good) return true;
+    std::vector<std::string> text((size_t) nf);
+    std::vector<char> redone((size_t) nf, 0);
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const int f = jobFile[j];
+        if (res[j].status == MBGC_INFLATE_OK && res[j].outLen == jobs[j].outCap) continue;
+        inflateGzip(std::string((const char *) S.pin + S.gzOff[f], S.gzLen[f]), text[f]);    // (its message and the run's end, when zlib refuses it too)
+        redone[f] = 1;
+    }
+    redoOff.assign(1, 0);
+    for (int f = 0; f < nf; f++) redoOff.push_back(redoOff.back() + (redone[f] ? text[f].size() : S.fileOff[f + 1] - S.fileOff[f]));
+    redo.resize(redoOff.back() + 1);
+    for (int f = 0; f < nf; f++) {
+        char *dst = &redo[0] + redoOff[f];
+        const uint64_t len = redoOff[f + 1] - redoOff[f];
+        if (!len) continue;
+        if (redone[f]) memcpy(dst, text[f].data(), len);
+        else if (S.gzLen[f]) check(mbgc_fasta_download(fasta, dst, rawDev + S.fileOff[f], len));
+        else memcpy(dst, S.pin + S.fileOff[f], len);
+    }
+    return false;
+}
+
+// the headers of a parsed batch whose file bytes lie in HBM only: the header lines alone are packed there and come back
+void MultipleGenomeMatchingProcessor::keepHeadersFromDevice(RoundBatch &B, const uint8_t *filesDev, uint64_t n, const uint64_t *fileOff, const uint64_t *recBase,
+                                                            const uint64_t *lineLen, int nf) {
+    const uint64_t nrecs = recBase[nf];
+    std::vector<uint64_t> off(nrecs), len(nrecs);
+    uint64_t bytes = 0;
+    for (int f = 0; f < nf; f++)
+        for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) { off[k] = fileOff[f] + records[k].headerOff; len[k] = records[k].headerLen; bytes += len[k] + 1; }
+    std::string packed(bytes, '\0');
+    uint64_t got = 0;
+    if (mbgc_fasta_gather_dev(fasta, filesDev, n, off.data(), len.data(), nrecs, '\n', (uint8_t *) &packed[0], bytes, &got) != 0) {
+        fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error());
+        exit(EXIT_FAILURE);
+    }
+    B.unitHeaders.assign((size_t) std::max(nf, 0), std::string());
+    B.unitLineLen.assign(lineLen, lineLen + std::max(nf, 0));
+    uint64_t at = 0;
+    for (int f = 0; f < nf; f++) {
+        uint64_t u = 0;
+        for (uint64_t k = recBase[f]; k < recBase[f + 1]; k++) u += len[k] + 1;
+        B.unitHeaders[f].assign(packed, at, u);
+        at += u;
+    }
 }
 
 // ---------------------------------------------------------------- single fasta file mode (`-i`)
@@ -1268,6 +1370,7 @@ void MultipleGenomeMatchingProcessor::performMatching() {
         for (int k = 0; k < SWSEM_K_COUNT; k++) fprintf(stderr, "%s\"%s\": {\"ms\": %.3f, \"launches\": %llu}", k ? ", " : "", fam[k], ms[k], (unsigned long long) nl[k]);
         fprintf(stderr, "}\n");
     }
+    if (getenv("MBGC_HIP_TIMES") && params->inflateOnDevice) fprintf(stderr, "  --inflate device: the inflate kernel ran %.0f ms in all\n", g_tInflateKernel * 1e3);
     if (getenv("MBGC_HIP_TIMES"))
         fprintf(stderr, "  reader threads: reading files %.0f ms; input thread: waiting for them %.0f ms, upload + parse %.0f ms; main thread: waiting for it %.0f ms, taking the streams over %.0f ms"
                         " (%.0f of them waiting for the bytes; appends on their thread %.0f ms, waited for %.0f ms); rounds prepared by the main thread itself %.0f ms; match-finding calls %.0f ms, processMatches calls %.0f ms, loadRef calls %.0f ms; rounds whose first pass gave contigs up as dissimilar: %llu, contigs matched again in units: %llu\n",

@@ -46,6 +46,7 @@ struct MGMP_Params {                                   // matching/MGMP_Params.h
     int roundSize = 0;
     static constexpr int MAX_TARGETS_IN_FLIGHT = 64;
     bool uppercaseDNA = false;                         // :196 (-U)
+    bool inflateOnDevice = false;                      // mbgc-hip c --inflate device: the gzip files of a list travel compressed and are inflated in HBM (mbgc_fasta_inflate_dev)
     bool allowLossyParsing = false;                    // :213 (the reference's -L; mbgc-hip c --lossy): the files of a list are read by kseq_read_lossy
     // mbgc-hip c --bench: every round's contigs are put into HBM first, the rounds after `benchWarmup` are timed and the
     // emitted streams stay packed in HBM (what bench.py measures, from the C++ host)
@@ -148,6 +149,9 @@ protected:
     struct StagedFiles {
         uint8_t *pin = nullptr; size_t cap = 0;
         std::vector<uint64_t> fileOff;
+        // --inflate device: a gzip file's place among fileOff is as long as its ISIZE trailer says and stays empty on the host; its
+        // compressed bytes lie at pin[gzOff, gzOff + gzLen), behind the last file's place (gzLen 0: not such a file)
+        std::vector<uint64_t> gzOff, gzLen;
         std::string error;
     } staged[2];
     struct Ahead { std::future<void> done; uint32_t f0 = 0, f1 = 0; RoundBatch *B = nullptr; bool active = false; } ahead;
@@ -156,6 +160,10 @@ protected:
     void startReadAhead(uint32_t f0, uint32_t f1, int slot, bool bothBuffers = false);                            // files [f0, f1) into staged[slot], on a thread of its own
     // read (unless read ahead) + upload + device parse, synchronous; [afterF0, afterF1) = the files to read meanwhile
     void prepareRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t afterF0 = 0, uint32_t afterF1 = 0);
+    // --inflate device: the staged files [0, nf) into rawDev, the gzip ones inflated there; false: one of them did not inflate to its
+    // ISIZE there, and the round's bytes are in `redo` instead, that file inflated by the host, with redoOff as their fileOff
+    bool uploadAndInflate(StagedFiles &S, int nf, std::string &redo, std::vector<uint64_t> &redoOff);
+    void keepHeadersFromDevice(RoundBatch &B, const uint8_t *filesDev, uint64_t n, const uint64_t *fileOff, const uint64_t *recBase, const uint64_t *lineLen, int nf);
     uint8_t *rawDev = nullptr; size_t rawCap = 0;
     uint8_t *extScratch = nullptr; size_t extScratchCap = 0;                            // extension strings that are not a span of the round's buffer
     void extensionStrings(const RoundBatch &B, const std::vector<char> &ext, const std::vector<char> &rc, uint32_t ta, uint32_t tb,
