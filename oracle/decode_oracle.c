@@ -11,6 +11,11 @@
  *
  * The six streams are those of ONE contig (what processMatches appends); the SEQ_SEPARATOR_MARK the encoder's
  * caller puts behind a contig's literals is the end of the literal buffer here.
+ *
+ * The automaton itself is orc_decode_contig_bounded: it knows how long the reference buffer is and refuses what would
+ * read outside it, stops a pairing-ring walk that finds no free slot in a whole lap, and says how far it got in every
+ * stream. That makes it a referee for streams no encoder wrote (tests/_decmut.py). orc_decode_contig is that function
+ * without a bound on the reference plus the demand that every stream byte was used: the form the reference pins.
  */
 #include "oracle.h"
 
@@ -26,6 +31,8 @@
 
 typedef struct {
     const uint8_t *ref;
+    uint64_t refBytes;                         /* a read at or beyond it is malformed (UINT64_MAX: no bound) */
+    orc_decode_info *info;                     /* may be NULL */
     const orc_emit_params *p;
     const uint8_t *lit, *off, *off5, *len, *gap, *flags;
     uint64_t nLit, nOff, nOff5, nLen, nGap, nFlags;
@@ -51,7 +58,20 @@ static uint8_t code2mismatch(dec_t *d, uint8_t actual, uint8_t code) {   /* :72-
 
 static uint8_t lit_next(dec_t *d) { if (d->litPos >= d->nLit) { d->bad = 1; return 0; } return d->lit[d->litPos++]; }
 static uint8_t flag_at(dec_t *d, uint64_t i) { if (i >= d->nFlags) { d->bad = 1; return 0; } return d->flags[i]; }
-static uint8_t ref_at(dec_t *d, int64_t i) { if (i < 0) { d->bad = 1; return 0; } return d->ref[i]; }
+static uint8_t ref_at(dec_t *d, int64_t i) { if (i < 0 || (uint64_t) i >= d->refBytes) { d->bad = 1; return 0; } return d->ref[i]; }
+/* the reference bytes the extensions read, for the caller who asked: a plain copy (litPos ORC_NO_LIT) or under a literal code */
+static void note_read(dec_t *d, int64_t src, uint64_t litPos) {
+    orc_decode_info *o = d->info;
+    if (!o || !o->trace || d->bad) return;
+    if (o->nTrace < o->traceCap) { o->trace[o->nTrace].refPos = src; o->trace[o->nTrace].litPos = litPos; }
+    o->nTrace++;
+}
+static uint8_t ref_plain(dec_t *d, int64_t src) { const uint8_t a = ref_at(d, src); note_read(d, src, ORC_NO_LIT); return a; }
+static uint8_t ref_coded(dec_t *d, int64_t src) {
+    const uint8_t a = ref_at(d, src);
+    note_read(d, src, d->litPos);
+    return code2mismatch(d, a, lit_next(d));
+}
 static void push(dec_t *d, uint8_t c) { if (d->destLen >= d->destCap) { d->bad = 1; return; } d->dest[d->destLen++] = c; }
 static void append(dec_t *d, const uint8_t *s, uint64_t n) {
     if (d->destLen + n > d->destCap) { d->bad = 1; return; }
@@ -70,7 +90,7 @@ static uint64_t extend_right(dec_t *d, int64_t offsetDelta, int isGap, int gapSt
     if (d->litPos == guardLitPos && !gapMiddle) return 0;
     const uint64_t destStart = d->destLen;
     int64_t src = (int64_t) d->destLen + offsetDelta;
-    if (gapStart || !isGap) push(d, code2mismatch(d, ref_at(d, src), lit_next(d)));
+    if (gapStart || !isGap) push(d, ref_coded(d, src));
     else src--;
     int score = p->mmsMismatchesInitialScore;
     while (!d->bad && (!gapEnd || d->litPos != guardLitPos) && (isGap || score < p->mmsMismatchesScoreThreshold)) {
@@ -79,7 +99,7 @@ static uint64_t extend_right(dec_t *d, int64_t offsetDelta, int isGap, int gapSt
         if (mismatch) score += p->mmsMismatchPenalty;
         else { score -= p->mmsMatchBonus; if (score < 0) score = 0; }
         ++src;
-        push(d, mismatch ? code2mismatch(d, ref_at(d, src), lit_next(d)) : ref_at(d, src));
+        push(d, mismatch ? ref_coded(d, src) : ref_plain(d, src));
     }
     return d->destLen - destStart;
 }
@@ -115,7 +135,7 @@ static uint64_t extend_left(dec_t *d, uint8_t *extEnd, uint64_t *matchSrcPos, in
         srcMatch += (int64_t) matchingChars;
     }
     int64_t src = srcMatch - 1;
-    *(--ptr) = code2mismatch(d, ref_at(d, src), lit_next(d));
+    *(--ptr) = ref_coded(d, src);
     int score = p->mmsMismatchesInitialScore;
     while (!d->bad && --src >= srcGuard && score < p->mmsMismatchesScoreThreshold) {
         if ((uint64_t) (extEnd - ptr) >= MAX_EXTEND_MATCH_LEFT_LENGTH) { d->bad = 1; break; }
@@ -123,7 +143,7 @@ static uint64_t extend_left(dec_t *d, uint8_t *extEnd, uint64_t *matchSrcPos, in
         if (mismatch && d->litPos == markPos) break;
         if (mismatch) score += p->mmsMismatchPenalty;
         else { score -= p->mmsMatchBonus; if (score < 0) score = 0; }
-        *(--ptr) = mismatch ? code2mismatch(d, ref_at(d, src), lit_next(d)) : ref_at(d, src);
+        *(--ptr) = mismatch ? ref_coded(d, src) : ref_plain(d, src);
     }
     return (uint64_t) (extEnd - ptr);
 }
@@ -151,14 +171,16 @@ static uint32_t next_len(dec_t *d) {
 }
 
 /* decodeSequenceAndReturnUnmatchedChars, :319-432. streams[] in the ORC_* order. Returns unmatchedChars, or -1
- * when a stream ran out, an index left its buffer or not every stream byte was consumed. */
-int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const uint8_t *const streams[ORC_NSTREAMS],
-                          const uint64_t sizes[ORC_NSTREAMS], uint64_t refLockPos, uint8_t *dest, uint64_t destCap,
-                          uint64_t *destLen) {
+ * when a stream ran out, an index left its buffer (the reference buffer: [0, refBytes)) or the pairing ring is full.
+ * Stream bytes may be left over: info->cur says how far every stream was read. */
+int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const orc_emit_params *p,
+                                  const uint8_t *const streams[ORC_NSTREAMS], const uint64_t sizes[ORC_NSTREAMS],
+                                  uint64_t refLockPos, uint8_t *dest, uint64_t destCap, uint64_t *destLen, orc_decode_info *info) {
     dec_t D;
     memset(&D, 0, sizeof D);
     dec_t *d = &D;
-    d->ref = ref; d->p = p;
+    d->ref = ref; d->refBytes = refBytes; d->info = info; d->p = p;
+    if (info) { info->maxRingWalk = 0; info->nTrace = 0; }
     d->lit = streams[ORC_LIT]; d->nLit = sizes[ORC_LIT];
     d->off = streams[ORC_OFF]; d->nOff = sizes[ORC_OFF];
     d->off5 = streams[ORC_OFF5]; d->nOff5 = sizes[ORC_OFF5];
@@ -213,6 +235,7 @@ int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const ui
         matchLength += minMatchLength;
         if (d->bad) break;
         prevMatchDestPos = d->destLen;
+        if (matchSrcPos > refBytes || matchLength > refBytes - matchSrcPos) { d->bad = 1; break; }   /* a match outside the buffer */
         append(d, ref + matchSrcPos, matchLength);
         markPos = find_mark(d, d->litPos);
         uint8_t gapDelta = 0;
@@ -227,11 +250,15 @@ int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const ui
                 gapIdx = (gapIdx + 1) % MAX_GAP_DEPTH;
                 g++;
             }
+            uint64_t walk = 0, sinceFree = 0;
             while (gapDelta) {
                 gapIdx = (gapIdx + 1) % MAX_GAP_DEPTH;
-                if (paired[gapIdx] == INT64_MAX) gapDelta--;
-                else g++;
+                walk++;
+                if (paired[gapIdx] == INT64_MAX) { gapDelta--; sinceFree = 0; }
+                else { g++; if (++sinceFree >= MAX_GAP_DEPTH) { d->bad = 1; break; } }   /* a lap without a free slot: the reference never ends */
             }
+            if (info && walk > info->maxRingWalk) info->maxRingWalk = walk;
+            if (d->bad) break;
             paired[gapIdx] = (int64_t) matchSrcPos - (int64_t) prevMatchDestPos;
             if (p->enableExtensionsWithMismatches && gapEndIdx <= j + g && g <= p->gapDepthMismatchesEncoding) {
                 gapStartIdx = j;
@@ -259,8 +286,24 @@ int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const ui
     }
     free(ext);
     *destLen = d->destLen;
+    if (info) {
+        info->cur[ORC_LIT] = d->litPos; info->cur[ORC_OFF] = d->offPos; info->cur[ORC_OFF5] = d->off5Pos;
+        info->cur[ORC_LEN] = d->lenPos; info->cur[ORC_GAP] = d->gapPos; info->cur[ORC_FLAGS] = d->flPos;
+    }
     if (d->bad) return -1;
-    /* every byte of every stream belongs to exactly one step of the automaton */
-    if (d->offPos != d->nOff || d->off5Pos != d->nOff5 || d->lenPos != d->nLen || d->gapPos != d->nGap || d->flPos != d->nFlags) return -1;
     return (int64_t) unmatchedChars;
+}
+
+/* The form the reference pins: no bound on the reference buffer, and every byte of every stream belongs to exactly one step
+ * of the automaton. Returns unmatchedChars, or -1 when a stream ran out, an index left its buffer or stream bytes were left over. */
+int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const uint8_t *const streams[ORC_NSTREAMS],
+                          const uint64_t sizes[ORC_NSTREAMS], uint64_t refLockPos, uint8_t *dest, uint64_t destCap,
+                          uint64_t *destLen) {
+    orc_decode_info info;
+    memset(&info, 0, sizeof info);
+    const int64_t r = orc_decode_contig_bounded(ref, UINT64_MAX, p, streams, sizes, refLockPos, dest, destCap, destLen, &info);
+    if (r < 0) return -1;
+    for (int i = 1; i < ORC_NSTREAMS; i++)
+        if (info.cur[i] != sizes[i]) return -1;
+    return r;
 }

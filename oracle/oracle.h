@@ -120,6 +120,27 @@ int64_t orc_decode_contig(const uint8_t *ref, const orc_emit_params *p, const ui
                           const uint64_t sizes[ORC_NSTREAMS], uint64_t refLockPos, uint8_t *dest, uint64_t destCap,
                           uint64_t *destLen);
 
+/* The same automaton with the reference buffer's size known: a match or an extension read below 0 or at or beyond refBytes
+ * is malformed (UINT64_MAX: no bound), and so is a pairing-ring walk that passes MAX_GAP_DEPTH (128) slots in a row without a
+ * free one (the reference would not end). Stream bytes may be left over: cur[] are the six cursors reached (ORC_* order), the
+ * caller decides. maxRingWalk: the longest walk over the pairing ring, in steps. trace (may be NULL): the reference bytes the
+ * two extensions read, in the order read, the first traceCap of nTrace. orc_decode_contig is this function with
+ * refBytes = UINT64_MAX and cur[] == sizes[] demanded of the five streams that are not the literals. */
+#define ORC_NO_LIT UINT64_MAX
+typedef struct {
+    int64_t refPos;
+    uint64_t litPos;                           /* the literal code that stands for the byte; ORC_NO_LIT: copied as it is */
+} orc_ext_read;
+typedef struct {
+    uint64_t cur[ORC_NSTREAMS];
+    uint64_t maxRingWalk;
+    orc_ext_read *trace;
+    uint64_t traceCap, nTrace;
+} orc_decode_info;
+int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const orc_emit_params *p,
+                                  const uint8_t *const streams[ORC_NSTREAMS], const uint64_t sizes[ORC_NSTREAMS],
+                                  uint64_t refLockPos, uint8_t *dest, uint64_t destCap, uint64_t *destLen, orc_decode_info *info);
+
 /* writeUInt64Frugal, utils/helper.cpp:237-246 */
 void orc_write_frugal64(orc_buf *b, uint64_t v);
 void orc_buf_put(orc_buf *b, const void *p, uint64_t n);

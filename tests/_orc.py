@@ -48,7 +48,7 @@ def lib():
     global _lib
     if _lib is None:
         so = os.path.join(ORACLE_DIR, "liboracle.so")
-        srcs = [os.path.join(ORACLE_DIR, f) for f in ("swsem_oracle.c", "emit_oracle.c", "oracle.h")]
+        srcs = [os.path.join(ORACLE_DIR, f) for f in ("swsem_oracle.c", "emit_oracle.c", "fasta_oracle.c", "decode_oracle.c", "rcmatch_oracle.c", "oracle.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, "oracle"])
         L = C.CDLL(so)
@@ -238,6 +238,43 @@ def decode_contig(ref, params, streams, lock=NO_LOCK, cap=None):
     if r < 0:
         raise ValueError("orc_decode_contig: malformed streams (consumed into %d output bytes)" % n.value)
     return out[: n.value], int(r)
+
+
+class OrcExtRead(C.Structure):
+    _fields_ = [("refPos", C.c_int64), ("litPos", C.c_uint64)]
+
+
+class OrcDecodeInfo(C.Structure):
+    _fields_ = [("cur", C.c_uint64 * 6), ("maxRingWalk", C.c_uint64), ("trace", C.POINTER(OrcExtRead)),
+                ("traceCap", C.c_uint64), ("nTrace", C.c_uint64)]
+
+
+def decode_contig_bounded(ref, ref_bytes, params, streams, lock=NO_LOCK, cap=1 << 18, trace=0):
+    """orc_decode_contig_bounded (oracle/decode_oracle.c): the decoder's automaton with the reference buffer's size known, for
+    stream sets no encoder wrote. `streams`: the six streams in STREAM_NAMES order (bytes). `ref`: a uint8 array of at least
+    ref_bytes bytes. Never raises on a malformed set: -> dict(unmatched (-1: malformed), dest (the bytes written, uint8 array),
+    cur (the six cursors reached), walk (longest pairing-ring walk), trace ((refPos, litPos or NO_LOCK) per extension read, when
+    trace > 0 entries were asked for))."""
+    assert isinstance(ref, np.ndarray) and ref.dtype == np.uint8 and ref.size >= ref_bytes
+    keep = [C.create_string_buffer(bytes(s), len(s)) if len(s) else None for s in streams]      # (exactly as long as declared)
+    ptrs = (C.c_void_p * 6)(*[C.addressof(k) if k is not None else None for k in keep])
+    sizes = (C.c_uint64 * 6)(*[len(s) for s in streams])
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_uint64(0)
+    info = OrcDecodeInfo()
+    tr = (OrcExtRead * trace)() if trace else None
+    if trace:
+        info.trace, info.traceCap = C.cast(tr, C.POINTER(OrcExtRead)), trace
+    f = lib().orc_decode_contig_bounded
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    r = f(ref.ctypes.data_as(C.c_void_p), ref_bytes, C.byref(params), ptrs, sizes, lock, out.ctypes.data_as(C.c_void_p), cap,
+          C.byref(n), C.byref(info))
+    res = dict(unmatched=int(r), dest=out[: n.value].copy(), cur=[int(x) for x in info.cur], walk=int(info.maxRingWalk))
+    if trace:
+        assert info.nTrace <= trace, "decode_contig_bounded: %d extension reads, room for %d" % (info.nTrace, trace)
+        res["trace"] = [(tr[i].refPos, tr[i].litPos) for i in range(info.nTrace)]
+    return res
 
 
 def fingerprint(matches):
