@@ -10,7 +10,8 @@
 //   fill    every output position is resolved on its own: binary search of d[] for the match or literal run it lies in; inside
 //           a match it is mirrored into the source (one hop, strictly lower position) and searched again; a literal is read from
 //           the cut stream. complementsLUT is applied as it would be after that many hops (lut . lut . lut == lut).
-// Included by copmem.hip (uses cm::Buf, cm::fail, CCHK).
+// Included by copmem.hip (uses cm::Buf, cm::fail, CCHK). What one item or lane does is copmem_restore_lane.h, plain C++ that
+// tests/rcrestore_emu.cpp runs on the CPU; here are the kernels around it — staging, tile loops, scan, atomics — and the host's calls.
 #pragma once
 
 #include <rocprim/block/block_scan.hpp>
@@ -21,26 +22,7 @@ namespace cmr {
 using cm::Buf;
 using cm::fail;
 
-constexpr uint8_t MARK = (uint8_t) ('$' + 128);      // MBGC_Params::RC_MATCH_MARK, MBGC_Params.h:48
-constexpr int LANE = 16;                             // output bytes per lane
-constexpr int TPB = 256;
-constexpr uint64_t TILE = (uint64_t) TPB * LANE;     // output (or input) bytes per workgroup step
-constexpr uint64_t SAT = ~0ull, CAP = 1ull << 62;    // sums beyond CAP saturate: an overflow is seen, never wrapped
-constexpr int MAX_VARINT = 10;                       // bytes of a 64-bit value
-enum { E_VARINT_LONG = 1, E_SOURCE = 2 };
-
-struct SatAdd {
-    __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return (a > CAP || b > CAP || a + b > CAP) ? SAT : a + b; }
-};
-struct EndsValue {
-    __host__ __device__ uint64_t operator()(uint8_t b) const { return b < 128 ? 1u : 0u; }
-};
-
-struct Plan {                                        // what the fill reads
-    const uint8_t *cut;                              // n bytes (+ 64 zero bytes)
-    const uint64_t *d, *src, *len, *cum;             // per match; cum has M + 1 entries
-    uint64_t M, n, orgLen;
-};
+#include "copmem_restore_lane.h"                     // constants, Plan, and what one item or lane does: plain C++
 
 struct State {
     Buf<uint8_t> dCut, dMapOff, dMapLen, dLut, dTmp, dOut;
@@ -114,25 +96,17 @@ __global__ void __launch_bounds__(TPB) k_varint_decode(const uint8_t *__restrict
                                                        uint64_t *__restrict__ val, uint64_t nval, uint64_t *__restrict__ res) {
     const uint64_t stride = (uint64_t) gridDim.x * TPB;
     for (uint64_t j = (uint64_t) blockIdx.x * TPB + threadIdx.x; j < nbytes; j += stride) {
-        if (j && bytes[j - 1] >= 128) continue;
-        uint64_t v = 0;
-        bool tooLong = true;
-        for (int k = 0; k < MAX_VARINT && j + k < nbytes; k++) {
-            const uint8_t b = bytes[j + k];
-            const uint64_t digit = b & 127u;
-            if (k == MAX_VARINT - 1) { if (digit) v = SAT; }               // 128^9 = 2^63: beyond CAP
-            else if (v != SAT) v |= digit << (7 * k);
-            if (b < 128) { tooLong = false; break; }
-        }
+        if (!value_starts_at(bytes, j)) continue;
+        bool tooLong;
+        const uint64_t v = value_at(bytes, nbytes, j, tooLong);
         if (tooLong) atomicOr((unsigned long long *) &res[0], (unsigned long long) E_VARINT_LONG);
-        if (v > CAP) v = SAT;
         const uint64_t at = valIdx[j];
         if (at < nval) val[at] = v;
     }
 }
 __global__ void __launch_bounds__(TPB) k_lengths(const uint64_t *__restrict__ val, uint64_t M, uint64_t *__restrict__ len) {
     const uint64_t stride = (uint64_t) gridDim.x * TPB;
-    for (uint64_t i = (uint64_t) blockIdx.x * TPB + threadIdx.x; i <= M; i += stride) len[i] = i < M ? SatAdd()(val[i + 1], val[0]) : 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * TPB + threadIdx.x; i <= M; i += stride) len[i] = length_of(val, M, i);
 }
 // d[i], src[i], and the check that makes the fill's walk end inside the text: src[i] + len[i] <= d[i]
 __global__ void __launch_bounds__(TPB) k_check(const uint64_t *__restrict__ markPos, const uint8_t *__restrict__ mapOff, int offBytes,
@@ -140,54 +114,16 @@ __global__ void __launch_bounds__(TPB) k_check(const uint64_t *__restrict__ mark
                                                uint64_t *__restrict__ d, uint64_t *__restrict__ src, uint64_t *__restrict__ res) {
     const uint64_t stride = (uint64_t) gridDim.x * TPB;
     for (uint64_t i = (uint64_t) blockIdx.x * TPB + threadIdx.x; i < M; i += stride) {
-        const uint64_t L = len[i], c = cum[i];
-        uint64_t di = 0, s = 0;
-        if (L != SAT && c != SAT) {                                        // (a saturated sum is reported from cum[M])
-            di = markPos[i] - i + c;
-            s = offBytes == 4 ? (uint64_t) cm::ld32(mapOff + 4 * i) : cm::ld64(mapOff + 8 * i);
-            if (s > di || L > di - s) {
-                atomicOr((unsigned long long *) &res[0], (unsigned long long) E_SOURCE);
-                atomicMin((unsigned long long *) &res[1], (unsigned long long) i);
-            }
+        uint64_t di, s;
+        if (!match_in_bounds(markPos, mapOff, offBytes, len, cum, i, di, s)) {
+            atomicOr((unsigned long long *) &res[0], (unsigned long long) E_SOURCE);
+            atomicMin((unsigned long long *) &res[1], (unsigned long long) i);
         }
         d[i] = di; src[i] = s;
     }
 }
 
 // ---- fill ----------------------------------------------------------------------------------------------------------------
-// the number k in [lo, hi] with d[j] <= p for every j < k and d[j] > p for every j >= k (true of lo and hi on entry)
-__device__ __forceinline__ uint64_t matches_at_or_before(const uint64_t *__restrict__ d, uint64_t lo, uint64_t hi, uint64_t p) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (d[mid] <= p) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint8_t complemented(const uint8_t *sl, uint8_t x, uint32_t hops) {
-    if (hops == 0) return x;
-    x = sl[x];
-    return (hops & 1) ? x : sl[x];
-}
-// restored position p, k = matches_at_or_before(p) -> its byte; every hop lands below the match it leaves (the plan's check)
-__device__ __forceinline__ uint8_t restored_byte(const Plan &P, const uint8_t *sl, uint64_t p, uint64_t k, uint32_t &maxHops) {
-    uint32_t hops = 0;
-    while (k) {
-        const uint64_t i = k - 1, di = P.d[i], L = P.len[i];
-        if (p - di >= L) break;
-        p = P.src[i] + L - 1 - (p - di);
-        hops++;
-        k = matches_at_or_before(P.d, 0, i, p);
-    }
-    if (hops > maxHops) maxHops = hops;
-    return complemented(sl, P.cut[p - P.cum[k] + k], hops);
-}
-// [p, p + 16) lies in one literal run: where it starts in the cut stream, else SAT
-__device__ __forceinline__ uint64_t literal_run_of_16(const Plan &P, uint64_t p, uint64_t k) {
-    if (k && p - P.d[k - 1] < P.len[k - 1]) return SAT;
-    const uint64_t runEnd = k < P.M ? P.d[k] : P.orgLen;
-    return p + LANE <= runEnd ? p - P.cum[k] + k : SAT;
-}
-
 __global__ void __launch_bounds__(TPB) k_restore_fill(Plan P, uint8_t *__restrict__ dst, const uint8_t *__restrict__ lut, uint32_t *__restrict__ deepest) {
     __shared__ uint8_t sl[256];
     __shared__ uint64_t sLo, sHi;
@@ -197,63 +133,14 @@ __global__ void __launch_bounds__(TPB) k_restore_fill(Plan P, uint8_t *__restric
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         __syncthreads();
         if (threadIdx.x == 0) {                                            // the matches that start inside the tile: [sLo, sHi)
-            const uint64_t last = tile * TILE + TILE < P.orgLen ? tile * TILE + TILE - 1 : P.orgLen - 1;
-            sLo = matches_at_or_before(P.d, 0, P.M, tile * TILE);
-            sHi = matches_at_or_before(P.d, sLo, P.M, last);
+            uint64_t lo, hi;
+            matches_of_tile(P, tile, lo, hi);
+            sLo = lo; sHi = hi;
         }
         __syncthreads();
         const uint64_t p0 = tile * TILE + (uint64_t) threadIdx.x * LANE;
         if (p0 >= P.orgLen) continue;
-        uint64_t k = matches_at_or_before(P.d, sLo, sHi, p0);
-        const bool whole = p0 + LANE <= P.orgLen;
-#ifndef MBGC_RC_RESTORE_BYTEWISE                                          /* (defined for the measurement of what the vector path buys) */
-        if (whole) {
-            uint64_t at = literal_run_of_16(P, p0, k);
-            if (at != SAT) {                                               // 16 literals
-                uint4 v;
-                __builtin_memcpy(&v, P.cut + at, 16);
-                __builtin_memcpy(dst + p0, &v, 16);
-                continue;
-            }
-            const uint64_t i = k - 1;                                      // (k != 0: p0 is inside match i, or the run ends within 16 bytes)
-            if (k && p0 - P.d[i] < P.len[i] && p0 + LANE <= P.d[i] + P.len[i]) {
-                const uint64_t s0 = P.src[i] + P.len[i] - 1 - (p0 + LANE - 1 - P.d[i]);   // the source of the lane's last byte
-                at = literal_run_of_16(P, s0, matches_at_or_before(P.d, 0, i, s0));
-                if (at != SAT) {                                           // 16 bytes of one match over 16 literals
-                    uint4 v;
-                    __builtin_memcpy(&v, P.cut + at, 16);
-                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                    uint32_t o[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int b = 0; b < LANE; b++) {
-                        const int f = LANE - 1 - b;
-                        o[b >> 2] |= (uint32_t) sl[(w[f >> 2] >> (8 * (f & 3))) & 0xFFu] << (8 * (b & 3));
-                    }
-                    v = make_uint4(o[0], o[1], o[2], o[3]);
-                    __builtin_memcpy(dst + p0, &v, 16);
-                    if (maxHops < 1) maxHops = 1;
-                    continue;
-                }
-            }
-        }
-#endif
-        uint32_t o[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int b = 0; b < LANE; b++) {
-            const uint64_t p = p0 + b;
-            if (p < P.orgLen) {
-                while (k < sHi && P.d[k] <= p) k++;
-                o[b >> 2] |= (uint32_t) restored_byte(P, sl, p, k, maxHops) << (8 * (b & 3));
-            }
-        }
-        if (whole) {
-            const uint4 v = make_uint4(o[0], o[1], o[2], o[3]);
-            __builtin_memcpy(dst + p0, &v, 16);
-        } else {
-#pragma unroll
-            for (int b = 0; b < LANE; b++)
-                if (p0 + b < P.orgLen) dst[p0 + b] = (uint8_t) (o[b >> 2] >> (8 * (b & 3)));
-        }
+        restore_lane(P, sl, dst, p0, sLo, sHi, maxHops);
     }
     if (maxHops) atomicMax(deepest, maxHops);
 }
@@ -275,14 +162,14 @@ static int plan(State &S, hipStream_t st, const uint8_t *seq, uint64_t n, const 
     if (!S.ev0) { CCHK(hipEventCreate(&S.ev0)); CCHK(hipEventCreate(&S.ev1)); }
     int r;
     const uint64_t ntiles = (n + TILE - 1) / TILE;
-    if ((r = S.dCut.reserve(ntiles * TILE + 64)) || (r = S.dMapOff.reserve(mapOffLen + 8)) || (r = S.dMapLen.reserve(mapLenLen + 8)) || (r = S.dLut.reserve(256)) ||
+    if ((r = S.dCut.reserve(ntiles * TILE + CUT_PAD)) || (r = S.dMapOff.reserve(mapOffLen + 8)) || (r = S.dMapLen.reserve(mapLenLen + 8)) || (r = S.dLut.reserve(256)) ||
         (r = S.dCounts.reserve(ntiles + 1)) || (r = S.dTileOff.reserve(ntiles + 1)) || (r = S.dValIdx.reserve(mapLenLen + 1)) || (r = S.dRes.reserve(4)))
         return r;
     uint8_t lut[256];
     cm::complements_lut(lut);
     CCHK(hipMemcpyAsync(S.dLut.p, lut, 256, hipMemcpyHostToDevice, st));
     if (n) CCHK(hipMemcpyAsync(S.dCut.p, seq, n, hipMemcpyHostToDevice, st));
-    CCHK(hipMemsetAsync(S.dCut.p + n, 0, ntiles * TILE + 64 - n, st));
+    CCHK(hipMemsetAsync(S.dCut.p + n, 0, ntiles * TILE + CUT_PAD - n, st));
     if (mapOffLen) CCHK(hipMemcpyAsync(S.dMapOff.p, mapOff, mapOffLen, hipMemcpyHostToDevice, st));
     if (mapLenLen) CCHK(hipMemcpyAsync(S.dMapLen.p, mapLen, mapLenLen, hipMemcpyHostToDevice, st));
     const uint64_t res0[4] = {0, SAT, 0, 0};                               // error bits, first match with a bad source

@@ -93,3 +93,82 @@ def inputs():
             s[(s == MARK) | (s == 127)] = ord("A")
             out[name] = s
     return out
+
+
+CAP = 1 << 62                                            # sums beyond it are refused (mbgc_amd/csrc/copmem_restore_lane.h)
+MAX_VARINT = 10
+
+
+def values_of(map_len):
+    """every value of rcMapLen with the number of bytes it takes -> [(value, bytes)], or None if the last value does not end"""
+    vals, at = [], 0
+    while at < len(map_len):
+        v, k = 0, 0
+        while True:
+            if at + k >= len(map_len):
+                return None
+            y = map_len[at + k]
+            v += (y % 128) << (7 * k)
+            k += 1
+            if y < 128:
+                break
+        vals.append((v, k))
+        at += k
+    return vals
+
+
+def restore_bounded(cut, map_off, map_len, off_bytes):
+    """The referee of the device's inverse pass: restore() with exactly the refusals include/mbgc_copmem.h documents for the plan
+    -> (bytes, M, bytes restored from matches, deepest chain, minMatchLength), or a string that names the refusal (those of a
+    source bound begin with "source"). off_bytes is 4 or 8, the width the caller states. The deepest chain is the most matches any
+    byte was copied through: a literal has depth 0, a byte of a match one more than the byte it was copied from."""
+    assert off_bytes in (4, 8)
+    cut = np.frombuffer(bytes(cut), dtype=np.uint8)
+    marks = np.flatnonzero(cut == MARK)
+    m = len(marks)
+    if m == 0 and len(map_off):
+        return "rcMapOff: %d bytes, and no mark" % len(map_off)
+    if m and len(map_off) not in (4 * m, 8 * m):
+        return "rcMapOff: %d bytes for %d marks" % (len(map_off), m)
+    if m and len(map_off) != off_bytes * m:
+        return "rcMapOff: %d bytes for %d marks of %d bytes each" % (len(map_off), m, off_bytes)
+    min_len, deltas = 0, []
+    if not map_len:
+        if m:
+            return "rcMapLen: empty, and %d marks" % m
+    else:
+        vals = values_of(map_len)
+        if vals is None:
+            return "rcMapLen: the last value does not end"
+        if len(vals) != m + 1:
+            return "rcMapLen: %d values for %d marks" % (len(vals), m)
+        if any(k > MAX_VARINT for _, k in vals):
+            return "rcMapLen: a value of more than %d bytes" % MAX_VARINT
+        min_len, deltas = vals[0][0], [v for v, _ in vals[1:]]
+        if min_len > 0xFFFFFFFF:
+            return "rcMapLen: a minimal length beyond 32 bits"
+    lens = [v + min_len for v in deltas]
+    total = sum(lens)
+    if total > CAP:
+        return "rcMapLen: the lengths add up beyond 2^62"
+    srcs = [int.from_bytes(map_off[off_bytes * i:off_bytes * (i + 1)], "little") for i in range(m)]
+    cum = 0
+    for i in range(m):
+        d = int(marks[i]) - i + cum
+        if srcs[i] + lens[i] > d:
+            return "source: match %d at %d copies [%d, %d)" % (i, d, srcs[i], srcs[i] + lens[i])
+        cum += lens[i]
+    out = np.empty(len(cut) - m + total, dtype=np.uint8)
+    dep = np.zeros(len(out), dtype=np.uint32)
+    at = prev = 0
+    for i in range(m):
+        k = int(marks[i]) - prev
+        out[at:at + k] = cut[prev:prev + k]
+        at += k
+        prev = int(marks[i]) + 1
+        s, ln = srcs[i], lens[i]
+        out[at:at + ln] = LUT[out[s:s + ln]][::-1]
+        dep[at:at + ln] = dep[s:s + ln][::-1] + 1
+        at += ln
+    out[at:] = cut[prev:]
+    return out.tobytes(), m, total, int(dep.max()) if len(dep) else 0, min_len

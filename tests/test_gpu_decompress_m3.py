@@ -1,6 +1,7 @@
 """`mbgc-hip c -m 3`, then `mbgc-hip d --restore-rc` in a fresh process: the reverse-complement pass over the literals is inverted on
 the device and the collection comes back — the same bytes from default `d`, `--serial` and `--no-index`, the FASTA files with
-`--fasta`; on streams without the pass the switch changes nothing; damaged maps end with a message and exit 1."""
+`--fasta`; on streams without the pass the switch changes nothing; damaged maps end with a message and exit 1, and so do three
+mutants of a run's own maps that the referee of tests/_rcrestore.py refuses, while three it accepts give the collection back."""
 import json
 import lzma
 import os
@@ -9,6 +10,8 @@ import numpy as np
 import pytest
 
 import _rcdata
+import _rcmut
+import _rcrestore
 from mbgc_amd import synth
 from test_gpu_decompress import LIST, OUTS, check_outputs, copy_run, cut, expected, tool, write_collection
 from test_gpu_decompress_fasta import files_of
@@ -151,3 +154,57 @@ def test_bench_line(m3_run):
     line = json.loads(next(l for l in out.splitlines() if l.startswith("{")))
     assert line["rc_restore_ms"] > 0 and line["rc_marks"] == read(tmp, "out.literals").count(MARK) and line["rc_max_chain"] >= 1
     assert line["value"] > 0
+
+
+@pytest.fixture(scope="module")
+def m3_t1_run(tmp_path_factory):
+    tmp = str(tmp_path_factory.mktemp("m3t1"))
+    paths = write_m3_collection(tmp)
+    tool(["c", "-m", "3", "-t1", "list.txt", "out"], tmp)
+    the_pass_cut_something(tmp)
+    return tmp, paths
+
+
+def own_map_mutants(tmp):
+    """mutants of the run's own rcMapOff / rcMapLen (other literals would invalidate the streams that count them), labelled by the
+    referee -> ({name: (rcMapOff, rcMapLen)} accepted: the same restored literals from other bytes; {name: (rcMapOff, rcMapLen,
+    the plan's words)} refused)"""
+    cut, off, ln = read(tmp, "out.literals"), read(tmp, "out.rcMapOff"), read(tmp, "out.rcMapLen")
+    want = _rcrestore.restore_bounded(cut, off, ln, 4)
+    vals = _rcrestore.values_of(ln)
+    min_len, deltas = vals[0][0], [v for v, _ in vals[1:]]
+    put = _rcrestore.put_byte_frugal
+    assert not isinstance(want, str) and want[1] == len(deltas) >= 1 and min_len >= 1
+    d0 = cut.index(MARK)                                                         # where match 0 starts, in restored coordinates
+    accepted = {
+        "every value in 3 bytes": (off, b"".join(_rcmut.padded(v, 3) for v, _ in vals)),
+        "a minimal length of 1 less under differences of 1 more": (off, put(min_len - 1) + b"".join(put(v + 1) for v in deltas)),
+        "the minimal length in 10 bytes": (off, _rcmut.padded(min_len, 10) + ln[vals[0][1]:]),
+    }
+    refused = {
+        "a source one byte into its match": ((d0 - (min_len + deltas[0]) + 1).to_bytes(4, "little") + off[4:], ln, "the source of match 0 does not end before the match starts"),
+        "a length of 2^63": (off, put(min_len) + put(2 ** 63) + ln[vals[0][1] + vals[1][1]:], "the lengths add up beyond 64 bits"),
+        "one value too few": (off, ln[:-vals[-1][1]], "%d values for the minimal length and %d marks" % (len(deltas), len(deltas))),
+    }
+    for name, (o, l) in accepted.items():
+        assert (o, l) != (off, ln) and _rcrestore.restore_bounded(cut, o, l, 4)[:4] == want[:4], name   # (all but the minimal length)
+    for name, (o, l, _) in refused.items():
+        assert isinstance(_rcrestore.restore_bounded(cut, o, l, 4), str), name
+    return accepted, refused
+
+
+def test_mutants_of_the_runs_own_maps(m3_t1_run, tmp_path):
+    src, paths = m3_t1_run
+    accepted, refused_ones = own_map_mutants(src)
+    for k, (name, (off, ln)) in enumerate(sorted(accepted.items())):
+        tmp = str(tmp_path / ("a%d" % k))
+        os.mkdir(tmp)
+        copy_run(src, tmp, lambda f, d: off if f == "rcMapOff" else ln if f == "rcMapLen" else d)
+        tool(["d", "--restore-rc", "out", "back"], tmp)
+        check_outputs(tmp, "back", expected(paths, False))
+    for k, (name, (off, ln, words)) in enumerate(sorted(refused_ones.items())):
+        tmp = str(tmp_path / ("r%d" % k))
+        os.mkdir(tmp)
+        copy_run(src, tmp, lambda f, d: off if f == "rcMapOff" else ln if f == "rcMapLen" else d)
+        err = refused(tmp)
+        assert "malformed" in err and words in err, (name, err)
