@@ -185,6 +185,30 @@ typedef struct { int32_t status; uint32_t members; uint64_t outLen, inUsed; } mb
 int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBytes, uint8_t *out_dev, uint64_t outBytes,
                            const mbgc_fasta_inflate_job_t *jobs, uint64_t njobs, mbgc_fasta_inflate_result_t *results, double *kernelMs);
 
+/* The way back, compressed (`mbgc-hip d --fasta dir --gzip`; the reference's `mbgc d -c`, MBGC_Decoder.cpp:185-203): text that lies
+ * in HBM becomes gzip files there. Job k compresses text_dev[inOff, inOff + inLen) (any alignment; inside the buffer of textBytes
+ * bytes) into one gzip member: the header 1f 8b 08 00 00 00 00 00 00 ff (no name, no time: the bytes are a function of the text
+ * alone), DEFLATE, CRC-32 and ISIZE. The text is cut into chunks of MBGC_DEFLATE_CHUNK bytes, max(1, ceil(inLen / CHUNK)) per job,
+ * one wave each: no back-reference crosses a chunk's start, a chunk is one dynamic block (matches of 8 bytes and more, exact
+ * histograms, length-limited Huffman codes, always complete code sets) or, where that is not smaller, one stored block, and ends on a
+ * byte boundary (an empty stored block; the last chunk sets BFINAL) — any inflater reads the result. The files land back to back in
+ * gz_dev in job order; results[k] (host, njobs entries) says where: outOff, outLen, the text's CRC-32, its chunks and how many of
+ * them went out stored. *gzBytes = the total, never more than the sum of mbgc_fasta_deflate_bound(inLen). When the total exceeds
+ * gzCap nothing is written to gz_dev and the call returns -104 with the size needed in *gzBytes; no byte outside gz_dev[0, *gzBytes)
+ * is ever written. A job that lies outside the text is refused before anything is launched (-103, message in
+ * mbgc_fasta_last_error; results untouched). The same text gives the same bytes, on every run and whatever other jobs share the
+ * call. kernelMs (may be NULL): both kernels' time (the chunks, then the pack) from events on the stream. Runs on the input stage's
+ * stream; synchronous. */
+#define MBGC_DEFLATE_CHUNK 32768
+#define MBGC_DEFLATE_OK 0
+typedef struct { uint64_t inOff, inLen; } mbgc_fasta_deflate_job_t;
+typedef struct { uint64_t outOff, outLen; uint32_t crc32, chunks, storedChunks, reserved; } mbgc_fasta_deflate_result_t;
+uint64_t mbgc_fasta_deflate_bound(uint64_t inLen);   /* 18 + max(1, ceil(inLen / CHUNK)) * 10 + inLen */
+int mbgc_fasta_deflate_dev(mbgc_fasta_t *p, const uint8_t *text_dev, uint64_t textBytes,
+                           const mbgc_fasta_deflate_job_t *jobs, uint64_t njobs,
+                           uint8_t *gz_dev, uint64_t gzCap, mbgc_fasta_deflate_result_t *results,
+                           uint64_t *gzBytes, double *kernelMs);
+
 /* A download that runs beside the kernels of the input stage's stream (the decoder's text batches: batch b travels while batch b + 1
  * is formatted): begin queues the copy on a stream of its own and returns; wait returns when it has arrived, with the copy's time
  * from events on that stream in *copyMs (may be NULL). One download at a time: begin before the last one's wait is refused (-103).

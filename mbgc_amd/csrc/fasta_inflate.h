@@ -25,13 +25,14 @@
 // A job is ONE wave (a block of INF_WAVE threads). What one lane writes to LDS and another reads is separated by INF_SYNC() wherever
 // lanes work side by side; the single values the first lane writes between two such sections (a literal's byte, a code length) and
 // the whole wave reads back lean on that: a wave's LDS operations are carried out in the order it issues them.
+#include "fasta_gzip_common.h"
+
 constexpr uint32_t INF_WAVE = 64;
 constexpr uint32_t INF_RING = 32768, INF_RMASK = INF_RING - 1;
 constexpr uint32_t INF_INBUF = 4096;                 // the input window (a multiple of INF_WAVE * 16)
 constexpr uint32_t INF_DRAIN = 16384;                // the ring is drained when this much of it is neither flushed nor summed
 constexpr uint32_t INF_CL = 256;                     // bytes per lane and CRC step; INF_WAVE * INF_CL == INF_DRAIN
 constexpr uint32_t INF_LFAST = 10, INF_DFAST = 8, INF_CFAST = 7;
-constexpr uint32_t INF_POLY = 0xEDB88320u;
 constexpr int INF_OK = 0, INF_ESHORT = 1, INF_EDATA = 2, INF_ECHECK = 3;   // MBGC_INFLATE_*
 // (after a drain less than INF_DRAIN bytes are pending, and one step adds at most INF_INBUF: nothing pending is overwritten)
 static_assert(INF_WAVE * INF_CL == INF_DRAIN && INF_INBUF % (INF_WAVE * 16) == 0 && INF_DRAIN + INF_INBUF + 258 <= INF_RING, "ring arithmetic");
@@ -56,30 +57,6 @@ struct InfShared {
 };
 
 INF_CONST const uint8_t INF_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-__device__ __forceinline__ uint32_t inf_mulmod(uint32_t a, uint32_t b) {          // a * b mod P, bit-reflected (zlib's multmodp)
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        if (a & m) p ^= b;
-        b = b & 1u ? (b >> 1) ^ INF_POLY : b >> 1;
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t inf_xpow8(uint32_t nbytes) {                  // x^(8 * nbytes) mod P
-    uint32_t p = 0x80000000u, sq = 0x00800000u;
-    for (; nbytes; nbytes >>= 1) {
-        if (nbytes & 1u) p = inf_mulmod(sq, p);
-        sq = inf_mulmod(sq, sq);
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t inf_bitrev(uint32_t v, uint32_t bits) {       // the low `bits` bits of v, reversed (1 <= bits <= 15)
-    v = (v & 0x5555u) << 1 | (v >> 1 & 0x5555u);
-    v = (v & 0x3333u) << 2 | (v >> 2 & 0x3333u);
-    v = (v & 0x0f0fu) << 4 | (v >> 4 & 0x0f0fu);
-    v = (v & 0x00ffu) << 8 | (v >> 8 & 0x00ffu);
-    return v >> (16 - bits);
-}
 
 struct Inf {
     InfShared &S;

@@ -668,6 +668,45 @@ __global__ void __launch_bounds__(INF_WAVE) k_fa_inflate(const uint8_t *gz, uint
     if (threadIdx.x == 0) results[j] = r;
 }
 
+#define DEF_ATOMIC_ADD(p, v) atomicAdd(p, v)
+#define DEF_ATOMIC_OR(p, v) atomicOr(p, v)
+#define DEF_ATOMIC_MAX(p, v) atomicMax(p, v)
+// arr[0, 64) in LDS -> its exclusive prefix sums; the total (the callers put a barrier on either side)
+__device__ __forceinline__ uint32_t def_wave_exscan(uint32_t *arr) {
+    const uint32_t lane = threadIdx.x, v = arr[lane];
+    uint32_t x = v;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t) __shfl_up((int) x, d);
+        if (lane >= d) x += y;
+    }
+    arr[lane] = x - v;
+    return (uint32_t) __shfl((int) x, 63);
+}
+#define DEF_EXSCAN(arr) def_wave_exscan(arr)
+#include "fasta_deflate.h"
+
+// mbgc_fasta_deflate_dev: one chunk of DEF_CHUNK text bytes per block of one wave (the encoder: fasta_deflate.h) into its slot of the
+// handle's staging buffer, then one block per chunk from the slot to its place between its job's gzip header and trailer
+__global__ void __launch_bounds__(DEF_WAVE) k_fa_deflate(const uint8_t *__restrict__ text, const DefChunk *__restrict__ chunks, uint32_t chunk0, uint32_t nchunks,
+                                                         uint8_t *__restrict__ slots, DefChunkOut *__restrict__ outs) {
+    __shared__ DefShared S;
+    const uint32_t c = chunk0 + blockIdx.x;
+    if (c >= nchunks) return;
+    const DefChunk ch = chunks[c];
+    Def D(S, text + ch.inOff, ch.n, ch.last != 0, slots + (uint64_t) c * DEF_SLOT);
+    const DefChunkOut r = D.run();
+    if (threadIdx.x == 0) outs[c] = r;
+}
+
+__global__ void __launch_bounds__(DEF_WAVE) k_fa_deflate_pack(const uint8_t *__restrict__ slots, const DefChunkOut *__restrict__ outs, const DefPackIn *__restrict__ pk,
+                                                              const DefJobIn *__restrict__ jobs, uint32_t chunk0, uint32_t nchunks, uint8_t *__restrict__ gz,
+                                                              uint32_t *__restrict__ jobCrc) {
+    __shared__ uint32_t red[DEF_WAVE];
+    const uint32_t c = chunk0 + blockIdx.x;
+    if (c >= nchunks) return;
+    def_pack_chunk(red, slots, outs, pk, jobs, c, gz, jobCrc);
+}
+
 // mbgc_fasta_compare_dev: a wave's steps, then — only when a lane found a difference — one 64-bit atomicMin per piece the wave
 // touches, from the lowest differing lane of that piece (its offset is the smallest: the steps of a piece ascend with the lanes).
 // Equal data issues no atomic.
@@ -814,6 +853,12 @@ struct mbgc_fasta {
     fa::Buf<unsigned long long> dCmpOut;
     fa::Buf<fa::InfJob> dInfJobs;               // mbgc_fasta_inflate_dev: the jobs and their results
     fa::Buf<fa::InfResult> dInfResults;
+    fa::Buf<fa::DefChunk> dDefChunks;           // mbgc_fasta_deflate_dev: the chunk table, the chunks' slots and what they hold, the pack tables
+    fa::Buf<uint8_t> dDefSlots;
+    fa::Buf<fa::DefChunkOut> dDefOuts;
+    fa::Buf<fa::DefPackIn> dDefPack;
+    fa::Buf<fa::DefJobIn> dDefJobs;
+    fa::Buf<uint32_t> dDefCrc;
     hipStream_t copyStream = nullptr;           // mbgc_fasta_download_begin / _wait: a download beside the kernels of `stream`
     hipEvent_t copyEv[2] = {nullptr, nullptr};
     bool copyPending = false;
@@ -851,6 +896,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
     p->dInfJobs.release(); p->dInfResults.release();
+    p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
@@ -1190,6 +1236,89 @@ int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBy
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
     memcpy(results, got.data(), njobs * sizeof(InfResult));
+    return 0;
+}
+
+uint64_t mbgc_fasta_deflate_bound(uint64_t inLen) {
+    return 18 + std::max<uint64_t>(1, (inLen + MBGC_DEFLATE_CHUNK - 1) / MBGC_DEFLATE_CHUNK) * 10 + inLen;
+}
+
+int mbgc_fasta_deflate_dev(mbgc_fasta_t *p, const uint8_t *text_dev, uint64_t textBytes, const mbgc_fasta_deflate_job_t *jobs, uint64_t njobs,
+                           uint8_t *gz_dev, uint64_t gzCap, mbgc_fasta_deflate_result_t *results, uint64_t *gzBytes, double *kernelMs) {
+    using namespace fa;
+    static_assert(DEF_CHUNK == MBGC_DEFLATE_CHUNK, "the chunk of the ABI");
+    if (kernelMs) *kernelMs = 0;
+    if (gzBytes) *gzBytes = 0;
+    uint64_t nc64 = 0;
+    for (uint64_t k = 0; k < njobs; k++) {
+        const mbgc_fasta_deflate_job_t &x = jobs[k];
+        if (x.inOff > textBytes || x.inLen > textBytes - x.inOff) return fail(-103, "deflate: job %llu lies outside the text", (unsigned long long) k);
+        nc64 += std::max<uint64_t>(1, (x.inLen + DEF_CHUNK - 1) / DEF_CHUNK);
+    }
+    if (njobs >= 0xffffffffull || nc64 >= 0xffffffffull) return fail(-103, "deflate: %llu jobs, %llu chunks in one call", (unsigned long long) njobs, (unsigned long long) nc64);
+    if (njobs == 0) return 0;
+    const uint32_t nc = (uint32_t) nc64;
+    std::vector<DefChunk> chunks(nc);
+    std::vector<DefJobIn> jtab(njobs);
+    std::vector<DefPackIn> pack(nc);
+    for (uint64_t k = 0, c = 0; k < njobs; k++) {
+        const uint32_t m = (uint32_t) std::max<uint64_t>(1, (jobs[k].inLen + DEF_CHUNK - 1) / DEF_CHUNK);
+        jtab[k] = {jobs[k].inLen, (uint32_t) c, m};
+        for (uint32_t i = 0; i < m; i++, c++) {
+            const uint64_t at = (uint64_t) i * DEF_CHUNK;
+            chunks[c] = {jobs[k].inOff + at, (uint32_t) std::min<uint64_t>(DEF_CHUNK, jobs[k].inLen - at), i + 1 == m ? 1u : 0u};
+            pack[c] = {0, (uint32_t) k, (i == 0 ? 1u : 0u) | (i + 1 == m ? 2u : 0u)};
+        }
+    }
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dDefChunks.reserve(nc)) || (rc = p->dDefSlots.reserve((size_t) nc * DEF_SLOT)) || (rc = p->dDefOuts.reserve(nc)) || (rc = p->dDefPack.reserve(nc)) ||
+        (rc = p->dDefJobs.reserve(njobs)) || (rc = p->dDefCrc.reserve(njobs)))
+        return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dDefChunks.p, chunks.data(), nc * sizeof(DefChunk), hipMemcpyHostToDevice, p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint32_t c0 = 0; c0 < nc; c0 += FMT_SLICE)
+        k_fa_deflate<<<dim3(std::min(FMT_SLICE, nc - c0)), dim3(DEF_WAVE), 0, p->stream>>>(text_dev, p->dDefChunks.p, c0, nc, p->dDefSlots.p, p->dDefOuts.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    // the chunks' sizes come back (8 bytes per chunk with their CRCs); the scan that places them runs here
+    std::vector<DefChunkOut> outs(nc);
+    FCHK(hipMemcpyAsync(outs.data(), p->dDefOuts.p, nc * sizeof(DefChunkOut), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    double ms = 0;
+    if (kernelMs) { float t = 0; FCHK(hipEventElapsedTime(&t, p->fmtEv[0], p->fmtEv[1])); ms = t; }
+    std::vector<mbgc_fasta_deflate_result_t> res(njobs);
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < njobs; k++) {
+        res[k] = {at, 0, 0, jtab[k].nchunks, 0, 0};
+        at += 10;
+        for (uint32_t c = jtab[k].chunk0; c < jtab[k].chunk0 + jtab[k].nchunks; c++) {
+            const uint32_t bytes = outs[c].bytes & ~DEF_STORED;
+            if (bytes > DEF_CHUNK + 10) return fail(-100, "deflate: chunk %u reports %u bytes", c, bytes);
+            pack[c].dst = at;
+            at += bytes;
+            res[k].storedChunks += (outs[c].bytes & DEF_STORED) != 0;
+        }
+        at += 8;
+        res[k].outLen = at - res[k].outOff;
+    }
+    if (gzBytes) *gzBytes = at;
+    if (at > gzCap) return fail(-104, "gzip output needs %llu bytes, capacity %llu", (unsigned long long) at, (unsigned long long) gzCap);
+    FCHK(hipMemcpyAsync(p->dDefPack.p, pack.data(), nc * sizeof(DefPackIn), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dDefJobs.p, jtab.data(), njobs * sizeof(DefJobIn), hipMemcpyHostToDevice, p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint32_t c0 = 0; c0 < nc; c0 += FMT_SLICE)
+        k_fa_deflate_pack<<<dim3(std::min(FMT_SLICE, nc - c0)), dim3(DEF_WAVE), 0, p->stream>>>(p->dDefSlots.p, p->dDefOuts.p, p->dDefPack.p, p->dDefJobs.p, c0, nc, gz_dev,
+                                                                                               p->dDefCrc.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    std::vector<uint32_t> crcs(njobs);
+    FCHK(hipMemcpyAsync(crcs.data(), p->dDefCrc.p, njobs * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float t = 0; FCHK(hipEventElapsedTime(&t, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms + t; }
+    for (uint64_t k = 0; k < njobs; k++) res[k].crc32 = crcs[k];
+    memcpy(results, res.data(), njobs * sizeof(mbgc_fasta_deflate_result_t));
     return 0;
 }
 

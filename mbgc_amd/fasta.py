@@ -7,7 +7,7 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -38,6 +38,30 @@ class InflateJob(C.Structure):
 
 class InflateResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("members", C.c_uint32), ("outLen", C.c_uint64), ("inUsed", C.c_uint64)]
+
+
+DEFLATE_CHUNK = 32768                # MBGC_DEFLATE_CHUNK
+
+
+class DeflateJob(C.Structure):
+    _fields_ = [("inOff", C.c_uint64), ("inLen", C.c_uint64)]
+
+
+class DeflateResult(C.Structure):
+    _fields_ = [("outOff", C.c_uint64), ("outLen", C.c_uint64), ("crc32", C.c_uint32), ("chunks", C.c_uint32), ("storedChunks", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class GzipTooSmall(binding.SwsemError):
+    """deflate_dev: the gzip files do not fit the buffer; .needed = their size"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
+def deflate_bound(n):
+    """mbgc_fasta_deflate_bound: the most a text of n bytes takes as a gzip file of deflate_dev"""
+    return 18 + max(1, -(-int(n) // DEFLATE_CHUNK)) * 10 + int(n)
 
 
 PROBE_MIN_LEN, PROBE_MAX_LEN = 256, 65536      # MBGC_FASTA_PROBE_MIN_LEN, MBGC_FASTA_PROBE_MAX_LEN
@@ -88,6 +112,10 @@ def _lib():
                                              C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_double)]
         L.mbgc_fasta_inflate_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(InflateJob), C.c_uint64,
                                              C.POINTER(InflateResult), C.POINTER(C.c_double)]
+        L.mbgc_fasta_deflate_bound.argtypes = [C.c_uint64]
+        L.mbgc_fasta_deflate_bound.restype = C.c_uint64
+        L.mbgc_fasta_deflate_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DeflateJob), C.c_uint64, C.c_void_p, C.c_uint64,
+                                             C.POINTER(DeflateResult), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L._fasta_ready = True
     return L
 
@@ -259,6 +287,21 @@ class FastaParser:
         if _lib().mbgc_fasta_inflate_dev(self.h, gz_ptr, int(gz_bytes), out_ptr, int(out_bytes), arr, len(rows), res, C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return [(r.status, r.members, r.outLen, r.inUsed) for r in res[: len(rows)]], ms.value
+
+    def deflate_dev(self, text_ptr, text_bytes, jobs, gz_ptr, gz_cap):
+        """jobs = rows of (inOff, inLen): text[inOff, inOff + inLen) compressed on the device into one gzip file each, back to back in
+        gz[0, total) -> ([(outOff, outLen, crc32, chunks, storedChunks)] per job, total, both kernels' ms). GzipTooSmall when the
+        files do not fit gz_cap (nothing written). A refused call (a job outside the text) raises and launches nothing."""
+        rows = [tuple(int(v) for v in r) for r in jobs]
+        arr = (DeflateJob * max(len(rows), 1))(*rows)
+        res = (DeflateResult * max(len(rows), 1))()
+        total, ms = C.c_uint64(0), C.c_double(0)
+        r = _lib().mbgc_fasta_deflate_dev(self.h, text_ptr, int(text_bytes), arr, len(rows), gz_ptr, int(gz_cap), res, C.byref(total), C.byref(ms))
+        if r == -104:
+            raise GzipTooSmall(_lib().mbgc_fasta_last_error().decode(), int(total.value))
+        if r:
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return [(x.outOff, x.outLen, x.crc32, x.chunks, x.storedChunks) for x in res[: len(rows)]], int(total.value), ms.value
 
     def gather_dev(self, src_ptr, src_bytes, offsets, lengths, sep=10):
         """pieces of a device buffer, each followed by the byte sep, packed on the device and downloaded -> bytes"""

@@ -323,9 +323,10 @@ struct FastaLayout {
     std::vector<std::string> names;                                // per unit (one for a single-FASTA collection)
     std::vector<std::string> outNames;                             // the files to write, in order
 };
-struct FastaTimes { double format = 0, download = 0, write = 0; uint64_t text = 0, batches = 0; };
+struct FastaTimes { double format = 0, download = 0, write = 0, deflate = 0; uint64_t text = 0, batches = 0, gz = 0, chunks = 0, storedChunks = 0; };
 struct FastaBuffers {                                              // freed on every way out
     mbgc_fasta_t *fa = nullptr; uint8_t *hdrDev = nullptr, *textDev[2] = {nullptr, nullptr}; void *pin[2] = {nullptr, nullptr};
+    uint8_t *gzDev[2] = {nullptr, nullptr};                        // --gzip: the gzip files of a batch (not allocated without it)
     std::future<bool> writing;
     ~FastaBuffers() {
         if (writing.valid()) writing.wait();
@@ -333,6 +334,7 @@ struct FastaBuffers {                                              // freed on e
         mbgc_fasta_download_wait(fa, nullptr);                     // (a way out between begin and wait)
         if (hdrDev) mbgc_fasta_dev_free(fa, hdrDev);
         for (uint8_t *t : textDev) if (t) mbgc_fasta_dev_free(fa, t);
+        for (uint8_t *t : gzDev) if (t) mbgc_fasta_dev_free(fa, t);
         for (void *p : pin) if (p) mbgc_fasta_host_free(fa, p);
         mbgc_fasta_destroy(fa);
     }
@@ -820,15 +822,18 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                     units.push_back(x);
                 }
             }
-            uint64_t maxBatch = 0;
+            uint64_t maxBatch = 0, maxGz = 0;                                                    // (maxGz: --gzip, the most a batch's gzip files take)
             std::vector<size_t> batchEnd;                                                       // units [batchEnd[b - 1], batchEnd[b])
             {
-                uint64_t cur = 0;
+                uint64_t cur = 0, curGz = 0;
                 for (size_t u = 0; u < units.size(); u++) {
-                    if (cur && cur + units[u].text > (opt.batchText ? opt.batchText : FASTA_BATCH_TEXT)) { batchEnd.push_back(u); maxBatch = std::max(maxBatch, cur); cur = 0; }
+                    if (cur && cur + units[u].text > (opt.batchText ? opt.batchText : FASTA_BATCH_TEXT)) {
+                        batchEnd.push_back(u); maxBatch = std::max(maxBatch, cur); maxGz = std::max(maxGz, curGz); cur = curGz = 0;
+                    }
                     cur += units[u].text;
+                    if (opt.gzip) curGz += mbgc_fasta_deflate_bound(units[u].text);
                 }
-                batchEnd.push_back(units.size()); maxBatch = std::max(maxBatch, cur);
+                batchEnd.push_back(units.size()); maxBatch = std::max(maxBatch, cur); maxGz = std::max(maxGz, curGz);
             }
             const bool writeFiles = !opt.validate && (!opt.bench || pass == 0);                  // (bench: the timed pass formats and downloads only)
             if (std::string failed; writeFiles && !makeDirs(opt.fastaDir, &failed)) return fail("cannot create the directory " + failed);
@@ -836,7 +841,8 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             if (mbgc_fasta_create(&fb.fa, opt.device)) return faFail("--fasta");
             if (mbgc_fasta_dev_alloc(fb.fa, layout.headers.size() + 64, &fb.hdrDev)) return faFail("--fasta");
             for (uint8_t *&t : fb.textDev) if (mbgc_fasta_dev_alloc(fb.fa, maxBatch + 64, &t)) return faFail("--fasta");
-            for (void *&p : fb.pin) if (mbgc_fasta_host_alloc(fb.fa, std::max<uint64_t>(maxBatch, layout.headers.size()) + 64, &p)) return faFail("--fasta");
+            if (opt.gzip) for (uint8_t *&t : fb.gzDev) if (mbgc_fasta_dev_alloc(fb.fa, maxGz + 64, &t)) return faFail("--gzip");
+            for (void *&p : fb.pin) if (mbgc_fasta_host_alloc(fb.fa, std::max<uint64_t>(opt.gzip ? maxGz : maxBatch, layout.headers.size()) + 64, &p)) return faFail("--fasta");
             {   // the headers go up through page-locked memory like everything else
                 memcpy(fb.pin[0], layout.headers.data(), layout.headers.size());
                 if (mbgc_fasta_upload(fb.fa, fb.hdrDev, fb.pin[0], layout.headers.size())) return faFail("--fasta");
@@ -863,13 +869,13 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                 ftimes.write += nowMs() - w0;                                                   // (what the writes hold the pipeline up by)
                 if (!ok) return 2;
                 if (writeFiles) {
-                    const std::string dir = opt.fastaDir;
+                    const std::string dir = opt.fastaDir, suffix = opt.gzip ? ".gz" : "";
                     const std::vector<std::string> *outNames = &layout.outNames;
                     const std::vector<Piece> pieces = inFlight;
                     const uint8_t *host = inFlightHost;
-                    fb.writing = std::async(std::launch::async, [pieces, host, dir, outNames] {
+                    fb.writing = std::async(std::launch::async, [pieces, host, dir, suffix, outNames] {
                         for (const Piece &p : pieces) {
-                            std::ofstream f(dir + "/" + (*outNames)[p.file], std::ios::binary | (p.first ? std::ios::trunc : std::ios::app));
+                            std::ofstream f(dir + "/" + (*outNames)[p.file] + suffix, std::ios::binary | (p.first ? std::ios::trunc : std::ios::app));
                             f.write((const char *) host + p.off, (std::streamsize) p.len);
                             f.close();                                                          // (an error may only show when the last bytes leave the buffer)
                             if (!f) return false;
@@ -1151,8 +1157,26 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                     at += units[u].text;
                 }
                 if (at != bytes) return fail("internal error: the text of a batch is not the sum of its units");
+                const uint8_t *src = fb.textDev[b & 1];
+                if (opt.gzip) {
+                    // --gzip: one deflate call over the batch, a job per piece; a piece becomes one gzip member, appended to its file
+                    // like the text would be, and only the gzip bytes travel (gzDev[b & 1]: the download of batch b - 2 has been settled)
+                    std::vector<mbgc_fasta_deflate_job_t> jobs;
+                    for (const Piece &pc : inFlight) jobs.push_back({pc.off, pc.len});
+                    std::vector<mbgc_fasta_deflate_result_t> res(jobs.size());
+                    uint64_t gzBytes = 0;
+                    double dms = 0;
+                    if (mbgc_fasta_deflate_dev(fb.fa, fb.textDev[b & 1], bytes, jobs.data(), jobs.size(), fb.gzDev[b & 1], maxGz, res.data(), &gzBytes, &dms)) return faFail("deflate");
+                    for (size_t k = 0; k < res.size(); k++) {
+                        inFlight[k].off = res[k].outOff; inFlight[k].len = res[k].outLen;
+                        ftimes.chunks += res[k].chunks; ftimes.storedChunks += res[k].storedChunks;
+                    }
+                    ftimes.deflate += dms; ftimes.gz += gzBytes;
+                    bytes = gzBytes;
+                    src = fb.gzDev[b & 1];
+                }
                 inFlightHost = (uint8_t *) fb.pin[b & 1];
-                if (mbgc_fasta_download_begin(fb.fa, inFlightHost, fb.textDev[b & 1], bytes)) return faFail("download");
+                if (mbgc_fasta_download_begin(fb.fa, inFlightHost, src, bytes)) return faFail("download");
                 downloading = true;
                 u0 = u1;
             }
@@ -1161,9 +1185,11 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             if (fb.writing.valid() && !fb.writing.get()) return fail("cannot write under " + opt.fastaDir);
             ftimes.write += nowMs() - w0;
             // (files of units without a record exist too, empty)
+            static const unsigned char emptyGz[20] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (--gzip: the gzip file of no text)
             if (writeFiles)
                 for (size_t f = 0; f < opened.size(); f++)
-                    if (!opened[f] && fileWanted[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f], "", 0)) return fail("cannot write under " + opt.fastaDir);
+                    if (!opened[f] && fileWanted[f] && !writeFile(opt.fastaDir + "/" + layout.outNames[f] + (opt.gzip ? ".gz" : ""), opt.gzip ? (const char *) emptyGz : "", opt.gzip ? sizeof emptyGz : 0))
+                        return fail("cannot write under " + opt.fastaDir);
         }
 
         if (pass + 1 == passes && !opt.bench && !opt.validate) {
@@ -1225,6 +1251,11 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                "\"format_kernel_ms\": %.3f, \"download_ms\": %.3f, \"write_ms\": %.3f}\n",
                ftimes.format > 0 ? ftimes.text / (ftimes.format * 1e-3) / 1e9 : 0.0, (unsigned long long) ftimes.text, (unsigned long long) ftimes.batches,
                ftimes.format, ftimes.download, ftimes.write);
+    if (opt.bench && wantFasta && !opt.validate && opt.gzip)
+        printf("{\"metric\": \"gzip GB/s of text (deflate kernels)\", \"value\": %.4f, \"unit\": \"GB/s\", \"text_bytes\": %llu, \"gz_bytes\": %llu, "
+               "\"deflate_kernel_ms\": %.3f, \"download_ms\": %.3f, \"write_ms\": %.3f, \"chunks\": %llu, \"stored_chunks\": %llu}\n",
+               ftimes.deflate > 0 ? ftimes.text / (ftimes.deflate * 1e-3) / 1e9 : 0.0, (unsigned long long) ftimes.text, (unsigned long long) ftimes.gz, ftimes.deflate,
+               ftimes.download, ftimes.write, (unsigned long long) ftimes.chunks, (unsigned long long) ftimes.storedChunks);
     if (selecting)
         printf("closure: %llu of %llu contigs, %llu of %llu bases, %llu selected, %llu dependency targets\n", (unsigned long long) closureContigs, (unsigned long long) planned,
                (unsigned long long) closureBases, (unsigned long long) plannedBases, (unsigned long long) selectedFiles, (unsigned long long) dependencyTargets);
@@ -1245,6 +1276,8 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--bench") opt.bench = true;
         else if (a == "--restore-rc") opt.restoreRc = true;
         else if (a == "--fasta" && i + 1 < argc) opt.fastaDir = argv[++i];
+        else if (a == "--gzip") opt.gzip = true;
+        else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--select" && i + 1 < argc) { opt.select.push_back(argv[++i]); selectAsked = true; }
         else if (a == "--select-list" && i + 1 < argc) {
             std::ifstream f(argv[++i]);
@@ -1260,12 +1293,15 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else pos.push_back(a);
     }
     if (pos.size() != 2) {
-        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir] [--select pattern]... [--select-list file]\n"
-                        "                  [--closure-out file] [-d device] <streamsPrefix> <outputPrefix>\n"
+        fprintf(stderr, "usage: mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir [--gzip] [--batch-kib K]] [--select pattern]...\n"
+                        "                  [--select-list file] [--closure-out file] [-d device] <streamsPrefix> <outputPrefix>\n"
                         "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
                         "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
                         "  --fasta dir: also the input FASTA files again, formatted on the device, as <dir>/<basename of each name of the list> (a .gz suffix\n"
                         "  is dropped: the text is written inflated; -i: the one file) from <streamsPrefix>.names / .headers / .dnaLineLengths\n"
+                        "  --gzip (with --fasta): every file is written as <name>.gz, compressed on the device (one encoder: no level; the bytes are a\n"
+                        "  function of the text alone); a file whose text spans batches is several gzip members back to back, which zlib, gzip -d and\n"
+                        "  mbgc-hip v read as one text. --batch-kib K: text per batch (default 262144)\n"
                         "  --serial: contig by contig, each contig's loads before the next; --no-index: one chain plans the whole collection\n"
                         "  --restore-rc: streams of c -m 3 — the reverse-complement pass over the literals is inverted first, on the device, from\n"
                         "  <streamsPrefix>.rcMapOff / .rcMapLen (without it such streams are refused; no effect on other streams)\n"
@@ -1274,6 +1310,7 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
                         "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n");
         return EXIT_FAILURE;
     }
+    if (opt.gzip && opt.fastaDir.empty()) { fprintf(stderr, "mbgc-hip d: --gzip needs --fasta dir (it compresses the FASTA files that --fasta writes)\n"); return EXIT_FAILURE; }
     if (selectAsked) for (const std::string &pat : opt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip d: --select: an empty pattern\n"); return EXIT_FAILURE; }
     if (selectAsked && opt.select.empty()) { fprintf(stderr, "mbgc-hip d: --select-list: the list of patterns is empty\n"); return EXIT_FAILURE; }
     if (!selectAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }

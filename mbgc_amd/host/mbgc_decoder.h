@@ -52,11 +52,12 @@ public:
         uint64_t loaded() const { return reachedRefLengthCount * (refTotalLength - 1) + (refPos - 1); }
     };
     struct ContigInfo { uint64_t length, unmatched; };
+    // gzip: --gzip, the files of --fasta are written as <name>.gz, compressed on the device (mbgc_fasta_deflate_dev)
     // fastaDir: --fasta, empty = not asked for; restoreRc: --restore-rc, the -m 3 pass over the literals is inverted first
     // select: --select / --select-list, the files to bring back (a unit is chosen when its line of <prefix>.names contains one of the
     // patterns; empty = the whole collection); closureOut: --closure-out, one byte per planned contig
     struct Options {
-        bool serial = false, noIndex = false, bench = false, restoreRc = false; int device = 0; std::string fastaDir;
+        bool serial = false, noIndex = false, bench = false, restoreRc = false, gzip = false; int device = 0; std::string fastaDir;
         std::vector<std::string> select; std::string closureOut;
         // `mbgc-hip v`: validate — the units are formatted as for --fasta and compared on the device with the originals named by
         // <prefix>.names, nothing is downloaded or written; root / flat: where the originals lie (--root is put before relative names,

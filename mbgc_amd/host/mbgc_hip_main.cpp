@@ -139,7 +139,7 @@ int main(int argc, char **argv) {
                         "  file of the list and a gzip file given with -i are always inflated by the host\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir] [-d device] <streamsPrefix> <outputPrefix>\n");
+        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir [--gzip] [--batch-kib K]] [-d device] <streamsPrefix> <outputPrefix>\n");
         fprintf(stderr, "       mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat] [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n");
         return EXIT_FAILURE;
     }
