@@ -164,6 +164,20 @@ typedef struct { uint64_t aOff, bOff, len; uint32_t slot; } mbgc_fasta_compare_p
 int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aBytes, const uint8_t *b_dev, uint64_t bBytes,
                            const mbgc_fasta_compare_piece_t *pieces, uint64_t npieces, uint64_t *firstDiff, uint32_t nslots, double *kernelMs);
 
+/* Pieces of a device buffer back to back in another one (`mbgc-hip r`: the chosen units' contigs out of the decoder's sequence buffer,
+ * where the contigs they depend on lie among them, into the buffer the encoder's rounds are slices of). Piece k is src_dev[srcOff,
+ * srcOff + len) of a buffer of srcBytes bytes; the pieces land in dst_dev in order, without a separator; pieces of no bytes are
+ * legal and may overlap each other in the source. dstOff (host, n + 1 entries) receives every piece's offset in dst_dev and, last,
+ * the total. When the total exceeds dstCap the call writes nothing to dst_dev and returns -104 with the size needed in dstOff[n]. A
+ * piece that does not lie inside the source, or a source that overlaps dst_dev[0, dstCap), is refused (-103, message in
+ * mbgc_fasta_last_error): nothing is launched. No byte outside dst_dev[0, total) is written, no byte outside a piece is read; any
+ * alignment of either side (the stores are aligned 16-byte vectors, the loads go unaligned). flags: 0, or MBGC_FASTA_UPPERCASE — the
+ * bytes are folded as the parser folds a base under that flag (a..z only). kernelMs (may be NULL): the kernel's time from events on
+ * the stream. Runs on the input stage's stream; synchronous. */
+typedef struct { uint64_t srcOff, len; } mbgc_fasta_pack_piece_t;
+int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcBytes, const mbgc_fasta_pack_piece_t *pieces, uint64_t n, uint32_t flags,
+                        uint8_t *dst_dev, uint64_t dstCap, uint64_t *dstOff, double *kernelMs);
+
 /* gzip files that lie compressed in HBM, inflated there (mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

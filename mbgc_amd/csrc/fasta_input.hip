@@ -647,6 +647,7 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
 
 #include "fasta_format.h"
 #include "fasta_compare.h"
+#include "fasta_pack.h"
 
 #define INF_CONST static __device__
 #define INF_LANES_DO(lane) for (uint32_t lane = threadIdx.x, once_ = 1; once_; once_ = 0)
@@ -725,6 +726,14 @@ __global__ void __launch_bounds__(THREADS) k_fa_compare(const uint8_t *__restric
         if (lane == (uint32_t) leader) atomicMin(firstDiff + P[piece].slot, (unsigned long long) d);
         m &= ~__ballot(piece == leaderPiece);
     }
+}
+
+// mbgc_fasta_pack_dev: one lane step per thread (fasta_pack.h); nothing passes between the lanes
+__global__ void __launch_bounds__(THREADS) k_fa_pack(const uint8_t *__restrict__ src, const PackPiece *__restrict__ P, const uint32_t *__restrict__ owner,
+                                                     uint32_t tile0, uint32_t ntiles, uint32_t mis, uint64_t total, int fold, uint8_t *__restrict__ dst) {
+    const uint32_t tile = tile0 + blockIdx.x;
+    if (tile >= ntiles) return;
+    pack_lane_step(src, P, owner, tile, threadIdx.x, mis, total, fold != 0, dst);
 }
 
 // pieces of a device buffer packed back to back, each followed by one separator byte (the headers of a -i batch: only they travel
@@ -851,6 +860,8 @@ struct mbgc_fasta {
     fa::Buf<fa::CmpPiece> dCmpPieces;           // mbgc_fasta_compare_dev: the piece table, the tiles' owners, the slots' results
     fa::Buf<uint32_t> dCmpOwner;
     fa::Buf<unsigned long long> dCmpOut;
+    fa::Buf<fa::PackPiece> dPackPieces;         // mbgc_fasta_pack_dev: the piece table and the tiles' owners
+    fa::Buf<uint32_t> dPackOwner;
     fa::Buf<fa::InfJob> dInfJobs;               // mbgc_fasta_inflate_dev: the jobs and their results
     fa::Buf<fa::InfResult> dInfResults;
     fa::Buf<fa::DefChunk> dDefChunks;           // mbgc_fasta_deflate_dev: the chunk table, the chunks' slots and what they hold, the pack tables
@@ -895,6 +906,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
     p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
+    p->dPackPieces.release(); p->dPackOwner.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
@@ -1188,6 +1200,45 @@ int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aByte
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
     for (uint32_t s = 0; s < nslots; s++) firstDiff[s] = out[s];
+    return 0;
+}
+
+int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcBytes, const mbgc_fasta_pack_piece_t *pieces, uint64_t n, uint32_t flags,
+                        uint8_t *dst_dev, uint64_t dstCap, uint64_t *dstOff, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(PackIn) == sizeof(mbgc_fasta_pack_piece_t), "the table builder reads the ABI's pieces");
+    if (kernelMs) *kernelMs = 0;
+    if (flags & ~(uint32_t) MBGC_FASTA_UPPERCASE) return fail(-103, "pack: unknown flags %#x", flags);
+    if (n >= 0xffffffffull) return fail(-103, "pack: %llu pieces in one call", (unsigned long long) n);
+    for (uint64_t k = 0; k < n; k++)
+        if (pieces[k].srcOff > srcBytes || pieces[k].len > srcBytes - pieces[k].srcOff)
+            return fail(-103, "pack: piece %llu lies outside the source", (unsigned long long) k);
+    const uintptr_t s0 = (uintptr_t) src_dev, d0 = (uintptr_t) dst_dev;
+    if (srcBytes && dstCap && s0 < d0 + dstCap && d0 < s0 + srcBytes) return fail(-103, "pack: the source and the destination overlap");
+    std::vector<PackPiece> table;
+    const uint64_t total = pack_build_table((const PackIn *) pieces, n, table, dstOff);
+    if (total > dstCap) return fail(-104, "packed output needs %llu bytes, capacity %llu", (unsigned long long) total, (unsigned long long) dstCap);
+    if (total == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    const uint32_t mis = (uint32_t) (d0 & (uintptr_t) (PER - 1));
+    const uint64_t nt64 = (total + mis + CHUNK - 1) / CHUNK;
+    if (nt64 >= 0xffffffffull) return fail(-103, "pack: %llu bytes in one call", (unsigned long long) total);
+    const uint32_t ntiles = (uint32_t) nt64;
+    std::vector<uint32_t> owner;
+    pack_build_owner(table, mis, ntiles, owner);
+    int rc;
+    if ((rc = p->dPackPieces.reserve(table.size())) || (rc = p->dPackOwner.reserve((size_t) ntiles + 1))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dPackPieces.p, table.data(), table.size() * sizeof(PackPiece), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dPackOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
+        k_fa_pack<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(src_dev, p->dPackPieces.p, p->dPackOwner.p, t0, ntiles, mis, total,
+                                                                                          (flags & MBGC_FASTA_UPPERCASE) ? 1 : 0, dst_dev);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
     return 0;
 }
 

@@ -7,7 +7,7 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -24,6 +24,17 @@ class FormatRecord(C.Structure):
 
 class ComparePiece(C.Structure):
     _fields_ = [("aOff", C.c_uint64), ("bOff", C.c_uint64), ("len", C.c_uint64), ("slot", C.c_uint32)]
+
+
+class PackPiece(C.Structure):
+    _fields_ = [("srcOff", C.c_uint64), ("len", C.c_uint64)]
+
+
+class PackTooSmall(binding.SwsemError):
+    """pack_dev: the pieces do not fit the buffer; .needed = their size"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
 
 
 NO_DIFFERENCE = 2 ** 64 - 1          # UINT64_MAX: what compare_dev leaves in a slot whose pieces are equal
@@ -116,6 +127,8 @@ def _lib():
         L.mbgc_fasta_deflate_bound.restype = C.c_uint64
         L.mbgc_fasta_deflate_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DeflateJob), C.c_uint64, C.c_void_p, C.c_uint64,
                                              C.POINTER(DeflateResult), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_pack_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PackPiece), C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L._fasta_ready = True
     return L
 
@@ -275,6 +288,23 @@ class FastaParser:
                                          int(nslots), C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out, ms.value
+
+    def pack_dev(self, src_ptr, src_bytes, pieces, dst_ptr, dst_cap, uppercase=False):
+        """pieces = rows of (srcOff, len): src[srcOff, srcOff + len) back to back in dst on the device, folded to upper case as the
+        parser folds a base when `uppercase` -> (the pieces' offsets in dst [n + 1], the last one the total; the kernel's ms).
+        PackTooSmall when they do not fit dst_cap (nothing written). A refused call (a piece outside the source, buffers that
+        overlap) raises and launches nothing."""
+        rows = np.ascontiguousarray(pieces, dtype=np.uint64).reshape(-1, 2)
+        n = rows.shape[0]
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        ms = C.c_double(0)
+        r = _lib().mbgc_fasta_pack_dev(self.h, src_ptr, int(src_bytes), rows.ctypes.data_as(C.POINTER(PackPiece)), n, UPPERCASE if uppercase else 0,
+                                       dst_ptr, int(dst_cap), offs.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ms))
+        if r == -104:
+            raise PackTooSmall(_lib().mbgc_fasta_last_error().decode(), int(offs[-1]))
+        if r:
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return offs, ms.value
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

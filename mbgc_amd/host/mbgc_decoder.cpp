@@ -508,6 +508,8 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     if (!readFile(prefix + ".meta", metaBytes)) return fail("cannot open " + prefix + ".meta (written by mbgc-hip c beside the streams)");
     MbgcMeta meta;
     { std::string e; if (!meta.parse(metaBytes, &e)) return fail(e); }
+    if (opt.resident && meta.singleFastaFile)
+        return fail("the streams hold one FASTA file (mbgc-hip c -i): a single-FASTA stream set is not repacked (it has one unit, and its elements are no files)");
     if (meta.rcRedundancyRemoval && !opt.restoreRc)
         return fail("the streams were written with -m 3: its reverse-complement pass over the literal stream (rcMapOff / rcMapLen) is not inverted by mbgc-hip d"
                     " unless --restore-rc is given");
@@ -564,7 +566,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     if (planned > stream[SWSEM_LIT].size()) return fail("malformed .meta: more sequences than literal bytes");
     uint64_t sizes[SWSEM_NSTREAMS];
     for (int s = 0; s < SWSEM_NSTREAMS; s++) sizes[s] = stream[s].size();
-    const bool wantFasta = !opt.fastaDir.empty() || opt.validate;   // (`v` builds the units and batches of --fasta, and formats them)
+    const bool wantFasta = !opt.fastaDir.empty() || opt.validate || opt.resident;   // (`v` builds the units and batches of --fasta, and formats them; `r` takes the units)
     FastaLayout layout;
     if (wantFasta) { std::string m; if (!readFastaLayout(prefix, meta, g0n + planned, layout, m)) return fail(m); }
     FastaTimes ftimes;
@@ -799,6 +801,39 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             }
             for (const Interval &r : outRanges) for (uint64_t k = r.from; k < r.to; k++) { outBases += contigLen[k]; outContigs++; }
             for (uint64_t k = g0n; k < N; k++) plannedBases += contigLen[k];
+        }
+        if (opt.resident) {
+            // ---- `mbgc-hip r`: the units --fasta would write, packed out of the sequence buffer — where the contigs of
+            // the closure lie among them — into a buffer of the caller's input stage; this handle and all it holds end with the return
+            ResidentCollection &R = *opt.resident;
+            R.units.clear();
+            std::vector<mbgc_fasta_pack_piece_t> pieces;
+            uint64_t c = 0;
+            for (size_t u = 0; u <= T; u++) {
+                const uint64_t n = u == 0 ? g0n : seqCount[u - 1], c0 = c;
+                c += n;
+                if ((u == 0 && meta.sequentialMatching) || !unitSel[u]) continue;
+                ResidentUnit x;
+                x.name = layout.names[u];
+                x.lineLen = R.lineLenGiven ? R.lineLen : layout.lineLen[u];
+                for (uint64_t k = c0; k < c0 + n; k++) {
+                    x.headers.append(layout.headers, layout.hdrOff[k], layout.hdrLen[k]); x.headers.push_back('\n');
+                    x.contigLen.push_back(contigLen[k]);
+                    x.text += recordText(layout.hdrLen[k], contigLen[k], x.lineLen);
+                    pieces.push_back({seqOff[k], contigLen[k]});
+                }
+                R.units.push_back(std::move(x));
+            }
+            auto faFail = [&](const char *what) { return fail(std::string(what) + ": " + mbgc_fasta_last_error()); };
+            if (mbgc_fasta_dev_alloc(R.fasta, outBases + 64, &R.packedDev)) return faFail("the chosen units' bases");
+            std::vector<uint64_t> dstOff(pieces.size() + 1);
+            if (mbgc_fasta_pack_dev(R.fasta, seqDev, totalBases, pieces.data(), pieces.size(), R.packFlags, R.packedDev, outBases + 64, dstOff.data(), &R.packKernelMs))
+                return faFail("pack");
+            R.packedBytes = dstOff[pieces.size()];
+            if (R.packedBytes != outBases) return fail("internal error: the packed units are not the chosen contigs");
+            R.contigsDecoded = g0n + (selecting ? closureContigs : planned); R.contigsChosen = outContigs;
+            R.decodeMs = times.plan + times.closure + times.fill + times.load + rcRestoreMs;
+            return 0;
         }
         if (wantFasta) {
             // ---- the FASTA files again: units in order, batches of whole units of at most FASTA_BATCH_TEXT bytes of
@@ -1265,6 +1300,16 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     return opt.validate && invalidFiles ? 2 : 0;
 }
 
+bool mbgc_hip_read_pattern_list(const char *path, std::vector<std::string> &out) {
+    std::ifstream f(path);
+    if (!f) return false;
+    for (std::string line; std::getline(f, line);) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (!line.empty()) out.push_back(line);
+    }
+    return true;
+}
+
 int mbgc_hip_decompress_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     std::vector<std::string> pos;
@@ -1280,12 +1325,7 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--select" && i + 1 < argc) { opt.select.push_back(argv[++i]); selectAsked = true; }
         else if (a == "--select-list" && i + 1 < argc) {
-            std::ifstream f(argv[++i]);
-            if (!f) { fprintf(stderr, "mbgc-hip d: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
-            for (std::string line; std::getline(f, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                if (!line.empty()) opt.select.push_back(line);
-            }
+            if (!mbgc_hip_read_pattern_list(argv[++i], opt.select)) { fprintf(stderr, "mbgc-hip d: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
             selectAsked = true;
         }
         else if (a == "--closure-out" && i + 1 < argc) opt.closureOut = argv[++i];
@@ -1346,12 +1386,7 @@ int mbgc_hip_validate_main(int argc, char **argv) {
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--select" && i + 1 < argc) { opt.select.push_back(argv[++i]); selectAsked = true; }
         else if (a == "--select-list" && i + 1 < argc) {
-            std::ifstream f(argv[++i]);
-            if (!f) { fprintf(stderr, "mbgc-hip v: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
-            for (std::string line; std::getline(f, line);) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                if (!line.empty()) opt.select.push_back(line);
-            }
+            if (!mbgc_hip_read_pattern_list(argv[++i], opt.select)) { fprintf(stderr, "mbgc-hip v: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
             selectAsked = true;
         }
         else if (a == "--gpus") { fprintf(stderr, "mbgc-hip v: validation runs on one GPU (--gpus is an option of mbgc-hip c)\n"); return EXIT_FAILURE; }

@@ -42,6 +42,25 @@ struct LoadSegment {
     bool reverseComplement;
 };
 
+// `mbgc-hip r`: what a decode that ends RESIDENT hands over instead of downloading — the chosen units (the files `d --fasta` would
+// write, in its order) with their names, headers, line lengths and contig lengths, and their contigs packed back to back on the
+// device (mbgc_fasta_pack_dev) in a buffer of the caller's input stage, which outlives the decoder's handle: that handle, with the
+// streams, the reference buffer and the decoder's sequence buffer, is gone when decode() returns.
+struct ResidentUnit {
+    std::string name, headers;                           // its line of <prefix>.names; its contigs' headers, '\n' behind each
+    uint64_t lineLen = 0, text = 0;                      // text: the bytes of the FASTA file `d --fasta` would write at that line length
+    std::vector<uint64_t> contigLen;
+};
+struct ResidentCollection {
+    mbgc_fasta_t *fasta = nullptr;                       // in: the input stage that allocates and packs
+    uint32_t packFlags = 0;                              // in: 0 or MBGC_FASTA_UPPERCASE
+    bool lineLenGiven = false; uint64_t lineLen = 0;     // in: -l N, every unit's line length becomes N
+    std::vector<ResidentUnit> units;
+    uint8_t *packedDev = nullptr; uint64_t packedBytes = 0;   // unit u's contigs follow unit u - 1's; mbgc_fasta_dev_free(fasta, packedDev)
+    uint64_t contigsDecoded = 0, contigsChosen = 0;
+    double decodeMs = 0, packKernelMs = 0;
+};
+
 class MBGC_Decoder {
 public:
     struct RefState {                                    // MBGC_Decoder.h: refPos, refTotalLength, reachedRefLengthCount
@@ -64,6 +83,8 @@ public:
         // --flat keeps the basename `d --fasta` writes); skipCompare: decode and format only; dumpDir: the text of the first invalid
         // files is written there; batchText: text bytes per batch, 0 = the default of --fasta
         bool validate = false, flat = false, skipCompare = false, inflateOnDevice = false; std::string root, dumpDir; uint64_t batchText = 0;
+        // `mbgc-hip r`: nothing is downloaded or written; the chosen units stay on the device and are described here
+        ResidentCollection *resident = nullptr;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -87,3 +108,5 @@ public:
 
 int mbgc_hip_decompress_main(int argc, char **argv);
 int mbgc_hip_validate_main(int argc, char **argv);
+// --select-list: the file's non-empty lines behind `out`; false: it cannot be opened
+bool mbgc_hip_read_pattern_list(const char *path, std::vector<std::string> &out);

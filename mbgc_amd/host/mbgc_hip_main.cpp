@@ -64,7 +64,137 @@ static void dump(const std::string &prefix, const char *name, const std::string 
     f.write(data.data(), (std::streamsize) data.size());
 }
 
+// the stream set of a finished encode under `prefix`: the seven streams (rcMapOff / rcMapLen beside them under -m 3), .meta, and —
+// unless the rounds were sharded over several GPUs — .names, .headers and .dnaLineLengths (what `c` and `r` write)
+static void writeStreamSet(const std::string &prefix, const MBGC_Encoder &enc, const MBGC_Params &params) {
+    dump(prefix, "literals", enc.literals);
+    if (params.rcRedundancyRemoval) { dump(prefix, "rcMapOff", enc.rcMapOff); dump(prefix, "rcMapLen", enc.rcMapLen); }
+    dump(prefix, "locksPos", enc.locksPosStream);
+    dump(prefix, "gapDelta", enc.gapDeltas);
+    dump(prefix, "flags", enc.gapMismatchesFlags);
+    dump(prefix, "mapOff", enc.mapOff);
+    dump(prefix, "mapOff5th", enc.mapOff5thByte);
+    dump(prefix, "mapLen", enc.mapLen);
+    dump(prefix, "refExtSize", enc.refExtSizeStream);
+    dump(prefix, "meta", enc.metaBytes());                                      // what `mbgc-hip d` needs beyond the streams
+    if (!params.exchange) {                                                     // ... and `d --fasta` beyond that: names, headers, line lengths
+        dump(prefix, "names", enc.namesStream);
+        dump(prefix, "headers", enc.headersStream);
+        dump(prefix, "dnaLineLengths", enc.lineLengthsStream);
+    }
+}
+
+static const char *REPACK_USAGE =
+    "       mbgc-hip r [--select pattern]... [--select-list file] [--restore-rc] [--serial] [--no-index] [-m mode] [-k kmerLength] [-s samplingStep] [-t1]\n"
+    "                  [-R targetsPerRound] [-U] [--proteins] [-l basesPerRow] [--verify | --verify-every K] [--ref-factor F] [-d device] [--bench]\n"
+    "                  <inStreamsPrefix> <outputPrefix>\n"
+    "  repacks the chosen files of a stream set (all of them without --select) into a new one, on the device: they are decoded as mbgc-hip d\n"
+    "  decodes them (--select, --select-list, --restore-rc, --serial, --no-index: as there), packed back to back in HBM and matched again from\n"
+    "  scratch as mbgc-hip c matches the files d --fasta would write (-m, -k, -s, -t1, -R, -U, --proteins, --verify, --ref-factor: as there, with\n"
+    "  c's defaults, not the input set's values). No base leaves the device in between, no FASTA text is made. <outputPrefix> receives what c\n"
+    "  writes; <outputPrefix>.names keeps the files' names of <inStreamsPrefix>.names. -l N: every file's line length becomes N (0: unlimited).\n"
+    "  The chosen bases and the matcher's reference are resident together: the collection is not streamed through in pieces, and a device\n"
+    "  allocation that fails ends the run with its message. A single-FASTA stream set (c -i) is refused; --gpus, -i, --lossy, --inflate and\n"
+    "  --backend are options of c, over files. --bench: one JSON line (units, contigs decoded and chosen, bases, decode_ms, pack_kernel_ms,\n"
+    "  pack_bytes, encode_s) behind the report\n";
+
+// `mbgc-hip r`: MBGC_Decoder::decode that ends resident, then MBGC_Encoder::encodeResident over what it left
+static int repackMain(int argc, char **argv) {
+    MBGC_Params params;
+    MBGC_Decoder::Options dopt;
+    ResidentCollection coll;
+    std::vector<std::string> pos;
+    bool selectAsked = false, bench = false;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--select" && i + 1 < argc) { dopt.select.push_back(argv[++i]); selectAsked = true; }
+        else if (a == "--select-list" && i + 1 < argc) {
+            if (!mbgc_hip_read_pattern_list(argv[++i], dopt.select)) { fprintf(stderr, "mbgc-hip r: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
+            selectAsked = true;
+        }
+        else if (a == "--restore-rc") dopt.restoreRc = true;
+        else if (a == "--serial") dopt.serial = true;
+        else if (a == "--no-index") dopt.noIndex = true;
+        else if (a == "-t1") params.sequentialMatching = true;
+        else if (a == "-m" && i + 1 < argc) params.setCompressionMode(atoi(argv[++i]));
+        else if (a == "-R" && i + 1 < argc) params.roundSize = atoi(argv[++i]);
+        else if (a == "-s" && i + 1 < argc) {
+            params.k1 = atoi(argv[++i]);
+            if (params.k1 <= 0) { fprintf(stderr, "s - reference sampling step - should be a positive integer.\n\n"); return EXIT_FAILURE; }
+        }
+        else if (a == "-k" && i + 1 < argc) {
+            params.setKmerLength(atoi(argv[++i]));
+            if (params.k < 16 || params.k > 40) { fprintf(stderr, "k - matching kmer length - should be an integer between 16 and 40.\n\n"); return EXIT_FAILURE; }
+        }
+        else if (a == "-U") params.uppercaseDNA = true;
+        else if (a == "--proteins") params.setProteinsCompressionProfile();
+        else if (a == "-l" && i + 1 < argc) {
+            const long long n = atoll(argv[++i]);
+            if (n < 0) { fprintf(stderr, "l - bases per row - should be a non-negative integer (0: unlimited).\n\n"); return EXIT_FAILURE; }
+            coll.lineLenGiven = true; coll.lineLen = (uint64_t) n;
+        }
+        else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
+        else if (a == "--verify") params.verifyEmissions = true;
+        else if (a == "--ref-factor" && i + 1 < argc) params.referenceFactor = atoi(argv[++i]);
+        else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
+        else if (a == "--bench") bench = true;
+        else if (a == "--gpus" || a == "-i" || a == "--lossy" || a == "--inflate" || a == "--backend") {
+            fprintf(stderr, "mbgc-hip r: %s is an option of mbgc-hip c, over files: r takes its input from a stream set, on one GPU, and writes raw streams\n", a.c_str());
+            return EXIT_FAILURE;
+        }
+        else pos.push_back(a);
+    }
+    if (pos.size() != 2) { fprintf(stderr, "usage:\n%s", REPACK_USAGE); return EXIT_FAILURE; }
+    if (pos[0] == pos[1]) { fprintf(stderr, "mbgc-hip r: the output prefix is the input prefix (%s): the input set would be overwritten while it is the only copy\n", pos[0].c_str()); return EXIT_FAILURE; }
+    if (selectAsked) for (const std::string &pat : dopt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip r: --select: an empty pattern\n"); return EXIT_FAILURE; }
+    if (selectAsked && dopt.select.empty()) { fprintf(stderr, "mbgc-hip r: --select-list: the list of patterns is empty\n"); return EXIT_FAILURE; }
+    MultipleGenomeMatchingProcessor::bindHostThreadsToDeviceNode(params.device);
+    if (mbgc_fasta_create(&coll.fasta, params.device)) { fprintf(stderr, "mbgc-hip r: input stage: %s\n", mbgc_fasta_last_error()); return EXIT_FAILURE; }
+    coll.packFlags = params.uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u;
+    dopt.device = params.device;
+    dopt.resident = &coll;
+    std::string error;
+    if (MBGC_Decoder::decode(pos[0], std::string(), dopt, &error) != 0) {      // (its handle — streams, reference buffer, sequences — is gone when it returns)
+        fprintf(stderr, "mbgc-hip r: %s\n", error.c_str());
+        if (coll.packedDev) mbgc_fasta_dev_free(coll.fasta, coll.packedDev);
+        mbgc_fasta_destroy(coll.fasta);
+        return EXIT_FAILURE;
+    }
+    uint64_t contigs = 0;
+    for (const ResidentUnit &u : coll.units) contigs += u.contigLen.size();
+    printf("repacking %zu files: %llu contigs, %llu bases resident (%llu contigs decoded)\n", coll.units.size(), (unsigned long long) contigs,
+           (unsigned long long) coll.packedBytes, (unsigned long long) coll.contigsDecoded);
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    int rc = EXIT_SUCCESS;
+    {
+        MBGC_Encoder enc(&params);                                               // (takes the input stage over and destroys it)
+        enc.encodeResident(coll);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        writeStreamSet(pos[1], enc, params);
+        if (params.verifyEmissions) {
+            printf("verified on the device: %llu contigs, %llu bases decoded back to their bytes\n",
+                   (unsigned long long) params.verifiedContigs, (unsigned long long) params.verifiedBases);
+            if (params.verifiedContigs == 0 && coll.units.size() > 1) { fprintf(stderr, "--verify was asked for and no emission was verified\n"); rc = EXIT_FAILURE; }
+        }
+        if (!params.sequentialMatching)
+            printf("rounds of %d targets; reference extension bytes dropped at the sliding window's end: %zu\n", params.roundSize, enc.droppedExtensionBytes());
+        printf("final reference length: %zu\n", enc.finalReferenceLength());
+        printf("exact matches total: %zu\n", enc.exactMatches());
+        printf("final unmatched chars: %zu\n", enc.unmatchedChars() - enc.extensionsMatchedCharsAll);
+        if (bench)
+            printf("{\"metric\": \"repack (decode resident, pack, encode)\", \"units\": %zu, \"contigs_decoded\": %llu, \"contigs_chosen\": %llu, \"bases\": %llu, "
+                   "\"decode_ms\": %.3f, \"pack_kernel_ms\": %.3f, \"pack_bytes\": %llu, \"pack_gb_per_s\": %.3f, \"encode_s\": %.6f}\n",
+                   coll.units.size(), (unsigned long long) coll.contigsDecoded, (unsigned long long) coll.contigsChosen, (unsigned long long) coll.packedBytes,
+                   coll.decodeMs, coll.packKernelMs, (unsigned long long) coll.packedBytes,
+                   coll.packKernelMs > 0 ? coll.packedBytes / (coll.packKernelMs * 1e-3) / 1e9 : 0.0, (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9);
+        mbgc_fasta_dev_free(coll.fasta, coll.packedDev);
+    }
+    return rc;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "r") return repackMain(argc, argv);                 // chosen files of a stream set into a new one, resident in between
     if (argc > 1 && std::string(argv[1]) == "d") return mbgc_hip_decompress_main(argc, argv);   // the streams back to the collection (mbgc_decoder.cpp)
     if (argc > 1 && std::string(argv[1]) == "v") return mbgc_hip_validate_main(argc, argv);     // ... and compared with the files on disk, on the device
     MBGC_Params params;
@@ -141,6 +271,7 @@ int main(int argc, char **argv) {
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
         fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir [--gzip] [--batch-kib K]] [-d device] <streamsPrefix> <outputPrefix>\n");
         fprintf(stderr, "       mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat] [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n");
+        fprintf(stderr, "%s", REPACK_USAGE);
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
@@ -255,21 +386,7 @@ int main(int argc, char **argv) {
                gpus, params.exchange ? transport.c_str() : "none", params.specRounds, enc.droppedExtensionBytes(), enc.maxReferenceLength());
         return finish(0);
     }
-    dump(pos[1], "literals", enc.literals);
-    if (params.rcRedundancyRemoval) { dump(pos[1], "rcMapOff", enc.rcMapOff); dump(pos[1], "rcMapLen", enc.rcMapLen); }
-    dump(pos[1], "locksPos", enc.locksPosStream);
-    dump(pos[1], "gapDelta", enc.gapDeltas);
-    dump(pos[1], "flags", enc.gapMismatchesFlags);
-    dump(pos[1], "mapOff", enc.mapOff);
-    dump(pos[1], "mapOff5th", enc.mapOff5thByte);
-    dump(pos[1], "mapLen", enc.mapLen);
-    dump(pos[1], "refExtSize", enc.refExtSizeStream);
-    dump(pos[1], "meta", enc.metaBytes());                                      // what `mbgc-hip d` needs beyond the streams
-    if (!params.exchange) {                                                     // ... and `d --fasta` beyond that: names, headers, line lengths
-        dump(pos[1], "names", enc.namesStream);
-        dump(pos[1], "headers", enc.headersStream);
-        dump(pos[1], "dnaLineLengths", enc.lineLengthsStream);
-    }
+    writeStreamSet(pos[1], enc, params);
     if (enc.singleFastaFile()) {
         const std::vector<uint32_t> &counts = enc.sequenceCounts();
         dump(pos[1], "seqCounts", std::string((const char *) counts.data(), counts.size() * sizeof(uint32_t)));

@@ -368,6 +368,7 @@ void MultipleGenomeMatchingProcessor::noteUnitsArrived(const RoundBatch &B, uint
 // files [f0, f1) of the list -> their contigs back to back in B.seqDev; contig c belongs to target targetBase + (file - f0)
 void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t afterF0, uint32_t afterF1) {
     openInputStage();
+    if (resident) { prepareRoundResident(f0, f1, B); return; }
     if (singleFastaFileMode) { prepareRoundSingleFasta(f0, f1, B); return; }
     const int nf = (int) (f1 - f0);
     if (nf <= 0) {                                           // (a rank without targets in a short last round)
@@ -523,10 +524,64 @@ void MultipleGenomeMatchingProcessor::keepHeadersFromDevice(RoundBatch &B, const
     }
 }
 
-// ---------------------------------------------------------------- single fasta file mode (`-i`)
 static void inputStageCheck(int rc) {
     if (rc != 0) { fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error()); exit(EXIT_FAILURE); }
 }
+
+// ---------------------------------------------------------------- the resident source (`mbgc-hip r`)
+// The first unit: its contigs come down once (they become the reference string and the head of the literal stream on the host, as
+// the first file of a list does), and the protein probe runs over the records where they lie — already folded when -U packed
+// them, as the parser leaves a file's. The file's size is the unit's text size.
+void MultipleGenomeMatchingProcessor::readG0Resident(std::vector<Contig> &out, uint64_t *fileSize) {
+    const ResidentUnit &U = resident->units[0];
+    const uint64_t bytes = residentUnitOff[1] - residentUnitOff[0], nrec = U.contigLen.size();
+    std::vector<uint64_t> off(nrec), len(U.contigLen);
+    for (uint64_t k = 0, at = residentUnitOff[0]; k < nrec; at += len[k], k++) off[k] = at;
+    uint64_t probed = nrec;                                  // MGMP.cpp:85-87 / :91-98, the rule of probeG0Records
+    if (params->sequentialMatching && nrec) {
+        uint64_t seen = len[0];
+        for (probed = 1; seen < MBGC_FASTA_PROBE_MIN_LEN && probed < nrec; probed++) seen += len[probed];
+    }
+    mbgc_fasta_probe_result_t res;
+    inputStageCheck(mbgc_fasta_probe_dev(fasta, resident->packedDev, resident->packedBytes, off.data(), len.data(), probed, params->k, &params->probe, &res));
+    if (res.fired && (!params->sequentialMatching || res.record == 0)) setProteinsProfile();
+    std::string seq(bytes, '\0');
+    if (bytes) inputStageCheck(mbgc_fasta_download(fasta, &seq[0], resident->packedDev + residentUnitOff[0], bytes));
+    out.clear();
+    size_t h = 0;
+    for (uint64_t k = 0; k < nrec; k++) {
+        Contig c;
+        const size_t e = U.headers.find('\n', h);
+        c.header.assign(U.headers, h, e - h);
+        h = e + 1;
+        c.seq.assign(seq, off[k] - residentUnitOff[0], len[k]);
+        out.push_back(std::move(c));
+    }
+    hostLineLen = U.lineLen;
+    *fileSize = U.text;
+}
+
+// units [f0, f1) -> B: their contigs are a slice of the packed buffer, the layout `mbgc-hip d --fasta` needs comes with the units
+void MultipleGenomeMatchingProcessor::prepareRoundResident(uint32_t f0, uint32_t f1, RoundBatch &B) {
+    B.offsets.assign(1, 0); B.targetOf.clear(); B.bytes = 0;
+    B.unitHeaders.clear(); B.unitLineLen.clear();
+    B.seqDev = nullptr; B.seqCap = 0; B.borrowed = true;
+    if (f1 <= f0) return;
+    B.seqDev = resident->packedDev + residentUnitOff[f0];
+    for (uint32_t f = f0; f < f1; f++) {
+        const ResidentUnit &U = resident->units[f];
+        totalFilesLength += U.text;
+        for (uint64_t len : U.contigLen) {
+            largestContigSize = std::max<uint64_t>(largestContigSize, len);
+            B.offsets.push_back(B.offsets.back() + len);
+            B.targetOf.push_back(f - f0);
+        }
+        if (keepsLayout()) { B.unitHeaders.push_back(U.headers); B.unitLineLen.push_back(U.lineLen); }
+    }
+    B.bytes = B.offsets.back();
+}
+
+// ---------------------------------------------------------------- single fasta file mode (`-i`)
 
 void MultipleGenomeMatchingProcessor::sfOpen(const std::string &path) {
     openInputStage();
@@ -841,6 +896,7 @@ size_t MultipleGenomeMatchingProcessor::refLengthLimitFor(size_t basicRefLength,
 uint32_t MultipleGenomeMatchingProcessor::windowRoundSize(uint64_t window, int gpus) const {
     uint64_t largest = singleFastaFileMode ? 2 * MGMP_Params::MIN_BASIC_BLOCK_SIZE : 0;     // (elements: a block and the rest of a contig)
     for (uint32_t f = 1; f < filesCount; f++) {
+        if (resident) { largest = std::max<uint64_t>(largest, resident->units[f].text); continue; }
         struct stat st;
         if (stat(fileNames[f].c_str(), &st) != 0) continue;
         const std::string &n = fileNames[f];
@@ -866,7 +922,8 @@ void MultipleGenomeMatchingProcessor::loadG0Ref(const std::string &refName) {
     if (singleFastaFileMode) { loadG0RefSingleFasta(); return; }
     std::vector<Contig> contigs;
     uint64_t fileSize = 0;
-    readG0(refName, contigs, &fileSize);
+    if (resident) readG0Resident(contigs, &fileSize);
+    else readG0(refName, contigs, &fileSize);
     std::string refStr;
     initStreamsForG0Ref();
     g0LineLen = hostLineLen;
@@ -979,7 +1036,7 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
     collectPrev(false);
     appendsDone();
     if (ahead.active) { ahead.done.wait(); ahead.active = false; }
-    for (auto &B : three) if (B.seqDev) matcher->devFree(B.seqDev);
+    for (auto &B : three) if (B.seqDev && !B.borrowed) matcher->devFree(B.seqDev);
 }
 
 // The extension strings of the targets [ta, tb) of a round (indices inside the round), :389-398: a target's contigs (and
@@ -1338,7 +1395,7 @@ void MultipleGenomeMatchingProcessor::processTargetsRounds() {
         matchingLocksPos.resize(targetsCount);
         seqsCounts.resize(targetsCount);
     }
-    for (auto &B : slots) if (B.seqDev) matcher->devFree(B.seqDev);
+    for (auto &B : slots) if (B.seqDev && !B.borrowed) matcher->devFree(B.seqDev);
 }
 
 
@@ -1578,8 +1635,22 @@ void MBGC_Encoder::appendTargetStreams(uint32_t targetIdx) {
     if (backendStream && targetsAppended % BACKEND_FEED_EVERY == 0) feedBackendStream(false);
 }
 
+void MBGC_Encoder::encodeResident(const ResidentCollection &collection) {
+    resident = &collection;
+    fasta = collection.fasta;
+    residentUnitOff.assign(1, 0);
+    std::vector<std::string> names;
+    for (const ResidentUnit &U : collection.units) {
+        uint64_t bytes = 0;
+        for (uint64_t len : U.contigLen) bytes += len;
+        residentUnitOff.push_back(residentUnitOff.back() + bytes);
+        names.push_back(U.name);
+    }
+    encode(names);
+}
+
 void MBGC_Encoder::encode(const std::vector<std::string> &files) {
-    singleFastaFileMode = !params->inputFileName.empty();                                       // ENC.cpp:775
+    singleFastaFileMode = !resident && !params->inputFileName.empty();                          // ENC.cpp:775
     fileNames = singleFastaFileMode ? std::vector<std::string>(1, params->inputFileName) : files;
     filesCount = (uint32_t) fileNames.size();
     if (!filesCount) {
@@ -1599,7 +1670,7 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
     const bool autoRound = params->roundSize <= 0 && !params->sequentialMatching;
     if (autoRound && !singleFastaFileMode) {                                                    // a first guess from the file's size (the sequence is a little shorter): what the read-ahead starts with
         struct stat st;
-        const uint64_t g0 = stat(fileNames[0].c_str(), &st) == 0 ? (uint64_t) st.st_size : 0;
+        const uint64_t g0 = resident ? resident->units[0].text : (stat(fileNames[0].c_str(), &st) == 0 ? (uint64_t) st.st_size : 0);
         MBGC_Params guessParams = *params;
         if (guessParams.referenceFactor < 1) {
             int tmp = 15 - (__builtin_clz((unsigned) filesCount) / 3);
@@ -1613,7 +1684,7 @@ void MBGC_Encoder::encode(const std::vector<std::string> &files) {
         MultipleGenomeMatchingProcessor::params = keep;
         params->roundSize = (int) windowRoundSize(params->circularReference ? lim / (size_t) params->referenceSlidingWindowFactor : 0, gpus);
     }
-    if (!params->sequentialMatching && !params->exchange && !singleFastaFileMode)
+    if (!params->sequentialMatching && !params->exchange && !singleFastaFileMode && !resident)
         startReadAhead(1, std::min<uint32_t>(filesCount, 1 + (uint32_t) std::max(1, params->roundSize)), 1, readBesideUpload());
     const double tG0 = nowSeconds();
     loadG0Ref(fileNames[0]);

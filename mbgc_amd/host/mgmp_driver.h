@@ -94,10 +94,12 @@ struct MBGC_Params : MGMP_Params {                     // mbgccoder/MBGC_Params.
 };
 
 struct Contig { std::string header, seq; };
+struct ResidentCollection;                             // mbgc_decoder.h: a collection that a decode left on the device (`mbgc-hip r`)
 // A round's files parsed by the device input stage (include/mbgc_fasta.h: kseq_read_lossless_fasta, MGMP.cpp:349-372):
 // their contigs back to back in HBM, the layout matchRound takes.
 struct RoundBatch {
     uint8_t *seqDev = nullptr; size_t seqCap = 0;      // grow-only device buffer
+    bool borrowed = false;                             // seqDev is a slice of the resident source's buffer: not this batch's to free
     uint64_t bytes = 0;
     std::vector<uint64_t> offsets;                     // ncont + 1
     std::vector<uint32_t> targetOf;                    // target index of every contig
@@ -181,6 +183,13 @@ protected:
     void noteUnitArrived(LayoutUnit &&u);
     void keepHeaders(RoundBatch &B, const uint8_t *fileBytes, const uint64_t *fileOff, const uint64_t *recBase, const uint64_t *lineLen, int nf);
     void openInputStage();
+    // The resident source (`mbgc-hip r`), beside the file list and single fasta file mode: the units of a collection that
+    // MBGC_Decoder::decode left packed in HBM. fileNames holds their names, and nothing is read, uploaded or parsed: a round is a
+    // slice of the packed buffer. Wherever a file's size in bytes counts, the unit's text size does (ResidentUnit::text).
+    const ResidentCollection *resident = nullptr;
+    std::vector<uint64_t> residentUnitOff;                                              // unit u's contigs start here in the packed buffer (units + 1)
+    void readG0Resident(std::vector<Contig> &out, uint64_t *fileSize);                  // the first unit, down to the host once, probed where it lies
+    void prepareRoundResident(uint32_t f0, uint32_t f1, RoundBatch &B);
     void readG0(const std::string &path, std::vector<Contig> &out, uint64_t *fileSize);
     // probeG0: the file is the initial reference, and its parsed records are probed for the protein profile before they come down
     void parseHostBytes(const std::string &data, const std::string &name, std::vector<Contig> &out, bool probeG0 = false);
@@ -293,6 +302,9 @@ public:
 
     explicit MBGC_Encoder(MBGC_Params *p) : MultipleGenomeMatchingProcessor(p), params(p) { device = p->device; }
     void encode(const std::vector<std::string> &files);                                 // :759-807 up to performMatching()
+    // the same over a resident collection: its units are the files, in order; the encoder's input stage is the collection's from
+    // here on (and is destroyed with the encoder), the packed buffer stays the caller's
+    void encodeResident(const ResidentCollection &collection);
     // prepareAndCompressStreams' collective section (:641-710) for the streams this path produces — the file-name / header /
     // line-length streams belong to the part of the tool that is not rebuilt here and go in empty (eight zero bytes each) —
     // with the caller's leaf coders; what CompressionJob::writeCompressedCollectiveParallel would write for them
