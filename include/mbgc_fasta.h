@@ -133,6 +133,18 @@ int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, 
 int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
                              uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems);
 
+/* The same with a rule for what a mark is; flags = 0 is the call above (any '>'). What `mbgc-hip c --lossy-file` cuts its sequential
+ * batches with: under kseq_read_lossy a record starts at a line whose first byte is '>' or '@' and nowhere else, so a cut that is a
+ * mark by both flags stands between two records of the one stream — no record's state crosses it, and the byte before it is '\n'.
+ *   MBGC_FASTA_SPLIT_LINE_START   a mark counts only at offset 0 of the BUFFER (not of `start`) or right behind a '\n'
+ *   MBGC_FASTA_SPLIT_AT           '@' is a mark beside '>'
+ * Thresholds, isFileEnd, ends and scannedBefore as above; the tile array the handle keeps holds the marks of the flags it was made
+ * with, so a call whose flags differ from the last one's scans everything again. Other bits in flags are refused (-103). */
+#define MBGC_FASTA_SPLIT_LINE_START 1u
+#define MBGC_FASTA_SPLIT_AT 2u
+int mbgc_fasta_split_buf_dev2(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
+                              uint64_t firstMin, uint64_t nextMin, uint32_t flags, int maxElems, uint64_t *ends, int *nElems);
+
 /* The way back (`mbgc-hip d --fasta`): FASTA text from contigs in HBM. seq_dev[0..seqBytes) holds the contigs, headers_dev[0..
  * headerBytes) a copy of the header bytes, recs (host, nrec entries) says for every record of the text, in order, where its contig
  * and its header lie and the line length of its unit (KSEQ_DNA_LINE_LENGTH; 0: every sequence on one line). A record's text is

@@ -562,6 +562,17 @@ __device__ __forceinline__ uint32_t first_gt_in_word(uint32_t w) {
     return z ? (uint32_t) (__builtin_ctz(z) >> 3) : 4u;
 }
 
+// the split's marks under the flags of mbgc_fasta_split_buf_dev2; F = 0: any '>', the code as it was
+constexpr uint32_t SPLIT_LS = MBGC_FASTA_SPLIT_LINE_START, SPLIT_AT = MBGC_FASTA_SPLIT_AT;
+
+// 0x80 in every byte of w that equals the byte repeated in pat, and nowhere else (first_gt_in_word's cheaper form lets a borrow
+// run into the bytes above the first hit: good for a first hit, not for a mask that is shifted and ANDed)
+__device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t pat) {
+    const uint32_t x = w ^ pat;
+    return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+}
+
+template <uint32_t F>
 __global__ void __launch_bounds__(THREADS) k_fa_first_gt(const uint8_t *__restrict__ f, uint64_t n, uint32_t tile0, uint32_t ntiles,
                                                          uint32_t *__restrict__ tileFirst) {       // tiles [tile0, ntiles)
     const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -582,25 +593,68 @@ __global__ void __launch_bounds__(THREADS) k_fa_first_gt(const uint8_t *__restri
             memcpy(&v[i], t, PER);
         }
     }
+    // the byte in front of the tile: across the tile edge, and, for a scan that is resumed, across the seam of the kept tile
+    // array (the bytes before it have not changed); offset 0 of the buffer is a line start
+    uint32_t behind = '\n';
+    if constexpr ((F & SPLIT_LS) != 0) if (ts) behind = src[-1];
     uint32_t first = NO_GT;
+    if constexpr (F == 0) {
 #pragma unroll
-    for (int i = 0; i < TILE_LOADS; i++) {
-        const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-        uint32_t mine = NO_GT;
+        for (int i = 0; i < TILE_LOADS; i++) {
+            const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+            uint32_t mine = NO_GT;
 #pragma unroll
-        for (int k = 3; k >= 0; k--) {
-            const uint32_t b = first_gt_in_word(w[k]);
-            if (b < 4) mine = (uint32_t) k * 4 + b;
+            for (int k = 3; k >= 0; k--) {
+                const uint32_t b = first_gt_in_word(w[k]);
+                if (b < 4) mine = (uint32_t) k * 4 + b;
+            }
+            const unsigned long long m = __ballot(mine != NO_GT);
+            if (m && first == NO_GT) {
+                const int l = __builtin_ctzll(m);
+                first = (uint32_t) i * (WAVE * PER) + (uint32_t) l * PER + (uint32_t) __shfl((int) mine, l);
+            }
         }
-        const unsigned long long m = __ballot(mine != NO_GT);
-        if (m && first == NO_GT) {
-            const int l = __builtin_ctzll(m);
-            first = (uint32_t) i * (WAVE * PER) + (uint32_t) l * PER + (uint32_t) __shfl((int) mine, l);
+    } else {
+        // "the byte before is '\n'" is the LF mask moved up one byte: inside a dword a shift, from dword to dword a carried bit, from
+        // lane to lane one shuffle of the four loads' last-byte bits, from load to load lane 63's bits — bit i of `before` says it
+        // of the first byte of this lane's load i
+        uint32_t before = 0;
+        if constexpr ((F & SPLIT_LS) != 0) {
+            uint32_t last = 0;
+#pragma unroll
+            for (int i = 0; i < TILE_LOADS; i++) last |= (uint32_t) ((v[i].w >> 24) == '\n') << i;
+            const uint32_t up = (uint32_t) __shfl_up((int) last, 1), end = (uint32_t) __shfl((int) last, WAVE - 1);
+            before = lane ? up : (end << 1) | (uint32_t) (behind == '\n');
+        }
+#pragma unroll
+        for (int i = 0; i < TILE_LOADS; i++) {
+            const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+            uint32_t carry = ((before >> i) & 1u) << 7, hit[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint32_t marks = eq_bytes(w[k], 0x3e3e3e3eu);
+                if constexpr ((F & SPLIT_AT) != 0) marks |= eq_bytes(w[k], 0x40404040u);
+                if constexpr ((F & SPLIT_LS) != 0) {
+                    const uint32_t lf = eq_bytes(w[k], 0x0a0a0a0au);
+                    marks &= (lf << 8) | carry;
+                    carry = lf >> 24;
+                }
+                hit[k] = marks;
+            }
+            uint32_t mine = NO_GT;
+#pragma unroll
+            for (int k = 3; k >= 0; k--) if (hit[k]) mine = (uint32_t) k * 4 + (uint32_t) (__builtin_ctz(hit[k]) >> 3);
+            const unsigned long long m = __ballot(mine != NO_GT);
+            if (m && first == NO_GT) {
+                const int l = __builtin_ctzll(m);
+                first = (uint32_t) i * (WAVE * PER) + (uint32_t) l * PER + (uint32_t) __shfl((int) mine, l);
+            }
         }
     }
     if (lane == 0) tileFirst[tile] = first;
 }
 
+template <uint32_t F>
 __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restrict__ f, uint64_t n, const uint32_t *__restrict__ tileFirst,
                                                          uint32_t ntiles, uint64_t start, int isFileEnd, uint64_t firstMin, uint64_t nextMin,
                                                          int maxElems, uint64_t *__restrict__ res) {   // res[0] = elements found, res[1 + j] = end of element j
@@ -617,11 +671,18 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
             const uint64_t tbase = (uint64_t) t * CHUNK;
             const uint32_t tf = tileFirst[t];
             if (tf != NO_GT && tbase + tf >= thr) e = tbase + tf;
-            else if (tf != NO_GT) {                                // the tile's first '>' stands before the threshold: the rest of the tile
+            else if (tf != NO_GT) {                                // the tile's first mark stands before the threshold: the rest of the tile
                 const uint64_t tend = tbase + CHUNK < n ? tbase + CHUNK : n;
                 for (uint64_t b = thr; b < tend && e == NONE; b += WAVE) {
                     const uint64_t p = b + lane;
-                    const unsigned long long m = __ballot(p < tend && f[p] == '>');
+                    bool mark = false;
+                    if constexpr (F == 0) mark = p < tend && f[p] == '>';
+                    else if (p < tend) {                           // (p >= thr > 0: the byte before p is in the buffer)
+                        const uint8_t c = f[p];
+                        mark = c == '>' || ((F & SPLIT_AT) != 0 && c == '@');
+                        if constexpr ((F & SPLIT_LS) != 0) mark = mark && f[p - 1] == '\n';
+                    }
+                    const unsigned long long m = __ballot(mark);
                     if (m) e = b + (uint64_t) __builtin_ctzll(m);
                 }
             }
@@ -643,6 +704,15 @@ __global__ void __launch_bounds__(WAVE) k_fa_split_chain(const uint8_t *__restri
         s = e;
     }
     if (lane == 0) res[0] = (uint64_t) j;
+}
+
+// the two kernels of a split under F: one instantiation per rule, and the one without flags is the code as it was
+template <uint32_t F>
+static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint32_t tile0, uint32_t ntiles, int isFileEnd,
+                         uint64_t firstMin, uint64_t nextMin, int maxElems, uint32_t *tileFirst, uint64_t *res) {
+    if (tile0 < ntiles)
+        k_fa_first_gt<F><<<dim3((ntiles - tile0 + THREADS / WAVE - 1) / (THREADS / WAVE)), dim3(THREADS), 0, stream>>>(buf_dev, n, tile0, ntiles, tileFirst);
+    k_fa_split_chain<F><<<dim3(1), dim3(WAVE), 0, stream>>>(buf_dev, n, tileFirst, ntiles, start, isFileEnd, firstMin, nextMin, maxElems, res);
 }
 
 #include "fasta_format.h"
@@ -852,8 +922,9 @@ struct mbgc_fasta {
     fa::Buf<mbgc_fasta_record_t> dRecs;
     fa::Buf<uint64_t> dShift;                   // lossy rule: every file's bytes in front of its first marker
     fa::Buf<uint8_t> dHostIn, dHostOut;         // mbgc_fasta_parse_host: the file and its sequences on the device
-    fa::Buf<uint32_t> dTileFirst;               // mbgc_fasta_split_dev: first '>' of every tile, and its result
+    fa::Buf<uint32_t> dTileFirst;               // mbgc_fasta_split_dev: first '>' (first mark, under tileFlags) of every tile, and its result
     fa::Buf<uint64_t> dSplit;
+    uint32_t tileFlags = 0;                     // the flags dTileFirst was made with
     fa::Buf<fa::FmtRec> dFmtRecs;               // mbgc_fasta_format_dev: the record table and the tiles' owners
     fa::Buf<uint32_t> dFmtOwner;
     hipEvent_t fmtEv[2] = {nullptr, nullptr};   // around the format launches (made at the first call that asks for the time)
@@ -1078,10 +1149,11 @@ int mbgc_fasta_probe_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, u
     return mbgc_fasta_probe_dev(p, p->dHostOut.p, p->hostParsedBytes, off.data(), len.data(), nrec, k, state_inout, result_out);
 }
 
-int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
-                             uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems) {
+int mbgc_fasta_split_buf_dev2(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
+                              uint64_t firstMin, uint64_t nextMin, uint32_t flags, int maxElems, uint64_t *ends, int *nElems) {
     using namespace fa;
     *nElems = 0;
+    if (flags & ~(MBGC_FASTA_SPLIT_LINE_START | MBGC_FASTA_SPLIT_AT)) return fail(-103, "split: unknown flags %#x", flags);
     if (maxElems <= 0 || firstMin == 0 || nextMin == 0) return fail(-103, "split: maxElems and the minimal element sizes must be positive");
     if (start > n || scannedBefore > n) return fail(-103, "split: the window starts or was scanned behind its end");
     if (n == start) return 0;
@@ -1089,14 +1161,19 @@ int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t s
     FCHK(hipSetDevice(p->device));
     const uint32_t ntiles = (uint32_t) ((n + CHUNK - 1) / CHUNK);
     if (ntiles > p->dTileFirst.cap) scannedBefore = 0;              // (the tile array is made anew: nothing of it is kept)
+    if (flags != p->tileFlags) scannedBefore = 0;                   // (... or holds another rule's marks)
+    p->tileFlags = flags;
     int r;
     if ((r = p->dTileFirst.reserve(ntiles)) || (r = p->dSplit.reserve((size_t) maxElems + 1))) return r;
     // the tiles that were whole at the last call stand; the pass starts at the first one that was not, or that lies before the
     // window's start (nothing reads those)
     const uint32_t tile0 = (uint32_t) (std::max(scannedBefore, start / CHUNK * CHUNK) / CHUNK);
-    if (tile0 < ntiles)
-        k_fa_first_gt<<<dim3((ntiles - tile0 + THREADS / WAVE - 1) / (THREADS / WAVE)), dim3(THREADS), 0, p->stream>>>(buf_dev, n, tile0, ntiles, p->dTileFirst.p);
-    k_fa_split_chain<<<dim3(1), dim3(WAVE), 0, p->stream>>>(buf_dev, n, p->dTileFirst.p, ntiles, start, isFileEnd, firstMin, nextMin, maxElems, p->dSplit.p);
+    switch (flags) {
+    case 0: launch_split<0>(p->stream, buf_dev, start, n, tile0, ntiles, isFileEnd, firstMin, nextMin, maxElems, p->dTileFirst.p, p->dSplit.p); break;
+    case 1: launch_split<1>(p->stream, buf_dev, start, n, tile0, ntiles, isFileEnd, firstMin, nextMin, maxElems, p->dTileFirst.p, p->dSplit.p); break;
+    case 2: launch_split<2>(p->stream, buf_dev, start, n, tile0, ntiles, isFileEnd, firstMin, nextMin, maxElems, p->dTileFirst.p, p->dSplit.p); break;
+    default: launch_split<3>(p->stream, buf_dev, start, n, tile0, ntiles, isFileEnd, firstMin, nextMin, maxElems, p->dTileFirst.p, p->dSplit.p); break;
+    }
     FCHK(hipGetLastError());
     // the count and the ends in one copy (a round's elements are a handful; a longer list takes a second one)
     const size_t FIRST = 256;
@@ -1113,6 +1190,11 @@ int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t s
     }
     *nElems = (int) ne;
     return 0;
+}
+
+int mbgc_fasta_split_buf_dev(mbgc_fasta_t *p, const uint8_t *buf_dev, uint64_t start, uint64_t n, uint64_t scannedBefore, int isFileEnd,
+                             uint64_t firstMin, uint64_t nextMin, int maxElems, uint64_t *ends, int *nElems) {
+    return mbgc_fasta_split_buf_dev2(p, buf_dev, start, n, scannedBefore, isFileEnd, firstMin, nextMin, 0, maxElems, ends, nElems);
 }
 
 int mbgc_fasta_split_dev(mbgc_fasta_t *p, const uint8_t *bytes_dev, uint64_t n, int isFileEnd, uint64_t firstMin, uint64_t nextMin,

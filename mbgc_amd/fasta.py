@@ -6,12 +6,13 @@ import numpy as np
 from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
-           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
+           mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
 EFASTQ = -16                         # MBGC_FASTA_EFASTQ
+SPLIT_LINE_START, SPLIT_AT = 1, 2    # MBGC_FASTA_SPLIT_LINE_START, MBGC_FASTA_SPLIT_AT
 
 
 class Record(C.Structure):
@@ -112,6 +113,8 @@ def _lib():
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mbgc_fasta_split_buf_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.mbgc_fasta_split_buf_dev2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.mbgc_fasta_format_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(FormatRecord), C.c_uint64,
                                             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_gather_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint8,
@@ -256,6 +259,16 @@ class FastaParser:
         ne = C.c_int(0)
         if _lib().mbgc_fasta_split_buf_dev(self.h, buf_ptr, int(start), int(n), int(scanned_before), int(bool(is_file_end)), int(first_min),
                                            int(next_min), int(max_elems), ends.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ne)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return [int(e) for e in ends[:ne.value]]
+
+    def split_buf_dev2(self, buf_ptr, start, n, scanned_before, is_file_end, first_min, next_min, flags, max_elems):
+        """split_buf_dev with a rule for what a mark is: SPLIT_LINE_START (only at offset 0 of the buffer or right behind a line
+        feed), SPLIT_AT ('@' beside '>'); flags = 0 is split_buf_dev"""
+        ends = np.zeros(max(int(max_elems), 1), dtype=np.uint64)
+        ne = C.c_int(0)
+        if _lib().mbgc_fasta_split_buf_dev2(self.h, buf_ptr, int(start), int(n), int(scanned_before), int(bool(is_file_end)), int(first_min),
+                                            int(next_min), int(flags), int(max_elems), ends.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ne)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return [int(e) for e in ends[:ne.value]]
 

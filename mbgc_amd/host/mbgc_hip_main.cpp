@@ -138,7 +138,7 @@ static int repackMain(int argc, char **argv) {
         else if (a == "--ref-factor" && i + 1 < argc) params.referenceFactor = atoi(argv[++i]);
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "--bench") bench = true;
-        else if (a == "--gpus" || a == "-i" || a == "--lossy" || a == "--inflate" || a == "--backend") {
+        else if (a == "--gpus" || a == "-i" || a == "--lossy" || a == "--lossy-file" || a == "--inflate" || a == "--backend") {
             fprintf(stderr, "mbgc-hip r: %s is an option of mbgc-hip c, over files: r takes its input from a stream set, on one GPU, and writes raw streams\n", a.c_str());
             return EXIT_FAILURE;
         }
@@ -204,6 +204,7 @@ int main(int argc, char **argv) {
     size_t shmMb = 64;
     std::string backend;                                                        // a library with the reference's leaf coders (mbgc_leaf_compress)
     int backendThreads = 8, backendBlocksScale = 1, coderThreads = 0;
+    bool lossyList = false;                                                     // --lossy was given (the list's option; a single file takes --lossy-file)
     uint64_t backendOverlapBlock = 0;                                           // > 0: the backend runs beside the matching, blocks of this many bytes           // coderThreads: the reference's -t as the coders see it (0: the pool's size)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -220,12 +221,13 @@ int main(int argc, char **argv) {
             if (params.k < 16 || params.k > 40) { fprintf(stderr, "k - matching kmer length - should be an integer between 16 and 40.\n\n"); return EXIT_FAILURE; }
         }
         else if (a == "-i" && i + 1 < argc) params.inputFileName = argv[++i];      // single fasta file mode (MBGC_Params.h:793-803)
+        else if (a == "--lossy-file" && i + 1 < argc) { params.inputFileName = argv[++i]; params.allowLossyParsing = true; }   // the reference's -L -i <fastaFile>
         else if (a == "--window-kib" && i + 1 < argc) params.singleFileWindow = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "-L") params.lazyDecompressionSupport = false;             // disable lazy decompression support
         else if (a == "-U") params.uppercaseDNA = true;                          // MBGC_Params.h: converts bases to uppercase
         else if (a == "--proteins") params.setProteinsCompressionProfile();       // the reference's developer option -P (main.cpp:332-334); where it stands among the options matters as it does there
-        else if (a == "--lossy") params.allowLossyParsing = true;                 // the reference's -L (MGMP_Params.h:213): ragged lines, CRLF, leading junk are read, not refused
+        else if (a == "--lossy") params.allowLossyParsing = lossyList = true;                 // the reference's -L (MGMP_Params.h:213): ragged lines, CRLF, leading junk are read, not refused
         else if (a == "--inflate" && i + 1 < argc) {                             // where the gzip files of a list are inflated
             const std::string w = argv[++i];
             if (w != "host" && w != "device") { fprintf(stderr, "--inflate takes host or device\n"); return EXIT_FAILURE; }
@@ -251,7 +253,7 @@ int main(int argc, char **argv) {
     if (pos.size() != 2 || (single && !pos[0].empty())) {
         fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--inflate host|device] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
-                        "       mbgc-hip c -i <fastaFile> [--window-kib K] [the options above, without --gpus] <outputPrefix>\n"
+                        "       mbgc-hip c -i <fastaFile> | --lossy-file <fastaFile> [--window-kib K] [the options above, without --gpus and --lossy] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
                         "  2 MiB at '>' bytes, on the device, while it travels to the GPU in windows of K KiB (default 32768; host memory is bounded by two\n"
                         "  windows, except for a gzip file, which is inflated on the host and held whole in memory); also prints `single-file elements: <n>`\n"
@@ -263,6 +265,9 @@ int main(int argc, char **argv) {
                         "  probed length) > 10; -t1 / -m 3 take only the first record's verdict. An empty record is skipped (the reference divides by zero)\n"
                         "  --lossy: the files of the list are read as `mbgc c -L` reads them (any line lengths, empty lines, CRLF, bytes in front of the first\n"
                         "  '>'; the longest line becomes the file's line length); FASTQ files are refused; not with -i\n"
+                        "  --lossy-file <fastaFile>: -i <fastaFile> read by that rule (the reference's `mbgc c -L -i`): every element is read so, as a file\n"
+                        "  of its own, and keeps its own longest line; under -t1 / -m 3 and for a small file the file is one stream, cut into batches on\n"
+                        "  the device at lines that start with '>' or '@', and its longest line is the file's\n"
                         "  --inflate device: the gzip files of the list are uploaded compressed and inflated on the device, one wave per file, with their\n"
                         "  CRC-32 and length checked there; a file that does not inflate to the length its trailer states there (several members, a corrupt\n"
                         "  stream) is inflated by the host. The streams are the same either way. host (the default): zlib on the reader threads. The first\n"
@@ -282,8 +287,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "-i (single fasta file mode) runs on one GPU: the rounds sharded over --gpus N take a file list\n");
         return EXIT_FAILURE;
     }
-    if (single && params.allowLossyParsing) {
-        fprintf(stderr, "--lossy reads the files of a list: single fasta file mode (-i) cuts its elements by the lossless rule only\n");
+    if (single && lossyList) {
+        fprintf(stderr, "--lossy reads the files of a list and is not taken with -i: a single fasta file is read by the lossy rule when it is given as --lossy-file <fastaFile> (the reference's -L -i)\n");
         return EXIT_FAILURE;
     }
     if (gpus > 1 && params.verifyEmissions) {

@@ -94,7 +94,8 @@ static bool readWholeFile(const std::string &path, std::string &dest) {
     return true;
 }
 
-// the parser's flags for the files of a list (kseq_read_lossy under allowLossyParsing, MultipleGenomeMatchingProcessor.cpp:9-14)
+// the parser's flags for the files of a list and for the elements and batches of a single file: KSEQ_READ is one macro for all of
+// them (kseq_read_lossy under allowLossyParsing, MultipleGenomeMatchingProcessor.cpp:9-14)
 static uint32_t listParseFlags(const MGMP_Params *params) {
     return (params->uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u) | (params->allowLossyParsing ? MBGC_FASTA_LOSSY : 0u);
 }
@@ -165,7 +166,7 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
     // (the record table starts small and grows to what the parser asks for: one entry per two input bytes, the bound,
     // is gigabytes of zeroed memory for a round's files)
     if (records.size() < 4096) records.resize(4096);
-    const uint32_t flags = singleFastaFileMode ? (params->uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u) : listParseFlags(params);
+    const uint32_t flags = listParseFlags(params);                // (element 0 and the first record of -i are read as a list's files are)
     int rc = mbgc_fasta_parse_host2(fasta, (const uint8_t *) data.data(), data.size(), flags, (uint8_t *) &seq[0], &seqBytes,
                                     records.data(), records.size(), &nrec, &lineLen, &status);
     if (rc == -104) {
@@ -694,10 +695,15 @@ void MultipleGenomeMatchingProcessor::sfElements(uint32_t want, uint64_t firstMi
 }
 
 // the file's first record (the sequential schedule's initial reference, MGMP.cpp:91-100): up to the first line that starts
-// with '>' behind the first byte — read on the host, it is needed there
+// with '>' behind the first byte — read on the host, it is needed there. Under the lossy rule (kseq.h:288-313) the record
+// starts at the file's first '>' or '@', wherever in a line that byte stands, and ends in front of the next line that starts with
+// one of the two; what stands in front of it and a '+' line inside it (FASTQ) go to the parser, which drops the one and refuses
+// the other
 std::string MultipleGenomeMatchingProcessor::sfFirstRecord() {
     std::string data;
     const uint64_t step = 1 << 20;
+    const bool lossy = params->allowLossyParsing;
+    size_t marker = std::string::npos;
     for (uint64_t at = 0; at < sf.fileSize;) {
         const uint64_t len = std::min(step, sf.fileSize - at);
         const size_t from = data.empty() ? 0 : data.size() - 1;
@@ -709,7 +715,14 @@ std::string MultipleGenomeMatchingProcessor::sfFirstRecord() {
             if (got != len) { fprintf(stderr, "Problem reading from file: %s\n", params->inputFileName.c_str()); exit(EXIT_FAILURE); }
         }
         at += len;
-        const size_t hit = data.find("\n>", from);
+        size_t hit = std::string::npos;
+        if (!lossy) hit = data.find("\n>", from);
+        else {
+            if (marker == std::string::npos) marker = data.find_first_of(">@", from);
+            if (marker != std::string::npos)
+                for (size_t lf = std::max(marker, from); (lf = data.find('\n', lf)) != std::string::npos && lf + 1 < data.size(); lf++)
+                    if (data[lf + 1] == '>' || data[lf + 1] == '@') { hit = lf; break; }
+        }
         if (hit != std::string::npos) { data.resize(hit + 1); break; }
     }
     return data;
@@ -772,7 +785,9 @@ void MultipleGenomeMatchingProcessor::loadG0RefSingleFasta() {
 // The next batch of the file. Rounds: elements f0 .. f1 - 1 (they follow each other: the cut of one is the start of the next), each
 // a target, parsed on its own as the reference parses its split files. Sequential schedule: the file is ONE target, and a batch is
 // whatever whole records the window holds — the split proposes cuts, and a cut is taken where a line starts (a '>' inside a header
-// line would make two records of one).
+// line would make two records of one). Under the lossy rule (--lossy-file) elements and batches are read by the lossy rule (an element as a file of its
+// own: what stands in front of its first marker is dropped, its line length is its own maximum), and the sequential cuts are the
+// line starts that are a '>' or an '@', found on the device.
 void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint32_t f1, RoundBatch &B) {
     const uint64_t BLOCK = MGMP_Params::MIN_BASIC_BLOCK_SIZE;
     B.offsets.assign(1, 0); B.targetOf.clear(); B.recCounts.clear(); B.bytes = 0; B.endOfInput = false;
@@ -788,9 +803,15 @@ void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint3
                 std::vector<uint64_t> e(most);
                 int n = 0;
                 const double t0 = nowSeconds();
-                inputStageCheck(mbgc_fasta_split_buf_dev(fasta, sf.dev, 0, sf.have, sf.scanned, 0, BLOCK, BLOCK, (int) most, e.data(), &n));
+                // lossy rule: a record starts at a line that begins with '>' or '@' and nowhere else, and the device finds exactly
+                // those — the last one is the cut. (Behind a line feed no CR is a batch's last byte and no record's state crosses
+                // the cut: the batches read as the one stream does. No cut in the window — one long record, CR-only line ends, more
+                // junk than a window in front: the window grows.)
+                const uint32_t rule = params->allowLossyParsing ? MBGC_FASTA_SPLIT_LINE_START | MBGC_FASTA_SPLIT_AT : 0u;
+                inputStageCheck(mbgc_fasta_split_buf_dev2(fasta, sf.dev, 0, sf.have, sf.scanned, 0, BLOCK, BLOCK, rule, (int) most, e.data(), &n));
                 sf.scanned = sf.have;
                 g_tParse += nowSeconds() - t0;
+                if (rule && n) cut = e[n - 1];
                 for (int k = n - 1; k >= 0 && !cut; k--) {
                     uint8_t before = 0;
                     inputStageCheck(mbgc_fasta_download(fasta, &before, sf.dev + e[k] - 1, 1));
@@ -819,12 +840,12 @@ void MultipleGenomeMatchingProcessor::prepareRoundSingleFasta(uint32_t f0, uint3
         std::vector<uint64_t> seqBase(nf + 1), recBase(nf + 1), lineLen(nf);
         std::vector<int> status(nf);
         if (records.size() < 4096) records.resize(4096);
-        int rc = mbgc_fasta_parse_batch_dev(fasta, sf.dev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
-                                            records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+        int rc = mbgc_fasta_parse_batch_dev2(fasta, sf.dev, fileOff.data(), nf, listParseFlags(params), B.seqDev, B.seqCap, seqBase.data(),
+                                             records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
         if (rc == -104) {
             records.resize(recBase[nf] + recBase[nf] / 4 + 16);
-            rc = mbgc_fasta_parse_batch_dev(fasta, sf.dev, fileOff.data(), nf, params->uppercaseDNA, B.seqDev, B.seqCap, seqBase.data(),
-                                            records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
+            rc = mbgc_fasta_parse_batch_dev2(fasta, sf.dev, fileOff.data(), nf, listParseFlags(params), B.seqDev, B.seqCap, seqBase.data(),
+                                             records.data(), records.size(), recBase.data(), lineLen.data(), status.data());
         }
         inputStageCheck(rc);
         for (int f = 0; f < nf; f++) {
@@ -1000,7 +1021,8 @@ void MultipleGenomeMatchingProcessor::processTargetsWithParallelIO() {
         if (!single) noteUnitsArrived(B, i);
         else if (!B.unitHeaders.empty()) {                                                     // (the file is one unit, whatever its batches)
             openUnit.headers += B.unitHeaders[0];
-            if (!openUnit.lineLen) openUnit.lineLen = B.unitLineLen[0];
+            if (params->allowLossyParsing) openUnit.lineLen = std::max(openUnit.lineLen, B.unitLineLen[0]);   // (maxLastDnaLineLen runs over the file)
+            else if (!openUnit.lineLen) openUnit.lineLen = B.unitLineLen[0];
         }
         if (!single || i == 0) {
             startPos = matcher->getLoadedRefLength();                                          // :251
@@ -1437,7 +1459,7 @@ void MultipleGenomeMatchingProcessor::performMatching() {
 
 // ---------------------------------------------------------------- MBGC_Encoder
 
-void MBGC_Encoder::initStreamsForG0Ref() { literals.clear(); }
+void MBGC_Encoder::initStreamsForG0Ref() { literals.clear(); metaG0Contigs = 0; }   // (called again when -i falls back to the sequential schedule)
 void MBGC_Encoder::processG0RefContig(const char *seq, size_t len) {
     literals.append(seq, len);
     literals.push_back(SEQ_SEPARATOR_MARK);
