@@ -5,6 +5,16 @@
 //   MBGC_Decoder   mbgccoder/MBGC_Decoder.{h,cpp}: decodeTarget (:535-634) and loadRef (:651-675) restated as a load
 //                  SCHEDULE — computed from the plan's lengths and unmatched counts before a base exists — and the driver
 //                  that runs plan, fills and loads through the C ABI (include/mbgc_swsem.h). No HIP headers here.
+// mbgc_decoder.cpp is one translation unit: the meta, the load schedule, decode() as the list of its stages, the command lines
+// and the C exports of the tests. The stages are headers it includes once:
+//   mbgc_decoder_streams.h    what is on disk: StreamSet (the files held to the meta, the -m 3 restore, the chain starts),
+//                             Selection (--select), chosenUnits (THE walk over the units that leave the decoder)
+//   mbgc_decoder_run.h        one pass on the device: Provenance, FillUnit / partitionUnits, DecodedCollection (the handle and
+//                             all it holds: plan + schedule, the closure of --select, the forward run)
+//   mbgc_decoder_fasta.h      text out of a DecodedCollection: FastaLayout, FastaPlan (units and batches, shared by `d --fasta`
+//                             and `v`), FastaStage (device buffers, formatBatch), writeFastaFiles (--gzip: deflateBatch)
+//   mbgc_decoder_validate.h   `v`: Validation (read-ahead, originals to the device, compare, verdicts, --dump)
+// Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -108,5 +118,13 @@ public:
 
 int mbgc_hip_decompress_main(int argc, char **argv);
 int mbgc_hip_validate_main(int argc, char **argv);
+// the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE;
+// The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
+// --restore-rc, --select, --select-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
+// -1: refused, the message is on stderr.
+int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decoder::Options &opt, bool &selectAsked);
+// after the command line: no empty pattern, no empty list; false: the message is on stderr
+bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool selectAsked);
 // --select-list: the file's non-empty lines behind `out`; false: it cannot be opened
 bool mbgc_hip_read_pattern_list(const char *path, std::vector<std::string> &out);

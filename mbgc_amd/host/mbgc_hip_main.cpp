@@ -107,14 +107,7 @@ static int repackMain(int argc, char **argv) {
     bool selectAsked = false, bench = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
-        if (a == "--select" && i + 1 < argc) { dopt.select.push_back(argv[++i]); selectAsked = true; }
-        else if (a == "--select-list" && i + 1 < argc) {
-            if (!mbgc_hip_read_pattern_list(argv[++i], dopt.select)) { fprintf(stderr, "mbgc-hip r: cannot open the pattern list %s\n", argv[i]); return EXIT_FAILURE; }
-            selectAsked = true;
-        }
-        else if (a == "--restore-rc") dopt.restoreRc = true;
-        else if (a == "--serial") dopt.serial = true;
-        else if (a == "--no-index") dopt.noIndex = true;
+        if (const int r = mbgc_hip_decode_option('r', argc, argv, i, dopt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }   // (-d: the device of both halves)
         else if (a == "-t1") params.sequentialMatching = true;
         else if (a == "-m" && i + 1 < argc) params.setCompressionMode(atoi(argv[++i]));
         else if (a == "-R" && i + 1 < argc) params.roundSize = atoi(argv[++i]);
@@ -136,7 +129,6 @@ static int repackMain(int argc, char **argv) {
         else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
         else if (a == "--verify") params.verifyEmissions = true;
         else if (a == "--ref-factor" && i + 1 < argc) params.referenceFactor = atoi(argv[++i]);
-        else if (a == "-d" && i + 1 < argc) params.device = atoi(argv[++i]);
         else if (a == "--bench") bench = true;
         else if (a == "--gpus" || a == "-i" || a == "--lossy" || a == "--lossy-file" || a == "--inflate" || a == "--backend") {
             fprintf(stderr, "mbgc-hip r: %s is an option of mbgc-hip c, over files: r takes its input from a stream set, on one GPU, and writes raw streams\n", a.c_str());
@@ -146,12 +138,11 @@ static int repackMain(int argc, char **argv) {
     }
     if (pos.size() != 2) { fprintf(stderr, "usage:\n%s", REPACK_USAGE); return EXIT_FAILURE; }
     if (pos[0] == pos[1]) { fprintf(stderr, "mbgc-hip r: the output prefix is the input prefix (%s): the input set would be overwritten while it is the only copy\n", pos[0].c_str()); return EXIT_FAILURE; }
-    if (selectAsked) for (const std::string &pat : dopt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip r: --select: an empty pattern\n"); return EXIT_FAILURE; }
-    if (selectAsked && dopt.select.empty()) { fprintf(stderr, "mbgc-hip r: --select-list: the list of patterns is empty\n"); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('r', dopt, selectAsked)) return EXIT_FAILURE;
+    params.device = dopt.device;
     MultipleGenomeMatchingProcessor::bindHostThreadsToDeviceNode(params.device);
     if (mbgc_fasta_create(&coll.fasta, params.device)) { fprintf(stderr, "mbgc-hip r: input stage: %s\n", mbgc_fasta_last_error()); return EXIT_FAILURE; }
     coll.packFlags = params.uppercaseDNA ? MBGC_FASTA_UPPERCASE : 0u;
-    dopt.device = params.device;
     dopt.resident = &coll;
     std::string error;
     if (MBGC_Decoder::decode(pos[0], std::string(), dopt, &error) != 0) {      // (its handle — streams, reference buffer, sequences — is gone when it returns)
@@ -274,9 +265,7 @@ int main(int argc, char **argv) {
                         "  file of the list and a gzip file given with -i are always inflated by the host\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       mbgc-hip d [--serial] [--no-index] [--bench] [--fasta dir [--gzip] [--batch-kib K]] [-d device] <streamsPrefix> <outputPrefix>\n");
-        fprintf(stderr, "       mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat] [--skip-compare] [--dump dir] [--bench] [--batch-kib K] [-d device] <streamsPrefix>\n");
-        fprintf(stderr, "%s", REPACK_USAGE);
+        fprintf(stderr, "       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_V_USAGE, REPACK_USAGE);
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
