@@ -190,6 +190,21 @@ typedef struct { uint64_t srcOff, len; } mbgc_fasta_pack_piece_t;
 int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcBytes, const mbgc_fasta_pack_piece_t *pieces, uint64_t n, uint32_t flags,
                         uint8_t *dst_dev, uint64_t dstCap, uint64_t *dstOff, double *kernelMs);
 
+/* The record selection of `mbgc-hip d --select-seq`: which headers contain one of a list of patterns. Record r is chosen iff its header
+ * bytes [hdrOff[r], hdrOff[r] + hdrLen[r]) of headers_dev (a buffer of headerBytes bytes) contain at least one pattern as a byte
+ * substring (case-sensitive, as std::string::find). patterns (host): the patterns back to back, pattern k at [patOff[k], patOff[k + 1]);
+ * every pattern is non-empty and holds no '\n' — one that is not is refused, as is a header outside the buffer (-103, message in
+ * mbgc_fasta_last_error; nothing is launched, chosen is left as it was). chosen (host, (nrec + 31) / 32 words) receives bit r & 31 of
+ * word r >> 5 per record; the bits behind the last record are 0. No pattern: no record is chosen.
+ * What a header byte costs does not grow with the number of patterns: a table keyed by the first m = min(8, shortest pattern) bytes of
+ * every pattern is probed once per position, and only the patterns that share those bytes are compared (the same pattern given twice
+ * is one). One wave per header, 64 positions at a time, the bytes staged in LDS; a wave leaves its header at the first hit and sets
+ * the record's bit with one atomic. No byte outside a record's own header is read or counted — not the line feed behind it, not the
+ * next header: a pattern longer than the header cannot match, a header of no bytes matches nothing. kernelMs (may be NULL): the
+ * kernel's time from events on the stream. Runs on the input stage's stream; synchronous. */
+int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, uint64_t headerBytes, const uint64_t *hdrOff, const uint64_t *hdrLen,
+                                 uint64_t nrec, const uint8_t *patterns, const uint64_t *patOff, uint64_t npat, uint32_t *chosen, double *kernelMs);
+
 /* gzip files that lie compressed in HBM, inflated there (mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

@@ -718,6 +718,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_format.h"
 #include "fasta_compare.h"
 #include "fasta_pack.h"
+#include "fasta_select.h"
 
 #define INF_CONST static __device__
 #define INF_LANES_DO(lane) for (uint32_t lane = threadIdx.x, once_ = 1; once_; once_ = 0)
@@ -804,6 +805,31 @@ __global__ void __launch_bounds__(THREADS) k_fa_pack(const uint8_t *__restrict__
     const uint32_t tile = tile0 + blockIdx.x;
     if (tile >= ntiles) return;
     pack_lane_step(src, P, owner, tile, threadIdx.x, mis, total, fold != 0, dst);
+}
+
+// mbgc_fasta_match_headers_dev: one wave per header, SEL_TILE positions at a time (the two lane steps: fasta_select.h). A block is one
+// wave, so the barrier between the steps stands in a loop whose trip count differs from header to header. The wave leaves its header
+// at the first tile with a hit, and one lane sets the record's bit: records share words, hence the atomic; no hit, no atomic.
+__global__ void __launch_bounds__(WAVE) k_fa_match_headers(const uint8_t *__restrict__ headers, const uint64_t *__restrict__ hdrOff, const uint64_t *__restrict__ hdrLen,
+                                                           uint64_t nrec, uint32_t m, const SelSlot *__restrict__ slots, uint32_t bits,
+                                                           const SelPat *__restrict__ pats, const uint8_t *__restrict__ patBytes, uint32_t *__restrict__ chosen) {
+    __shared__ uint8_t stage[SEL_STAGE + 1];
+    const uint32_t lane = threadIdx.x;
+    for (uint64_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        const uint8_t *hdr = headers + hdrOff[r];
+        const uint64_t len = hdrLen[r];
+        for (uint64_t base = 0; base + m <= len; base += SEL_TILE) {     // (uniform over the wave)
+            sel_stage_step(hdr, len, base, lane, m, stage);
+            __syncthreads();
+            const bool hit = sel_lane_step(hdr, len, base, lane, m, stage, slots, bits, pats, patBytes);
+            const unsigned long long any = __ballot(hit);
+            __syncthreads();                                             // (the next tile's stores wait for this tile's reads)
+            if (any) {
+                if (lane == 0) atomicOr(chosen + (r >> 5), 1u << (r & 31));
+                break;
+            }
+        }
+    }
 }
 
 // pieces of a device buffer packed back to back, each followed by one separator byte (the headers of a -i batch: only they travel
@@ -933,6 +959,11 @@ struct mbgc_fasta {
     fa::Buf<unsigned long long> dCmpOut;
     fa::Buf<fa::PackPiece> dPackPieces;         // mbgc_fasta_pack_dev: the piece table and the tiles' owners
     fa::Buf<uint32_t> dPackOwner;
+    fa::Buf<uint64_t> dSelRecs;                 // mbgc_fasta_match_headers_dev: the headers' offsets and lengths, the pattern table, the bits
+    fa::Buf<fa::SelSlot> dSelSlots;
+    fa::Buf<fa::SelPat> dSelPats;
+    fa::Buf<uint8_t> dSelBytes;
+    fa::Buf<uint32_t> dSelChosen;
     fa::Buf<fa::InfJob> dInfJobs;               // mbgc_fasta_inflate_dev: the jobs and their results
     fa::Buf<fa::InfResult> dInfResults;
     fa::Buf<fa::DefChunk> dDefChunks;           // mbgc_fasta_deflate_dev: the chunk table, the chunks' slots and what they hold, the pack tables
@@ -978,6 +1009,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
     p->dPackPieces.release(); p->dPackOwner.release();
+    p->dSelRecs.release(); p->dSelSlots.release(); p->dSelPats.release(); p->dSelBytes.release(); p->dSelChosen.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
@@ -1321,6 +1353,47 @@ int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcByt
     if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    return 0;
+}
+
+int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, uint64_t headerBytes, const uint64_t *hdrOff, const uint64_t *hdrLen,
+                                 uint64_t nrec, const uint8_t *patterns, const uint64_t *patOff, uint64_t npat, uint32_t *chosen, double *kernelMs) {
+    using namespace fa;
+    if (kernelMs) *kernelMs = 0;
+    if (nrec >= 0xffffffffull || npat >= 0x7fffffffull) return fail(-103, "match: %llu records, %llu patterns in one call", (unsigned long long) nrec, (unsigned long long) npat);
+    for (uint64_t r = 0; r < nrec; r++)
+        if (hdrOff[r] > headerBytes || hdrLen[r] > headerBytes - hdrOff[r]) return fail(-103, "match: header %llu lies outside the headers", (unsigned long long) r);
+    for (uint64_t k = 0; k < npat; k++) {
+        if (patOff[k + 1] <= patOff[k]) return fail(-103, "match: pattern %llu is empty", (unsigned long long) k);
+        if (memchr(patterns + patOff[k], '\n', patOff[k + 1] - patOff[k])) return fail(-103, "match: pattern %llu holds a line feed", (unsigned long long) k);
+    }
+    const size_t words = (size_t) ((nrec + 31) / 32);
+    if (nrec == 0) return 0;
+    if (npat == 0) { memset(chosen, 0, words * sizeof(uint32_t)); return 0; }
+    SelTable T;
+    sel_build_table(patterns, patOff, npat, T);
+    FCHK(hipSetDevice(p->device));
+    const uint64_t patBytes = patOff[npat];                          // (the table's offsets count from the caller's `patterns`)
+    int rc;
+    if ((rc = p->dSelRecs.reserve(2 * nrec)) || (rc = p->dSelSlots.reserve(T.slots.size())) || (rc = p->dSelPats.reserve(T.pats.size())) ||
+        (rc = p->dSelBytes.reserve(patBytes)) || (rc = p->dSelChosen.reserve(words))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dSelRecs.p, hdrOff, nrec * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dSelRecs.p + nrec, hdrLen, nrec * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dSelSlots.p, T.slots.data(), T.slots.size() * sizeof(SelSlot), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dSelPats.p, T.pats.data(), T.pats.size() * sizeof(SelPat), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dSelBytes.p, patterns, patBytes, hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemsetAsync(p->dSelChosen.p, 0, words * sizeof(uint32_t), p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    k_fa_match_headers<<<dim3((uint32_t) std::min<uint64_t>(nrec, 1u << 16)), dim3(WAVE), 0, p->stream>>>(headers_dev, p->dSelRecs.p, p->dSelRecs.p + nrec, nrec, T.m,
+                                                                                                        p->dSelSlots.p, T.bits, p->dSelPats.p, p->dSelBytes.p, p->dSelChosen.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    std::vector<uint32_t> out(words);                                // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(out.data(), p->dSelChosen.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    memcpy(chosen, out.data(), words * sizeof(uint32_t));
     return 0;
 }
 

@@ -7,7 +7,7 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -132,6 +132,8 @@ def _lib():
                                              C.POINTER(DeflateResult), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_pack_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PackPiece), C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_match_headers_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p,
+                                                   C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L._fasta_ready = True
     return L
 
@@ -318,6 +320,26 @@ class FastaParser:
         if r:
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return offs, ms.value
+
+    def match_headers_dev(self, headers_ptr, header_bytes, offsets, lengths, patterns):
+        """which of the headers headers_ptr[offsets[r], offsets[r] + lengths[r]) of a device buffer of header_bytes bytes contain one of
+        `patterns` (bytes objects) as a substring -> (a bool per record, the kernel's ms). A refused call (an empty pattern, one with a
+        line feed, a header outside the buffer) raises and launches nothing."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        assert off.size == ln.size
+        pats = [bytes(x) for x in patterns]
+        blob = np.frombuffer(b"".join(pats) + b"\0", dtype=np.uint8)      # (one byte more: an empty list still has an address)
+        pat_off = np.concatenate([[0], np.cumsum([len(x) for x in pats], dtype=np.uint64)]).astype(np.uint64)
+        words = np.zeros((off.size + 31) // 32, dtype=np.uint32)
+        ms = C.c_double(0)
+        P = C.POINTER(C.c_uint64)
+        if _lib().mbgc_fasta_match_headers_dev(self.h, headers_ptr, int(header_bytes), off.ctypes.data_as(P), ln.ctypes.data_as(P), off.size,
+                                               blob.ctypes.data_as(C.c_void_p), pat_off.ctypes.data_as(P), len(pats),
+                                               words.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(ms)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        bits = (words[np.arange(off.size) >> 5] >> (np.arange(off.size, dtype=np.uint32) & 31)) & 1 if off.size else np.zeros(0, dtype=np.uint32)
+        return bits.astype(bool), ms.value
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

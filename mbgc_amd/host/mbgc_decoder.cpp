@@ -234,8 +234,9 @@ bool handOverResident(const DecodedCollection &D, const StreamSet &S, const Sele
 }
 
 // <outPrefix>.seq / .contigLens / .seqCounts of the chosen units, and --closure-out
+// (--select-seq: a file's runs of chosen records count into its one entry; oneFile: a single-FASTA set, all of them into the one)
 bool writeSequenceFiles(const DecodedCollection &D, const std::vector<ChosenUnit> &chosen, const OutputCount &out, const std::string &closureOut,
-                        const std::string &outPrefix, std::string &msg) {
+                        const std::string &outPrefix, bool oneFile, std::string &msg) {
     std::string seq(out.bases, '\0');
     std::vector<uint64_t> outLens;
     uint64_t at = 0;
@@ -246,7 +247,10 @@ bool writeSequenceFiles(const DecodedCollection &D, const std::vector<ChosenUnit
         outLens.insert(outLens.end(), D.contigLen.begin() + r.from, D.contigLen.begin() + r.to);
     }
     std::vector<uint32_t> counts;
-    for (const ChosenUnit &x : chosen) counts.push_back((uint32_t) (x.c1 - x.c0));
+    for (size_t i = 0; i < chosen.size(); i++) {
+        if (i && (oneFile || chosen[i].unit == chosen[i - 1].unit)) counts.back() += (uint32_t) (chosen[i].c1 - chosen[i].c0);
+        else counts.push_back((uint32_t) (chosen[i].c1 - chosen[i].c0));
+    }
     if (!closureOut.empty() && !writeFile(closureOut, D.mark.data(), D.mark.size())) { msg = "cannot write " + closureOut; return false; }
     if (!writeFile(outPrefix + ".seq", seq.data(), seq.size()) ||
         !writeFile(outPrefix + ".contigLens", outLens.data(), outLens.size() * sizeof(uint64_t)) ||
@@ -284,10 +288,15 @@ void reportBench(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamS
     if (S.meta.rcRedundancyRemoval)
         snprintf(rcJson, sizeof rcJson, ", \"rc_restore_ms\": %.3f, \"rc_marks\": %llu, \"rc_max_chain\": %llu", S.rcRestoreMs,
                  (unsigned long long) S.rcStats.marks, (unsigned long long) S.rcStats.maxChain);
-    char selJson[256] = "";
+    char selJson[512] = "";
+    int selAt = 0;
     if (sel.selecting)
-        snprintf(selJson, sizeof selJson, ", \"closure_ms\": %.3f, \"closure_contigs\": %llu, \"closure_bases\": %llu, \"selected_targets\": %llu, \"dependency_targets\": %llu",
-                 times.closure, (unsigned long long) D.closureContigs, (unsigned long long) D.closureBases, (unsigned long long) sel.selectedFiles, (unsigned long long) D.dependencyTargets);
+        selAt = snprintf(selJson, sizeof selJson, ", \"closure_ms\": %.3f, \"closure_contigs\": %llu, \"closure_bases\": %llu, \"selected_targets\": %llu, \"dependency_targets\": %llu",
+                         times.closure, (unsigned long long) D.closureContigs, (unsigned long long) D.closureBases, (unsigned long long) sel.selectedFiles, (unsigned long long) D.dependencyTargets);
+    if (sel.selectingSeq)
+        selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_ms\": %.3f, \"records_chosen\": %llu, \"records\": %llu, \"patterns\": %zu", sel.matchMs,
+                          (unsigned long long) sel.recordsChosen, (unsigned long long) sel.recordsAll, opt.selectSeq.size());
+    if (sel.selectingSeq && opt.selectSeqHost) snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_host_ms\": %.3f", sel.matchHostMs);
     printf("{\"metric\": \"output Gbases/s (decompress: streams in HBM to sequences in HBM)\", \"value\": %.4f, \"unit\": \"Gbases/s\", \"bases\": %llu, "
            "\"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, \"chain_starts\": %zu, \"plan_ms_per_target\": %.4f, \"waves\": %llu, "
            "\"serial\": %s, \"index\": %s%s%s}\n",
@@ -312,6 +321,8 @@ void report(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamSet &S
     if (sel.selecting)
         printf("closure: %llu of %llu contigs, %llu of %llu bases, %llu selected, %llu dependency targets\n", (unsigned long long) D.closureContigs, (unsigned long long) S.planned,
                (unsigned long long) D.closureBases, (unsigned long long) out.plannedBases, (unsigned long long) sel.selectedFiles, (unsigned long long) D.dependencyTargets);
+    if (sel.selectingSeq)
+        printf("records: %llu of %llu chosen in %llu files\n", (unsigned long long) sel.recordsChosen, (unsigned long long) sel.recordsAll, (unsigned long long) sel.selectedFiles);
     printf("waves: %llu for %zu targets\n", (unsigned long long) D.times.waves, S.T());
     printf("widest wave: %llu targets\n", (unsigned long long) D.times.widest);
     printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) out.contigs, (unsigned long long) out.bases);
@@ -330,10 +341,13 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     Selection sel;
     if (!readStreamFiles(prefix, opt, S, msg) || !restoreRcLiterals(prefix, opt, S, msg) || !checkStreams(S, msg)) return failed();
     if (wantFasta && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
+    if (!wantFasta && !opt.selectSeq.empty() && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
-    // --select: with a layout its names are used, without one (plain `d`) .names is read for it
-    if (!chooseUnits(prefix, S, opt.select, wantFasta ? &layout.names : nullptr, sel, msg)) return failed();
-    const std::vector<ChosenUnit> chosen = chosenUnits(S.g0n, S.seqCount.data(), S.T(), sel.unitSel.data(), S.meta.sequentialMatching);
+    // --select: with a layout its names are used, without one (plain `d`) .names is read for it; --select-seq: the records of the
+    // files that passed, by their headers, on the device
+    if (!chooseUnits(prefix, S, opt.select, wantFasta ? &layout.names : nullptr, sel, msg) || !chooseRecords(prefix, S, opt, layout, sel, msg)) return failed();
+    const std::vector<ChosenUnit> chosen = chosenUnits(S.g0n, S.seqCount.data(), S.T(), sel.unitSel.data(), sel.selectingSeq ? sel.contigSel.data() : nullptr,
+                                                      S.meta.sequentialMatching);
     // --bench: two passes, a fresh handle for each; the second one is the timed one, and the only one `v` and the report speak of
     const int passes = opt.bench ? 2 : 1;
     int status = 0;
@@ -347,7 +361,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         FastaTimes ftimes;
         ValidateResult vres;
         if (wantFasta) {
-            const FastaPlan plan = planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip);
+            const FastaPlan plan = planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip, sel.selectingSeq);
             const bool writeFiles = !opt.validate && (!opt.bench || pass == 0);                  // (bench: pass 0 writes, the timed pass formats and downloads only)
             if (std::string dir; writeFiles && !makeDirs(opt.fastaDir, &dir)) { msg = "cannot create the directory " + dir; return failed(); }
             FastaStage stage;                                                                    // (behind D: it ends before the collection it reads)
@@ -360,7 +374,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             ftimes = stage.times;
         }
         // the sequence files and --closure-out: on the last pass, and only without --bench and without `v`
-        if (last && !opt.bench && !opt.validate && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, msg)) return failed();
+        if (last && !opt.bench && !opt.validate && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, sel.selectingSeq && S.meta.singleFastaFile, msg)) return failed();
         if (last) {
             report(opt, wantFasta, S, sel, D, out, ftimes, vres);
             status = opt.validate && vres.invalidFiles ? 2 : 0;
@@ -390,6 +404,11 @@ int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decode
         if (!mbgc_hip_read_pattern_list(argv[++i], opt.select)) { fprintf(stderr, "mbgc-hip %c: cannot open the pattern list %s\n", tool, argv[i]); return -1; }
         selectAsked = true;
     }
+    else if (a == "--select-seq" && i + 1 < argc) { opt.selectSeq.push_back(argv[++i]); opt.selectSeqAsked = true; }
+    else if (a == "--select-seq-list" && i + 1 < argc) {
+        if (!mbgc_hip_read_pattern_list(argv[++i], opt.selectSeq)) { fprintf(stderr, "mbgc-hip %c: cannot open the pattern list %s\n", tool, argv[i]); return -1; }
+        opt.selectSeqAsked = true;
+    }
     else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
     else return 0;
     return 1;
@@ -398,12 +417,18 @@ int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decode
 bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool selectAsked) {
     if (selectAsked) for (const std::string &pat : opt.select) if (pat.empty()) { fprintf(stderr, "mbgc-hip %c: --select: an empty pattern\n", tool); return false; }
     if (selectAsked && opt.select.empty()) { fprintf(stderr, "mbgc-hip %c: --select-list: the list of patterns is empty\n", tool); return false; }
+    for (const std::string &pat : opt.selectSeq) {
+        if (pat.empty()) { fprintf(stderr, "mbgc-hip %c: --select-seq: an empty pattern\n", tool); return false; }
+        if (pat.find('\n') != std::string::npos) { fprintf(stderr, "mbgc-hip %c: --select-seq: a pattern holds a line feed, a header holds none\n", tool); return false; }
+    }
+    if (opt.selectSeqAsked && opt.selectSeq.empty()) { fprintf(stderr, "mbgc-hip %c: --select-seq-list: the list of patterns is empty\n", tool); return false; }
     return true;
 }
 
 const char *const MBGC_HIP_D_USAGE =
     "mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir [--gzip] [--batch-kib K]] [--select pattern]...\n"
-    "                  [--select-list file] [--closure-out file] [-d device] <streamsPrefix> <outputPrefix>\n"
+    "                  [--select-list file] [--select-seq pattern]... [--select-seq-list file] [--closure-out file] [-d device]\n"
+    "                  <streamsPrefix> <outputPrefix>\n"
     "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
     "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
     "  --fasta dir: also the input FASTA files again, formatted on the device, as <dir>/<basename of each name of the list> (a .gz suffix\n"
@@ -416,6 +441,10 @@ const char *const MBGC_HIP_D_USAGE =
     "  <streamsPrefix>.rcMapOff / .rcMapLen (without it such streams are refused; no effect on other streams)\n"
     "  --select pattern (repeatable) / --select-list file (a pattern per line): only the files whose line in <streamsPrefix>.names\n"
     "  contains a pattern, and the contigs they depend on, are decoded; the outputs and --fasta hold the chosen files only\n"
+    "  --select-seq pattern (repeatable) / --select-seq-list file (a pattern per line): only the records whose header line (without the\n"
+    "  '>') contains a pattern — a plain substring, case-sensitive, matched on the device against <streamsPrefix>.headers — and the contigs\n"
+    "  they depend on are decoded; with --select a record's file must pass that too. A file holds its chosen records in order, a file\n"
+    "  without one is not written, .seqCounts counts the chosen records per written file; -i streams: the one file, one count\n"
     "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n";
 
 const char *const MBGC_HIP_V_USAGE =
@@ -446,12 +475,13 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--gzip") opt.gzip = true;
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--closure-out" && i + 1 < argc) opt.closureOut = argv[++i];
+        else if (a == "--select-seq-host") opt.selectSeqHost = true;                           // (a developer switch: the host's loop beside the kernel, timed and compared)
         else pos.push_back(a);
     }
     if (pos.size() != 2) { fprintf(stderr, "usage: %s", MBGC_HIP_D_USAGE); return EXIT_FAILURE; }
     if (opt.gzip && opt.fastaDir.empty()) { fprintf(stderr, "mbgc-hip d: --gzip needs --fasta dir (it compresses the FASTA files that --fasta writes)\n"); return EXIT_FAILURE; }
     if (!mbgc_hip_check_selection('d', opt, selectAsked)) return EXIT_FAILURE;
-    if (!selectAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
+    if (!selectAsked && !opt.selectSeqAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
     std::string error;
     if (MBGC_Decoder::decode(pos[0], pos[1], opt, &error) != 0) {
         fprintf(stderr, "mbgc-hip d: %s\n", error.c_str());
@@ -484,6 +514,10 @@ int mbgc_hip_validate_main(int argc, char **argv) {
         else pos.push_back(a);
     }
     if (pos.size() != 1) { fprintf(stderr, "usage: %s", MBGC_HIP_V_USAGE); return EXIT_FAILURE; }
+    if (opt.selectSeqAsked) {
+        fprintf(stderr, "mbgc-hip v: --select-seq / --select-seq-list select records, and a file that holds only some of its records has no original to be validated against (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
     if (!mbgc_hip_check_selection('v', opt, selectAsked)) return EXIT_FAILURE;
     std::string error;
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
@@ -539,18 +573,25 @@ int mbgc_decoder_provenance(const int64_t *segs, uint64_t nsegs, uint64_t refTot
     return n > cap ? -2 : 0;
 }
 
-// The walk over the chosen units (chosenUnits / mergedRanges, mbgc_decoder_streams.h): g0n contigs in the initial reference,
-// seqCount[T] per target, unitSel[T + 1] (G0's unit first), sequentialMatching = -t1. rows: {unit, c0, c1} per chosen unit;
+// The walk over what was chosen (chosenUnits / mergedRanges, mbgc_decoder_streams.h) under --select-seq: g0n contigs in the initial
+// reference, seqCount[T] per target, unitSel[T + 1] (G0's unit first), contigSel[g0n + sum(seqCount)] per contig of the collection
+// (G0's first; NULL: whole units), sequentialMatching = -t1. rows: {unit, c0, c1} per maximal run of chosen contigs of a chosen unit;
 // ranges: {from, to} of the merged output ranges. 0, or -2 (a cap too small; *nrows / *nranges = what is needed).
-int mbgc_decoder_units(uint64_t g0n, const uint32_t *seqCount, uint64_t T, const uint8_t *unitSel, int sequentialMatching, uint64_t *rows, uint64_t rowCap,
-                       uint64_t *nrows, uint64_t *ranges, uint64_t rangeCap, uint64_t *nranges) {
-    const std::vector<ChosenUnit> chosen = chosenUnits(g0n, seqCount, (size_t) T, (const char *) unitSel, sequentialMatching != 0);
+int mbgc_decoder_runs(uint64_t g0n, const uint32_t *seqCount, uint64_t T, const uint8_t *unitSel, const uint8_t *contigSel, int sequentialMatching, uint64_t *rows,
+                      uint64_t rowCap, uint64_t *nrows, uint64_t *ranges, uint64_t rangeCap, uint64_t *nranges) {
+    const std::vector<ChosenUnit> chosen = chosenUnits(g0n, seqCount, (size_t) T, (const char *) unitSel, (const char *) contigSel, sequentialMatching != 0);
     const std::vector<Interval> merged = mergedRanges(chosen);
     *nrows = chosen.size(); *nranges = merged.size();
     if (chosen.size() > rowCap || merged.size() > rangeCap) return -2;
     for (size_t i = 0; i < chosen.size(); i++) { rows[3 * i] = chosen[i].unit; rows[3 * i + 1] = chosen[i].c0; rows[3 * i + 2] = chosen[i].c1; }
     for (size_t i = 0; i < merged.size(); i++) { ranges[2 * i] = merged[i].from; ranges[2 * i + 1] = merged[i].to; }
     return 0;
+}
+
+// The walk over whole chosen units (no contigSel: a row per chosen unit, one without a contig too), otherwise as above.
+int mbgc_decoder_units(uint64_t g0n, const uint32_t *seqCount, uint64_t T, const uint8_t *unitSel, int sequentialMatching, uint64_t *rows, uint64_t rowCap,
+                       uint64_t *nrows, uint64_t *ranges, uint64_t rangeCap, uint64_t *nranges) {
+    return mbgc_decoder_runs(g0n, seqCount, T, unitSel, nullptr, sequentialMatching, rows, rowCap, nrows, ranges, rangeCap, nranges);
 }
 
 // parse + serialize: 0 and the bytes again, or -1 (malformed; the message in err)

@@ -8,7 +8,7 @@
 // mbgc_decoder.cpp is one translation unit: the meta, the load schedule, decode() as the list of its stages, the command lines
 // and the C exports of the tests. The stages are headers it includes once:
 //   mbgc_decoder_streams.h    what is on disk: StreamSet (the files held to the meta, the -m 3 restore, the chain starts),
-//                             Selection (--select), chosenUnits (THE walk over the units that leave the decoder)
+//                             Selection (--select, --select-seq), chosenUnits (THE walk over what leaves the decoder)
 //   mbgc_decoder_run.h        one pass on the device: Provenance, FillUnit / partitionUnits, DecodedCollection (the handle and
 //                             all it holds: plan + schedule, the closure of --select, the forward run)
 //   mbgc_decoder_fasta.h      text out of a DecodedCollection: FastaLayout, FastaPlan (units and batches, shared by `d --fasta`
@@ -85,9 +85,14 @@ public:
     // fastaDir: --fasta, empty = not asked for; restoreRc: --restore-rc, the -m 3 pass over the literals is inverted first
     // select: --select / --select-list, the files to bring back (a unit is chosen when its line of <prefix>.names contains one of the
     // patterns; empty = the whole collection); closureOut: --closure-out, one byte per planned contig
+    // selectSeq: --select-seq / --select-seq-list, the records to bring back (a record is chosen when its header contains one of the
+    // patterns — matched on the device, mbgc_fasta_match_headers_dev — and its file passes `select`); selectSeqAsked: one of the two
+    // options stood on the command line; selectSeqHost: --select-seq-host, a developer switch — the match is made again by the host,
+    // find by find, timed, and held against the device's
     struct Options {
         bool serial = false, noIndex = false, bench = false, restoreRc = false, gzip = false; int device = 0; std::string fastaDir;
         std::vector<std::string> select; std::string closureOut;
+        std::vector<std::string> selectSeq; bool selectSeqAsked = false, selectSeqHost = false;
         // `mbgc-hip v`: validate — the units are formatted as for --fasta and compared on the device with the originals named by
         // <prefix>.names, nothing is downloaded or written; root / flat: where the originals lie (--root is put before relative names,
         // --flat keeps the basename `d --fasta` writes); skipCompare: decode and format only; dumpDir: the text of the first invalid
@@ -121,10 +126,10 @@ int mbgc_hip_validate_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
 extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
-// --restore-rc, --select, --select-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
+// --restore-rc, --select, --select-list, --select-seq, --select-seq-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.
 int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decoder::Options &opt, bool &selectAsked);
-// after the command line: no empty pattern, no empty list; false: the message is on stderr
+// after the command line: no empty pattern, no empty list (--select and --select-seq alike); false: the message is on stderr
 bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool selectAsked);
 // --select-list: the file's non-empty lines behind `out`; false: it cannot be opened
 bool mbgc_hip_read_pattern_list(const char *path, std::vector<std::string> &out);

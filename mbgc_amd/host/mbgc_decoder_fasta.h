@@ -36,16 +36,8 @@ bool makeDirs(const std::string &dir, std::string *failed) {
     return true;
 }
 
-// reads and checks the three side files against the meta: false and a message, or the layout
-bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t contigs, FastaLayout &L, std::string &msg) {
-    std::string names, lens;
-    for (const char *ext : {"names", "headers", "dnaLineLengths"})
-        if (!readFile(prefix + "." + ext, ext[0] == 'n' ? names : (ext[0] == 'h' ? L.headers : lens))) {
-            msg = "malformed stream set: cannot open " + prefix + "." + ext + " (--fasta needs the names, headers and line lengths mbgc-hip c writes beside the streams)";
-            return false;
-        }
-    const size_t T = meta.targets.size();
-    if (!parseNames(names, meta, L.names, msg)) return false;
+// the lines of L.headers, held to the collection: one per contig
+bool parseHeaders(FastaLayout &L, uint64_t contigs, std::string &msg) {
     if (!L.headers.empty() && L.headers.back() != '\n') { msg = "malformed .headers: the last header does not end"; return false; }
     for (size_t at = 0; at < L.headers.size();) {
         const char *e = (const char *) memchr(L.headers.data() + at, '\n', L.headers.size() - at);
@@ -57,6 +49,28 @@ bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t c
         msg = "malformed .headers: " + std::to_string(L.hdrOff.size()) + " headers for " + std::to_string(contigs) + " contigs";
         return false;
     }
+    return true;
+}
+// --select-seq without a sink that needs the whole layout: <prefix>.headers alone
+bool readHeaders(const std::string &prefix, uint64_t contigs, FastaLayout &L, std::string &msg) {
+    if (!readFile(prefix + ".headers", L.headers)) {
+        msg = "malformed stream set: cannot open " + prefix + ".headers (--select-seq needs the headers mbgc-hip c writes beside the streams)";
+        return false;
+    }
+    return parseHeaders(L, contigs, msg);
+}
+
+// reads and checks the three side files against the meta: false and a message, or the layout
+bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t contigs, FastaLayout &L, std::string &msg) {
+    std::string names, lens;
+    for (const char *ext : {"names", "headers", "dnaLineLengths"})
+        if (!readFile(prefix + "." + ext, ext[0] == 'n' ? names : (ext[0] == 'h' ? L.headers : lens))) {
+            msg = "malformed stream set: cannot open " + prefix + "." + ext + " (--fasta needs the names, headers and line lengths mbgc-hip c writes beside the streams)";
+            return false;
+        }
+    const size_t T = meta.targets.size();
+    if (!parseNames(names, meta, L.names, msg)) return false;
+    if (!parseHeaders(L, contigs, msg)) return false;
     if (lens.size() != (T + 1) * sizeof(uint64_t)) {
         msg = "malformed .dnaLineLengths: " + std::to_string(lens.size()) + " bytes for " + std::to_string(T + 1) + " units";
         return false;
@@ -75,17 +89,19 @@ bool readFastaLayout(const std::string &prefix, const MbgcMeta &meta, uint64_t c
     return true;
 }
 
-// ---- the FASTA files again: the chosen units in order, in batches of whole units of at most FASTA_BATCH_TEXT
-// (--batch-kib) bytes of text. `d --fasta` and `v` run over the same plan.
+// ---- the FASTA files again: the chosen units (--select-seq: their runs of chosen records) in order, in batches of
+// whole units of at most FASTA_BATCH_TEXT (--batch-kib) bytes of text. `d --fasta` and `v` run over the same plan.
 struct FastaPlan {
     std::vector<FastaUnit> units;
     std::vector<size_t> batchEnd;                                  // batch b: units [batchEnd[b - 1], batchEnd[b])
     uint64_t maxBatch = 0, maxGz = 0;                              // the most text of a batch; --gzip: the most a batch's gzip files take
     std::vector<char> fileWanted;                                  // per output file (--select: no other file is made, empty ones included)
+    bool runs = false;                                             // --select-seq: a unit is a run of chosen records, a file may have many in a batch
 };
 FastaPlan planFasta(const std::vector<ChosenUnit> &chosen, const MbgcMeta &meta, const FastaLayout &layout, const std::vector<uint64_t> &contigLen,
-                    uint64_t batchText, bool gzip) {
+                    uint64_t batchText, bool gzip, bool runs) {
     FastaPlan P;
+    P.runs = runs;
     P.fileWanted.assign(layout.outNames.size(), 0);
     for (const ChosenUnit &c : chosen) {
         FastaUnit x = {c.c0, c.c1, layout.lineLen[c.unit], 0, 0};
@@ -107,6 +123,63 @@ FastaPlan planFasta(const std::vector<ChosenUnit> &chosen, const MbgcMeta &meta,
 }
 
 bool faFail(std::string &msg, const char *what) { msg = std::string(what) + ": " + mbgc_fasta_last_error(); return false; }
+
+// ---- --select-seq: the records to bring back. The headers go to the device once, the match runs there (mbgc_fasta_match_headers_dev:
+// what a header byte costs does not grow with the list), and a record is chosen when its header matched and its file passed --select
+// (sel.unitSel as chooseUnits left it). Afterwards unitSel holds the units with a chosen record: the files that are written. G0's
+// unit under -t1 is no file — its one contig is the first of target 0 again, and is chosen there. --bench: run twice, the second
+// run is the timed one.
+bool chooseRecords(const std::string &prefix, const StreamSet &S, const MBGC_Decoder::Options &opt, const FastaLayout &layout, Selection &sel, std::string &msg) {
+    const std::vector<std::string> &pats = opt.selectSeq;
+    if (pats.empty()) return true;
+    const uint64_t N = S.g0n + S.planned;
+    std::string patBytes;
+    std::vector<uint64_t> patOff(1, 0);
+    for (const std::string &p : pats) { patBytes += p; patOff.push_back(patBytes.size()); }
+    std::vector<uint32_t> bits((N + 31) / 32, 0);
+    {
+        struct Stage {                                               // freed on every way out
+            mbgc_fasta_t *fa = nullptr; uint8_t *hdrDev = nullptr;
+            ~Stage() { if (hdrDev) mbgc_fasta_dev_free(fa, hdrDev); if (fa) mbgc_fasta_destroy(fa); }
+        } st;
+        if (mbgc_fasta_create(&st.fa, opt.device) || mbgc_fasta_dev_alloc(st.fa, layout.headers.size() + 64, &st.hdrDev) ||
+            mbgc_fasta_upload(st.fa, st.hdrDev, layout.headers.data(), layout.headers.size())) return faFail(msg, "--select-seq");
+        for (int run = 0; run < (opt.bench ? 2 : 1); run++)
+            if (mbgc_fasta_match_headers_dev(st.fa, st.hdrDev, layout.headers.size(), layout.hdrOff.data(), layout.hdrLen.data(), N, (const uint8_t *) patBytes.data(),
+                                             patOff.data(), pats.size(), bits.data(), &sel.matchMs)) return faFail(msg, "--select-seq");
+    }
+    if (opt.selectSeqHost) {                                         // the loop --select runs over the names, over the headers: a yardstick, and a check
+        const double t0 = nowMs();
+        std::vector<uint32_t> host((N + 31) / 32, 0);
+        for (uint64_t c = 0; c < N; c++) {
+            const std::string h(layout.headers, layout.hdrOff[c], layout.hdrLen[c]);
+            for (const std::string &p : pats) if (h.find(p) != std::string::npos) { host[c >> 5] |= 1u << (c & 31); break; }
+        }
+        sel.matchHostMs = nowMs() - t0;
+        if (host != bits) { msg = "--select-seq-host: the device and the host choose different records"; return false; }
+    }
+    const size_t T = S.T();
+    sel.selecting = sel.selectingSeq = true;
+    sel.contigSel.assign(N, 0);
+    sel.selectedFiles = sel.recordsChosen = 0;
+    sel.recordsAll = S.meta.sequentialMatching ? S.planned : N;
+    uint64_t c = 0;
+    for (size_t u = 0; u <= T; u++) {
+        const uint64_t n = u == 0 ? S.g0n : S.seqCount[u - 1];
+        char any = 0;
+        if (sel.unitSel[u] && !(u == 0 && S.meta.sequentialMatching))
+            for (uint64_t k = c; k < c + n; k++) if ((bits[k >> 5] >> (k & 31)) & 1u) { sel.contigSel[k] = any = 1; sel.recordsChosen++; }
+        sel.unitSel[u] = any;
+        if (!S.meta.singleFastaFile) sel.selectedFiles += any;
+        c += n;
+    }
+    if (!sel.recordsChosen) {
+        msg = "--select-seq: no record of the collection matches (" + std::to_string(pats.size()) + " patterns against " + prefix + ".headers)";
+        return false;
+    }
+    if (S.meta.singleFastaFile) sel.selectedFiles = 1;              // its elements are no files: the one file holds what was chosen
+    return true;
+}
 
 // ---- the stage that turns batches of a plan into text on the device: its handle, the headers and two text buffers in HBM (--gzip:
 // two more for a batch's gzip files), two page-locked host buffers, and the record table of the batch formatted last. Freed on
@@ -235,7 +308,9 @@ bool writeFastaFiles(const FastaPlan &plan, FastaStage &stage, const FastaLayout
         uint64_t at = 0;
         for (size_t u = u0; u < u1; u++) {
             const FastaUnit &x = plan.units[u];
-            dl.inFlight.push_back({x.file, at, x.text, !opened[x.file]});
+            // --select-seq: the runs of one file that follow each other in the batch are one piece — one write, one gzip member
+            if (plan.runs && !dl.inFlight.empty() && dl.inFlight.back().file == x.file) dl.inFlight.back().len += x.text;
+            else dl.inFlight.push_back({x.file, at, x.text, !opened[x.file]});
             opened[x.file] = 1;
             at += x.text;
         }

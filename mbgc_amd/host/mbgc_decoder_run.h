@@ -224,7 +224,7 @@ bool DecodedCollection::planAndSchedule(const StreamSet &S, bool serial, std::st
     return true;
 }
 
-// what is filled: everything, or (--select) the closure of the chosen units, before a base exists
+// what is filled: everything, or the closure of the chosen units (--select) or records (--select-seq), before a base exists
 bool DecodedCollection::closure(const StreamSet &S, const Selection &sel, std::string &msg) {
     const size_t T = S.T();
     const uint64_t planned = S.planned, g0n = S.g0n;
@@ -245,7 +245,7 @@ bool DecodedCollection::closure(const StreamSet &S, const Selection &sel, std::s
             for (; s < S.seqCount[t] && segAt[t][s] == i; s++) timeOf[c + s] = prov.cur;
             if (i < tSegs[t].size()) prov.add(tSegs[t][i], g0n);
         }
-        if (sel.unitSel[t + 1]) for (uint32_t k = 0; k < S.seqCount[t]; k++) { mark[c + k] = 2; need[(c + k) >> 5] |= 1u << ((c + k) & 31); }
+        for (uint32_t k = 0; k < S.seqCount[t]; k++) if (sel.chosen(t, c + k, g0n)) { mark[c + k] = 2; need[(c + k) >> 5] |= 1u << ((c + k) & 31); }
         c += S.seqCount[t];
     }
     std::vector<swsem_fill_unit_t> sweep;

@@ -1,5 +1,5 @@
 // Part of mbgc_decoder.cpp (included there once, behind its file helpers): what is on disk. The stream set as `mbgc-hip c` wrote
-// it, held to its meta; the units --select chooses; and THE walk over the chosen units, which every sink uses. Host only,
+// it, held to its meta; the units --select chooses; and THE walk over what was chosen, which every sink uses. Host only,
 // but for the -m 3 restore, which runs on the device before anything reads the literals.
 #pragma once
 
@@ -142,11 +142,17 @@ bool parseNames(const std::string &names, const MbgcMeta &meta, std::vector<std:
     return true;
 }
 
-// ---- --select: the units to bring back (G0, then every target), by the names mbgc-hip c wrote beside the streams
+// ---- --select: the units to bring back (G0, then every target), by the names mbgc-hip c wrote beside the streams; --select-seq:
+// the records to bring back, by the headers written there (chooseRecords, mbgc_decoder_fasta.h: the match runs on the device)
 struct Selection {
-    std::vector<char> unitSel;                                     // per unit; all of them without --select
-    uint64_t selectedFiles = 0;
-    bool selecting = false;
+    std::vector<char> unitSel;                                     // per unit; all of them without a selection. --select-seq: the units that hold a chosen record
+    std::vector<char> contigSel;                                   // --select-seq: per contig of the collection, G0's first; empty without it
+    uint64_t selectedFiles = 0;                                    // the files that are written
+    bool selecting = false, selectingSeq = false;
+    uint64_t recordsChosen = 0, recordsAll = 0;                    // --select-seq
+    double matchMs = 0, matchHostMs = 0;                           // the match kernel; --select-seq-host: the host's loop over the same input
+    // planned contig c of target t is among what is brought back
+    bool chosen(size_t t, uint64_t c, uint64_t g0n) const { return contigSel.empty() ? unitSel[t + 1] != 0 : contigSel[g0n + c] != 0; }
 };
 
 // layoutNames: the names a sink has read already (--fasta, v, r: the layout's); without them --select reads <prefix>.names itself
@@ -181,21 +187,34 @@ bool chooseUnits(const std::string &prefix, const StreamSet &S, const std::vecto
     return true;
 }
 
-// ---- the chosen units, in collection order: unit u (0: G0, u: target u - 1) holds contigs [c0, c1) of the collection. Under -t1
-// the initial reference is the first contig of target 0 again and no unit of its own; a unit that was not chosen is none.
-// Everything that leaves the decoder — the sequence files, the FASTA files, what `v` compares, what `r` packs — walks this list.
+// ---- what is brought back, in collection order: unit u (0: G0, u: target u - 1) holds contigs [c0, c1) of the collection. Under -t1
+// the initial reference is the first contig of target 0 again and no unit of its own; a unit that was not chosen is none. A row is a
+// whole chosen unit (contigSel == nullptr: --select, or no selection; a unit without a contig has its row too) or, under
+// --select-seq, one of a chosen unit's maximal runs of chosen contigs — a run never reaches over a unit's end, so a row is always
+// one file's. Everything that leaves the decoder — the sequence files, the FASTA files, what `v` compares, what `r` packs — walks
+// this list.
 struct ChosenUnit { size_t unit; uint64_t c0, c1; };
-std::vector<ChosenUnit> chosenUnits(uint64_t g0n, const uint32_t *seqCount, size_t T, const char *unitSel, bool sequentialMatching) {
+std::vector<ChosenUnit> chosenUnits(uint64_t g0n, const uint32_t *seqCount, size_t T, const char *unitSel, const char *contigSel, bool sequentialMatching) {
     std::vector<ChosenUnit> out;
     uint64_t c = 0;
     for (size_t u = 0; u <= T; u++) {
         const uint64_t n = u == 0 ? g0n : seqCount[u - 1];
-        if (unitSel[u] && !(u == 0 && sequentialMatching)) out.push_back({u, c, c + n});
+        if (unitSel[u] && !(u == 0 && sequentialMatching)) {
+            if (!contigSel) out.push_back({u, c, c + n});
+            else
+                for (uint64_t k = c; k < c + n;) {
+                    if (!contigSel[k]) { k++; continue; }
+                    uint64_t e = k;
+                    while (e < c + n && contigSel[e]) e++;
+                    out.push_back({u, k, e});
+                    k = e;
+                }
+        }
         c += n;
     }
     return out;
 }
-// what is written: the chosen units' contigs as ranges [from, to) of the collection's contigs, adjacent ones merged
+// what is written: the rows' contigs as ranges [from, to) of the collection's contigs, adjacent ones merged (over a unit's end too)
 std::vector<Interval> mergedRanges(const std::vector<ChosenUnit> &chosen) {
     std::vector<Interval> out;
     for (const ChosenUnit &x : chosen) {

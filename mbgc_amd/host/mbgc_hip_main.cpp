@@ -138,6 +138,10 @@ static int repackMain(int argc, char **argv) {
     }
     if (pos.size() != 2) { fprintf(stderr, "usage:\n%s", REPACK_USAGE); return EXIT_FAILURE; }
     if (pos[0] == pos[1]) { fprintf(stderr, "mbgc-hip r: the output prefix is the input prefix (%s): the input set would be overwritten while it is the only copy\n", pos[0].c_str()); return EXIT_FAILURE; }
+    if (dopt.selectSeqAsked) {
+        fprintf(stderr, "mbgc-hip r: --select-seq / --select-seq-list select records, and files that hold only some of their records are not repacked (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
     if (!mbgc_hip_check_selection('r', dopt, selectAsked)) return EXIT_FAILURE;
     params.device = dopt.device;
     MultipleGenomeMatchingProcessor::bindHostThreadsToDeviceNode(params.device);
