@@ -205,7 +205,25 @@ int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcByt
 int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, uint64_t headerBytes, const uint64_t *hdrOff, const uint64_t *hdrLen,
                                  uint64_t nrec, const uint8_t *patterns, const uint64_t *patOff, uint64_t npat, uint32_t *chosen, double *kernelMs);
 
-/* gzip files that lie compressed in HBM, inflated there (mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
+/* One CRC-32 per byte range of a device buffer (`mbgc-hip c --checksums`, `d --check`, `t`: a contig's bases are checked where they
+ * lie). crc_out_host[k] (host, n entries) = zlib's crc32(0, seq_dev + recs[k].off, recs[k].len): polynomial 0xEDB88320 reflected,
+ * initial value and final XOR 0xffffffff; 0 for len == 0. The ranges may overlap, repeat, be unsorted and start at any byte; a range
+ * with off + len > seqBytes is refused (-103, message in mbgc_fasta_last_error; nothing is launched, crc_out_host is left as it
+ * was). One kernel launch per call whatever n is, none for n == 0 or ranges of no bytes only: ranges of up to 256 bytes take one lane
+ * each, up to 1024 / 4096 / 16384 bytes a group of 4 / 16 / 64 lanes, longer ones are cut into pieces of 16384 bytes over as many waves
+ * and folded with the arithmetic of crc32_combine. No byte outside a range is read on its behalf (aligned vector loads only where a
+ * whole vector lies inside it). kernelMs (may be NULL): the kernel's time from events on the stream. Runs on the input stage's
+ * stream; synchronous. */
+typedef struct { uint64_t off, len; } mbgc_fasta_crc_rec_t;
+int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                       uint32_t *crc_out_host, double *kernelMs);
+/* the same over the records mbgc_fasta_parse_host2 has just parsed, whose sequences it left in HBM (as mbgc_fasta_probe_host reads
+ * them): crc_out_host[r] is record r's. The initial reference is parsed that way; its bases are checked without a second upload. */
+int mbgc_fasta_crc_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, uint64_t nrec, uint32_t *crc_out_host, double *kernelMs);
+/* host: the CRC-32 of A followed by B from crc32(A), crc32(B) and B's length (zlib's crc32_combine); needs no device */
+uint32_t mbgc_fasta_crc_combine(uint32_t crcA, uint32_t crcB, uint64_t lenB);
+
+/* gzip files that lie compressed in HBM, inflated there(mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three
  * block types) — and writes the text to out_dev[outOff, outOff + outCap). One wave per job; no byte outside either range is touched,

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -719,6 +720,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_compare.h"
 #include "fasta_pack.h"
 #include "fasta_select.h"
+#include "fasta_crc.h"
 
 #define INF_CONST static __device__
 #define INF_LANES_DO(lane) for (uint32_t lane = threadIdx.x, once_ = 1; once_; once_ = 0)
@@ -829,6 +831,40 @@ __global__ void __launch_bounds__(WAVE) k_fa_match_headers(const uint8_t *__rest
                 break;
             }
         }
+    }
+}
+
+// mbgc_fasta_crc_dev: a wave per 64 / G rows of one class (the lane step, the classes and the tables: fasta_crc.h). The lanes of a group
+// fold their values by shuffles; a row that is a whole range stores its word, a piece of a cut range moves its value over the bytes
+// behind it (the lanes' factors multiplied by shuffles) and XORs it into the range's word.
+template <uint32_t LOOKUP>
+__global__ void __launch_bounds__(CRC_THREADS) k_fa_crc(const uint8_t *__restrict__ seq, const CrcRow *__restrict__ rows, const uint64_t *__restrict__ behind,
+                                                        const CrcPlan plan, const CrcConsts *__restrict__ K, uint32_t *__restrict__ out) {
+    __shared__ CrcShared<LOOKUP> S;
+    crc_fill_shared(S, K, threadIdx.x, CRC_THREADS);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & (CRC_LANES - 1), nwaves = plan.wave0[CRC_CLASSES];
+    for (uint32_t w = blockIdx.x * CRC_WAVES + threadIdx.x / CRC_LANES; w < nwaves; w += gridDim.x * CRC_WAVES) {     // (the same w for a whole wave)
+        uint32_t c = 0, wave0 = plan.wave0[0], row0 = plan.row0[0], rowEnd = plan.row0[1];
+#pragma unroll
+        for (uint32_t k = 1; k < CRC_CLASSES; k++)
+            if (w >= plan.wave0[k]) { c = k; wave0 = plan.wave0[k]; row0 = plan.row0[k]; rowEnd = plan.row0[k + 1]; }
+        const uint32_t G = 1u << (2 * c), row = row0 + (w - wave0) * (CRC_LANES >> (2 * c)) + (lane >> (2 * c));
+        CrcRow R = {0, 0, 0};
+        uint32_t v = 0;
+        if (row < rowEnd) { R = rows[row]; v = crc_lane_step<LOOKUP>(seq, R, G, lane, S); }
+        for (uint32_t d = 1; d < G; d <<= 1) v ^= (uint32_t) __shfl_xor((int) v, (int) d);
+        if (c + 1 < CRC_CLASSES) {
+            if ((lane & (G - 1)) == 0 && row < rowEnd) out[R.rec & ~CRC_FIRST] = v;
+            continue;
+        }
+        const uint64_t b = behind[row - row0];                             // (one row per wave: uniform)
+        if (b) {
+            uint32_t f = crc_pow_lane(b, lane, S);
+            for (uint32_t d = 1; d < CRC_LANES; d <<= 1) f = crc_mulmod(f, (uint32_t) __shfl_xor((int) f, (int) d));
+            v = crc_mulmod(v, f);
+        }
+        if (lane == 0) atomicXor(out + (R.rec & ~CRC_FIRST), v);
     }
 }
 
@@ -964,6 +1000,10 @@ struct mbgc_fasta {
     fa::Buf<fa::SelPat> dSelPats;
     fa::Buf<uint8_t> dSelBytes;
     fa::Buf<uint32_t> dSelChosen;
+    fa::Buf<fa::CrcRow> dCrcRows;               // mbgc_fasta_crc_dev: the rows, the bytes behind the cut ranges' pieces, the ranges' words, the constants
+    fa::Buf<uint64_t> dCrcBehind;
+    fa::Buf<uint32_t> dCrcOut;
+    fa::Buf<fa::CrcConsts> dCrcConsts;
     fa::Buf<fa::InfJob> dInfJobs;               // mbgc_fasta_inflate_dev: the jobs and their results
     fa::Buf<fa::InfResult> dInfResults;
     fa::Buf<fa::DefChunk> dDefChunks;           // mbgc_fasta_deflate_dev: the chunk table, the chunks' slots and what they hold, the pack tables
@@ -1010,6 +1050,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
     p->dPackPieces.release(); p->dPackOwner.release();
     p->dSelRecs.release(); p->dSelSlots.release(); p->dSelPats.release(); p->dSelBytes.release(); p->dSelChosen.release();
+    p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
@@ -1396,6 +1437,63 @@ int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, ui
     memcpy(chosen, out.data(), words * sizeof(uint32_t));
     return 0;
 }
+
+int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t *crc_out_host,
+                       double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(CrcIn) == sizeof(mbgc_fasta_crc_rec_t), "the table builder reads the ABI's ranges");
+    if (kernelMs) *kernelMs = 0;
+    if (n >= CRC_FIRST) return fail(-103, "crc: %llu ranges in one call", (unsigned long long) n);
+    uint64_t nrows = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        if (recs[k].off > seqBytes || recs[k].len > seqBytes - recs[k].off) return fail(-103, "crc: range %llu lies outside the buffer", (unsigned long long) k);
+        nrows += recs[k].len ? (recs[k].len + CRC_PIECE - 1) / CRC_PIECE : 0;
+    }
+    if (nrows >= 0xffffffffull) return fail(-103, "crc: %llu rows in one call", (unsigned long long) nrows);
+    if (nrows == 0) {
+        for (uint64_t k = 0; k < n; k++) crc_out_host[k] = 0;
+        return 0;
+    }
+    std::vector<CrcRow> rows;
+    std::vector<uint64_t> behind;
+    CrcPlan plan;
+    const uint64_t nwaves = crc_build_table((const CrcIn *) recs, n, rows, behind, plan);
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dCrcRows.reserve(rows.size())) || (rc = p->dCrcBehind.reserve(behind.size() + 1)) || (rc = p->dCrcOut.reserve(n))) return rc;
+    if (!p->dCrcConsts.p) {
+        static const CrcConsts consts = [] { CrcConsts K; crc_build_consts(K); return K; }();
+        if ((rc = p->dCrcConsts.reserve(1))) return rc;
+        FCHK(hipMemcpyAsync(p->dCrcConsts.p, &consts, sizeof consts, hipMemcpyHostToDevice, p->stream));
+    }
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dCrcRows.p, rows.data(), rows.size() * sizeof(CrcRow), hipMemcpyHostToDevice, p->stream));
+    if (!behind.empty()) FCHK(hipMemcpyAsync(p->dCrcBehind.p, behind.data(), behind.size() * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemsetAsync(p->dCrcOut.p, 0, n * sizeof(uint32_t), p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    // one launch whatever n is: the waves stride over the rows. MBGC_HIP_CRC_LOOKUP=nibble: the per-bank nibble tables, the alternative
+    // profiles/crc_bench.py measures the byte table against
+    static const bool byteTable = !(getenv("MBGC_HIP_CRC_LOOKUP") && strcmp(getenv("MBGC_HIP_CRC_LOOKUP"), "nibble") == 0);
+    const dim3 grid((uint32_t) std::min<uint64_t>((nwaves + CRC_WAVES - 1) / CRC_WAVES, 2048));
+    if (byteTable) k_fa_crc<CRC_LOOKUP_BYTE><<<grid, dim3(CRC_THREADS), 0, p->stream>>>(seq_dev, p->dCrcRows.p, p->dCrcBehind.p, plan, p->dCrcConsts.p, p->dCrcOut.p);
+    else k_fa_crc<CRC_LOOKUP_NIBBLE><<<grid, dim3(CRC_THREADS), 0, p->stream>>>(seq_dev, p->dCrcRows.p, p->dCrcBehind.p, plan, p->dCrcConsts.p, p->dCrcOut.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    std::vector<uint32_t> out(n);                                    // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(out.data(), p->dCrcOut.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    for (uint64_t k = 0; k < n; k++) crc_out_host[k] = recs[k].len ? ~out[k] : 0u;      // the final XOR, once per range
+    return 0;
+}
+
+int mbgc_fasta_crc_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, uint64_t nrec, uint32_t *crc_out_host, double *kernelMs) {
+    std::vector<mbgc_fasta_crc_rec_t> recs(nrec);
+    for (uint64_t r = 0; r < nrec; r++) recs[r] = mbgc_fasta_crc_rec_t{records[r].seqOff, records[r].seqLen};
+    return mbgc_fasta_crc_dev(p, p->dHostOut.p, p->hostParsedBytes, recs.data(), nrec, crc_out_host, kernelMs);
+}
+
+uint32_t mbgc_fasta_crc_combine(uint32_t crcA, uint32_t crcB, uint64_t lenB) { return fa::crc_mulmod(fa::crc_xpow8(lenB), crcA) ^ crcB; }
 
 int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBytes, uint8_t *out_dev, uint64_t outBytes,
                            const mbgc_fasta_inflate_job_t *jobs, uint64_t njobs, mbgc_fasta_inflate_result_t *results, double *kernelMs) {

@@ -7,7 +7,8 @@ from . import binding
 
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
-           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev""".split()
+           mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
+           mbgc_fasta_crc_dev mbgc_fasta_crc_combine""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -29,6 +30,10 @@ class ComparePiece(C.Structure):
 
 class PackPiece(C.Structure):
     _fields_ = [("srcOff", C.c_uint64), ("len", C.c_uint64)]
+
+
+class CrcRec(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
 
 
 class PackTooSmall(binding.SwsemError):
@@ -134,6 +139,9 @@ def _lib():
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_match_headers_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p,
                                                    C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        L.mbgc_fasta_crc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+        L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
     return L
 
@@ -341,6 +349,19 @@ class FastaParser:
         bits = (words[np.arange(off.size) >> 5] >> (np.arange(off.size, dtype=np.uint32) & 31)) & 1 if off.size else np.zeros(0, dtype=np.uint32)
         return bits.astype(bool), ms.value
 
+    def crc_dev(self, seq_ptr, seq_bytes, ranges):
+        """ranges = rows of (off, len): zlib's crc32 of seq[off, off + len) of a device buffer of seq_bytes bytes, one per range, taken
+        on the device in one launch -> (uint32 per range, the kernel's ms). The ranges may overlap, repeat and come in any order; one
+        of no bytes gives 0. A refused call (a range outside the buffer) raises and launches nothing."""
+        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        n = rows.shape[0]
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        ms = C.c_double(0)
+        if _lib().mbgc_fasta_crc_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), n, out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     C.byref(ms)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return out[:n], ms.value
+
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into
         out[outOff, outOff + outCap) -> ([(status, members, outLen, inUsed)] per job, the kernel's ms). A refused call (a job outside
@@ -379,3 +400,8 @@ class FastaParser:
                                         out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out[: n.value].tobytes()
+
+
+def crc_combine(crc_a, crc_b, len_b):
+    """mbgc_fasta_crc_combine: the CRC-32 of A followed by B from crc32(A), crc32(B) and B's length (host arithmetic; no device)"""
+    return int(_lib().mbgc_fasta_crc_combine(int(crc_a), int(crc_b), int(len_b)))

@@ -1,6 +1,7 @@
 #include "mbgc_decoder.h"
 #include "simple_sequence_matcher.h"
 #include "gzip_inflate.h"
+#include "mbgc_checksums.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -193,6 +194,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_run.h"        // one pass on the device: DecodedCollection
 #include "mbgc_decoder_fasta.h"      // text out of it: FastaLayout, FastaPlan, FastaStage, the writer of d --fasta
 #include "mbgc_decoder_validate.h"   // v: Validation
+#include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -263,7 +265,7 @@ bool writeSequenceFiles(const DecodedCollection &D, const std::vector<ChosenUnit
 
 // the JSON lines of --bench, from the numbers of the pass it is called behind (the last one)
 void reportBench(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamSet &S, const Selection &sel, const DecodedCollection &D, const OutputCount &out,
-                 const FastaTimes &ftimes, const ValidateResult &v) {
+                 const FastaTimes &ftimes, const ValidateResult &v, const CheckResult &chk) {
     const PassTimes &times = D.times;
     const ValidateTimes &vtimes = v.times;
     const size_t T = S.T();
@@ -296,7 +298,10 @@ void reportBench(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamS
     if (sel.selectingSeq)
         selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_ms\": %.3f, \"records_chosen\": %llu, \"records\": %llu, \"patterns\": %zu", sel.matchMs,
                           (unsigned long long) sel.recordsChosen, (unsigned long long) sel.recordsAll, opt.selectSeq.size());
-    if (sel.selectingSeq && opt.selectSeqHost) snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_host_ms\": %.3f", sel.matchHostMs);
+    if (sel.selectingSeq && opt.selectSeqHost) selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_host_ms\": %.3f", sel.matchHostMs);
+    if (opt.check)
+        snprintf(selJson + selAt, sizeof selJson - selAt, ", \"crc_kernel_ms\": %.3f, \"crc_bytes\": %llu, \"crc_gb_per_s\": %.3f", chk.kernelMs, (unsigned long long) chk.bytes,
+                 chk.kernelMs > 0 ? chk.bytes / (chk.kernelMs * 1e-3) / 1e9 : 0.0);
     printf("{\"metric\": \"output Gbases/s (decompress: streams in HBM to sequences in HBM)\", \"value\": %.4f, \"unit\": \"Gbases/s\", \"bases\": %llu, "
            "\"plan_ms\": %.3f, \"fill_ms\": %.3f, \"load_ms\": %.3f, \"targets\": %zu, \"chain_starts\": %zu, \"plan_ms_per_target\": %.4f, \"waves\": %llu, "
            "\"serial\": %s, \"index\": %s%s%s}\n",
@@ -316,8 +321,8 @@ void reportBench(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamS
 
 // what `d` and `v` say behind their last pass (`r` says none of it: it returns right after the pack)
 void report(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamSet &S, const Selection &sel, const DecodedCollection &D, const OutputCount &out,
-            const FastaTimes &ftimes, const ValidateResult &v) {
-    if (opt.bench) reportBench(opt, wantFasta, S, sel, D, out, ftimes, v);
+            const FastaTimes &ftimes, const ValidateResult &v, const CheckResult &chk) {
+    if (opt.bench) reportBench(opt, wantFasta, S, sel, D, out, ftimes, v, chk);
     if (sel.selecting)
         printf("closure: %llu of %llu contigs, %llu of %llu bases, %llu selected, %llu dependency targets\n", (unsigned long long) D.closureContigs, (unsigned long long) S.planned,
                (unsigned long long) D.closureBases, (unsigned long long) out.plannedBases, (unsigned long long) sel.selectedFiles, (unsigned long long) D.dependencyTargets);
@@ -326,11 +331,13 @@ void report(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamSet &S
     printf("waves: %llu for %zu targets\n", (unsigned long long) D.times.waves, S.T());
     printf("widest wave: %llu targets\n", (unsigned long long) D.times.widest);
     printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) out.contigs, (unsigned long long) out.bases);
+    if (opt.check) reportCheck(chk);
 }
 }  // namespace
 
 // The stages, in the order their failures are reported in. Per pass: decode to the device, then exactly one sink — resident (`r`),
-// validate (`v`) or the FASTA files (--fasta) — and/or the sequence files, then the report.
+// validate (`v`) or the FASTA files (--fasta) — and/or the sequence files, then the report. `d --check` puts the check between the
+// decode and the sinks; `t` is the decode and the check with no sink at all.
 int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix, const Options &opt, std::string *error) {
     std::string msg;
     const auto failed = [&msg, error]() { if (error) *error = msg; return 1; };
@@ -340,8 +347,12 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     FastaLayout layout;
     Selection sel;
     if (!readStreamFiles(prefix, opt, S, msg) || !restoreRcLiterals(prefix, opt, S, msg) || !checkStreams(S, msg)) return failed();
-    if (wantFasta && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
-    if (!wantFasta && !opt.selectSeq.empty() && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
+    mbgc_checksums::Manifest manifest;
+    if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
+    // (--check names a differing contig by its file and header: the whole layout)
+    const bool wantLayout = wantFasta || opt.check;
+    if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
+    if (!wantLayout && !opt.selectSeq.empty() && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
     // --select: with a layout its names are used, without one (plain `d`) .names is read for it; --select-seq: the records of the
     // files that passed, by their headers, on the device
@@ -360,6 +371,8 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         if (opt.resident) return handOverResident(D, S, sel, layout, chosen, out, *opt.resident, msg) ? 0 : failed();
         FastaTimes ftimes;
         ValidateResult vres;
+        CheckResult chk;
+        if (opt.check && last && !checkChecksums(prefix, D, S, layout, chosen, manifest, opt.device, chk, msg)) return failed();
         if (wantFasta) {
             const FastaPlan plan = planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip, sel.selectingSeq);
             const bool writeFiles = !opt.validate && (!opt.bench || pass == 0);                  // (bench: pass 0 writes, the timed pass formats and downloads only)
@@ -374,10 +387,10 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             ftimes = stage.times;
         }
         // the sequence files and --closure-out: on the last pass, and only without --bench and without `v`
-        if (last && !opt.bench && !opt.validate && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, sel.selectingSeq && S.meta.singleFastaFile, msg)) return failed();
+        if (last && !opt.bench && !opt.validate && !opt.writeNothing && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, sel.selectingSeq && S.meta.singleFastaFile, msg)) return failed();
         if (last) {
-            report(opt, wantFasta, S, sel, D, out, ftimes, vres);
-            status = opt.validate && vres.invalidFiles ? 2 : 0;
+            report(opt, wantFasta, S, sel, D, out, ftimes, vres, chk);
+            status = (opt.validate && vres.invalidFiles) || (opt.check && chk.differs()) ? 2 : 0;
         }
     }
     return status;
@@ -427,7 +440,7 @@ bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool 
 
 const char *const MBGC_HIP_D_USAGE =
     "mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir [--gzip] [--batch-kib K]] [--select pattern]...\n"
-    "                  [--select-list file] [--select-seq pattern]... [--select-seq-list file] [--closure-out file] [-d device]\n"
+    "                  [--select-list file] [--select-seq pattern]... [--select-seq-list file] [--closure-out file] [--check] [-d device]\n"
     "                  <streamsPrefix> <outputPrefix>\n"
     "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
     "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
@@ -445,7 +458,19 @@ const char *const MBGC_HIP_D_USAGE =
     "  '>') contains a pattern — a plain substring, case-sensitive, matched on the device against <streamsPrefix>.headers — and the contigs\n"
     "  they depend on are decoded; with --select a record's file must pass that too. A file holds its chosen records in order, a file\n"
     "  without one is not written, .seqCounts counts the chosen records per written file; -i streams: the one file, one count\n"
-    "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n";
+    "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n"
+    "  --check: before anything is written, the CRC-32 of every chosen contig's bases is taken on the device and held against\n"
+    "  <streamsPrefix>.checksums (mbgc-hip c --checksums), the side files' on the host; prints `checksums: <checked> of <N> contigs checked,\n"
+    "  <bad> differ` and a `checksum ERROR` line per differing contig (the first 100) or side file. Exit status 2 when anything differs —\n"
+    "  the outputs are written all the same —, 1 when the manifest is missing or does not fit the set. --bench gains crc_kernel_ms,\n"
+    "  crc_bytes, crc_gb_per_s\n";
+
+const char *const MBGC_HIP_T_USAGE =
+    "mbgc-hip t [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--select-seq pattern]...\n"
+    "                  [--select-seq-list file] [--bench] [-d device] <streamsPrefix>\n"
+    "  tests the stream set against <streamsPrefix>.checksums without the FASTA files: d --check that writes nothing. Exit status 0: every\n"
+    "  chosen contig and the side files are as mbgc-hip c --checksums (or r --checksums) saw them; 2: something differs; 1: malformed streams,\n"
+    "  no manifest, or one that does not fit the set\n";
 
 const char *const MBGC_HIP_V_USAGE =
     "mbgc-hip v [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--root dir] [--flat]\n"
@@ -475,6 +500,7 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--gzip") opt.gzip = true;
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--closure-out" && i + 1 < argc) opt.closureOut = argv[++i];
+        else if (a == "--check") opt.check = true;
         else if (a == "--select-seq-host") opt.selectSeqHost = true;                           // (a developer switch: the host's loop beside the kernel, timed and compared)
         else pos.push_back(a);
     }
@@ -483,11 +509,29 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
     if (!mbgc_hip_check_selection('d', opt, selectAsked)) return EXIT_FAILURE;
     if (!selectAsked && !opt.selectSeqAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
     std::string error;
-    if (MBGC_Decoder::decode(pos[0], pos[1], opt, &error) != 0) {
-        fprintf(stderr, "mbgc-hip d: %s\n", error.c_str());
-        return EXIT_FAILURE;
+    const int r = MBGC_Decoder::decode(pos[0], pos[1], opt, &error);
+    if (r == 1) { fprintf(stderr, "mbgc-hip d: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return r;                                                                                   // (2: --check found a difference)
+}
+
+// `mbgc-hip t`: the stages of `d --check` without a sink
+int mbgc_hip_test_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.check = opt.writeNothing = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (const int r = mbgc_hip_decode_option('t', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else pos.push_back(a);
     }
-    return EXIT_SUCCESS;
+    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_T_USAGE); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('t', opt, selectAsked)) return EXIT_FAILURE;
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r == 1) { fprintf(stderr, "mbgc-hip t: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return r;
 }
 
 // `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device

@@ -100,6 +100,9 @@ public:
         bool validate = false, flat = false, skipCompare = false, inflateOnDevice = false; std::string root, dumpDir; uint64_t batchText = 0;
         // `mbgc-hip r`: nothing is downloaded or written; the chosen units stay on the device and are described here
         ResidentCollection *resident = nullptr;
+        // `d --check` / `mbgc-hip t`: the chosen contigs' CRC-32s, taken on the device, are held against <prefix>.checksums before
+        // anything is written (2 = a contig or a side file differs); writeNothing: `t`, no sequence files
+        bool check = false, writeNothing = false;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -123,8 +126,9 @@ public:
 
 int mbgc_hip_decompress_main(int argc, char **argv);
 int mbgc_hip_validate_main(int argc, char **argv);
+int mbgc_hip_test_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
-extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE;
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.

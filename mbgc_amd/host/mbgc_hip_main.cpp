@@ -27,6 +27,7 @@
 
 #include "mgmp_driver.h"
 #include "mbgc_decoder.h"
+#include "mbgc_checksums.h"
 
 // what the ranks share before their exchange exists: the RCCL ids rank 0 makes, then (host-memory transport) its mapping
 struct Bootstrap {
@@ -82,12 +83,20 @@ static void writeStreamSet(const std::string &prefix, const MBGC_Encoder &enc, c
         dump(prefix, "headers", enc.headersStream);
         dump(prefix, "dnaLineLengths", enc.lineLengthsStream);
     }
+    if (params.checksums) {                                                     // --checksums: the manifest `mbgc-hip t` / `d --check` hold the set against
+        mbgc_checksums::Manifest m;
+        const std::string meta = enc.metaBytes();
+        const std::string *side[4] = {&meta, &enc.namesStream, &enc.headersStream, &enc.lineLengthsStream};
+        for (int k = 0; k < 4; k++) m.side[k] = mbgc_checksums::crc32(side[k]->data(), side[k]->size());
+        m.contigs = enc.contigChecksums();
+        dump(prefix, "checksums", m.serialize());
+    }
 }
 
 static const char *REPACK_USAGE =
     "       mbgc-hip r [--select pattern]... [--select-list file] [--restore-rc] [--serial] [--no-index] [-m mode] [-k kmerLength] [-s samplingStep] [-t1]\n"
     "                  [-R targetsPerRound] [-U] [--proteins] [-l basesPerRow] [--verify | --verify-every K] [--ref-factor F] [-d device] [--bench]\n"
-    "                  <inStreamsPrefix> <outputPrefix>\n"
+    "                  [--checksums] <inStreamsPrefix> <outputPrefix>\n"
     "  repacks the chosen files of a stream set (all of them without --select) into a new one, on the device: they are decoded as mbgc-hip d\n"
     "  decodes them (--select, --select-list, --restore-rc, --serial, --no-index: as there), packed back to back in HBM and matched again from\n"
     "  scratch as mbgc-hip c matches the files d --fasta would write (-m, -k, -s, -t1, -R, -U, --proteins, --verify, --ref-factor: as there, with\n"
@@ -96,7 +105,9 @@ static const char *REPACK_USAGE =
     "  The chosen bases and the matcher's reference are resident together: the collection is not streamed through in pieces, and a device\n"
     "  allocation that fails ends the run with its message. A single-FASTA stream set (c -i) is refused; --gpus, -i, --lossy, --inflate and\n"
     "  --backend are options of c, over files. --bench: one JSON line (units, contigs decoded and chosen, bases, decode_ms, pack_kernel_ms,\n"
-    "  pack_bytes, encode_s) behind the report\n";
+    "  pack_bytes, encode_s) behind the report\n"
+    "  --checksums: also <outputPrefix>.checksums, as mbgc-hip c --checksums writes it — the contigs' CRC-32s are taken from the packed bases\n"
+    "  in HBM; mbgc-hip t <outputPrefix> then checks the new set without the old one (--bench gains crc_kernel_ms, crc_bytes)\n";
 
 // `mbgc-hip r`: MBGC_Decoder::decode that ends resident, then MBGC_Encoder::encodeResident over what it left
 static int repackMain(int argc, char **argv) {
@@ -130,6 +141,7 @@ static int repackMain(int argc, char **argv) {
         else if (a == "--verify") params.verifyEmissions = true;
         else if (a == "--ref-factor" && i + 1 < argc) params.referenceFactor = atoi(argv[++i]);
         else if (a == "--bench") bench = true;
+        else if (a == "--checksums") params.checksums = true;
         else if (a == "--gpus" || a == "-i" || a == "--lossy" || a == "--lossy-file" || a == "--inflate" || a == "--backend") {
             fprintf(stderr, "mbgc-hip r: %s is an option of mbgc-hip c, over files: r takes its input from a stream set, on one GPU, and writes raw streams\n", a.c_str());
             return EXIT_FAILURE;
@@ -183,6 +195,7 @@ static int repackMain(int argc, char **argv) {
                    coll.units.size(), (unsigned long long) coll.contigsDecoded, (unsigned long long) coll.contigsChosen, (unsigned long long) coll.packedBytes,
                    coll.decodeMs, coll.packKernelMs, (unsigned long long) coll.packedBytes,
                    coll.packKernelMs > 0 ? coll.packedBytes / (coll.packKernelMs * 1e-3) / 1e9 : 0.0, (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9);
+        if (bench && params.checksums) printf("{\"crc_kernel_ms\": %.3f, \"crc_bytes\": %llu}\n", params.crcKernelMs, (unsigned long long) params.crcBytes);
         mbgc_fasta_dev_free(coll.fasta, coll.packedDev);
     }
     return rc;
@@ -192,6 +205,7 @@ int main(int argc, char **argv) {
     if (argc > 1 && std::string(argv[1]) == "r") return repackMain(argc, argv);                 // chosen files of a stream set into a new one, resident in between
     if (argc > 1 && std::string(argv[1]) == "d") return mbgc_hip_decompress_main(argc, argv);   // the streams back to the collection (mbgc_decoder.cpp)
     if (argc > 1 && std::string(argv[1]) == "v") return mbgc_hip_validate_main(argc, argv);     // ... and compared with the files on disk, on the device
+    if (argc > 1 && std::string(argv[1]) == "t") return mbgc_hip_test_main(argc, argv);         // ... or held against <prefix>.checksums, nothing written
     MBGC_Params params;
     std::vector<std::string> pos;
     int gpus = 1;
@@ -228,6 +242,7 @@ int main(int argc, char **argv) {
             if (w != "host" && w != "device") { fprintf(stderr, "--inflate takes host or device\n"); return EXIT_FAILURE; }
             params.inflateOnDevice = w == "device";
         }
+        else if (a == "--checksums") params.checksums = true;                     // <outputPrefix>.checksums: the CRC-32 of every contig's bases, taken on the device
         else if (a == "--bench") params.benchMode = true;                        // rounds timed with every contig resident in HBM (no streams written)
         else if (a == "--verify-every" && i + 1 < argc) { params.verifyEmissions = true; params.verifyEvery = atoi(argv[++i]); }
         else if (a == "--verify") params.verifyEmissions = true;                  // every emission decoded again on the device before the reference moves on
@@ -246,7 +261,7 @@ int main(int argc, char **argv) {
     const bool single = !params.inputFileName.empty();
     if (single && pos.size() == 1) pos.insert(pos.begin(), std::string());      // (no list file in this mode)
     if (pos.size() != 2 || (single && !pos[0].empty())) {
-        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--inflate host|device] [--verify | --verify-every K] [--ref-factor F] [--bench [--warmup rounds]] "
+        fprintf(stderr, "usage: mbgc-hip c [-t1] [-m mode] [-k kmerLength] [-s samplingStep] [-R targetsPerRound] [-d device] [-U] [--proteins] [--lossy] [--inflate host|device] [--verify | --verify-every K] [--ref-factor F] [--checksums] [--bench [--warmup rounds]] "
                         "[--gpus N [--exchange rccl|hostmem] [--shm-mb M]] [--backend coders.so [--backend-threads T] [--backend-blocks K | --backend-overlap MiB] [--coder-threads t]] <sequencesListFile> <outputPrefix>\n"
                         "       mbgc-hip c -i <fastaFile> | --lossy-file <fastaFile> [--window-kib K] [the options above, without --gpus and --lossy] <outputPrefix>\n"
                         "  -i: the collection is one multi-FASTA file (single fasta file mode): it is cut into the initial reference and targets of at least\n"
@@ -267,9 +282,12 @@ int main(int argc, char **argv) {
                         "  CRC-32 and length checked there; a file that does not inflate to the length its trailer states there (several members, a corrupt\n"
                         "  stream) is inflated by the host. The streams are the same either way. host (the default): zlib on the reader threads. The first\n"
                         "  file of the list and a gzip file given with -i are always inflated by the host\n"
+                        "  --checksums: also writes <outputPrefix>.checksums — the CRC-32 of every contig's bases as the streams hold them (after -U, after the\n"
+                        "  lossy rule), taken on the device where the input stage leaves the contigs, and of .meta / .names / .headers / .dnaLineLengths;\n"
+                        "  mbgc-hip t <outputPrefix> and d --check hold the set against it without the FASTA files. One GPU, not with --bench\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_V_USAGE, REPACK_USAGE);
+        fprintf(stderr, "       %s       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_T_USAGE, MBGC_HIP_V_USAGE, REPACK_USAGE);
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
@@ -282,6 +300,14 @@ int main(int argc, char **argv) {
     }
     if (single && lossyList) {
         fprintf(stderr, "--lossy reads the files of a list and is not taken with -i: a single fasta file is read by the lossy rule when it is given as --lossy-file <fastaFile> (the reference's -L -i)\n");
+        return EXIT_FAILURE;
+    }
+    if (params.checksums && (gpus > 1 || transport == "hostmem")) {
+        fprintf(stderr, "--checksums runs on one GPU: the rounds sharded over --gpus N / --exchange hostmem write no .names / .headers, and their contigs live on several ranks\n");
+        return EXIT_FAILURE;
+    }
+    if (params.checksums && params.benchMode) {
+        fprintf(stderr, "--checksums is not taken with --bench: c --bench writes no stream set, so there is nothing a manifest would describe\n");
         return EXIT_FAILURE;
     }
     if (gpus > 1 && params.verifyEmissions) {

@@ -124,6 +124,8 @@ MultipleGenomeMatchingProcessor::~MultipleGenomeMatchingProcessor() {
     delete matcher;
 }
 
+static void inputStageCheck(int rc);
+
 void MultipleGenomeMatchingProcessor::openInputStage() {
     if (!fasta && mbgc_fasta_create(&fasta, device) != 0) {
         fprintf(stderr, "input stage: %s\n", mbgc_fasta_last_error());
@@ -180,6 +182,12 @@ void MultipleGenomeMatchingProcessor::parseHostBytes(const std::string &data, co
     }
     validate_kseq_status(path, status);
     if (probeG0) probeG0Records(nrec);
+    if (probeG0 && params->checksums) {                          // (the initial reference: its sequences are still where the parser left them)
+        g0Crcs.assign(nrec, 0);
+        double ms = 0;
+        inputStageCheck(mbgc_fasta_crc_host(fasta, records.data(), nrec, g0Crcs.data(), &ms));
+        params->crcKernelMs += ms; params->crcBytes += seqBytes;
+    }
     hostLineLen = lineLen;
     out.clear();
     for (uint64_t k = 0; k < nrec; k++) {
@@ -322,6 +330,7 @@ void MultipleGenomeMatchingProcessor::loadRound(uint32_t f0, uint32_t f1, RoundB
     }
     g_tWait += nowSeconds() - t0;
     if (!have) { const double tp0 = nowSeconds(); prepareRound(f0, f1, B, nextF0, nextF1); g_tPrepareSync += nowSeconds() - tp0; }
+    targetCrcs.insert(targetCrcs.end(), B.crcs.begin(), B.crcs.end());                       // (the batches are taken in collection order)
     if (nextB && nextF1 > nextF0 && !(singleFastaFileMode && B.endOfInput)) {
         // the round after the next one: the callers' rounds are ranges of equal length at equal distance (a wrong guess
         // costs a read that nobody takes)
@@ -369,12 +378,12 @@ void MultipleGenomeMatchingProcessor::noteUnitsArrived(const RoundBatch &B, uint
 // files [f0, f1) of the list -> their contigs back to back in B.seqDev; contig c belongs to target targetBase + (file - f0)
 void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, RoundBatch &B, uint32_t afterF0, uint32_t afterF1) {
     openInputStage();
-    if (resident) { prepareRoundResident(f0, f1, B); return; }
-    if (singleFastaFileMode) { prepareRoundSingleFasta(f0, f1, B); return; }
+    if (resident) { prepareRoundResident(f0, f1, B); crcBatch(B); return; }
+    if (singleFastaFileMode) { prepareRoundSingleFasta(f0, f1, B); crcBatch(B); return; }
     const int nf = (int) (f1 - f0);
     if (nf <= 0) {                                           // (a rank without targets in a short last round)
         B.offsets.assign(1, 0); B.targetOf.clear(); B.bytes = 0;
-        B.unitHeaders.clear(); B.unitLineLen.clear();
+        B.unitHeaders.clear(); B.unitLineLen.clear(); B.crcs.clear();
         return;
     }
     const double tWait0 = nowSeconds();
@@ -441,7 +450,22 @@ void MultipleGenomeMatchingProcessor::prepareRound(uint32_t f0, uint32_t f1, Rou
         if (onDevice) keepHeadersFromDevice(B, rawDev, n, fileOff.data(), recBase.data(), lineLen.data(), nf);
         else keepHeaders(B, hostBytes, fileOff.data(), recBase.data(), lineLen.data(), nf);   // (before the slot is read into again)
     }
+    crcBatch(B);
     g_tParse += nowSeconds() - tParse0;
+}
+
+// --checksums: every contig of a batch is whole in B.seqDev on every path — a list's files, the elements of -i (cut at '>' bytes),
+// the sequential batches of -i (cut at record starts; a window without one grows), the units of `r` — so one call gives the batch's
+// CRC-32s and no contig has to be joined from pieces. Runs where the batch is prepared: on the input stage's stream, beside the matching.
+void MultipleGenomeMatchingProcessor::crcBatch(RoundBatch &B) {
+    B.crcs.clear();
+    if (!params->checksums || B.offsets.size() < 2) return;
+    std::vector<mbgc_fasta_crc_rec_t> recs(B.offsets.size() - 1);
+    for (size_t c = 0; c + 1 < B.offsets.size(); c++) recs[c] = mbgc_fasta_crc_rec_t{B.offsets[c], B.offsets[c + 1] - B.offsets[c]};
+    B.crcs.assign(recs.size(), 0);
+    double ms = 0;
+    inputStageCheck(mbgc_fasta_crc_dev(fasta, B.seqDev, B.bytes, recs.data(), recs.size(), B.crcs.data(), &ms));
+    params->crcKernelMs += ms; params->crcBytes += B.bytes;
 }
 
 // --inflate device. The round's bytes in rawDev: every file at its place fileOff[f] — the plain ones uploaded there, run by run,
@@ -546,6 +570,14 @@ void MultipleGenomeMatchingProcessor::readG0Resident(std::vector<Contig> &out, u
     mbgc_fasta_probe_result_t res;
     inputStageCheck(mbgc_fasta_probe_dev(fasta, resident->packedDev, resident->packedBytes, off.data(), len.data(), probed, params->k, &params->probe, &res));
     if (res.fired && (!params->sequentialMatching || res.record == 0)) setProteinsProfile();
+    if (params->checksums) {
+        std::vector<mbgc_fasta_crc_rec_t> recs(nrec);
+        for (uint64_t k = 0; k < nrec; k++) recs[k] = mbgc_fasta_crc_rec_t{off[k], len[k]};
+        g0Crcs.assign(nrec, 0);
+        double ms = 0;
+        inputStageCheck(mbgc_fasta_crc_dev(fasta, resident->packedDev, resident->packedBytes, recs.data(), nrec, g0Crcs.data(), &ms));
+        params->crcKernelMs += ms; params->crcBytes += bytes;
+    }
     std::string seq(bytes, '\0');
     if (bytes) inputStageCheck(mbgc_fasta_download(fasta, &seq[0], resident->packedDev + residentUnitOff[0], bytes));
     out.clear();

@@ -51,6 +51,10 @@ struct MGMP_Params {                                   // matching/MGMP_Params.h
     // mbgc-hip c --bench: every round's contigs are put into HBM first, the rounds after `benchWarmup` are timed and the
     // emitted streams stay packed in HBM (what bench.py measures, from the C++ host)
     bool benchMode = false;
+    // mbgc-hip c / r --checksums: the CRC-32 of every contig's bases is taken on the device where the input stage leaves them
+    // (mbgc_fasta_crc_dev) and kept for <outputPrefix>.checksums; crcKernelMs / crcBytes: what the kernel ran over
+    bool checksums = false;
+    double crcKernelMs = 0; uint64_t crcBytes = 0;
     // mbgc-hip c --verify: every emission is decoded again on the device (SlidingWindowSparseEMMatcher::emitVerify) before the
     // reference moves on, and the run fails on the first contig that does not come back; rounds then load on the host's decision
     bool verifyEmissions = false;
@@ -112,6 +116,7 @@ struct RoundBatch {
     // each followed by '\n', and the line length the parser found — copied out of the staged file bytes while they are there
     std::vector<std::string> unitHeaders;
     std::vector<uint64_t> unitLineLen;
+    std::vector<uint32_t> crcs;                        // --checksums: the CRC-32 of every contig
 };
 
 class MultipleGenomeMatchingProcessor {
@@ -178,6 +183,9 @@ protected:
     uint32_t layoutArrived = 0;
     bool keepsLayout() const { return !params->benchMode && !params->exchange; }         // (not under --bench, not on the sharded host)
     std::mutex layoutMu;
+    // --checksums: the contigs' CRC-32s — the initial reference's, and the targets' in the order their batches are taken
+    std::vector<uint32_t> g0Crcs, targetCrcs;
+    void crcBatch(RoundBatch &B);                                                       // B.crcs from B.seqDev, on the input stage's stream
     std::string g0Headers; uint64_t g0LineLen = 0, hostLineLen = 0;                      // the initial reference's; hostLineLen: of parseHostBytes' last file
     void noteUnitsArrived(const RoundBatch &B, uint32_t firstFile);                     // the batch's units behind those that wait
     void noteUnitArrived(LayoutUnit &&u);
@@ -329,6 +337,13 @@ public:
     uint32_t singleFastaElements() const { return params->sequentialMatching ? 1 : targetsCount + 1; }
     const std::vector<uint32_t> &sequenceCounts() const { return seqsCounts; }
     size_t exactMatches() const { return resCount; }
+    // --checksums: per contig in the order of an unselected `mbgc-hip d` (under -t1 the initial reference is target 0's first contig again)
+    std::vector<uint32_t> contigChecksums() const {
+        std::vector<uint32_t> out;
+        if (!params->sequentialMatching) out = g0Crcs;
+        out.insert(out.end(), targetCrcs.begin(), targetCrcs.end());
+        return out;
+    }
     size_t finalReferenceLength() const { return refFinalTotalLength; }          // writeStats' refFinalTotalLength, ENC.cpp:734-743
     size_t droppedExtensionBytes() const { return matcher ? matcher->getDroppedBytes() : 0; }
     size_t maxReferenceLength() const { return matcher ? matcher->getMaxRefLength() : 0; }
