@@ -286,6 +286,36 @@ typedef struct { uint64_t vstart, len; int64_t owner; } swsem_prov_row_t;
 typedef struct { uint64_t c0, c1; } swsem_fill_unit_t;
 int swsem_decode_closure_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_t *rows, uint64_t ncontigs,
                              const uint64_t *timeOf, uint64_t nunits, const swsem_fill_unit_t *units, uint32_t *need);
+/* The closure of `mbgc-hip d --region`: the same sweep at the grain of granules of 2^granuleShift bytes of every planned contig's
+ * own coordinates. A row also says which bytes of its owner the load wrote: ownerFirst = the owner's byte the load's first byte is
+ * made of, reversed = the load ran backwards over the owner (a SWSEM_SEG_RC segment: byte vstart + k is the complement of owner
+ * byte ownerFirst - k; otherwise it is owner byte ownerFirst + k). granBase[c] (host, one entry per planned contig + 1): the bit of
+ * contig c's first granule, a prefix sum of ceil(destLen / granule). needGranules (bit g & 31 of word g >> 5) and needContigs (as
+ * `need` above), in: the granules the chosen regions lie in and the contigs that have one; out: those and, for every record
+ * whose destination range [destAt, the next record's destAt) holds a byte of a needed granule, the granules of the owners'
+ * bytes behind everything the record reads, and the owners. A record runs whole or not at all: the superset rule of the closure
+ * above, with "a granule is needed whole" and "a record that touches one runs whole" added. *filledBases (may be NULL): the bases
+ * those records write, what swsem_decode_fill_region_dev will fill. Both bitmaps stay in the handle for
+ * swsem_decode_fill_region_dev until the next plan or closure. */
+typedef struct { uint64_t vstart, len; int64_t owner; uint64_t ownerFirst; uint32_t reversed, pad; } swsem_prov_row_region_t;
+int swsem_decode_closure_region_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_region_t *rows, uint64_t ncontigs,
+                                    const uint64_t *timeOf, uint64_t nunits, const swsem_fill_unit_t *units, uint32_t granuleShift,
+                                    const uint64_t *granBase, uint32_t *needGranules, uint32_t *needContigs, uint64_t *filledBases);
+/* swsem_decode_fill_range_dev against that bitmap: of contigs [c0, c1) only the records whose destination range holds a byte of a
+ * needed granule are read and written; every other byte of dest_dev stays as it was. */
+int swsem_decode_fill_region_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *dest_dev, const uint64_t *destOff, uint64_t *nbad);
+/* One record of the plan, as swsem_decode_plan_chain_dev left it in the handle (a test hook, and what the host referee of the
+ * granule closure reads): flags bit 4 (16) = the pseudo-record of the literals behind the last match. *n = the contig's records,
+ * of which the first min(cap, *n) are copied. */
+typedef struct {
+    uint64_t litFrom, mark, destAt, src;
+    int64_t leftSrcMatch, leftSrcGuard;
+    uint64_t flLeft, flRight;
+    int64_t offsetDelta;
+    uint64_t guardLit;
+    uint32_t len, leftLen, leftCodes, rightLen, flags, pad;
+} swsem_decode_record_t;
+int swsem_debug_copy_records(swsem_t *h, uint64_t contig, swsem_decode_record_t *out, uint64_t cap, uint64_t *n);
 /* MBGC_Decoder::loadRef as a schedule: segments applied to the reference buffer in order. src: offset into src_dev (the decoded
  * contigs), or a reference position (FROM_REF: the per-target reverse complement of :608-616); dst: reference position;
  * RC: upperReverseComplement of the len source bytes; BYTE: the single byte `src & 0xFF` (a region separator). */

@@ -23,7 +23,8 @@ swsem_acquire_lock swsem_release_lock swsem_get_K swsem_get_hash_size swsem_load
 swsem_load_separator swsem_finalize_targets swsem_revcomp_dev swsem_match swsem_match_batch_dev swsem_batch_counts swsem_batch_matches
 swsem_batch_fingerprint swsem_emit_params_default swsem_emit swsem_emit_batch swsem_emit_batch_begin swsem_emit_batch_begin_spec swsem_emit_batch_end swsem_emit_select swsem_emit_result swsem_emit_set_host_copy swsem_emit_unmatched swsem_emit_pack_dev swsem_emit_pack_dev_on swsem_emit_counters swsem_debug_copy_ref swsem_debug_write_ref swsem_debug_copy_ht swsem_debug_emit_stats swsem_debug_tags swsem_debug_tag_summary
 swsem_profile_enable swsem_profile_get swsem_batch_stats swsem_dev_malloc swsem_dev_free swsem_dev_upload swsem_dev_download swsem_dev_copy swsem_decode_contigs_dev swsem_emit_verify
-swsem_create_decoder swsem_decode_plan_chain_dev swsem_decode_fill_range_dev swsem_decode_load_dev""".split()
+swsem_create_decoder swsem_decode_plan_chain_dev swsem_decode_fill_range_dev swsem_decode_load_dev
+swsem_decode_closure_region_dev swsem_decode_fill_region_dev swsem_debug_copy_records""".split()
 
 
 class SpecFinalize(C.Structure):
@@ -72,6 +73,22 @@ class LoadSeg(C.Structure):
 
 
 SEG_RC, SEG_FROM_REF, SEG_BYTE = 1, 2, 4
+
+
+class ProvRowRegion(C.Structure):
+    """swsem_prov_row_region_t: a load of the schedule and the bytes of its owner it wrote (`d --region`)"""
+    _fields_ = [("vstart", C.c_uint64), ("len", C.c_uint64), ("owner", C.c_int64), ("ownerFirst", C.c_uint64), ("reversed", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class FillUnit(C.Structure):
+    _fields_ = [("c0", C.c_uint64), ("c1", C.c_uint64)]
+
+
+class DecodeRecord(C.Structure):
+    """swsem_decode_record_t: one record of the plan"""
+    _fields_ = [("litFrom", C.c_uint64), ("mark", C.c_uint64), ("destAt", C.c_uint64), ("src", C.c_uint64), ("leftSrcMatch", C.c_int64), ("leftSrcGuard", C.c_int64),
+                ("flLeft", C.c_uint64), ("flRight", C.c_uint64), ("offsetDelta", C.c_int64), ("guardLit", C.c_uint64), ("len", C.c_uint32), ("leftLen", C.c_uint32),
+                ("leftCodes", C.c_uint32), ("rightLen", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class Streams(C.Structure):
@@ -150,6 +167,10 @@ def lib():
                                                   C.POINTER(C.c_uint32), pu64, u64, C.POINTER(ChainContig), C.POINTER(ci)]
         L.swsem_decode_fill_range_dev.argtypes = [vp, u64, u64, vp, pu64, pu64]
         L.swsem_decode_load_dev.argtypes = [vp, vp, ci, C.POINTER(LoadSeg)]
+        pu32 = C.POINTER(C.c_uint32)
+        L.swsem_decode_closure_region_dev.argtypes = [vp, u64, u64, C.POINTER(ProvRowRegion), u64, pu64, u64, C.POINTER(FillUnit), C.c_uint32, pu64, pu32, pu32, pu64]
+        L.swsem_decode_fill_region_dev.argtypes = [vp, u64, u64, vp, pu64, pu64]
+        L.swsem_debug_copy_records.argtypes = [vp, u64, C.POINTER(DecodeRecord), u64, pu64]
         L.swsem_debug_copy_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_write_ref.argtypes = [vp, u64, u64, vp]
         L.swsem_debug_copy_ht.argtypes = [vp, vp]

@@ -647,16 +647,47 @@ __global__ void __launch_bounds__(256) k_decode_load(const LoadSeg *__restrict__
 // ------------------------------------------------------------------------------------------------------------------
 // pass 2: the bytes — one thread per record
 // ------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_decode_fill(const uint8_t *__restrict__ ref, swsem_emit_params_t p, const DecodeJob *__restrict__ jobs,
-                                                     const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase,
-                                                     const DecPlanOut *__restrict__ plans, uint32_t *__restrict__ badFlags, uint64_t refBytes, uint32_t c0) {
+// The need state of a region decode (`mbgc-hip d --region`): one bit per granule of 2^shift bytes of every planned contig's own
+// coordinates, contig c's granules from bit granBase[c] on, and one bit per contig that has any (k_decode_closure_region).
+struct GranuleNeed { const uint32_t *bits; const uint32_t *contigBits; const uint64_t *granBase; uint32_t shift; };
+// any bit of [a, b) set (a < b): whole words between the two partial ones
+__device__ __forceinline__ bool granule_any(const uint32_t *__restrict__ bits, uint64_t a, uint64_t b) {
+    const uint64_t wa = a >> 5, wb = (b - 1) >> 5;
+    const uint32_t ma = 0xFFFFFFFFu << (a & 31u), mb = 0xFFFFFFFFu >> (31u - (uint32_t) ((b - 1) & 31u));
+    if (wa == wb) return (bits[wa] & ma & mb) != 0;
+    if (bits[wa] & ma) return true;
+    for (uint64_t w = wa + 1; w < wb; w++) if (bits[w]) return true;
+    return (bits[wb] & mb) != 0;
+}
+// record i of contig c writes [destAt, the next record's destAt) — the tail pseudo-record up to the contig's end; does that
+// range hold a byte of a needed granule
+__device__ __forceinline__ bool rec_needed(const GranuleNeed &g, const DecRec *__restrict__ crecs, uint64_t i, uint64_t nrec, uint64_t destLen, uint32_t c) {
+    const uint64_t a = crecs[i].destAt, b = i + 1 < nrec ? crecs[i + 1].destAt : destLen;
+    if (a >= b) return false;
+    return granule_any(g.bits, g.granBase[c] + (a >> g.shift), g.granBase[c] + ((b - 1) >> g.shift) + 1);
+}
+
+// The body of k_decode_fill and of k_decode_fill_region. MASKED: a record whose destination range holds no byte of a needed
+// granule is not read and writes nothing — its lane goes on as a lane without a record does, so the wave-wide copy loops and
+// their ballots see all 64 lanes; the decision sits where the record is fetched, not in an early return. Without MASKED the
+// need state is not looked at and the code is the one the kernel had before the split.
+template <bool MASKED>
+__device__ __forceinline__ void decode_fill_body(const uint8_t *__restrict__ ref, const swsem_emit_params_t &p, const DecodeJob *__restrict__ jobs,
+                                                 const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase,
+                                                 const DecPlanOut *__restrict__ plans, uint32_t *__restrict__ badFlags, uint64_t refBytes, uint32_t c0,
+                                                 const GranuleNeed &g) {
     const uint32_t c = c0 + blockIdx.y;                                     // (grid.y holds at most 65 535: the host launches slices of contigs)
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (plans[c].unmatched < 0 || (uint64_t) blockIdx.x * blockDim.x >= plans[c].nrec) return;
+    if constexpr (MASKED) { if (!((g.contigBits[c >> 5] >> (c & 31u)) & 1u)) return; }   // (block-uniform: no granule of this contig is needed)
     // (a lane without a record of its own stays: the long pieces below are the work of all 64 lanes of a wave)
     DecRec r = {};
     r.flags = REC_TAIL;
-    if (i < plans[c].nrec) r = recs[recBase[c] + i];
+    if constexpr (MASKED) {
+        if (i < plans[c].nrec && rec_needed(g, recs + recBase[c], i, plans[c].nrec, plans[c].destLen, c)) r = recs[recBase[c] + i];
+    } else {
+        if (i < plans[c].nrec) r = recs[recBase[c] + i];
+    }
     const DecodeJob &jb = jobs[c];
     Dec d;
     d.ref = ref; d.solo = true; d.refBytes = refBytes;
@@ -756,6 +787,21 @@ __global__ void __launch_bounds__(256) k_decode_fill(const uint8_t *__restrict__
     }
     if (d.bad) atomicOr(&badFlags[c], 1u);
 }
+__global__ void __launch_bounds__(256) k_decode_fill(const uint8_t *__restrict__ ref, swsem_emit_params_t p, const DecodeJob *__restrict__ jobs,
+                                                     const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase,
+                                                     const DecPlanOut *__restrict__ plans, uint32_t *__restrict__ badFlags, uint64_t refBytes, uint32_t c0) {
+    decode_fill_body<false>(ref, p, jobs, recs, recBase, plans, badFlags, refBytes, c0, GranuleNeed{});
+}
+// `d --region`: the records of contigs [c0, c0 + grid.y) that write into a needed granule, and no other. The loads that follow
+// (k_decode_load) stay whole-segment: a contig that is filled in part goes into the reference buffer whole, its unfilled bytes
+// as whatever the sequence buffer held — the closure marked every byte a needed record reads, so a byte that was never needed
+// is never read by a needed record, and no other record runs.
+__global__ void __launch_bounds__(256) k_decode_fill_region(const uint8_t *__restrict__ ref, swsem_emit_params_t p, const DecodeJob *__restrict__ jobs,
+                                                            const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase,
+                                                            const DecPlanOut *__restrict__ plans, uint32_t *__restrict__ badFlags, uint64_t refBytes, uint32_t c0,
+                                                            GranuleNeed g) {
+    decode_fill_body<true>(ref, p, jobs, recs, recBase, plans, badFlags, refBytes, c0, g);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // the dependency closure of a selection (`mbgc-hip d --select`): which contigs' loads wrote the bytes a contig reads
@@ -805,6 +851,71 @@ __global__ void __launch_bounds__(256) k_decode_closure(const DecRec *__restrict
         if (b > refPos && lap) {
             const uint64_t base = (lap - 1) * refTotalLength;
             closure_mark(rows, nrows, base + (a > refPos ? a : refPos), base + b, need, firstOfUnit);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// the closure of `mbgc-hip d --region`: the same sweep at the grain of granules
+// ------------------------------------------------------------------------------------------------------------------
+// The need state is GranuleNeed's bitmap (and the contig bits, which say where a block has anything to do). A provenance row
+// also says WHICH bytes of its owner the load wrote: ownerFirst = the owner's byte that the load's first byte is (made of),
+// reversed = the load ran backwards over the owner (SWSEM_SEG_RC: byte vstart + k is the complement of owner byte
+// ownerFirst - k; else it is owner byte ownerFirst + k). So a virtual range maps to a byte range of the owner, and a record
+// that must run marks the granules of exactly the owners' bytes behind its rec_read_ranges. A record must run when its
+// destination range [destAt, next destAt) — REC_TAIL: up to the contig's length — holds a byte of a needed granule; a record
+// runs whole or not at all (k_decode_fill_region), so everything it reads is marked, not only what the needed bytes come from.
+// The in-unit argument carries over granule by granule: a contig reads only what units in front of its own loaded
+// (firstOfUnit: a row whose owner lies at or behind it is never read, its granules stay as they are), the units are swept
+// last first, one launch each, so every granule bit of a block's own contig was set by a launch that has ended — it is final
+// when the block reads it, and one pass is the fixpoint. A superset, never a subset: the ranges are the hull's, a separator
+// inside a segment keeps the segment's owner, a granule is needed whole, and a record that touches it runs whole.
+struct ProvRowG { uint64_t vstart, len; int64_t owner; uint64_t ownerFirst; uint32_t reversed, pad; };   // == swsem_prov_row_region_t
+__device__ __forceinline__ void closure_mark_region(const ProvRowG *__restrict__ rows, uint64_t nrows, uint64_t va, uint64_t vb, uint32_t *need, uint32_t *contigNeed,
+                                                    const uint64_t *__restrict__ granBase, uint32_t shift, uint32_t firstOfUnit) {
+    uint64_t lo = 0, hi = nrows;                                              // the first row that ends behind va
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (rows[mid].vstart + rows[mid].len > va) hi = mid; else lo = mid + 1;
+    }
+    for (; lo < nrows && rows[lo].vstart < vb; lo++) {
+        const ProvRowG w = rows[lo];
+        if (w.owner < 0 || w.owner >= (int64_t) firstOfUnit) continue;
+        const uint64_t a = (va > w.vstart ? va : w.vstart) - w.vstart, b = (vb < w.vstart + w.len ? vb : w.vstart + w.len) - w.vstart;   // [a, b) of the load, a < b
+        const uint64_t oa = w.reversed ? w.ownerFirst + 1 - b : w.ownerFirst + a, ob = oa + (b - a);                                    // ... is [oa, ob) of the owner
+        const uint32_t cbit = 1u << ((uint32_t) w.owner & 31u);
+        if (!(contigNeed[w.owner >> 5] & cbit)) atomicOr(&contigNeed[w.owner >> 5], cbit);
+        const uint64_t g1 = granBase[w.owner] + ((ob - 1) >> shift);
+        for (uint64_t gq = granBase[w.owner] + (oa >> shift); gq <= g1; gq++) {
+            const uint32_t bit = 1u << ((uint32_t) gq & 31u);
+            if (!(need[gq >> 5] & bit)) atomicOr(&need[gq >> 5], bit);        // (a plain read first: most granules are marked already)
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_decode_closure_region(const DecRec *__restrict__ recs, const uint64_t *__restrict__ recBase, const DecPlanOut *__restrict__ plans,
+                                                               const ProvRowG *__restrict__ rows, uint64_t nrows, const uint64_t *__restrict__ timeOf, uint32_t *need,
+                                                               uint32_t *contigNeed, const uint64_t *__restrict__ granBase, uint32_t shift,
+                                                               uint64_t refTotalLength, uint32_t c0, uint32_t firstOfUnit, unsigned long long *filled) {
+    const uint32_t c = c0 + blockIdx.y;                                     // (grid.y holds at most 65 535: slices, as k_decode_fill)
+    if (!((contigNeed[c >> 5] >> (c & 31u)) & 1u)) return;                    // no granule of this contig is needed
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (plans[c].unmatched < 0 || i >= plans[c].nrec) return;
+    const GranuleNeed g = {need, contigNeed, granBase, shift};
+    if (!rec_needed(g, recs + recBase[c], i, plans[c].nrec, plans[c].destLen, c)) return;   // the record does not run
+    const DecRec r = recs[recBase[c] + i];
+    // (every record of a needed contig is seen once, here, with its contig's bits final: the bases the fill will write)
+    atomicAdd(filled, (unsigned long long) ((i + 1 < plans[c].nrec ? recs[recBase[c] + i + 1].destAt : plans[c].destLen) - r.destAt));
+    DecRange rg[3];
+    const int nr = rec_read_ranges(r, rg);
+    const uint64_t tv = timeOf[c], lap = tv / refTotalLength, refPos = tv % refTotalLength;
+    for (int q = 0; q < nr; q++) {
+        const uint64_t a = rg[q].lo, b = rg[q].hi < refTotalLength ? rg[q].hi : refTotalLength;   // (nothing is loaded beyond the buffer)
+        if (a >= b) continue;
+        // a range that straddles the loader's position is split there
+        if (a < refPos) closure_mark_region(rows, nrows, lap * refTotalLength + a, lap * refTotalLength + (b < refPos ? b : refPos), need, contigNeed, granBase, shift, firstOfUnit);
+        if (b > refPos && lap) {
+            const uint64_t base = (lap - 1) * refTotalLength;
+            closure_mark_region(rows, nrows, base + (a > refPos ? a : refPos), base + b, need, contigNeed, granBase, shift, firstOfUnit);
         }
     }
 }

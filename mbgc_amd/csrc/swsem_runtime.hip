@@ -658,6 +658,33 @@ int swsem_decode_closure_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows
     return decode_closure(h, refTotalLength, nrows, rows, ncontigs, timeOf, nunits, units, need);
 }
 
+int swsem_decode_closure_region_dev(swsem_t *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_region_t *rows, uint64_t ncontigs, const uint64_t *timeOf,
+                                    uint64_t nunits, const swsem_fill_unit_t *units, uint32_t granuleShift, const uint64_t *granBase, uint32_t *needGranules,
+                                    uint32_t *needContigs, uint64_t *filledBases) {
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->decoder) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: the handle is no decoder's (swsem_create_decoder)");
+    if (!timeOf || !granBase || !needGranules || !needContigs || (nrows && !rows) || (nunits && !units)) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: a table is missing");
+    return decode_closure_region(h, refTotalLength, nrows, rows, ncontigs, timeOf, nunits, units, granuleShift, granBase, needGranules, needContigs, filledBases);
+}
+
+int swsem_decode_fill_region_dev(swsem_t *h, uint64_t c0, uint64_t c1, uint8_t *dest_dev, const uint64_t *destOff, uint64_t *nbad) {
+    HIPCHK(hipSetDevice(h->device));
+    int r = decode_fill_range(h, c0, c1, dest_dev, destOff, true);
+    if (r || !nbad) return r;
+    std::vector<uint32_t> bad(c1 - c0);
+    if (c1 > c0) HIPCHK(hipMemcpyAsync(bad.data(), h->chain.dBad.p + c0, (c1 - c0) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *nbad = 0;
+    for (uint32_t b : bad) *nbad += b != 0;
+    return SWSEM_OK;
+}
+
+int swsem_debug_copy_records(swsem_t *h, uint64_t contig, swsem_decode_record_t *out, uint64_t cap, uint64_t *n) {
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->decoder || !n || (cap && !out)) return fail(SWSEM_EINVAL, "swsem_debug_copy_records: a decoder's handle, a count and a buffer");
+    return decode_copy_records(h, contig, out, cap, n);
+}
+
 int swsem_decode_load_dev(swsem_t *h, const uint8_t *src_dev, int n, const swsem_load_seg_t *segs) {
     HIPCHK(hipSetDevice(h->device));
     return decode_load(h, src_dev, n, segs);

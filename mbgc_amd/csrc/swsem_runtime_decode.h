@@ -54,7 +54,7 @@ int decode_plan_chain(swsem *h, const swsem_emit_params_t *p, const ChainStreams
                       const uint32_t *seqCount, const uint64_t *lockPos, uint64_t ncontigs, swsem_chain_contig_t *out, int *firstBadChain) {
     static_assert(sizeof(ChainContig) == sizeof(swsem_chain_contig_t), "swsem_chain_contig_t");
     auto &C = h->chain;
-    C.n = 0; C.jobsDest = nullptr;
+    C.n = 0; C.jobsDest = nullptr; C.regionFor = 0;
     int r;
     const uint64_t w = p->frugal64bitLenEncoding ? 2 : 4;
     // records a chain can need: one per mapLen entry of its span (two bytes at least, four without the frugal encoding) and a
@@ -107,9 +107,11 @@ int decode_plan_chain(swsem *h, const swsem_emit_params_t *p, const ChainStreams
     return SWSEM_OK;
 }
 
-// contigs [c0, c1) of the planned collection into dest + destOff[c]: one k_decode_fill launch (slices of 65 535 contigs)
-int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const uint64_t *destOff) {
+// contigs [c0, c1) of the planned collection into dest + destOff[c]: one k_decode_fill launch (slices of 65 535 contigs);
+// masked: k_decode_fill_region against the granule bitmap decode_closure_region left in the handle
+int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const uint64_t *destOff, bool masked = false) {
     auto &C = h->chain;
+    if (masked && (C.regionFor != C.n || C.n == 0)) return fail(SWSEM_EINVAL, "swsem_decode_fill_region_dev: no granule closure has been made for this plan (swsem_decode_closure_region_dev)");
     if (c1 > C.n || c0 > c1) return fail(SWSEM_EINVAL, "swsem_decode_fill_range_dev: contigs [%llu, %llu) of %llu planned", (unsigned long long) c0, (unsigned long long) c1, (unsigned long long) C.n);
     int r;
     if (C.jobsDest != dest || !dest) {
@@ -134,7 +136,12 @@ int decode_fill_range(swsem *h, uint64_t c0, uint64_t c1, uint8_t *dest, const u
         uint64_t maxRec = 0;
         for (uint64_t c = a; c < a + cn; c++) maxRec = std::max(maxRec, C.nrec[c]);
         if ((maxRec + 255) / 256 > 0x7FFFFFFFull) return fail(SWSEM_EINVAL, "swsem decode: a contig too long for one launch");
-        if (maxRec) k_decode_fill<<<dim3((unsigned) ((maxRec + 255) / 256), (unsigned) cn), dim3(256), 0, h->stream>>>(h->ref, C.params, h->dJobs.p, h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dBad.p, h->maxRefLength + REF_SLACK, (uint32_t) a);
+        if (!maxRec) continue;
+        const dim3 grid((unsigned) ((maxRec + 255) / 256), (unsigned) cn);
+        if (masked) {
+            const GranuleNeed g = {C.dNeedG.p, C.dNeed.p, C.dGranBase.p, C.granShift};
+            k_decode_fill_region<<<grid, dim3(256), 0, h->stream>>>(h->ref, C.params, h->dJobs.p, h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dBad.p, h->maxRefLength + REF_SLACK, (uint32_t) a, g);
+        } else k_decode_fill<<<grid, dim3(256), 0, h->stream>>>(h->ref, C.params, h->dJobs.p, h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dBad.p, h->maxRefLength + REF_SLACK, (uint32_t) a);
     }
     HIPCHK(hipGetLastError());
     return SWSEM_OK;
@@ -173,6 +180,82 @@ int decode_closure(swsem *h, uint64_t refTotalLength, uint64_t nrows, const swse
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(need, C.dNeed.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SWSEM_OK;
+}
+
+// The closure of `d --region` (k_decode_closure_region): as decode_closure, the need state a bitmap over granules of 2^shift
+// bytes (contig c's from bit granBase[c] on) beside the contig bits. Every row and offset is held to the plan before a launch:
+// a row that names bytes its owner does not have would set bits of another contig's granules, or beyond the bitmap. Both
+// bitmaps stay in the handle for swsem_decode_fill_region_dev.
+int decode_closure_region(swsem *h, uint64_t refTotalLength, uint64_t nrows, const swsem_prov_row_region_t *rows, uint64_t ncontigs, const uint64_t *timeOf,
+                          uint64_t nunits, const swsem_fill_unit_t *units, uint32_t granuleShift, const uint64_t *granBase, uint32_t *needGranules, uint32_t *needContigs,
+                          uint64_t *filledBases) {
+    static_assert(sizeof(ProvRowG) == sizeof(swsem_prov_row_region_t) && sizeof(ProvRowG) == 40, "swsem_prov_row_region_t");
+    auto &C = h->chain;
+    C.regionFor = 0;
+    if (ncontigs != C.n || ncontigs == 0 || ncontigs > 0xFFFFFFFFull) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: %llu contigs, %llu planned", (unsigned long long) ncontigs, (unsigned long long) C.n);
+    if (refTotalLength == 0) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: reference length");
+    if (granuleShift < 4 || granuleShift > 30) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: a granule of 2^%u bytes (16 B to 1 GiB)", granuleShift);
+    const uint64_t G = 1ull << granuleShift;
+    if (granBase[0] != 0) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: the granule offsets do not start at 0");
+    for (uint64_t c = 0; c < ncontigs; c++)
+        if (granBase[c + 1] - granBase[c] != (C.destLen[c] + G - 1) / G) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: contig %llu does not have the granules of its length", (unsigned long long) c);
+    for (uint64_t k = 0; k < nrows; k++) {
+        const swsem_prov_row_region_t &w = rows[k];
+        if (w.owner >= (int64_t) ncontigs || (k && w.vstart < rows[k - 1].vstart + rows[k - 1].len))
+            return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: row %llu of the provenance table is out of order or names no planned contig", (unsigned long long) k);
+        if (w.owner < 0 || w.len == 0) continue;
+        const uint64_t n = C.destLen[w.owner];
+        const bool inside = w.reversed ? (w.ownerFirst < n && w.len <= w.ownerFirst + 1) : (w.ownerFirst <= n && w.len <= n - w.ownerFirst);
+        if (!inside) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: row %llu of the provenance table names bytes its owner does not have", (unsigned long long) k);
+    }
+    for (uint64_t u = 0; u < nunits; u++)
+        if (units[u].c0 > units[u].c1 || units[u].c1 > ncontigs) return fail(SWSEM_EINVAL, "swsem_decode_closure_region_dev: unit %llu leaves the plan", (unsigned long long) u);
+    const size_t words = (size_t) ((ncontigs + 31) / 32), gwords = (size_t) ((granBase[ncontigs] + 31) / 32);
+    int r;
+    if ((r = C.dProvG.reserve(nrows + 1)) || (r = C.dTime.reserve(ncontigs)) || (r = C.dNeed.reserve(words)) || (r = C.dNeedG.reserve(gwords + 3)) || (r = C.dGranBase.reserve(ncontigs + 1))) return r;
+    if (nrows) HIPCHK(hipMemcpyAsync(C.dProvG.p, rows, nrows * sizeof(ProvRowG), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dTime.p, timeOf, ncontigs * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dGranBase.p, granBase, (ncontigs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(C.dNeed.p, needContigs, words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (gwords) HIPCHK(hipMemcpyAsync(C.dNeedG.p, needGranules, gwords * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    // (the counter of filled bases: eight bytes behind the bitmap, on an eight-byte boundary)
+    unsigned long long *dFilled = (unsigned long long *) (C.dNeedG.p + ((gwords + 1) & ~(size_t) 1));
+    HIPCHK(hipMemsetAsync(dFilled, 0, sizeof *dFilled, h->stream));
+    constexpr uint64_t YMAX = 65535;
+    for (uint64_t u = nunits; u-- > 0;) {
+        for (uint64_t a = units[u].c0; a < units[u].c1; a += YMAX) {
+            const uint64_t cn = std::min<uint64_t>(YMAX, units[u].c1 - a);
+            uint64_t maxRec = 0;
+            for (uint64_t c = a; c < a + cn; c++) maxRec = std::max(maxRec, C.nrec[c]);
+            if ((maxRec + 255) / 256 > 0x7FFFFFFFull) return fail(SWSEM_EINVAL, "swsem decode: a contig too long for one launch");
+            if (maxRec) k_decode_closure_region<<<dim3((unsigned) ((maxRec + 255) / 256), (unsigned) cn), dim3(256), 0, h->stream>>>(h->dDecRecs.p, C.dRecBase.p, h->dDecPlan.p, C.dProvG.p, nrows, C.dTime.p, C.dNeedG.p, C.dNeed.p, C.dGranBase.p, granuleShift, refTotalLength, (uint32_t) a, (uint32_t) units[u].c0, dFilled);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(needContigs, C.dNeed.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (gwords) HIPCHK(hipMemcpyAsync(needGranules, C.dNeedG.p, gwords * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    unsigned long long filled = 0;
+    HIPCHK(hipMemcpyAsync(&filled, dFilled, sizeof filled, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (filledBases) *filledBases = filled;
+    C.granShift = granuleShift; C.regionFor = C.n;
+    return SWSEM_OK;
+}
+
+// the planned records of contig c as the plan left them (tests and the host referee of the granule closure)
+int decode_copy_records(swsem *h, uint64_t c, swsem_decode_record_t *out, uint64_t cap, uint64_t *n) {
+    static_assert(sizeof(DecRec) == sizeof(swsem_decode_record_t) && sizeof(DecRec) == 104, "swsem_decode_record_t");
+    auto &C = h->chain;
+    if (c >= C.n) return fail(SWSEM_EINVAL, "swsem_debug_copy_records: contig %llu of %llu planned", (unsigned long long) c, (unsigned long long) C.n);
+    *n = C.nrec[c];
+    const uint64_t m = std::min(cap, C.nrec[c]);
+    if (!m) return SWSEM_OK;
+    uint64_t base = 0;
+    HIPCHK(hipMemcpyAsync(&base, C.dRecBase.p + c, sizeof base, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(out, h->dDecRecs.p + base, m * sizeof(DecRec), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SWSEM_OK;
 }

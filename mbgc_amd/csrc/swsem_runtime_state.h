@@ -298,6 +298,11 @@ struct swsem {
         DevBuf<ProvRow> dProv;               // the closure of a selection: provenance table, per-contig times, need bitmap
         DevBuf<uint64_t> dTime;
         DevBuf<uint32_t> dNeed;
+        DevBuf<ProvRowG> dProvG;             // the closure of --region: rows that name the owner's bytes, the granule bitmap, its prefix offsets
+        DevBuf<uint32_t> dNeedG;
+        DevBuf<uint64_t> dGranBase;
+        uint32_t granShift = 0;              // log2 of the granule; regionFor: the plan (its contig count) the bitmap was made for, 0 = none
+        uint64_t regionFor = 0;
         ChainStreams streams = {};
         swsem_emit_params_t params = {};
         uint64_t n = 0;                      // contigs planned

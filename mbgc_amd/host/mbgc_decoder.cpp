@@ -11,6 +11,7 @@
 #include <fstream>
 #include <future>
 #include <set>
+#include <tuple>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -193,6 +194,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_streams.h"    // what is on disk: StreamSet, Selection, the walk over the chosen units
 #include "mbgc_decoder_run.h"        // one pass on the device: DecodedCollection
 #include "mbgc_decoder_fasta.h"      // text out of it: FastaLayout, FastaPlan, FastaStage, the writer of d --fasta
+#include "mbgc_decoder_region.h"     // d --region: the specs, the pieces, their outputs
 #include "mbgc_decoder_validate.h"   // v: Validation
 #include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
 
@@ -298,6 +300,9 @@ void reportBench(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamS
     if (sel.selectingSeq)
         selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_ms\": %.3f, \"records_chosen\": %llu, \"records\": %llu, \"patterns\": %zu", sel.matchMs,
                           (unsigned long long) sel.recordsChosen, (unsigned long long) sel.recordsAll, opt.selectSeq.size());
+    if (sel.selectingRegion)
+        selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_ms\": %.3f, \"regions\": %zu, \"region_bases\": %llu, \"granule_bytes\": %u", sel.matchMs,
+                          sel.pieces.size(), (unsigned long long) sel.regionBases, 1u << sel.granuleShift);
     if (sel.selectingSeq && opt.selectSeqHost) selAt += snprintf(selJson + selAt, sizeof selJson - selAt, ", \"header_match_host_ms\": %.3f", sel.matchHostMs);
     if (opt.check)
         snprintf(selJson + selAt, sizeof selJson - selAt, ", \"crc_kernel_ms\": %.3f, \"crc_bytes\": %llu, \"crc_gb_per_s\": %.3f", chk.kernelMs, (unsigned long long) chk.bytes,
@@ -328,6 +333,9 @@ void report(const MBGC_Decoder::Options &opt, bool wantFasta, const StreamSet &S
                (unsigned long long) D.closureBases, (unsigned long long) out.plannedBases, (unsigned long long) sel.selectedFiles, (unsigned long long) D.dependencyTargets);
     if (sel.selectingSeq)
         printf("records: %llu of %llu chosen in %llu files\n", (unsigned long long) sel.recordsChosen, (unsigned long long) sel.recordsAll, (unsigned long long) sel.selectedFiles);
+    if (sel.selectingRegion)
+        printf("regions: %zu pieces of %llu records, %llu bases, %llu out of range\n", sel.pieces.size(), (unsigned long long) sel.regionRecords, (unsigned long long) sel.regionBases,
+               (unsigned long long) sel.regionSkipped);
     printf("waves: %llu for %zu targets\n", (unsigned long long) D.times.waves, S.T());
     printf("widest wave: %llu targets\n", (unsigned long long) D.times.widest);
     printf("decoded: %llu contigs, %llu bases\n", (unsigned long long) out.contigs, (unsigned long long) out.bases);
@@ -352,11 +360,12 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     // (--check names a differing contig by its file and header: the whole layout)
     const bool wantLayout = wantFasta || opt.check;
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
-    if (!wantLayout && !opt.selectSeq.empty() && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
+    if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
     // --select: with a layout its names are used, without one (plain `d`) .names is read for it; --select-seq: the records of the
     // files that passed, by their headers, on the device
-    if (!chooseUnits(prefix, S, opt.select, wantFasta ? &layout.names : nullptr, sel, msg) || !chooseRecords(prefix, S, opt, layout, sel, msg)) return failed();
+    if (!chooseUnits(prefix, S, opt.select, wantFasta ? &layout.names : nullptr, sel, msg) || !chooseRecords(prefix, S, opt, layout, sel, msg) ||
+        !chooseRegions(prefix, S, opt, layout, sel, msg)) return failed();
     const std::vector<ChosenUnit> chosen = chosenUnits(S.g0n, S.seqCount.data(), S.T(), sel.unitSel.data(), sel.selectingSeq ? sel.contigSel.data() : nullptr,
                                                       S.meta.sequentialMatching);
     // --bench: two passes, a fresh handle for each; the second one is the timed one, and the only one `v` and the report speak of
@@ -365,8 +374,13 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     for (int pass = 0; pass < passes; pass++) {
         const bool last = pass + 1 == passes;
         DecodedCollection D;
-        if (!D.upload(S, opt.device, msg) || !D.planAndSchedule(S, opt.serial, msg) || !D.closure(S, sel, msg) || !D.forwardRun(S, sel.selecting, msg)) return failed();
-        const OutputCount out = countOutput(D, S.g0n, chosen);
+        if (!D.upload(S, opt.device, msg) || !D.planAndSchedule(S, opt.serial, msg)) return failed();
+        if (sel.selectingRegion) resolveRegions(D.contigLen, S.meta.singleFastaFile, sel);       // (the plan has said how long every record is)
+        if (!D.closure(S, sel, msg) || !D.forwardRun(S, sel.selecting, msg)) return failed();
+        OutputCount out = countOutput(D, S.g0n, chosen);
+        // --region: what leaves the decoder is the pieces, not the chosen records they are cut from
+        const RegionOutput pieces = sel.selectingRegion ? regionOutput(D, sel, layout, wantFasta) : RegionOutput();
+        if (sel.selectingRegion) { out.bases = sel.regionBases; out.contigs = sel.pieces.size(); }
         // `r` ends here: no report, no sequence files
         if (opt.resident) return handOverResident(D, S, sel, layout, chosen, out, *opt.resident, msg) ? 0 : failed();
         FastaTimes ftimes;
@@ -374,20 +388,25 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         CheckResult chk;
         if (opt.check && last && !checkChecksums(prefix, D, S, layout, chosen, manifest, opt.device, chk, msg)) return failed();
         if (wantFasta) {
-            const FastaPlan plan = planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip, sel.selectingSeq);
+            const FastaPlan plan = sel.selectingRegion ? planFasta(pieces.rows, S.meta, pieces.layout, pieces.len, opt.batchText, opt.gzip, true)
+                                                       : planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip, sel.selectingSeq);
+            const FastaLayout &text = sel.selectingRegion ? pieces.layout : layout;              // (the pieces carry headers of their own)
             const bool writeFiles = !opt.validate && (!opt.bench || pass == 0);                  // (bench: pass 0 writes, the timed pass formats and downloads only)
             if (std::string dir; writeFiles && !makeDirs(opt.fastaDir, &dir)) { msg = "cannot create the directory " + dir; return failed(); }
             FastaStage stage;                                                                    // (behind D: it ends before the collection it reads)
-            if (!stage.open(D, plan, layout, opt.device, opt.gzip, msg)) return failed();
+            if (sel.selectingRegion) { stage.recOff = &pieces.off; stage.recLen = &pieces.len; }
+            if (!stage.open(D, plan, text, opt.device, opt.gzip, msg)) return failed();
             if (opt.validate) {
                 Validation v(D, plan, stage, layout, S.meta, opt, last);
                 if (!v.run(msg)) return failed();
                 vres = v.res;
-            } else if (!writeFastaFiles(plan, stage, layout, opt, writeFiles, msg)) return failed();
+            } else if (!writeFastaFiles(plan, stage, text, opt, writeFiles, msg)) return failed();
             ftimes = stage.times;
         }
         // the sequence files and --closure-out: on the last pass, and only without --bench and without `v`
-        if (last && !opt.bench && !opt.validate && !opt.writeNothing && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, sel.selectingSeq && S.meta.singleFastaFile, msg)) return failed();
+        const bool writeSeq = last && !opt.bench && !opt.validate && !opt.writeNothing;
+        if (writeSeq && sel.selectingRegion && !writeRegionFiles(D, pieces, out.bases, opt.device, opt.closureOut, outPrefix, S.meta.singleFastaFile, msg)) return failed();
+        if (writeSeq && !sel.selectingRegion && !writeSequenceFiles(D, chosen, out, opt.closureOut, outPrefix, sel.selectingSeq && S.meta.singleFastaFile, msg)) return failed();
         if (last) {
             report(opt, wantFasta, S, sel, D, out, ftimes, vres, chk);
             status = (opt.validate && vres.invalidFiles) || (opt.check && chk.differs()) ? 2 : 0;
@@ -422,9 +441,48 @@ int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decode
         if (!mbgc_hip_read_pattern_list(argv[++i], opt.selectSeq)) { fprintf(stderr, "mbgc-hip %c: cannot open the pattern list %s\n", tool, argv[i]); return -1; }
         opt.selectSeqAsked = true;
     }
+    else if (a == "--region" && i + 1 < argc) {
+        MBGC_Decoder::RegionSpec spec;
+        std::string why;
+        if (!MBGC_Decoder::parseRegionSpec(argv[++i], spec, &why)) { fprintf(stderr, "mbgc-hip %c: --region '%s': %s\n", tool, argv[i], why.c_str()); return -1; }
+        opt.regions.push_back(spec); opt.regionAsked = true;
+    }
+    else if (a == "--region-list" && i + 1 < argc) {
+        std::vector<std::string> lines;
+        if (!mbgc_hip_read_pattern_list(argv[++i], lines)) { fprintf(stderr, "mbgc-hip %c: cannot open the region list %s\n", tool, argv[i]); return -1; }
+        for (const std::string &line : lines) {
+            MBGC_Decoder::RegionSpec spec;
+            std::string why;
+            if (!MBGC_Decoder::parseRegionSpec(line, spec, &why)) { fprintf(stderr, "mbgc-hip %c: --region-list: '%s': %s\n", tool, line.c_str(), why.c_str()); return -1; }
+            opt.regions.push_back(spec);
+        }
+        opt.regionAsked = true;
+    }
     else if (a == "-d" && i + 1 < argc) opt.device = atoi(argv[++i]);
     else return 0;
     return 1;
+}
+
+bool MBGC_Decoder::parseRegionSpec(const std::string &text, RegionSpec &out, std::string *why) {
+    const auto bad = [why](const char *what) { if (why) *why = what; return false; };
+    const size_t colon = text.rfind(':');
+    if (colon == std::string::npos) return bad("a region is PATTERN:FROM-TO (no ':')");
+    if (colon == 0) return bad("an empty pattern");
+    out.pattern = text.substr(0, colon);
+    if (out.pattern.find('\n') != std::string::npos) return bad("the pattern holds a line feed, a header holds none");
+    const std::string range = text.substr(colon + 1);
+    const size_t dash = range.find('-');
+    if (dash == std::string::npos) return bad("a region is PATTERN:FROM-TO (no '-' behind the last ':')");
+    uint64_t v[2];
+    const std::string part[2] = {range.substr(0, dash), range.substr(dash + 1)};
+    for (int k = 0; k < 2; k++) {
+        if (part[k].empty() || part[k].size() > 18 || part[k].find_first_not_of("0123456789") != std::string::npos) return bad("FROM and TO are positive decimal numbers");
+        v[k] = strtoull(part[k].c_str(), nullptr, 10);
+    }
+    if (v[0] < 1) return bad("FROM is 1-based: the first base is 1");
+    if (v[0] > v[1]) return bad("FROM lies behind TO");
+    out.from = v[0]; out.to = v[1];
+    return true;
 }
 
 bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool selectAsked) {
@@ -435,12 +493,22 @@ bool mbgc_hip_check_selection(char tool, const MBGC_Decoder::Options &opt, bool 
         if (pat.find('\n') != std::string::npos) { fprintf(stderr, "mbgc-hip %c: --select-seq: a pattern holds a line feed, a header holds none\n", tool); return false; }
     }
     if (opt.selectSeqAsked && opt.selectSeq.empty()) { fprintf(stderr, "mbgc-hip %c: --select-seq-list: the list of patterns is empty\n", tool); return false; }
+    if (opt.regionAsked && opt.regions.empty()) { fprintf(stderr, "mbgc-hip %c: --region-list: the list of regions is empty\n", tool); return false; }
+    if (opt.regionAsked && opt.selectSeqAsked) {
+        fprintf(stderr, "mbgc-hip %c: --region and --select-seq / --select-seq-list in one run: a region names its records itself (PATTERN:FROM-TO)\n", tool);
+        return false;
+    }
+    if (opt.regionAsked && opt.check) {
+        fprintf(stderr, "mbgc-hip %c: --region with --check: <streamsPrefix>.checksums holds the CRC-32 of whole contigs, a part of one has none to be held against\n", tool);
+        return false;
+    }
     return true;
 }
 
 const char *const MBGC_HIP_D_USAGE =
     "mbgc-hip d [--serial] [--no-index] [--bench] [--restore-rc] [--fasta dir [--gzip] [--batch-kib K]] [--select pattern]...\n"
-    "                  [--select-list file] [--select-seq pattern]... [--select-seq-list file] [--closure-out file] [--check] [-d device]\n"
+    "                  [--select-list file] [--select-seq pattern]... [--select-seq-list file] [--region 'pattern:from-to']...\n"
+    "                  [--region-list file] [--closure-out file] [--check] [-d device]\n"
     "                  <streamsPrefix> <outputPrefix>\n"
     "  rebuilds every sequence of the collection from the raw streams and <streamsPrefix>.meta of mbgc-hip c, on the device; writes\n"
     "  <outputPrefix>.seq (the bases of all contigs back to back), .contigLens (u64 each) and .seqCounts (u32 per file or target)\n"
@@ -458,6 +526,14 @@ const char *const MBGC_HIP_D_USAGE =
     "  '>') contains a pattern — a plain substring, case-sensitive, matched on the device against <streamsPrefix>.headers — and the contigs\n"
     "  they depend on are decoded; with --select a record's file must pass that too. A file holds its chosen records in order, a file\n"
     "  without one is not written, .seqCounts counts the chosen records per written file; -i streams: the one file, one count\n"
+    "  --region 'pattern:from-to' (repeatable) / --region-list file (a spec per line): only bases from..to (1-based, inclusive) of the records\n"
+    "  whose header line contains the pattern (as --select-seq; the spec is split at its last ':') are written, and only what they depend on\n"
+    "  is decoded — at the grain of granules of 256 bytes, not of contigs. to is clamped to the record's length; a region that starts behind the\n"
+    "  record's end yields nothing and is counted. The pieces are written in collection order, by record, from, to (identical ones once):\n"
+    "  .seq holds them back to back, .contigLens their lengths, .seqCounts the pieces per written file; --fasta writes a record per piece,\n"
+    "  its header the record's with :from-to behind the first word. Prints `regions: <pieces> pieces of <records> records, <bases> bases,\n"
+    "  <skipped> out of range`; the closure: line counts the bases actually filled. With --select a record's file must pass that too.\n"
+    "  Not with --select-seq or --check. --bench gains regions, region_bases, granule_bytes\n"
     "  --closure-out file: a byte per contig of the targets: 0 not filled, 1 filled as a dependency, 2 filled because chosen\n"
     "  --check: before anything is written, the CRC-32 of every chosen contig's bases is taken on the device and held against\n"
     "  <streamsPrefix>.checksums (mbgc-hip c --checksums), the side files' on the host; prints `checksums: <checked> of <N> contigs checked,\n"
@@ -501,13 +577,18 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
         else if (a == "--batch-kib" && i + 1 < argc) opt.batchText = (uint64_t) atoll(argv[++i]) << 10;
         else if (a == "--closure-out" && i + 1 < argc) opt.closureOut = argv[++i];
         else if (a == "--check") opt.check = true;
+        else if (a == "--region-granule" && i + 1 < argc) {                                     // (a knob of the measurements: bytes per granule of the closure)
+            const long long g = atoll(argv[++i]);
+            if (g < 16 || g > (1ll << 30) || (g & (g - 1))) { fprintf(stderr, "mbgc-hip d: --region-granule takes a power of two from 16 to 1073741824\n"); return EXIT_FAILURE; }
+            opt.regionGranule = (uint32_t) g;
+        }
         else if (a == "--select-seq-host") opt.selectSeqHost = true;                           // (a developer switch: the host's loop beside the kernel, timed and compared)
         else pos.push_back(a);
     }
     if (pos.size() != 2) { fprintf(stderr, "usage: %s", MBGC_HIP_D_USAGE); return EXIT_FAILURE; }
     if (opt.gzip && opt.fastaDir.empty()) { fprintf(stderr, "mbgc-hip d: --gzip needs --fasta dir (it compresses the FASTA files that --fasta writes)\n"); return EXIT_FAILURE; }
     if (!mbgc_hip_check_selection('d', opt, selectAsked)) return EXIT_FAILURE;
-    if (!selectAsked && !opt.selectSeqAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
+    if (!selectAsked && !opt.selectSeqAsked && !opt.regionAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
     std::string error;
     const int r = MBGC_Decoder::decode(pos[0], pos[1], opt, &error);
     if (r == 1) { fprintf(stderr, "mbgc-hip d: %s\n", error.c_str()); return EXIT_FAILURE; }
@@ -527,6 +608,10 @@ int mbgc_hip_test_main(int argc, char **argv) {
         else pos.push_back(a);
     }
     if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_T_USAGE); return EXIT_FAILURE; }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip t: --region / --region-list select parts of records, and the manifest holds the CRC-32 of whole contigs (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
     if (!mbgc_hip_check_selection('t', opt, selectAsked)) return EXIT_FAILURE;
     std::string error;
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
@@ -560,6 +645,10 @@ int mbgc_hip_validate_main(int argc, char **argv) {
     if (pos.size() != 1) { fprintf(stderr, "usage: %s", MBGC_HIP_V_USAGE); return EXIT_FAILURE; }
     if (opt.selectSeqAsked) {
         fprintf(stderr, "mbgc-hip v: --select-seq / --select-seq-list select records, and a file that holds only some of its records has no original to be validated against (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip v: --region / --region-list select parts of records, and a file that holds only parts of its records has no original to be validated against (an option of mbgc-hip d)\n");
         return EXIT_FAILURE;
     }
     if (!mbgc_hip_check_selection('v', opt, selectAsked)) return EXIT_FAILURE;
@@ -636,6 +725,150 @@ int mbgc_decoder_runs(uint64_t g0n, const uint32_t *seqCount, uint64_t T, const 
 int mbgc_decoder_units(uint64_t g0n, const uint32_t *seqCount, uint64_t T, const uint8_t *unitSel, int sequentialMatching, uint64_t *rows, uint64_t rowCap,
                        uint64_t *nrows, uint64_t *ranges, uint64_t rangeCap, uint64_t *nranges) {
     return mbgc_decoder_runs(g0n, seqCount, T, unitSel, nullptr, sequentialMatching, rows, rowCap, nrows, ranges, rangeCap, nranges);
+}
+
+// ---- --region for the tests. mbgc_region_parse: 0 and the spec's parts, or -1 and the reason in err.
+int mbgc_region_parse(const char *text, char *pattern, uint64_t cap, uint64_t *from, uint64_t *to, char *err, uint64_t errCap) {
+    MBGC_Decoder::RegionSpec spec;
+    std::string why;
+    if (!MBGC_Decoder::parseRegionSpec(text, spec, &why)) { if (err && errCap) snprintf(err, errCap, "%s", why.c_str()); return -1; }
+    snprintf(pattern, cap, "%s", spec.pattern.c_str());
+    *from = spec.from; *to = spec.to;
+    return 0;
+}
+// the header of a piece (regionHeader)
+int mbgc_region_header(const char *header, uint64_t from1, uint64_t to1, char *out, uint64_t cap) {
+    const std::string h = regionHeader(header, from1, to1);
+    if (h.size() + 1 > cap) return -2;
+    memcpy(out, h.c_str(), h.size() + 1);
+    return 0;
+}
+// resolveRegions: asks as rows of {contig, from, to} (1-based, inclusive) against contigLen; pieces as rows of {contig, from0, len} in
+// output order; *skipped: the asks that start behind their record's end. 0, or -2 (cap too small; *npieces = the rows needed).
+int mbgc_region_resolve(const uint64_t *asks, uint64_t nasks, const uint64_t *contigLen, uint64_t ncontigs, uint64_t *pieces, uint64_t cap, uint64_t *npieces, uint64_t *skipped) {
+    Selection sel;
+    for (uint64_t i = 0; i < nasks; i++) { if (asks[3 * i] >= ncontigs) return -1; sel.asks.push_back({asks[3 * i], asks[3 * i + 1], asks[3 * i + 2], 0}); }
+    resolveRegions(std::vector<uint64_t>(contigLen, contigLen + ncontigs), false, sel);
+    *npieces = sel.pieces.size(); *skipped = sel.regionSkipped;
+    if (sel.pieces.size() > cap) return -2;
+    for (size_t i = 0; i < sel.pieces.size(); i++) { pieces[3 * i] = sel.pieces[i].contig; pieces[3 * i + 1] = sel.pieces[i].from; pieces[3 * i + 2] = sel.pieces[i].len; }
+    return 0;
+}
+
+// The granule closure on the host (Provenance::closureRegion) over a schedule as mbgc_decoder_provenance takes it. timeSeg[c]: contig
+// c is filled against the buffer as the loader left it just before segment timeSeg[c]; recs / recBase: the planned records, contig
+// after contig; units: rows of {c0, c1} in the order they run; granBase (out, ncontigs + 1), needGranules / needContigs: in, the
+// chosen granules and their contigs; out, the closure. rows (may be NULL): the table as rows of {vstart, len, owner, ownerFirst,
+// reversed}. 0, -1 (arguments), -2 (rowCap too small; *nrows = the rows needed).
+int mbgc_decoder_region_closure(const int64_t *segs, uint64_t nsegs, uint64_t refTotalLength, uint64_t firstPlanned, uint64_t ncontigs, const uint64_t *destLen,
+                                const uint64_t *timeSeg, const swsem_decode_record_t *recs, const uint64_t *recBase, const uint64_t *units, uint64_t nunits, uint32_t shift,
+                                uint64_t *granBase, uint32_t *needGranules, uint32_t *needContigs, uint64_t *filled, int64_t *rows, uint64_t rowCap, uint64_t *nrows) {
+    if (refTotalLength < 2 || shift > 40) return -1;
+    Provenance prov;
+    prov.L = refTotalLength;
+    std::vector<uint64_t> curAt(nsegs + 1);
+    for (uint64_t i = 0; i < nsegs; i++) {
+        curAt[i] = prov.cur;
+        prov.add({segs[5 * i], (uint64_t) segs[5 * i + 1], (uint64_t) segs[5 * i + 2], (uint64_t) segs[5 * i + 3], segs[5 * i + 4] != 0}, firstPlanned);
+    }
+    curAt[nsegs] = prov.cur;
+    if (nrows) *nrows = prov.rows.size();
+    if (rows) {
+        if (prov.rows.size() > rowCap) return -2;
+        for (size_t i = 0; i < prov.rows.size(); i++) {
+            const int64_t row[5] = {(int64_t) prov.rows[i].vstart, (int64_t) prov.rows[i].len, prov.rows[i].owner, (int64_t) prov.ext[i].ownerFirst, (int64_t) prov.ext[i].reversed};
+            memcpy(rows + 5 * i, row, sizeof row);
+        }
+    }
+    Provenance::RegionNeed N;
+    N.shift = shift;
+    N.granBase.assign(ncontigs + 1, 0);
+    std::vector<uint64_t> len(destLen, destLen + ncontigs), timeOf(ncontigs);
+    std::vector<std::vector<swsem_decode_record_t>> perContig(ncontigs);
+    for (uint64_t c = 0; c < ncontigs; c++) {
+        if (timeSeg[c] > nsegs) return -1;
+        N.granBase[c + 1] = N.granBase[c] + ((len[c] + (1ull << shift) - 1) >> shift);
+        timeOf[c] = curAt[timeSeg[c]];
+        perContig[c].assign(recs + recBase[c], recs + recBase[c + 1]);
+    }
+    memcpy(granBase, N.granBase.data(), (ncontigs + 1) * sizeof(uint64_t));
+    const size_t gw = (size_t) ((N.granBase[ncontigs] + 31) / 32), cw = (size_t) ((ncontigs + 31) / 32);
+    N.gran.assign(needGranules, needGranules + gw); N.gran.push_back(0);
+    N.contig.assign(needContigs, needContigs + cw);
+    std::vector<swsem_fill_unit_t> sweep;
+    for (uint64_t u = 0; u < nunits; u++) sweep.push_back({units[2 * u], units[2 * u + 1]});
+    prov.closureRegion(perContig, len, timeOf, sweep, N);
+    memcpy(needGranules, N.gran.data(), gw * sizeof(uint32_t));
+    memcpy(needContigs, N.contig.data(), cw * sizeof(uint32_t));
+    *filled = N.filled;
+    return 0;
+}
+
+// The device's granule closure and masked fill held to the host's on a stream set on disk (needs a GPU): the streams under prefix
+// are planned and scheduled as `d` does it, the pieces — rows of {contig of the collection, from0, len} — go in as the need state,
+// and under outPrefix come back, as raw little-endian arrays: .granBase (u64), .needDev / .needHost (u32: the granule bitmap of
+// k_decode_closure_region and of Provenance::closureRegion over the records downloaded from the plan), .contigDev / .contigHost,
+// .filled (u64: device, host), .seqOff (u64, per contig of the collection + 1), .contigLen, .recBase (u64, per planned contig + 1),
+// .recDest (u64: every record's destAt), .masked (the sequence buffer after the masked forward run over a buffer of 0xEE bytes).
+int mbgc_decoder_region_probe(const char *prefix, int restoreRc, int serial, const uint64_t *pieces, uint64_t npieces, uint32_t granule, const char *outPrefix,
+                              char *err, uint64_t errCap) {
+    std::string msg;
+    const auto failed = [&]() { if (err && errCap) snprintf(err, errCap, "%s", msg.c_str()); return -1; };
+    MBGC_Decoder::Options opt;
+    opt.restoreRc = restoreRc != 0; opt.serial = serial != 0;
+    StreamSet S;
+    Selection sel;
+    if (!readStreamFiles(prefix, opt, S, msg) || !restoreRcLiterals(prefix, opt, S, msg) || !checkStreams(S, msg) || !chainStarts(false, S, msg)) return failed();
+    const uint64_t N = S.g0n + S.planned;
+    sel.unitSel.assign(S.T() + 1, 1);
+    sel.selecting = sel.selectingRegion = true;
+    sel.contigSel.assign(N, 0);
+    while ((1u << sel.granuleShift) < granule) sel.granuleShift++;
+    while ((1u << sel.granuleShift) > granule) sel.granuleShift--;
+    for (uint64_t i = 0; i < npieces; i++) {
+        if (pieces[3 * i] >= N) { msg = "a piece names no contig"; return failed(); }
+        sel.pieces.push_back({pieces[3 * i], pieces[3 * i + 1], pieces[3 * i + 2], 0});
+        sel.contigSel[pieces[3 * i]] = 1;
+    }
+    DecodedCollection D;
+    D.sentinel = 0xEE;
+    if (!D.upload(S, 0, msg) || !D.planAndSchedule(S, opt.serial, msg)) return failed();
+    for (const RegionPiece &p : sel.pieces) if (p.from + p.len > D.contigLen[p.contig] || !p.len) { msg = "a piece leaves its contig"; return failed(); }
+    if (!D.closure(S, sel, msg)) return failed();
+    // the referee: the records as the plan left them, the same table, times and units
+    std::vector<std::vector<swsem_decode_record_t>> recs(S.planned);
+    std::vector<uint64_t> destLen(S.planned), recBase(1, 0), recDest;
+    for (uint64_t c = 0; c < S.planned; c++) {
+        uint64_t n = 0;
+        if (swsem_debug_copy_records(D.h, c, nullptr, 0, &n)) { hipFail(msg, "records"); return failed(); }
+        recs[c].resize(n);
+        if (n && swsem_debug_copy_records(D.h, c, recs[c].data(), n, &n)) { hipFail(msg, "records"); return failed(); }
+        destLen[c] = D.contigLen[S.g0n + c];
+        for (const swsem_decode_record_t &r : recs[c]) recDest.push_back(r.destAt);
+        recBase.push_back(recDest.size());
+    }
+    Provenance::RegionNeed H;
+    H.shift = sel.granuleShift; H.granBase = D.regionNeed.granBase;
+    H.gran.assign(D.regionNeed.gran.size(), 0); H.contig.assign(D.regionNeed.contig.size(), 0);
+    for (const RegionPiece &p : sel.pieces) {
+        if (p.contig < S.g0n) continue;
+        const uint64_t k = p.contig - S.g0n;
+        H.contig[k >> 5] |= 1u << (k & 31);
+        for (uint64_t g = H.granBase[k] + (p.from >> H.shift); g <= H.granBase[k] + ((p.from + p.len - 1) >> H.shift); g++) H.gran[g >> 5] |= 1u << (g & 31);
+    }
+    D.prov.closureRegion(recs, destLen, D.timeOf, D.sweepUnits(), H);
+    if (!D.forwardRun(S, true, msg)) return failed();
+    std::string masked(D.totalBases, '\0');
+    if (D.totalBases && swsem_dev_download(D.h, &masked[0], D.seqDev, D.totalBases)) { hipFail(msg, "download"); return failed(); }
+    const uint64_t filled[2] = {D.regionNeed.filled, H.filled};
+    const std::string o = outPrefix;
+    const auto put = [&](const char *ext, const void *p, size_t n) { return writeFile(o + ext, p, n); };
+    if (!put(".granBase", H.granBase.data(), H.granBase.size() * 8) || !put(".needDev", D.regionNeed.gran.data(), D.regionNeed.gran.size() * 4) ||
+        !put(".needHost", H.gran.data(), H.gran.size() * 4) || !put(".contigDev", D.regionNeed.contig.data(), D.regionNeed.contig.size() * 4) ||
+        !put(".contigHost", H.contig.data(), H.contig.size() * 4) || !put(".filled", filled, sizeof filled) || !put(".seqOff", D.seqOff.data(), D.seqOff.size() * 8) ||
+        !put(".contigLen", D.contigLen.data(), D.contigLen.size() * 8) || !put(".recBase", recBase.data(), recBase.size() * 8) ||
+        !put(".recDest", recDest.data(), recDest.size() * 8) || !put(".masked", masked.data(), masked.size())) { msg = "cannot write under " + o; return failed(); }
+    return 0;
 }
 
 // parse + serialize: 0 and the bytes again, or -1 (malformed; the message in err)

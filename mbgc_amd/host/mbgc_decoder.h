@@ -13,6 +13,7 @@
 //                             all it holds: plan + schedule, the closure of --select, the forward run)
 //   mbgc_decoder_fasta.h      text out of a DecodedCollection: FastaLayout, FastaPlan (units and batches, shared by `d --fasta`
 //                             and `v`), FastaStage (device buffers, formatBatch), writeFastaFiles (--gzip: deflateBatch)
+//   mbgc_decoder_region.h     `d --region`: the specs held to the headers and the records' lengths, the pieces as outputs
 //   mbgc_decoder_validate.h   `v`: Validation (read-ahead, originals to the device, compare, verdicts, --dump)
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
@@ -89,7 +90,15 @@ public:
     // patterns — matched on the device, mbgc_fasta_match_headers_dev — and its file passes `select`); selectSeqAsked: one of the two
     // options stood on the command line; selectSeqHost: --select-seq-host, a developer switch — the match is made again by the host,
     // find by find, timed, and held against the device's
+    // --region 'PATTERN:FROM-TO': pattern, a substring of the header line as in --select-seq; from / to: 1-based, inclusive
+    struct RegionSpec { std::string pattern; uint64_t from = 0, to = 0; };
+    // the spec is split at its last ':'; false: *why says what is wrong with it
+    static bool parseRegionSpec(const std::string &text, RegionSpec &out, std::string *why);
     struct Options {
+        // regions: --region / --region-list, parts of records to bring back (mbgc_decoder_region.h); regionAsked: one of the two
+        // options stood on the command line; regionGranule: --region-granule, bytes per granule of the closure (a power of two; a
+        // knob of the measurements)
+        std::vector<RegionSpec> regions; bool regionAsked = false; uint32_t regionGranule = 256;
         bool serial = false, noIndex = false, bench = false, restoreRc = false, gzip = false; int device = 0; std::string fastaDir;
         std::vector<std::string> select; std::string closureOut;
         std::vector<std::string> selectSeq; bool selectSeqAsked = false, selectSeqHost = false;
@@ -130,7 +139,7 @@ int mbgc_hip_test_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
 extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
-// --restore-rc, --select, --select-list, --select-seq, --select-seq-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
+// --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.
 int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decoder::Options &opt, bool &selectAsked);
 // after the command line: no empty pattern, no empty list (--select and --select-seq alike); false: the message is on stderr

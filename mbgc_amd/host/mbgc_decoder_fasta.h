@@ -129,25 +129,31 @@ bool faFail(std::string &msg, const char *what) { msg = std::string(what) + ": "
 // (sel.unitSel as chooseUnits left it). Afterwards unitSel holds the units with a chosen record: the files that are written. G0's
 // unit under -t1 is no file — its one contig is the first of target 0 again, and is chosen there. --bench: run twice, the second
 // run is the timed one.
+// the match itself: bit k of `bits` = header k contains one of the patterns (what: the option, for the message)
+bool matchHeaders(const MBGC_Decoder::Options &opt, const FastaLayout &layout, uint64_t N, const std::vector<std::string> &pats, std::vector<uint32_t> &bits, double &ms,
+                  const char *what, std::string &msg) {
+    std::string patBytes;
+    std::vector<uint64_t> patOff(1, 0);
+    for (const std::string &p : pats) { patBytes += p; patOff.push_back(patBytes.size()); }
+    bits.assign((N + 31) / 32, 0);
+    struct Stage {                                                   // freed on every way out
+        mbgc_fasta_t *fa = nullptr; uint8_t *hdrDev = nullptr;
+        ~Stage() { if (hdrDev) mbgc_fasta_dev_free(fa, hdrDev); if (fa) mbgc_fasta_destroy(fa); }
+    } st;
+    if (mbgc_fasta_create(&st.fa, opt.device) || mbgc_fasta_dev_alloc(st.fa, layout.headers.size() + 64, &st.hdrDev) ||
+        mbgc_fasta_upload(st.fa, st.hdrDev, layout.headers.data(), layout.headers.size())) return faFail(msg, what);
+    for (int run = 0; run < (opt.bench ? 2 : 1); run++)
+        if (mbgc_fasta_match_headers_dev(st.fa, st.hdrDev, layout.headers.size(), layout.hdrOff.data(), layout.hdrLen.data(), N, (const uint8_t *) patBytes.data(),
+                                         patOff.data(), pats.size(), bits.data(), &ms)) return faFail(msg, what);
+    return true;
+}
+
 bool chooseRecords(const std::string &prefix, const StreamSet &S, const MBGC_Decoder::Options &opt, const FastaLayout &layout, Selection &sel, std::string &msg) {
     const std::vector<std::string> &pats = opt.selectSeq;
     if (pats.empty()) return true;
     const uint64_t N = S.g0n + S.planned;
-    std::string patBytes;
-    std::vector<uint64_t> patOff(1, 0);
-    for (const std::string &p : pats) { patBytes += p; patOff.push_back(patBytes.size()); }
-    std::vector<uint32_t> bits((N + 31) / 32, 0);
-    {
-        struct Stage {                                               // freed on every way out
-            mbgc_fasta_t *fa = nullptr; uint8_t *hdrDev = nullptr;
-            ~Stage() { if (hdrDev) mbgc_fasta_dev_free(fa, hdrDev); if (fa) mbgc_fasta_destroy(fa); }
-        } st;
-        if (mbgc_fasta_create(&st.fa, opt.device) || mbgc_fasta_dev_alloc(st.fa, layout.headers.size() + 64, &st.hdrDev) ||
-            mbgc_fasta_upload(st.fa, st.hdrDev, layout.headers.data(), layout.headers.size())) return faFail(msg, "--select-seq");
-        for (int run = 0; run < (opt.bench ? 2 : 1); run++)
-            if (mbgc_fasta_match_headers_dev(st.fa, st.hdrDev, layout.headers.size(), layout.hdrOff.data(), layout.hdrLen.data(), N, (const uint8_t *) patBytes.data(),
-                                             patOff.data(), pats.size(), bits.data(), &sel.matchMs)) return faFail(msg, "--select-seq");
-    }
+    std::vector<uint32_t> bits;
+    if (!matchHeaders(opt, layout, N, pats, bits, sel.matchMs, "--select-seq", msg)) return false;
     if (opt.selectSeqHost) {                                         // the loop --select runs over the names, over the headers: a yardstick, and a check
         const double t0 = nowMs();
         std::vector<uint32_t> host((N + 31) / 32, 0);
@@ -189,6 +195,7 @@ struct FastaStage {
     uint8_t *gzDev[2] = {nullptr, nullptr};                        // --gzip: the gzip files of a batch (not allocated without it)
     std::future<bool> writing;
     const DecodedCollection *D = nullptr; const FastaPlan *P = nullptr; const FastaLayout *L = nullptr;
+    const std::vector<uint64_t> *recOff = nullptr, *recLen = nullptr;   // where record k lies in the sequence buffer: the collection's contigs, or (--region) the pieces
     std::vector<mbgc_fasta_format_rec_t> recs;                     // the batch formatted last: its records,
     std::vector<uint64_t> textOff;                                 // and where their text starts in the batch
     FastaTimes times;
@@ -209,6 +216,7 @@ struct FastaStage {
 
     bool open(const DecodedCollection &d, const FastaPlan &p, const FastaLayout &l, int device, bool gzip, std::string &msg) {
         D = &d; P = &p; L = &l;
+        if (!recOff) { recOff = &d.seqOff; recLen = &d.contigLen; }
         if (mbgc_fasta_create(&fa, device)) return faFail(msg, "--fasta");
         if (mbgc_fasta_dev_alloc(fa, l.headers.size() + 64, &hdrDev)) return faFail(msg, "--fasta");
         for (uint8_t *&t : textDev) if (mbgc_fasta_dev_alloc(fa, p.maxBatch + 64, &t)) return faFail(msg, "--fasta");
@@ -223,7 +231,7 @@ struct FastaStage {
         recs.clear();
         for (size_t u = u0; u < u1; u++)
             for (uint64_t k = P->units[u].c0; k < P->units[u].c1; k++)
-                recs.push_back({D->seqOff[k], D->contigLen[k], L->hdrOff[k], L->hdrLen[k], P->units[u].lineLen});
+                recs.push_back({(*recOff)[k], (*recLen)[k], L->hdrOff[k], L->hdrLen[k], P->units[u].lineLen});
         textOff.assign(recs.size() + 1, 0);
         double kms = 0;
         if (mbgc_fasta_format_dev(fa, D->seqDev, D->totalBases, hdrDev, L->headers.size(), recs.data(), recs.size(), dst, P->maxBatch, textOff.data(), &kms))

@@ -16,11 +16,16 @@ struct PassTimes { double plan = 0, closure = 0, fill = 0, load = 0; uint64_t wa
 struct Provenance {
     uint64_t L = 0, cur = REF_SHIFT;                               // the loader's virtual position (refPos == L: (lap + 1) x L)
     std::vector<swsem_prov_row_t> rows;
+    // --region: which bytes of its owner a row's load wrote — ownerFirst: the owner's byte the load's first byte is made of;
+    // reversed: the load ran backwards over the owner (a reverse complement). One entry per row.
+    struct Ext { uint64_t ownerFirst; uint32_t reversed; };
+    std::vector<Ext> ext;
 
-    // the owned pieces of physical range [p0, p1) as the loader left the buffer at virtual position tv: f(physFrom, physTo, owner).
-    // Below the loader's position the bytes are this lap's, from it on the lap before's (before the first lap: never written);
-    // a range that straddles the position is split there. (k_decode_closure: the same on the device.)
-    template <class F> void query(uint64_t tv, uint64_t p0, uint64_t p1, F f) const {
+    // the rows that own a piece of physical range [p0, p1) as the loader left the buffer at virtual position tv: f(physFrom, physTo,
+    // row, base) with base + phys = the virtual position. Below the loader's position the bytes are this lap's, from it on the lap
+    // before's (before the first lap: never written); a range that straddles the position is split there. (k_decode_closure: the
+    // same on the device.)
+    template <class F> void queryRows(uint64_t tv, uint64_t p0, uint64_t p1, F f) const {
         if (p1 > L) p1 = L;
         if (p0 >= p1) return;
         const uint64_t lap = tv / L, rp = tv % L;
@@ -28,27 +33,85 @@ struct Provenance {
             const uint64_t va = base + a, vb = base + b;
             size_t i = (size_t) (std::partition_point(rows.begin(), rows.end(), [&](const swsem_prov_row_t &r) { return r.vstart + r.len <= va; }) - rows.begin());
             for (; i < rows.size() && rows[i].vstart < vb; i++)
-                f(std::max(va, rows[i].vstart) - base, std::min(vb, rows[i].vstart + rows[i].len) - base, rows[i].owner);
+                f(std::max(va, rows[i].vstart) - base, std::min(vb, rows[i].vstart + rows[i].len) - base, i, base);
         };
         if (p0 < rp) part(p0, std::min(p1, rp), lap * L);
         if (p1 > rp && lap) part(std::max(p0, rp), p1, (lap - 1) * L);
     }
+    // the owned pieces: f(physFrom, physTo, owner)
+    template <class F> void query(uint64_t tv, uint64_t p0, uint64_t p1, F f) const {
+        queryRows(tv, p0, p1, [&](uint64_t a, uint64_t b, size_t i, uint64_t) { f(a, b, rows[i].owner); });
+    }
+    // bytes [k0, k0 + n) of row i's load are bytes [*, * + n) of its owner
+    uint64_t ownerFrom(size_t i, uint64_t k0, uint64_t n) const { return ext[i].reversed ? ext[i].ownerFirst + 1 - (k0 + n) : ext[i].ownerFirst + k0; }
     // the next segment of the schedule, in serial order; contigs from firstPlanned on are the planned ones (owner = contig - firstPlanned)
     void add(const LoadSegment &s, uint64_t firstPlanned) {
         if (s.length == 0) return;
         if (s.contig == LoadSegment::SEPARATOR && s.length == 1 && (s.refPos + 1) % L == cur % L) return;   // written over the last loaded byte: the superset rule
         const uint64_t v = cur + (s.refPos + L - cur % L) % L;      // the next virtual position that lies at refPos
         if (s.contig == LoadSegment::FROM_REF) {
-            std::vector<swsem_prov_row_t> got;
-            query(cur, s.offset, s.offset + s.length, [&](uint64_t a, uint64_t b, int64_t owner) {
+            std::vector<std::pair<swsem_prov_row_t, Ext>> got;
+            queryRows(cur, s.offset, s.offset + s.length, [&](uint64_t a, uint64_t b, size_t i, uint64_t base) {
                 const uint64_t at = s.reverseComplement ? s.length - (b - s.offset) : a - s.offset;
-                got.push_back({v + at, b - a, owner});
+                // the same bytes of the same owner, read in the other direction when this load reverses them
+                const uint64_t oa = ownerFrom(i, base + a - rows[i].vstart, b - a);
+                const uint32_t rev = ext[i].reversed ^ (s.reverseComplement ? 1u : 0u);
+                got.push_back({{v + at, b - a, rows[i].owner}, {rev ? oa + (b - a) - 1 : oa, rev}});
             });
-            std::sort(got.begin(), got.end(), [](const swsem_prov_row_t &x, const swsem_prov_row_t &y) { return x.vstart < y.vstart; });
-            rows.insert(rows.end(), got.begin(), got.end());
-        } else if (s.contig >= 0 && (uint64_t) s.contig >= firstPlanned)
+            std::sort(got.begin(), got.end(), [](const std::pair<swsem_prov_row_t, Ext> &x, const std::pair<swsem_prov_row_t, Ext> &y) { return x.first.vstart < y.first.vstart; });
+            for (const auto &g : got) { rows.push_back(g.first); ext.push_back(g.second); }
+        } else if (s.contig >= 0 && (uint64_t) s.contig >= firstPlanned) {
             rows.push_back({v, s.length, (int64_t) ((uint64_t) s.contig - firstPlanned)});
+            ext.push_back({s.reverseComplement ? s.offset + s.length - 1 : s.offset, s.reverseComplement ? 1u : 0u});
+        }
         cur = v + s.length;
+    }
+    std::vector<swsem_prov_row_region_t> regionRows() const {
+        std::vector<swsem_prov_row_region_t> out(rows.size());
+        for (size_t i = 0; i < rows.size(); i++) out[i] = {rows[i].vstart, rows[i].len, rows[i].owner, ext[i].ownerFirst, ext[i].reversed, 0};
+        return out;
+    }
+
+    // ---- the closure of --region on the host: the referee of k_decode_closure_region, the same rule restated. N: the need state
+    // (granBase: bit of every contig's first granule, + 1 entry; gran / contig: the two bitmaps, in: the chosen regions', out: the
+    // closure; filled: the bases the needed records write). recs[c]: the plan's records of contig c. The units are swept last
+    // first; inside a unit the order is free, since an owner at or behind the unit's first contig is never marked.
+    struct RegionNeed { uint32_t shift = 8; std::vector<uint64_t> granBase; std::vector<uint32_t> gran, contig; uint64_t filled = 0; };
+    static bool anyGranule(const RegionNeed &N, uint64_t c, uint64_t a, uint64_t b) {             // a byte of [a, b) of contig c in a needed granule
+        for (uint64_t g = N.granBase[c] + (a >> N.shift); g <= N.granBase[c] + ((b - 1) >> N.shift); g++) if ((N.gran[g >> 5] >> (g & 31)) & 1u) return true;
+        return false;
+    }
+    void closureRegion(const std::vector<std::vector<swsem_decode_record_t>> &recs, const std::vector<uint64_t> &destLen, const std::vector<uint64_t> &timeOf,
+                       const std::vector<swsem_fill_unit_t> &units, RegionNeed &N) const {
+        for (size_t u = units.size(); u-- > 0;)
+            for (uint64_t c = units[u].c0; c < units[u].c1; c++) {
+                if (!((N.contig[c >> 5] >> (c & 31)) & 1u)) continue;
+                for (size_t i = 0; i < recs[c].size(); i++) {
+                    const swsem_decode_record_t &r = recs[c][i];
+                    const uint64_t end = i + 1 < recs[c].size() ? recs[c][i + 1].destAt : destLen[c];
+                    if (r.destAt >= end || !anyGranule(N, c, r.destAt, end)) continue;
+                    N.filled += end - r.destAt;
+                    if (r.flags & 16u) continue;                                                   // (REC_TAIL: literals only)
+                    // rec_read_ranges (swsem_decode.hip): the match, the left extension, the right extension a byte wider at either end
+                    uint64_t lo[3], hi[3];
+                    int n = 0;
+                    lo[n] = r.src; hi[n] = r.src + r.len; n++;
+                    if (r.leftLen) { lo[n] = (uint64_t) (r.leftSrcMatch - (int64_t) r.leftLen); hi[n] = (uint64_t) r.leftSrcMatch; n++; }
+                    if (r.rightLen) {
+                        const uint64_t plain = (r.mark - r.litFrom) - r.leftCodes;
+                        const int64_t a = (int64_t) (r.destAt + plain + r.leftLen + r.len) + r.offsetDelta - 1;
+                        lo[n] = a < 0 ? 0 : (uint64_t) a; hi[n] = lo[n] + r.rightLen + 2; n++;
+                    }
+                    for (int q = 0; q < n; q++)
+                        queryRows(timeOf[c], lo[q], hi[q], [&](uint64_t a, uint64_t b, size_t row, uint64_t base) {
+                            const int64_t o = rows[row].owner;
+                            if (o < 0 || (uint64_t) o >= units[u].c0) return;
+                            const uint64_t oa = ownerFrom(row, base + a - rows[row].vstart, b - a), ob = oa + (b - a);
+                            N.contig[o >> 5] |= 1u << (o & 31);
+                            for (uint64_t g = N.granBase[o] + (oa >> N.shift); g <= N.granBase[o] + ((ob - 1) >> N.shift); g++) N.gran[g >> 5] |= 1u << (g & 31);
+                        });
+                }
+            }
     }
 };
 
@@ -144,6 +207,11 @@ struct DecodedCollection {
     uint64_t totalBases = 0;
     PassTimes times;
     uint64_t closureContigs = 0, closureBases = 0, dependencyTargets = 0;
+    int sentinel = -1;                                             // tests: the sequence buffer starts as this byte everywhere
+    bool region = false;                                           // --region: the fills are masked by the granule bitmap the closure left in the handle
+    Provenance::RegionNeed regionNeed;                             // ... as it came back from the device
+    std::vector<uint64_t> timeOf;                                  // (kept for the referee: mbgc_decoder_region_probe)
+    Provenance prov;
 
     DecodedCollection() = default;
     DecodedCollection(const DecodedCollection &) = delete;
@@ -153,6 +221,7 @@ struct DecodedCollection {
     bool upload(const StreamSet &S, int device, std::string &msg);
     bool planAndSchedule(const StreamSet &S, bool serial, std::string &msg);
     bool closure(const StreamSet &S, const Selection &sel, std::string &msg);
+    std::vector<swsem_fill_unit_t> sweepUnits() const { std::vector<swsem_fill_unit_t> out; for (const FillUnit &u : units) if (u.c1 > u.c0) out.push_back({u.c0, u.c1}); return out; }
     bool forwardRun(const StreamSet &S, bool selecting, std::string &msg);
 
 private:
@@ -232,9 +301,9 @@ bool DecodedCollection::closure(const StreamSet &S, const Selection &sel, std::s
     targetRuns.assign(T, 1);
     if (!sel.selecting) return true;
     std::vector<uint32_t> need((planned + 31) / 32, 0);
-    std::vector<uint64_t> timeOf(planned, 0);
+    timeOf.assign(planned, 0);
     const double t0 = nowMs();
-    Provenance prov;
+    prov = Provenance();
     prov.L = S.meta.maxRefLength;
     for (const LoadSegment &s : g0Segs) prov.add(s, g0n);
     uint64_t c = 0;
@@ -248,9 +317,33 @@ bool DecodedCollection::closure(const StreamSet &S, const Selection &sel, std::s
         for (uint32_t k = 0; k < S.seqCount[t]; k++) if (sel.chosen(t, c + k, g0n)) { mark[c + k] = 2; need[(c + k) >> 5] |= 1u << ((c + k) & 31); }
         c += S.seqCount[t];
     }
-    std::vector<swsem_fill_unit_t> sweep;
-    for (const FillUnit &u : units) if (u.c1 > u.c0) sweep.push_back({u.c0, u.c1});
-    if (planned && swsem_decode_closure_dev(h, prov.L, prov.rows.size(), prov.rows.data(), planned, timeOf.data(), sweep.size(), sweep.data(), need.data()))
+    const std::vector<swsem_fill_unit_t> sweep = sweepUnits();
+    if (sel.selectingRegion) {
+        // --region: the need state is a bitmap over granules; the chosen pieces' granules go in, the closure's come back, and the
+        // contig bits with them. A chosen record without a piece in range (every region behind its end) needs nothing.
+        region = true;
+        Provenance::RegionNeed &N = regionNeed;
+        N = Provenance::RegionNeed();
+        N.shift = sel.granuleShift;
+        N.granBase.assign(planned + 1, 0);
+        for (uint64_t k = 0; k < planned; k++) N.granBase[k + 1] = N.granBase[k] + ((contigLen[g0n + k] + (1ull << N.shift) - 1) >> N.shift);
+        N.gran.assign((N.granBase[planned] + 31) / 32 + 1, 0);
+        std::fill(need.begin(), need.end(), 0u);
+        for (const RegionPiece &p : sel.pieces) {
+            if (p.contig < g0n || !p.len) continue;
+            const uint64_t k = p.contig - g0n;
+            need[k >> 5] |= 1u << (k & 31);
+            for (uint64_t g = N.granBase[k] + (p.from >> N.shift); g <= N.granBase[k] + ((p.from + p.len - 1) >> N.shift); g++) N.gran[g >> 5] |= 1u << (g & 31);
+        }
+        N.contig = need;
+        const std::vector<swsem_prov_row_region_t> rows = prov.regionRows();
+        if (planned && swsem_decode_closure_region_dev(h, prov.L, rows.size(), rows.data(), planned, timeOf.data(), sweep.size(), sweep.data(), N.shift, N.granBase.data(),
+                                                       N.gran.data(), N.contig.data(), &N.filled))
+            return hipFail(msg, "closure");
+        need = N.contig;
+        // (a chosen contig that needs nothing is not filled: its mark is for --closure-out, which counts filled bytes)
+        for (uint64_t k = 0; k < planned; k++) if (mark[k] == 2 && !((need[k >> 5] >> (k & 31)) & 1u)) mark[k] = 0;
+    } else if (planned && swsem_decode_closure_dev(h, prov.L, prov.rows.size(), prov.rows.data(), planned, timeOf.data(), sweep.size(), sweep.data(), need.data()))
         return hipFail(msg, "closure");
     times.closure = nowMs() - t0;
     c = 0;
@@ -258,11 +351,12 @@ bool DecodedCollection::closure(const StreamSet &S, const Selection &sel, std::s
         bool any = false;
         for (uint32_t k = 0; k < S.seqCount[t]; k++, c++) {
             if (!mark[c] && ((need[c >> 5] >> (c & 31)) & 1u)) mark[c] = 1;
-            if (mark[c]) { any = true; closureContigs++; closureBases += contigLen[g0n + c]; }
+            if (mark[c]) { any = true; closureContigs++; closureBases += region ? 0 : contigLen[g0n + c]; }
         }
         targetRuns[t] = any;
         if (any && !sel.unitSel[t + 1]) dependencyTargets++;
     }
+    if (region) closureBases = regionNeed.filled;                  // the bases actually filled
     return true;
 }
 
@@ -296,7 +390,7 @@ bool DecodedCollection::fill(uint64_t c0, uint64_t c1, uint64_t g0n, std::string
     if (c1 == c0) return true;
     const double a = nowMs();
     uint64_t nbad = 0;
-    const int r = swsem_decode_fill_range_dev(h, c0, c1, seqDev, seqOff.data() + g0n, &nbad);
+    const int r = region ? swsem_decode_fill_region_dev(h, c0, c1, seqDev, seqOff.data() + g0n, &nbad) : swsem_decode_fill_range_dev(h, c0, c1, seqDev, seqOff.data() + g0n, &nbad);
     times.fill += nowMs() - a;
     if (r) return hipFail(msg, "fill");
     if (nbad) { msg = "malformed stream set: the bytes of a contig do not come out as planned"; return false; }
@@ -314,6 +408,10 @@ bool DecodedCollection::forwardRun(const StreamSet &S, bool selecting, std::stri
     if (swsem_dev_malloc(h, totalBases + 64, &seqp)) return hipFail(msg, "sequences");
     ptrs.push_back(seqp);
     seqDev = (uint8_t *) seqp;
+    if (sentinel >= 0 && totalBases) {
+        const std::string fillBytes(totalBases, (char) sentinel);
+        if (swsem_dev_upload(h, seqDev, fillBytes.data(), totalBases)) return hipFail(msg, "sequences");
+    }
     uint64_t at = 0;                                               // G0's bytes are literals
     for (uint64_t g = 0; g < g0n; g++) {
         if (swsem_dev_copy(h, seqDev + seqOff[g], sdev[SWSEM_LIT] + at, contigLen[g])) return hipFail(msg, "initial reference");

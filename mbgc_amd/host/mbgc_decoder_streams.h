@@ -144,7 +144,19 @@ bool parseNames(const std::string &names, const MbgcMeta &meta, std::vector<std:
 
 // ---- --select: the units to bring back (G0, then every target), by the names mbgc-hip c wrote beside the streams; --select-seq:
 // the records to bring back, by the headers written there (chooseRecords, mbgc_decoder_fasta.h: the match runs on the device)
+// --region: a piece is bases [from, from + len) of contig `contig` of the collection (0-based, clamped to the record), written to unit
+// `unit`'s file
+struct RegionPiece { uint64_t contig, from, len; size_t unit; };
+struct RegionAsk { uint64_t contig, from, to; size_t unit; };      // a spec on a chosen record, before the record's length is known
+
 struct Selection {
+    // --region (mbgc_decoder_region.h): asks: what the specs choose, by the headers; pieces: the asks held to the records' lengths, in
+    // output order; granuleShift: log2 of the closure's granule
+    bool selectingRegion = false;
+    std::vector<RegionAsk> asks;
+    std::vector<RegionPiece> pieces;
+    uint64_t regionRecords = 0, regionBases = 0, regionSkipped = 0;
+    uint32_t granuleShift = 8;
     std::vector<char> unitSel;                                     // per unit; all of them without a selection. --select-seq: the units that hold a chosen record
     std::vector<char> contigSel;                                   // --select-seq: per contig of the collection, G0's first; empty without it
     uint64_t selectedFiles = 0;                                    // the files that are written

@@ -154,6 +154,10 @@ static int repackMain(int argc, char **argv) {
         fprintf(stderr, "mbgc-hip r: --select-seq / --select-seq-list select records, and files that hold only some of their records are not repacked (an option of mbgc-hip d)\n");
         return EXIT_FAILURE;
     }
+    if (dopt.regionAsked) {
+        fprintf(stderr, "mbgc-hip r: --region / --region-list select parts of records, and files that hold only parts of their records are not repacked (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
     if (!mbgc_hip_check_selection('r', dopt, selectAsked)) return EXIT_FAILURE;
     params.device = dopt.device;
     MultipleGenomeMatchingProcessor::bindHostThreadsToDeviceNode(params.device);
