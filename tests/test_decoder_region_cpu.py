@@ -238,3 +238,173 @@ def test_whole_records_with_a_granule_per_contig_give_the_contig_closure(host, t
     # at a finer grain the same selection never needs a contig the contig closure does not
     _, _, fine, fine_filled = plan.closure(host, 4, chosen)
     assert not (fine & ~want).any() and fine_filled <= filled
+
+
+# ---- seeded random plans where the closure's arithmetic has edges, against a closure that works byte by byte
+class EdgePlan(Plan):
+    """Plan with what it lacks: contigs loaded forward only, reverse-complemented only, or both; owners shorter than a granule among
+    the contigs; and, once the loader has lapped, matches placed across the loader's position and across the buffer's end's
+    neighbour rows on purpose — the rest at random places, as Plan has them"""
+
+    def __init__(self, total, g0, lens, seed):
+        rng = np.random.default_rng(seed)
+        self.total, self.segs, self.pos = total, [], 1
+        self.load(0, g0, 0)
+        self.recs, self.time_seg, self.lens, self.src_of = [], [], lens, []
+        self.loaded, self.straddles, self.how = g0, 0, []
+        for c, n in enumerate(lens):
+            self.time_seg.append(len(self.segs))
+            rows, src_of, at, lit = [], np.full(n, -1, dtype=np.int64), 0, 0
+            lapped = self.loaded >= total - 1
+            while at < n:
+                plain = int(rng.integers(0, 12))
+                ln = int(rng.integers(8, 60))
+                if at + plain + ln > n:
+                    break
+                span = min(self.loaded, total - 1)
+                kind = int(rng.integers(0, 4))
+                if lapped and kind == 0 and ln < self.pos < total - ln:          # across the loader's position: this lap below it, the lap before from it on
+                    src = self.pos - int(rng.integers(1, ln))
+                    self.straddles += 1
+                elif lapped and kind == 1:                                       # up to the buffer's last byte
+                    src = total - ln
+                elif kind == 2 and self.segs:                                    # from the first byte of a load on, or up to its last
+                    _, _, sn, sp, _ = self.segs[int(rng.integers(len(self.segs)))]
+                    src = sp if rng.integers(2) or sp + sn < ln + 1 else sp + sn - ln
+                    src = min(max(src, 1), max(1, span - ln))
+                else:
+                    src = int(rng.integers(1, max(2, span - ln)))
+                r = np.zeros((), dtype=REC)
+                r["litFrom"], r["mark"], r["destAt"], r["src"], r["len"] = lit, lit + plain, at, src, ln
+                rows.append(r)
+                src_of[at + plain:at + plain + ln] = np.arange(src, src + ln)
+                lit += plain + 1
+                at += plain + ln
+            t = np.zeros((), dtype=REC)
+            t["litFrom"], t["mark"], t["destAt"], t["flags"] = lit, lit + (n - at), at, TAIL
+            rows.append(t)
+            self.recs.append(np.array(rows, dtype=REC))
+            self.src_of.append(src_of)
+            how = int(rng.integers(0, 3))                                        # 0: forward, 1: reverse complement, 2: both
+            self.how.append(how)
+            if how != 1:
+                self.load(c + 1, n, 0)
+            if how != 0:
+                self.load(c + 1, n, 1)
+            self.loaded += n * (2 if how == 2 else 1)
+
+    def byte_closure(self, chosen, granule=1):
+        """a set of needed bytes per contig: a needed byte makes its granule's bytes needed (granule = 1: itself only); a record
+        runs when its destination range holds a needed byte, and every byte it copies from is needed of its owner. -> (needed, filled)"""
+        maps = self.owner_maps()
+        needed = [set() for _ in self.lens]
+        ran = [set() for _ in self.lens]
+        todo = []
+
+        def want(c, p):
+            for q in range(p // granule * granule, min((p // granule + 1) * granule, self.lens[c])):
+                if q not in needed[c]:
+                    needed[c].add(q)
+                    todo.append((c, q))
+        for c, a, ln in chosen:
+            for p in range(a, a + ln):
+                want(c, p)
+        while todo:
+            c, p = todo.pop()
+            dest = self.recs[c]["destAt"].tolist() + [self.lens[c]]
+            i = max(k for k in range(len(dest) - 1) if dest[k] <= p and dest[k] < dest[k + 1])
+            if i in ran[c]:
+                continue
+            ran[c].add(i)
+            for s in self.src_of[c][dest[i]:dest[i + 1]]:
+                if s >= 0 and maps[c][s, 0] >= 0:
+                    want(int(maps[c][s, 0]), int(maps[c][s, 1]))
+        filled = 0
+        for c in range(len(self.lens)):
+            dest = self.recs[c]["destAt"].tolist() + [self.lens[c]]
+            filled += sum(dest[i + 1] - dest[i] for i in ran[c])
+        return needed, filled
+
+
+EDGE_LENS = [300, 15, 257, 16, 311, 17, 290, 7, 333, 256, 255, 280, 64, 301, 1, 320]
+EDGE_PLANS = [(1 << 20, 11), (1500, 12), (1100, 13), (1100, 14), (901, 15), (1500, 16)]
+
+
+@pytest.fixture(scope="module")
+def edge_plans():
+    return {(total, seed): EdgePlan(total, 200, EDGE_LENS, seed) for total, seed in EDGE_PLANS}
+
+
+def edge_chosen(plan, seed):
+    """single pieces at a record's destAt, a byte before it, a contig's ends and a granule's edge, in the later contigs"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for c in (15, 13, 11, 8, 6, 12):
+        n, d = plan.lens[c], plan.recs[c]["destAt"]
+        at = int(d[rng.integers(1, len(d))]) if len(d) > 1 else 0
+        out += [(c, max(at - 1, 0), min(2, n)), (c, at if at < n else n - 1, 1), (c, n - 1, 1), (c, 0, 1), (c, min(16 * int(rng.integers(0, 1 + n // 16)), n - 1), 1)]
+    return out
+
+
+def test_the_edge_plans_hold_what_they_are_for(edge_plans):
+    lapped = [p for (total, _), p in edge_plans.items() if total < 2000]
+    assert all(p.straddles >= 3 for p in lapped)                                  # read ranges across the loader's position on lap >= 1
+    for p in edge_plans.values():
+        assert {0, 1, 2} <= set(p.how)                                            # forward, reversed and both
+        assert any(rc for _, _, _, _, rc in p.segs)
+    for p in lapped:
+        ends = [s for s in p.segs if s[3] + s[2] == p.total]
+        assert len(ends) >= 2 and any(s[1] > 0 or s[2] < p.lens[s[0] - 1] for s in ends if s[0])   # loads split at the buffer's end
+
+
+@pytest.mark.parametrize("shift", [4, 8])
+@pytest.mark.parametrize("total,seed", EDGE_PLANS)
+def test_granule_closure_against_the_byte_closure(host, edge_plans, total, seed, shift):
+    """one piece per call: closureRegion covers the byte-exact closure coarsened to granules (never less than what is read), and is
+    the byte closure in which a needed byte makes its granule needed — bit for bit, with the same filled"""
+    plan = edge_plans[(total, seed)]
+    G = 1 << shift
+    followed = 0
+    for piece in edge_chosen(plan, seed):
+        pre, need, cont, filled = plan.closure(host, shift, [piece])
+        exact, exact_filled = plan.byte_closure([piece])
+        coarse, coarse_filled = plan.byte_closure([piece], G)
+        for c in range(len(plan.lens)):
+            gran = need[int(pre[c]):int(pre[c + 1])]
+            assert all(gran[p // G] for p in exact[c]), (piece, c)
+            assert sorted({p // G for p in coarse[c]}) == np.flatnonzero(gran).tolist(), (piece, c)
+            assert bool(cont[c]) == bool(coarse[c]), (piece, c)
+        assert exact_filled <= coarse_filled == filled, piece
+        followed += sum(1 for c in range(piece[0]) if exact[c])
+    assert followed >= 6                                                          # (the pieces have dependencies to follow)
+
+
+def edge_closure_bytes(plan, host, shift, chosen):
+    pre, need, cont, filled = plan.closure(host, shift, chosen)
+    masks = [np.repeat(need[int(pre[c]):int(pre[c + 1])], 1 << shift)[:n] for c, n in enumerate(plan.lens)]
+    return pre, need, cont, filled, masks
+
+
+@pytest.mark.parametrize("total,seed", EDGE_PLANS)
+def test_referee_union_refinement_idempotence(host, edge_plans, total, seed):
+    plan = edge_plans[(total, seed)]
+    e = edge_chosen(plan, seed)
+    for shift in (4, 8):
+        for a, b in ((e[0], e[6]), (e[1], e[3]), (e[10], e[21])):                  # different contigs, one contig, different contigs
+            _, na, ca, fa = plan.closure(host, shift, [a])
+            _, nb, cb, fb = plan.closure(host, shift, [b])
+            _, nu, cu, fu = plan.closure(host, shift, [a, b])
+            assert np.array_equal(nu, na | nb) and np.array_equal(cu, ca | cb) and max(fa, fb) <= fu <= fa + fb, (shift, a, b)
+    for chosen in ([e[0]], [e[5], e[12]]):
+        prev = None
+        for shift in (4, 6, 8, 10, 12):
+            pre, need, cont, filled, masks = edge_closure_bytes(plan, host, shift, chosen)
+            if prev is not None:
+                assert all(not (f & ~g).any() for f, g in zip(prev[2], masks)) and not (prev[0] & ~cont).any() and prev[1] <= filled, (shift, chosen)
+            prev = (cont, filled, masks)
+    for shift in (4, 8):
+        G = 1 << shift
+        pre, need, cont, filled = plan.closure(host, shift, [e[0], e[7], e[14]])
+        back = [(c, int(g) * G, min((int(g) + 1) * G, plan.lens[c]) - int(g) * G) for c in range(len(plan.lens)) for g in np.flatnonzero(need[int(pre[c]):int(pre[c + 1])])]
+        _, need2, cont2, filled2 = plan.closure(host, shift, back)
+        assert np.array_equal(need, need2) and np.array_equal(cont, cont2) and filled == filled2

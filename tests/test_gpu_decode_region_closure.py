@@ -4,7 +4,6 @@ bit for bit, and the masked fill (k_decode_fill_region) against the unmasked one
 need state, and both closures, the plan's record offsets and the sequence buffer after a masked forward run over 0xEE bytes come
 back. On the chain set of test_gpu_decompress_region.py and on a set whose circular reference buffer has wrapped twice, with
 reverse-complement loads."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -13,69 +12,14 @@ import pytest
 import _meta
 import test_gpu_decompress_region as region
 from mbgc_amd import synth
-from test_gpu_decompress_region import tool
+from _regionprobe import check, host_lib, probe, tool
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0xEE
 
 
 @pytest.fixture(scope="module")
 def host():
-    L = C.CDLL(os.path.join(ROOT, "mbgc_amd", "libmbgc_host.so"))
-    L.mbgc_decoder_region_probe.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint64]
-    return L
-
-
-def probe(host, tmp, prefix, pieces, granule, name, serial=0):
-    arr = np.ascontiguousarray(np.asarray(pieces, dtype=np.uint64).reshape(-1, 3))
-    err = C.create_string_buffer(512)
-    out = os.path.join(tmp, name)
-    r = host.mbgc_decoder_region_probe(os.path.join(tmp, prefix).encode(), 0, serial, arr.ctypes.data_as(C.POINTER(C.c_uint64)), len(arr), granule, out.encode(), err, 512)
-    assert r == 0, err.value
-    rd = lambda ext, dt: np.fromfile(out + "." + ext, dtype=dt)
-    return {k: rd(k, dt) for k, dt in (("granBase", "<u8"), ("needDev", "<u4"), ("needHost", "<u4"), ("contigDev", "<u4"), ("contigHost", "<u4"), ("filled", "<u8"),
-                                        ("seqOff", "<u8"), ("contigLen", "<u8"), ("recBase", "<u8"), ("recDest", "<u8"), ("masked", np.uint8))}
-
-
-def bits(words, n):
-    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
-
-
-def check(p, full_seq, pieces, granule):
-    """device == host; every byte a needed record writes is the unmasked fill's; every other byte of the buffer kept the sentinel"""
-    assert np.array_equal(p["needDev"], p["needHost"]) and np.array_equal(p["contigDev"], p["contigHost"])
-    assert p["filled"][0] == p["filled"][1]
-    lens, off = p["contigLen"], p["seqOff"]
-    g0n = lens.size - (p["granBase"].size - 1)
-    full_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    full = np.frombuffer(full_seq, dtype=np.uint8)
-    need = bits(p["needDev"], int(p["granBase"][-1]))
-    contig = bits(p["contigDev"], lens.size - g0n)
-    for c, a, n in pieces:                                         # what went in is in
-        if c >= g0n:
-            assert need[int(p["granBase"][c - g0n]) + a // granule] and need[int(p["granBase"][c - g0n]) + (a + n - 1) // granule] and contig[c - g0n]
-    filled = 0
-    for k in range(lens.size - g0n):
-        n = int(lens[g0n + k])
-        got = p["masked"][int(off[g0n + k]):int(off[g0n + k + 1])]
-        if not contig[k]:
-            assert got.size == 0                                   # no place in the buffer
-            continue
-        assert got.size == n
-        gneed = need[int(p["granBase"][k]):int(p["granBase"][k + 1])]
-        dest = np.append(p["recDest"][int(p["recBase"][k]):int(p["recBase"][k + 1])], n).astype(np.int64)
-        touched = np.zeros(n, dtype=bool)
-        for a, b in zip(dest[:-1], dest[1:]):
-            if b > a and gneed[a // granule:(b - 1) // granule + 1].any():
-                touched[a:b] = True
-        assert touched[np.repeat(gneed, granule)[:n]].all()        # a needed granule is written whole
-        want = full[full_off[g0n + k]:full_off[g0n + k + 1]]
-        assert np.array_equal(got[touched], want[touched]), k
-        assert (got[~touched] == SENTINEL).all(), k
-        filled += int(touched.sum())
-    assert filled == p["filled"][0]
-    return need, contig, filled
+    return host_lib()
 
 
 @pytest.fixture(scope="module")

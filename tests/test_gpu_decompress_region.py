@@ -4,30 +4,16 @@ FROM, TO, identical ones once. The set is a chain — 8 files of one 64 KiB cont
 every 500 bases — and a file of three records, compressed with `c` and with `c -m 3`."""
 import os
 import re
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+from _regionprobe import OUTS, WIDTH, Full, args_of, expect, fasta, piece_text, run_regions, tool
 from mbgc_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "mbgc_amd", "mbgc-hip")
-OUTS = ("seq", "contigLens", "seqCounts")
-LEN, CHAIN, WIDTH, G = 64 << 10, 8, 70, 256                       # G: the granule that ships (mbgc_decoder.h: regionGranule)
-
-
-def tool(args, cwd, ok=True):
-    r = subprocess.run([TOOL] + args, cwd=cwd, capture_output=True, text=True, timeout=300)
-    if ok:
-        assert r.returncode == 0, r.stderr
-    return r
-
-
-def fasta(header, seq):
-    return b">" + header + b"\n" + b"".join(seq[i:i + WIDTH] + b"\n" for i in range(0, len(seq), WIDTH))
+LEN, CHAIN, G = 64 << 10, 8, 256                       # G: the granule that ships (mbgc_decoder.h: regionGranule)
 
 
 def headers():
@@ -58,64 +44,6 @@ def write_set(tmp):
     return paths
 
 
-class Full:
-    """the unselected run: what every piece is a cut of"""
-
-    def __init__(self, tmp, extra=(), prefix="out", one_file=False):
-        self.tmp, self.extra, self.prefix, self.one_file = tmp, list(extra), prefix, one_file
-        self.stdout = tool(["d"] + self.extra + [prefix, prefix + "_full"], tmp).stdout
-        self.seq = open(os.path.join(tmp, prefix + "_full.seq"), "rb").read()
-        self.lens = np.fromfile(os.path.join(tmp, prefix + "_full.contigLens"), dtype="<u8")
-        self.off = np.concatenate([[0], np.cumsum(self.lens)]).astype(np.int64)
-        self.headers = [h for hs in headers() for h in hs]
-        self.file_of = [i for i, hs in enumerate(headers()) for _ in hs]
-        assert self.lens.size == len(self.headers)
-
-    def cut(self, specs, files=None):
-        """specs: [(pattern, FROM, TO)] -> (pieces [(record, from0, len)], skipped)"""
-        pieces, skipped = set(), 0
-        for pat, a, b in specs:
-            for r, h in enumerate(self.headers):
-                if pat in h and (files is None or self.file_of[r] in files):
-                    if a > self.lens[r]:
-                        skipped += 1
-                    else:
-                        pieces.add((r, a - 1, min(b, int(self.lens[r])) - a + 1))
-        return sorted(pieces), skipped
-
-
-def expect(full, pieces):
-    seq = b"".join(full.seq[full.off[r] + a:full.off[r] + a + n] for r, a, n in pieces)
-    lens = np.asarray([n for _, _, n in pieces], dtype="<u8").tobytes()
-    per_file = {}
-    for r, _, _ in pieces:
-        f = 0 if full.one_file else full.file_of[r]
-        per_file[f] = per_file.get(f, 0) + 1
-    return seq, lens, np.asarray([per_file[f] for f in sorted(per_file)], dtype="<u4").tobytes()
-
-
-def args_of(specs):
-    return sum((["--region", "%s:%d-%d" % (p.decode(), a, b)] for p, a, b in specs), [])
-
-
-def run_regions(full, specs, name, extra=(), files=None, fasta_args=None):
-    pieces, skipped = full.cut(specs, files)
-    sink = (["--fasta", name + "_fa"] + list(fasta_args)) if fasta_args is not None else []
-    out = tool(["d"] + full.extra + list(extra) + args_of(specs) + sink + [full.prefix, name], full.tmp).stdout
-    for ext, want in zip(OUTS, expect(full, pieces)):
-        assert open(os.path.join(full.tmp, name + "." + ext), "rb").read() == want, (name, ext)
-    records = len({r for r, _, _ in pieces})
-    assert "regions: %d pieces of %d records, %d bases, %d out of range\n" % (len(pieces), records, sum(n for _, _, n in pieces), skipped) in out, out
-    return out, pieces
-
-
-def piece_text(full, r, a, n):
-    h = full.headers[r]
-    word = h.split()[0]
-    hdr = word + b":%d-%d" % (a + 1, a + n) + h[len(word):]
-    return fasta(hdr, full.seq[full.off[r] + a:full.off[r] + a + n])
-
-
 @pytest.fixture(scope="module")
 def sets(tmp_path_factory):
     tmp = str(tmp_path_factory.mktemp("region"))
@@ -123,7 +51,7 @@ def sets(tmp_path_factory):
     tool(["c", "list.txt", "out"], tmp)
     tool(["c", "-m", "3", "list.txt", "m3"], tmp)
     tool(["c", "-i", "all.fa", "one"], tmp)
-    return {"plain": Full(tmp), "m3": Full(tmp, ["--restore-rc"], "m3"), "one": Full(tmp, [], "one", True)}
+    return {"plain": Full(tmp, headers=headers()), "m3": Full(tmp, ["--restore-rc"], "m3", headers=headers()), "one": Full(tmp, [], "one", True, headers=headers())}
 
 
 LAST = b"chain%d " % (CHAIN - 1)
