@@ -5,6 +5,8 @@
 //   k_emit_pass1  gap-breaking removal (:153-199). "removed[j]" only depends on removed[j-1] and a
 //                 locally computable predicate, so it is resolved per run of that predicate; the kept
 //                 rows are compacted and unmatchedChars / totalMatched reduced.      [1024 threads/contig]
+//   k_emit_regions_raw  every stitched row's source region (getMatchLoadedPos + upper_bound, :137-141,254-256), beside
+//                 pass 1; the compaction carries it to the kept rows.                       [one thread/row]
 //   k_emit_meta_* the pairing ring, gap deltas and gap bookkeeping (:229-278) — a chain over matches
 //                 that never looks at sequence bytes. The 64-deep look-ahead of every match is a mask made
 //                 lane-parallel from keys in LDS; the chain itself runs one LANE per block of 16 matches,
@@ -60,6 +62,9 @@ struct EmitView {
     // scratch (rows indexed by EmitContig::scratchBase + t)
     EMatch *em;                                      // compacted matches
     uint64_t *next0;                                 // upper_bound(loaded, lp)
+    // lp and next0 of every stitched row (scratchBase + row BEFORE the removal), looked up beside pass 1 (k_emit_regions_raw)
+    // and carried to the kept rows by k_emit_p1_compact; null: this emission's lookups are made behind pass 1 (k_emit_meta_regions)
+    uint64_t *rawLp, *rawNext0;
     uint8_t *removed;
     uint32_t *keepIdx;
     uint32_t *meta;                                  // per kept match, see META_*
@@ -110,6 +115,18 @@ __device__ __forceinline__ uint64_t loaded_pos(const EmitView &v, uint64_t pos) 
     return pos;
 }
 
+// the source region of a match that starts at posSrc: getMatchLoadedPos (:137-141) and the loading position of the region
+// behind it (std::upper_bound, :254-256) — what the pairing chain's lazy-decompression rule compares
+struct SrcRegion { uint64_t lp, next0; };
+__device__ __forceinline__ SrcRegion src_region(const EmitView &v, uint64_t posSrc) {
+    SrcRegion r;
+    r.lp = loaded_pos(v, posSrc);
+    uint32_t lo = 0, hi = v.nLoaded;
+    while (lo < hi) { const uint32_t mid = (lo + hi) / 2; if (v.loaded[mid] <= r.lp) lo = mid + 1; else hi = mid; }
+    r.next0 = lo == v.nLoaded ? UINT64_MAX : v.loaded[lo];
+    return r;
+}
+
 // block-wide exclusive scan of one u32 per thread (NT threads); returns the exclusive prefix,
 // *total = sum over the block. lds: NT / WAVE + 1 words.
 template <int NT>
@@ -145,6 +162,20 @@ __device__ __forceinline__ bool p1_flag(const EmitView &v, const Match *__restri
     const Match a = M[j - 1], b = M[j], c = M[j + 1];
     return paired(c.posSrc, c.posDest, a.posSrc, a.posDest) && !paired(b.posSrc, b.posDest, a.posSrc, a.posDest) &&
            b.len < v.p.gapBreakingMatchMinLength;
+}
+
+// Beside pass 1, on the pairing kernels' stream: the source region of every STITCHED row, from nothing pass 1 makes (the
+// stitched rows, the loaded-positions table, the reference's length). k_emit_p1_compact carries the values to the rows it
+// keeps. One thread per row; rows a contig reserved beyond its matches end at once.
+__global__ void __launch_bounds__(CH) k_emit_regions_raw(EmitView v, const EmitContig *__restrict__ cgs, const int *__restrict__ which) {
+    if (!v.p.lazyDecompressionSupport) return;
+    const uint32_t gk = v.chunkOwner[blockIdx.x];
+    const EmitContig cg = cgs[gk];
+    const uint64_t j = (uint64_t) (blockIdx.x - cg.chunk0) * CH + threadIdx.x;
+    if (j >= v.matchCount[which[gk]]) return;
+    const SrcRegion r = src_region(v, v.matches[cg.matchBase + j].posSrc);
+    v.rawLp[cg.scratchBase + j] = r.lp;
+    v.rawNext0[cg.scratchBase + j] = r.next0;
 }
 
 // (b) a removed match keeps its successor (the successor is then paired with the kept predecessor), so
@@ -229,6 +260,13 @@ __global__ void __launch_bounds__(CH) k_emit_p1_compact(EmitView v, const EmitCo
         EMatch e;
         e.posSrc = M[j].posSrc; e.len = M[j].len; e.posDest = M[j].posDest;
         const bool behindRemoved = j >= 1 && rm[j - 1];
+        e.lp = 0;                                                     // (k_emit_meta_regions, unless the lookups were made ahead)
+        if (v.rawLp) {
+            // the row's source region, looked up beside this pass from the stitched row (k_emit_regions_raw); a left extension
+            // below moves posSrc, and the few rows it touches look theirs up again
+            e.lp = v.rawLp[cg.scratchBase + j];
+            v.next0[cg.scratchBase + t] = v.rawNext0[cg.scratchBase + j];
+        }
         if (behindRemoved && M[j - 1].posDest + M[j - 1].len == M[j].posDest) {
             int64_t s = (int64_t) e.posSrc, d = (int64_t) e.posDest;
             uint64_t x = 0;
@@ -242,8 +280,12 @@ __global__ void __launch_bounds__(CH) k_emit_p1_compact(EmitView v, const EmitCo
             }
             while (d - 1 >= 0 && s - 1 >= 0 && q[d - 1] == v.ref[s - 1]) { d--; s--; x++; }
             e.posSrc -= x; e.posDest -= x; e.len += x;               // shiftStartPos(-leftExtension)
+            if (v.rawLp && x) {
+                const SrcRegion r = src_region(v, e.posSrc);
+                e.lp = r.lp;
+                v.next0[cg.scratchBase + t] = r.next0;
+            }
         }
-        e.lp = 0;                                                     // (k_emit_meta_regions: nothing in this pass asks for it)
         v.em[cg.scratchBase + t] = e;
         v.keepIdx[cg.scratchBase + t] = (uint32_t) j;
         const int64_t jp = behindRemoved ? j - 2 : j - 1;            // the kept match in front
@@ -517,9 +559,9 @@ __device__ __forceinline__ MetaSpan meta_span(const EmitView &v, const EmitConti
     return sp;
 }
 
-// the source region of every kept match: getMatchLoadedPos (:137-141) and the loading position of the region behind it
-// (std::upper_bound, :254-256) — what the pairing chain's lazy-decompression rule compares. Off pass 1's path: the
-// extension policy does not wait for a binary search per match.
+// the source region (src_region) of every kept match, behind pass 1 at the head of the pairing kernels: the path of an
+// emission that is not the first of its batch (emit_pairing). The first one's lookups are made beside pass 1
+// (k_emit_regions_raw), where the chip is idle, instead of here beside the table insertion.
 __global__ void __launch_bounds__(CH) k_emit_meta_regions(EmitView v, const EmitContig *__restrict__ cgs) {
     if (!v.p.lazyDecompressionSupport) return;
     const uint32_t gk = v.chunkOwner[blockIdx.x];
@@ -529,11 +571,9 @@ __global__ void __launch_bounds__(CH) k_emit_meta_regions(EmitView v, const Emit
     if (o.unmatchedChars == UINT64_MAX) return;
     const uint64_t t = (uint64_t) gx * CH + threadIdx.x;
     if (t >= o.nmatches) return;
-    const uint64_t lp = loaded_pos(v, v.em[cg.scratchBase + t].posSrc);
-    v.em[cg.scratchBase + t].lp = lp;
-    uint32_t lo = 0, hi = v.nLoaded;
-    while (lo < hi) { const uint32_t mid = (lo + hi) / 2; if (v.loaded[mid] <= lp) lo = mid + 1; else hi = mid; }
-    v.next0[cg.scratchBase + t] = lo == v.nLoaded ? UINT64_MAX : v.loaded[lo];
+    const SrcRegion r = src_region(v, v.em[cg.scratchBase + t].posSrc);
+    v.em[cg.scratchBase + t].lp = r.lp;
+    v.next0[cg.scratchBase + t] = r.next0;
 }
 
 // look-ahead masks of a span's matches: bit g-1 of match m = match m+g is within the depth, pairedWith m

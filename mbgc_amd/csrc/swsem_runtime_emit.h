@@ -77,7 +77,7 @@ int emit_reserve(swsem *h, EmitSlot &E, int n, uint64_t rows, uint64_t arena, ui
     const uint64_t N = h->capN, R = h->capRows, A = h->capArena, Cn = h->capChunks;
     int r;
     if ((r = E.dECg.reserve(N)) || (r = E.dEOut.reserve(N)) || (r = E.dEWhich.reserve(N)) || (r = E.dEM.reserve(R)) ||
-        (r = E.dENext0.reserve(R)) || (r = E.dERm.reserve(R)) ||
+        (r = E.dENext0.reserve(R)) || (r = E.dERawLp.reserve(R)) || (r = E.dERawNext0.reserve(R)) || (r = E.dERm.reserve(R)) ||
         (r = E.dEKeep.reserve(R)) || (r = E.dEMeta.reserve(R)) || (r = E.dECorr.reserve(R)) ||
         (r = E.dESz.reserve(R * 6)) || (r = E.dEOfs.reserve(R * 6)) || (r = E.dEArena.reserve(A)) || (r = E.dELoaded.reserve(h->capLoaded)) ||
         (r = E.dEStat.reserve(8)) || (r = E.dELong.reserve(LONG_COPY_CAP)) || (r = E.dELongCount.reserve(4)) || (r = E.dEPm.reserve(R)) ||
@@ -114,12 +114,13 @@ int emit_upload_tables(swsem *h, EmitSlot &E, int n, const uint64_t *refExtLoade
 
 // what the emission's kernels are given, and the emission on the books from here on (the plan of the speculative
 // finalize asks ref_write_guard about it)
-EmitView emit_book(swsem *h, EmitSlot &E, int si, const swsem_emit_params_t *p, int n, uint64_t nLoaded) {
+EmitView emit_book(swsem *h, EmitSlot &E, int si, const swsem_emit_params_t *p, int n, uint64_t nLoaded, bool regionsAhead) {
     EmitView v;
     v.ref = h->ref; v.qbuf = h->qdev; v.matches = h->dMatches.p; v.matchCount = h->dMatchCount.p;
     v.pos1 = (uint64_t) h->ld.pos1; v.refLength = h->refLength(); v.maxRefLength = h->maxRefLength;
     v.loaded = E.dELoaded.p; v.nLoaded = (uint32_t) nLoaded; v.p = *p;
     v.em = E.dEM.p; v.next0 = E.dENext0.p; v.removed = E.dERm.p; v.keepIdx = E.dEKeep.p;
+    v.rawLp = regionsAhead ? E.dERawLp.p : nullptr; v.rawNext0 = regionsAhead ? E.dERawNext0.p : nullptr;
     v.meta = E.dEMeta.p; v.corr = E.dECorr.p; v.sz = E.dESz.p; v.arena = E.dEArena.p; v.out = E.dEOut.p;
     v.packBase = E.dEPack.p;
     v.pairMask = E.dEPm.p; v.litBits = E.dELit.p; v.metaBad = E.dEBad.p;
@@ -160,15 +161,34 @@ int spec_plan(swsem *h, const swsem_spec_finalize_t *spec, const uint32_t *gate,
 
 // Pass 1 on the main stream behind the tables, and its results' way to the host (unmatchedChars, the dissimilarity
 // verdict), with the match counts and statistics: one pinned block, one wait (evP1).
+//
+// The source-region lookups of the pairing chain's lazy rule (k_emit_regions_raw, when v.rawLp is set) run beside it on
+// streamAux, behind the batch's match-finding (evMatched) and the tables: between the gather and the table insertion the
+// chip runs a handful of workgroups (30 µs there), while behind pass 1 the same lookups ran beside the request-bound insertion
+// and took 230 µs — with the next batch's resolve waiting for the chain they head (evMeta, batch_launch). They index the
+// stitched rows, so they need nothing of pass 1; k_emit_p1_compact takes their values along to the rows it keeps and is the
+// one kernel that waits for them (evRegions), two launches after they were queued. (No event bracket of their own: the
+// families' per-launch figures keep their meaning.)
+// Only the first emission of a batch takes this path (the caller decides: emit_begin_impl). A later one — another pass
+// over some of the same batch's contigs — has no "match-finding ended here" point that lies ahead of it: it keeps
+// k_emit_meta_regions behind pass 1. (A unit of stopped targets that is matched again is a batch of its own, and its
+// emission the first of that batch.)
 int emit_pass1(swsem *h, EmitSlot &E, const EmitView &v, int n) {
     const dim3 grid2(E.grid2b);
     int r;
     HIPCHK(hipEventRecord(h->evTables, h->streamUp));
+    if (v.rawLp) {
+        HIPCHK(hipStreamWaitEvent(h->streamAux, h->evMatched, 0));
+        HIPCHK(hipStreamWaitEvent(h->streamAux, h->evTables, 0));
+        k_emit_regions_raw<<<grid2, dim3(CH), 0, h->streamAux>>>(v, E.dECg.p, E.dEWhich.p);
+        HIPCHK(hipEventRecord(h->evRegions, h->streamAux));
+    }
     HIPCHK(hipStreamWaitEvent(h->stream, h->evTables, 0));
     hipStream_t sP = h->stream;
     h->mark(SWSEM_K_EMIT, true, sP);
     k_emit_p1_removed<<<grid2, dim3(CH), 0, sP>>>(v, E.dECg.p, E.dEWhich.p);
     k_emit_p1_scan<<<dim3(n), dim3(CH), 0, sP>>>(v, E.dECg.p, E.dEWhich.p);
+    if (v.rawLp) HIPCHK(hipStreamWaitEvent(sP, h->evRegions, 0));
     k_emit_p1_compact<<<grid2, dim3(CH), 0, sP>>>(v, E.dECg.p, E.dEWhich.p);
     k_emit_p1_finish<<<dim3(n), dim3(CH), 0, sP>>>(v, E.dECg.p);
     h->mark(SWSEM_K_EMIT, false, sP);
@@ -179,7 +199,8 @@ int emit_pass1(swsem *h, EmitSlot &E, const EmitView &v, int n) {
     return SWSEM_OK;
 }
 
-// The pairing kernels on streamAux behind pass 1. The byte automata (sizes .. write) that follow them are queued later
+// The pairing kernels on streamAux behind pass 1 (k_emit_meta_regions only where the lookups were not made beside pass 1:
+// emit_pass1). The byte automata (sizes .. write) that follow them are queued later
 // (run_phase2b): behind the speculative finalize, and not before the next batch's resolve kernel has been handed over.
 int emit_pairing(swsem *h, EmitSlot &E, const EmitView &v, int n) {
     const dim3 grid2(E.grid2b), spans((uint32_t) E.spanOwner.size());
@@ -188,7 +209,7 @@ int emit_pairing(swsem *h, EmitSlot &E, const EmitView &v, int n) {
     if (r) return r;
     HIPCHK(hipStreamWaitEvent(h->streamAux, h->evP1, 0));
     h->mark(SWSEM_K_EMIT2, true, h->streamAux);
-    k_emit_meta_regions<<<grid2, dim3(CH), 0, h->streamAux>>>(v, E.dECg.p);
+    if (!v.rawLp) k_emit_meta_regions<<<grid2, dim3(CH), 0, h->streamAux>>>(v, E.dECg.p);
     k_emit_meta_masks<<<spans, dim3(MLANES), 0, h->streamAux>>>(v, E.dECg.p);
     k_emit_meta_spec<<<spans, dim3(MLANES), 0, h->streamAux>>>(v, E.dECg.p, E.dEStates.p, h->sw.metaWarm, E.dEStat.p);
     // (the next batch's resolve is launched behind this kernel, batch_launch: a launch of thousands of waves that is still
@@ -259,12 +280,15 @@ int emit_begin_impl(swsem *h, const swsem_emit_params_t *p, int n, const int *co
         return fail(SWSEM_EINVAL, "gapDepthOffsetEncoding %d out of range (MAX_GAP_DEPTH / 2)", p->gapDepthOffsetEncoding);
     int r;
     uint64_t rows, arena;
+    // the first emission since the batch's match-finding was launched (emit_upload_tables takes the flag down): its region
+    // lookups run beside pass 1 (emit_pass1)
+    const bool regionsAhead = h->roundTopFresh && p->lazyDecompressionSupport;
     if ((r = emit_layout(h, E, n, contigIdx, lockPos, factor, processed, targetIdx, rows, arena)) ||
         (r = emit_reserve(h, E, n, rows, arena, nLoaded)) ||
         (r = emit_upload_tables(h, E, n, refExtLoadedPos, nLoaded, spec)))
         return r;
     // no synchronisation here: the kernels below queue up behind match-finding while it is still running
-    const EmitView v = emit_book(h, E, si, p, n, nLoaded);
+    const EmitView v = emit_book(h, E, si, p, n, nLoaded, regionsAhead);
     const LoaderState snap = h->ld;                                  // what a finalize that is not applied goes back to
     bool planned = false, queued = false, exchanged = false;
     uint32_t *gate = spec ? (spec->gate_dev ? spec->gate_dev : h->dGate.p) : nullptr;

@@ -163,6 +163,7 @@ struct EmitSlot {
     DevBuf<uint32_t> dEOwner, dESpanOwner;
     DevBuf<EMatch> dEM;
     DevBuf<uint64_t> dENext0, dELoaded, dEPack;
+    DevBuf<uint64_t> dERawLp, dERawNext0;  // per stitched row: the source regions looked up beside pass 1 (k_emit_regions_raw)
     DevBuf<uint8_t> dERm, dEArena;
     DevBuf<uint32_t> dEKeep, dEMeta, dECorr, dESz, dEOfs, dEChunk;
     DevBuf<MetaRec> dEStates;
@@ -327,6 +328,7 @@ struct swsem {
     Event evP1;
     Event evFin;                           // behind the speculative finalize (see emit_begin_impl)
     Event evMeta;                          // behind the last emission's k_emit_meta_spec
+    Event evRegions;                       // behind k_emit_regions_raw (k_emit_p1_compact waits for it)
     bool metaPending = false;
     bool emitHostCopy = true;              // copy the streams to the host inside swsem_emit_batch
     // Warm-up positions of a speculative block chain (at most OVERLAP_MAX): a chain started from the empty state falls into step with the
