@@ -208,6 +208,19 @@ uint64_t refrc_find_matches(const char *seq, uint64_t n, uint32_t targetMatchLen
     for (size_t i = 0; i < res.size() && i < cap; i++) { out[3 * i] = res[i].posSrcText; out[3 * i + 1] = res[i].length; out[3 * i + 2] = res[i].posDestText; }
     return res.size();
 }
+// the same, and what CopMEMMatcher's constructor derived from the text's length and the target length: K, k1, k2, log2(hash_size)
+uint64_t refrc_find_matches_params(const char *seq, uint64_t n, uint32_t targetMatchLength, uint32_t minMatchLength, uint64_t *out, uint64_t cap,
+                                   int *params) {
+    quiet();
+    std::string s(seq, n);
+    CopMEMMatcher m(s.data(), s.size(), targetMatchLength, minMatchLength);
+    params[0] = m.K; params[1] = m.k1; params[2] = m.k2; params[3] = 31 - __builtin_clz(m.hash_size);
+    std::string q = PgHelpers::reverseComplement(s);
+    std::vector<TextMatch> res;
+    m.matchTexts(res, q, true, true, minMatchLength == UINT32_MAX ? targetMatchLength : minMatchLength);
+    for (size_t i = 0; i < res.size() && i < cap; i++) { out[3 * i] = res[i].posSrcText; out[3 * i + 1] = res[i].length; out[3 * i + 2] = res[i].posDestText; }
+    return res.size();
+}
 
 // ---------------------------------------------------------------- backend: leaf coders and the collective section
 // One leaf coder call as Compress() makes it (coders/CodersLib.cpp:53-66): LzmaCompress / Ppmd7Compress with the given

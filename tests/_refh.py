@@ -164,6 +164,20 @@ def rc_find_matches(seq, target=55, min_len=0xFFFFFFFF):
     return out[:n].copy()
 
 
+def rc_find_matches_params(seq, target=55, min_len=0xFFFFFFFF):
+    """-> (rows, (K, k1, k2, log2 hash size) as the reference's constructor derived them)"""
+    a, p = _bytes_ptr(seq)
+    L = lib()
+    L.refrc_find_matches_params.restype = C.c_uint64
+    L.refrc_find_matches_params.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int)]
+    cap = max(1024, a.size // 8)
+    out = np.zeros((cap, 3), dtype=np.uint64)
+    params = (C.c_int * 4)()
+    n = L.refrc_find_matches_params(p, a.size, target, min_len, out.ctypes.data_as(C.c_void_p), cap, params)
+    assert n <= cap
+    return out[:n].copy(), tuple(params)
+
+
 def rc_match_sequence(seq, target=55, min_len=0xFFFFFFFF):
     a = np.array(seq, dtype=np.uint8, copy=True)
     L = lib()
