@@ -192,7 +192,11 @@ __global__ void __launch_bounds__(256) k_insert_multi(const uint8_t *__restrict_
         const int nw = K / 4;
         for (int j = 0; j < nw; j++) { const uint32_t w = ld_u32(s + 4 * j); h = hash_step(h, w, (uint32_t) j); f = fp_step(f, w); }
         const uint32_t off = (uint32_t) (p & ((1ull << k1ord) - 1));
-        if (off && p >= off && (!FROM_SRC || p - off >= pc.lo)) f = fp_at(s - off, nw);   // a sample off the grid (see fp_at)
+        // a sample off the grid (see fp_at). From the source the slot's first byte must lie in the piece: the one sample for which it
+        // does not is the one AT REF_SHIFT (the off-grid stretch is the first step of a lap, lo = 1, p - off = 0), which keeps its
+        // own fingerprint here while k_insert takes the K-mer at byte 0. No lookup can tell: that K-mer begins with the buffer's
+        // byte 0, which no query text holds, so a lookup sent to slot 0 fails its byte compare under either fingerprint.
+        if (off && p >= off && (!FROM_SRC || p - off >= pc.lo)) f = fp_at(s - off, nw);
         const ht_entry key = ht_key(pc.epoch + (tail ? 1u : 0u), (uint32_t) (p >> k1ord), f, fpBits);
         const ht_entry seen = ht[h & mask];
         if (seen >= key) continue;                         // (entries only grow: a stale read shows a smaller one at worst, then the atomic decides)

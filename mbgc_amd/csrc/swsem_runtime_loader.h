@@ -229,6 +229,23 @@ int insert_samples(swsem *h, const uint8_t *src = nullptr, uint64_t lo = 0, uint
 
 // private loadRef, .cpp:402-437, on a device-resident text
 int flush_tag_summary(swsem *h);
+int flush_inserts(swsem *h, const uint32_t *gate = nullptr);
+// A flush runs its copies in one launch, its separators behind them and its insertion over the result: fine as long as no step
+// writes where an earlier step of the same flush has written or sampled. A write to [a, b) that does — no sliding window and an
+// extension longer than what is left of the lap, so the loader comes round to its own pieces — would race the earlier copy
+// and have the earlier samples hashed from the later bytes (the reference hashes them before it goes on). Such a step has what
+// is pending launched first, in order. (The samples of a step start at most K + k1 bytes in front of the text it wrote.)
+bool hits_pending(const swsem *h, uint64_t a, uint64_t b) {
+    const uint64_t reach = (uint64_t) h->K + (uint64_t) h->k1;
+    for (auto &c : h->pendingCopies) if (a < c.dst + c.len && b + reach > c.dst) return true;
+    for (auto &p : h->pendingBytes) if (p.off >= a && p.off < b) return true;
+    return false;
+}
+int flush_if_hit(swsem *h, uint64_t a, uint64_t b) {
+    if (!h->deferInserts || !hits_pending(h, a, b)) return SWSEM_OK;
+    if (h->specMode) return SWSEM_ESPEC;                           // an ungated launch in the middle: give the speculation up
+    return flush_inserts(h);
+}
 int load_pieces(swsem *h, const uint8_t *text, uint64_t len, bool rc, bool addSep, int sep) {
     LoaderState &ld = h->ld;
     while (len != 0) {
@@ -249,6 +266,7 @@ int load_pieces(swsem *h, const uint8_t *text, uint64_t len, bool rc, bool addSe
             int g = ref_write_guard(h, first, last);
             if (g) return g;
         }
+        if (tmpLength) { int f = flush_if_hit(h, (uint64_t) ld.pos1, (uint64_t) ld.pos1 + tmpLength); if (f) return f; }
         if (tmpLength && !rc && h->deferInserts) {                  // (nothing is launched here: no profiling bracket)
             CopyPiece cp; cp.dst = (uint64_t) ld.pos1; cp.src = text; cp.len = tmpLength;
             h->pendingCopies.push_back(cp);
@@ -419,7 +437,7 @@ int launch_inserts(swsem *h, const uint32_t *gate) {
     return SWSEM_OK;
 }
 
-int flush_inserts(swsem *h, const uint32_t *gate = nullptr) {
+int flush_inserts(swsem *h, const uint32_t *gate) {
     int r = prepare_inserts(h, h->stream);
     return r ? r : launch_inserts(h, gate);
 }
@@ -447,6 +465,7 @@ int load_separator(swsem *h, int sep) {
         note_byte(h, (uint64_t) ld.pos1 - 1);
         ld.sep_end_set(ld.pos1, sep);
     } else if (h->deferInserts) {
+        { int f = flush_if_hit(h, (uint64_t) ld.pos1, (uint64_t) ld.pos1 + 1); if (f) return f; }
         note_byte(h, (uint64_t) ld.pos1);
         BytePiece bp; bp.off = (uint64_t) ld.pos1++; bp.val = (uint64_t) (uint8_t) sep;
         h->pendingBytes.push_back(bp);

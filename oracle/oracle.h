@@ -53,6 +53,11 @@ uint32_t orc_hash_size(const orc_matcher *m);
 const uint32_t *orc_ht(const orc_matcher *m);
 const uint8_t *orc_ref(const orc_matcher *m);
 int orc_K(const orc_matcher *m);
+uint64_t orc_sliding_window_size(const orc_matcher *m);      /* swSize, 0 without a circular buffer */
+uint64_t orc_sw_end(const orc_matcher *m);                   /* swEnd */
+uint64_t orc_sampling_position(const orc_matcher *m);        /* samplingPos, .cpp:146-171 */
+uint64_t orc_dropped_bytes(const orc_matcher *m);            /* bytes loadRef cut off at swEnd, .cpp:433 */
+int orc_laps(const orc_matcher *m);                          /* reachedRefLengthCount */
 void orc_set_prefilter(orc_matcher *m, int on);              /* .cpp:203-204,223-226 (result-neutral) */
 
 /* matchTexts, .cpp:478-492 -> :181-321. Returns the number of matches; *out is malloc'd (free with

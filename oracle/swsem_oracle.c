@@ -31,6 +31,7 @@ struct orc_matcher {
     uint64_t locks[MAX_LOCKS];           /* workersSwEndPositions (deque) */
     int lockHead, lockCount;
     int prefilter;
+    uint64_t droppedBytes;               /* what loadRef gives up at the window's end (.cpp:433) */
 };
 
 /* utils/Hashes.h:28-40 — the u64 accumulator's low 32 bits depend only on low 32 bits of every
@@ -110,6 +111,12 @@ uint32_t orc_hash_size(const orc_matcher *m) { return m->hash_size; }
 const uint32_t *orc_ht(const orc_matcher *m) { return m->ht; }
 const uint8_t *orc_ref(const orc_matcher *m) { return m->ref; }
 int orc_K(const orc_matcher *m) { return m->K; }
+/* the loader's own state, for tests that build their inputs from it */
+uint64_t orc_sliding_window_size(const orc_matcher *m) { return m->circular ? m->swSize : 0; }
+uint64_t orc_sw_end(const orc_matcher *m) { return m->swEnd; }
+uint64_t orc_sampling_position(const orc_matcher *m) { return m->samplingPos; }
+uint64_t orc_dropped_bytes(const orc_matcher *m) { return m->droppedBytes; }
+int orc_laps(const orc_matcher *m) { return m->laps; }
 void orc_set_prefilter(orc_matcher *m, int on) { m->prefilter = on; }
 void orc_free(void *p) { free(p); }
 
@@ -198,6 +205,7 @@ static void load_ref_piecewise(orc_matcher *m, const uint8_t *text, uint64_t len
         m->pos1 += (int64_t) tmpLength;
         insert_samples(m);
         text += rc ? 0 : tmpLength;
+        if ((uint64_t) m->pos1 == tmpEnd) m->droppedBytes += len - tmpLength;
         len = (uint64_t) m->pos1 == tmpEnd ? 0 : len - tmpLength;
     }
 }

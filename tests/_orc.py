@@ -64,7 +64,7 @@ def lib():
         L.orc_load_ref.argtypes = [vp, vp, u64, ci, ci, ci]
         L.orc_load_separator.argtypes = [vp, ci]
         for n in ("orc_ref_length", "orc_loading_position", "orc_loaded_ref_length", "orc_max_ref_length",
-                  "orc_acquire_lock"):
+                  "orc_acquire_lock", "orc_sliding_window_size", "orc_sw_end", "orc_sampling_position", "orc_dropped_bytes"):
             getattr(L, n).restype = u64
             getattr(L, n).argtypes = [vp]
         L.orc_set_position.argtypes = [vp, u64, ci]
@@ -78,6 +78,8 @@ def lib():
         L.orc_ref.argtypes = [vp]
         L.orc_K.restype = ci
         L.orc_K.argtypes = [vp]
+        L.orc_laps.restype = ci
+        L.orc_laps.argtypes = [vp]
         L.orc_set_prefilter.argtypes = [vp, ci]
         L.orc_match_texts.restype = u64
         L.orc_match_texts.argtypes = [vp, vp, u64, C.c_uint32, u64, C.POINTER(C.POINTER(OrcMatch)), C.POINTER(u64)]
@@ -139,6 +141,11 @@ class OracleMatcher:
     def release_lock(self, v): return lib().orc_release_lock(self.h, v)
     def hash_size(self): return lib().orc_hash_size(self.h)
     def K(self): return lib().orc_K(self.h)
+    def sliding_window_size(self): return lib().orc_sliding_window_size(self.h)
+    def sw_end(self): return lib().orc_sw_end(self.h)
+    def sampling_position(self): return lib().orc_sampling_position(self.h)
+    def dropped_bytes(self): return lib().orc_dropped_bytes(self.h)
+    def laps(self): return lib().orc_laps(self.h)
     def set_prefilter(self, on): lib().orc_set_prefilter(self.h, int(on))
 
     def ht(self):
