@@ -180,7 +180,7 @@ int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const o
     memset(&D, 0, sizeof D);
     dec_t *d = &D;
     d->ref = ref; d->refBytes = refBytes; d->info = info; d->p = p;
-    if (info) { info->maxRingWalk = 0; info->nTrace = 0; }
+    if (info) { info->maxRingWalk = 0; info->nTrace = 0; info->nRecs = 0; }
     d->lit = streams[ORC_LIT]; d->nLit = sizes[ORC_LIT];
     d->off = streams[ORC_OFF]; d->nOff = sizes[ORC_OFF];
     d->off5 = streams[ORC_OFF5]; d->nOff5 = sizes[ORC_OFF5];
@@ -227,6 +227,7 @@ int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const o
         }
         if (d->bad) break;
         const uint64_t literalLen = markPos - d->litPos + extLeftLen + extRightLen;
+        const uint64_t recDestAt = d->destLen, recPlain = markPos - d->litPos;
         append(d, d->lit + d->litPos, markPos - d->litPos);
         if (extLeftLen) append(d, extEnd - extLeftLen, extLeftLen);
         unmatchedChars += (uint32_t) literalLen;
@@ -275,6 +276,15 @@ int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const o
             if (!isGap || gapStart) offsetDelta = (int64_t) matchSrcPos + (int64_t) matchLength - (int64_t) d->destLen;
             extRightLen = extend_right(d, offsetDelta, isGap, gapStart, gapMiddle, gapEnd,
                                        markPos != NPOS && markPos < seqEnd ? markPos : seqEnd);
+        }
+        if (info && info->recs && !d->bad) {                              /* the match as it was taken, for the caller who asked */
+            if (info->nRecs < info->recCap) {
+                orc_match_rec *r = &info->recs[info->nRecs];
+                r->destAt = recDestAt; r->plain = recPlain; r->leftLen = extLeftLen; r->src = matchSrcPos; r->matchLen = matchLength;
+                r->rightLen = extRightLen; r->skipOffset = (uint32_t) skipOffset;
+                r->flags = (isGap ? ORC_REC_GAP : 0) | (gapStart ? ORC_REC_GAP_START : 0) | (gapMiddle ? ORC_REC_GAP_MIDDLE : 0) | (gapEnd ? ORC_REC_GAP_END : 0);
+            }
+            info->nRecs++;
         }
         j++;
     }

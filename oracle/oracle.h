@@ -136,11 +136,21 @@ typedef struct {
     int64_t refPos;
     uint64_t litPos;                           /* the literal code that stands for the byte; ORC_NO_LIT: copied as it is */
 } orc_ext_read;
+/* one match as the automaton took it (recs, may be NULL: the first recCap of nRecs, in order): the plain literals in front of it,
+ * its left extension, the match, its right extension, where the iteration started in the contig, and ORC_REC_* of the right
+ * extension's gap state */
+enum { ORC_REC_GAP = 1, ORC_REC_GAP_START = 2, ORC_REC_GAP_MIDDLE = 4, ORC_REC_GAP_END = 8 };
+typedef struct {
+    uint64_t destAt, plain, leftLen, src, matchLen, rightLen;
+    uint32_t flags, skipOffset;
+} orc_match_rec;
 typedef struct {
     uint64_t cur[ORC_NSTREAMS];
     uint64_t maxRingWalk;
     orc_ext_read *trace;
     uint64_t traceCap, nTrace;
+    orc_match_rec *recs;
+    uint64_t recCap, nRecs;
 } orc_decode_info;
 int64_t orc_decode_contig_bounded(const uint8_t *ref, uint64_t refBytes, const orc_emit_params *p,
                                   const uint8_t *const streams[ORC_NSTREAMS], const uint64_t sizes[ORC_NSTREAMS],

@@ -251,17 +251,27 @@ class OrcExtRead(C.Structure):
     _fields_ = [("refPos", C.c_int64), ("litPos", C.c_uint64)]
 
 
+class OrcMatchRec(C.Structure):
+    _fields_ = [("destAt", C.c_uint64), ("plain", C.c_uint64), ("leftLen", C.c_uint64), ("src", C.c_uint64), ("matchLen", C.c_uint64),
+                ("rightLen", C.c_uint64), ("flags", C.c_uint32), ("skipOffset", C.c_uint32)]
+
+
+REC_GAP, REC_GAP_START, REC_GAP_MIDDLE, REC_GAP_END = 1, 2, 4, 8       # ORC_REC_*, oracle/oracle.h (the device's REC_* of swsem_decode.hip)
+
+
 class OrcDecodeInfo(C.Structure):
     _fields_ = [("cur", C.c_uint64 * 6), ("maxRingWalk", C.c_uint64), ("trace", C.POINTER(OrcExtRead)),
-                ("traceCap", C.c_uint64), ("nTrace", C.c_uint64)]
+                ("traceCap", C.c_uint64), ("nTrace", C.c_uint64), ("recs", C.POINTER(OrcMatchRec)), ("recCap", C.c_uint64),
+                ("nRecs", C.c_uint64)]
 
 
-def decode_contig_bounded(ref, ref_bytes, params, streams, lock=NO_LOCK, cap=1 << 18, trace=0):
+def decode_contig_bounded(ref, ref_bytes, params, streams, lock=NO_LOCK, cap=1 << 18, trace=0, recs=0):
     """orc_decode_contig_bounded (oracle/decode_oracle.c): the decoder's automaton with the reference buffer's size known, for
     stream sets no encoder wrote. `streams`: the six streams in STREAM_NAMES order (bytes). `ref`: a uint8 array of at least
     ref_bytes bytes. Never raises on a malformed set: -> dict(unmatched (-1: malformed), dest (the bytes written, uint8 array),
     cur (the six cursors reached), walk (longest pairing-ring walk), trace ((refPos, litPos or NO_LOCK) per extension read, when
-    trace > 0 entries were asked for))."""
+    trace > 0 entries were asked for), recs (one dict per match as the automaton took it — destAt, plain, leftLen, src, matchLen,
+    rightLen, flags (REC_*), skipOffset — when recs > 0 entries were asked for))."""
     assert isinstance(ref, np.ndarray) and ref.dtype == np.uint8 and ref.size >= ref_bytes
     keep = [C.create_string_buffer(bytes(s), len(s)) if len(s) else None for s in streams]      # (exactly as long as declared)
     ptrs = (C.c_void_p * 6)(*[C.addressof(k) if k is not None else None for k in keep])
@@ -272,6 +282,9 @@ def decode_contig_bounded(ref, ref_bytes, params, streams, lock=NO_LOCK, cap=1 <
     tr = (OrcExtRead * trace)() if trace else None
     if trace:
         info.trace, info.traceCap = C.cast(tr, C.POINTER(OrcExtRead)), trace
+    rc = (OrcMatchRec * recs)() if recs else None
+    if recs:
+        info.recs, info.recCap = C.cast(rc, C.POINTER(OrcMatchRec)), recs
     f = lib().orc_decode_contig_bounded
     f.restype = C.c_int64
     f.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -281,6 +294,9 @@ def decode_contig_bounded(ref, ref_bytes, params, streams, lock=NO_LOCK, cap=1 <
     if trace:
         assert info.nTrace <= trace, "decode_contig_bounded: %d extension reads, room for %d" % (info.nTrace, trace)
         res["trace"] = [(tr[i].refPos, tr[i].litPos) for i in range(info.nTrace)]
+    if recs:
+        assert info.nRecs <= recs, "decode_contig_bounded: %d matches, room for %d" % (info.nRecs, recs)
+        res["recs"] = [{k: int(getattr(rc[i], k)) for k, _ in OrcMatchRec._fields_} for i in range(info.nRecs)]
     return res
 
 
