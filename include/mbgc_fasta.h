@@ -223,6 +223,31 @@ int mbgc_fasta_crc_host(mbgc_fasta_t *p, const mbgc_fasta_record_t *records, uin
 /* host: the CRC-32 of A followed by B from crc32(A), crc32(B) and B's length (zlib's crc32_combine); needs no device */
 uint32_t mbgc_fasta_crc_combine(uint32_t crcA, uint32_t crcB, uint64_t lenB);
 
+/* The search of `mbgc-hip f`: where do query sequences stand in byte ranges of a device buffer, with at most maxMismatches
+ * substitutions. Record r is seq_dev[recs[r].off, recs[r].off + recs[r].len) of a buffer of seqBytes bytes; the records may overlap,
+ * repeat, be empty and come in any order. patterns_host: the patterns back to back, pattern q at [patOff[q], patOff[q + 1]); the same
+ * pattern may be given twice. With fold(b) = b & 0xDF for an ASCII letter and b otherwise, a hit is (rec r, pattern q, pos p,
+ * mismatches d): p + len(q) <= recs[r].len, d = the positions j with fold(seq[recs[r].off + p + j]) != fold(pattern_q[j]), d <=
+ * maxMismatches. Every hit is reported exactly once, overlapping ones included; a hit never reaches over a record's end, whatever lies
+ * behind it in the buffer. The call knows nothing of strands or names.
+ * Refused before anything is launched (-103, message in mbgc_fasta_last_error; *nHits and hits_host are left as they were):
+ * maxMismatches > 3; a pattern that holds a byte that is no ASCII letter, is shorter than 8 (maxMismatches + 1) bytes or longer than
+ * 65535; a record that does not lie inside the buffer.
+ * *nHits is always the exact count. When it exceeds hitCap the call returns -104 and leaves hits_host as it was: call again with that
+ * capacity. Otherwise hits_host[0, *nHits) holds the hits sorted by (rec, pos, pattern). The device appends rows through one atomic
+ * cursor and writes only below hitCap; the host sorts.
+ * What a text byte costs does not grow with the number of patterns: a pattern is cut into maxMismatches + 1 disjoint seeds, one table
+ * keyed by the seeds' first 8 folded bytes is probed once per text position, and only the patterns that share those bytes are counted
+ * out. The records are cut into tiles of MBGC_FASTA_FIND_TILE positions on the 16-byte grid of the buffer's addresses, one list over
+ * all records; a block of 256 lanes stages a tile and the 16 bytes behind it in LDS with aligned 16-byte loads and takes the next
+ * tile of the list. The table lies in LDS up to 2048 slots, in global memory beyond. No byte outside seq_dev[0, seqBytes) is read.
+ * kernelMs (may be NULL): the kernel's time from events on the stream. Runs on the input stage's stream; synchronous. */
+#define MBGC_FASTA_FIND_TILE 4096
+typedef struct { uint64_t pos; uint32_t rec, pattern, mismatches, reserved; } mbgc_fasta_hit_t;
+int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                        const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
+                        mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs);
+
 /* gzip files that lie compressed in HBM, inflated there(mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

@@ -720,6 +720,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_compare.h"
 #include "fasta_pack.h"
 #include "fasta_select.h"
+#include "fasta_find.h"
 #include "fasta_crc.h"
 
 #define INF_CONST static __device__
@@ -831,6 +832,35 @@ __global__ void __launch_bounds__(WAVE) k_fa_match_headers(const uint8_t *__rest
                 break;
             }
         }
+    }
+}
+
+// mbgc_fasta_find_dev: a block takes tile after tile of the flat list over all records (the record by bisection of the tiles' prefix sum,
+// the two lane steps: fasta_find.h). The table is copied to LDS once per block when it fits (LDS_TABLE), and read where it lies in
+// global memory — from L2 — otherwise. A hit takes a row of the buffer through the one cursor; rows at or past the capacity are
+// counted and not written, so the cursor ends as the exact count.
+template <bool LDS_TABLE>
+__global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+                                                          uint32_t nrec, uint64_t ntiles, const FindSlot *__restrict__ slotsGlobal, uint32_t bits,
+                                                          const FindSeed *__restrict__ seeds, const FindPat *__restrict__ pats, const uint8_t *__restrict__ patBytes, uint32_t K,
+                                                          mbgc_fasta_hit_t *__restrict__ hits, uint64_t hitCap, unsigned long long *__restrict__ cursor) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[FIND_STAGE];
+    __shared__ FindSlot slotsLds[LDS_TABLE ? (1u << FIND_LDS_BITS) : 1];
+    const uint32_t lane = threadIdx.x;
+    if (LDS_TABLE) for (uint32_t s = lane; s < (1u << bits); s += FIND_THREADS) slotsLds[s] = slotsGlobal[s];   // (visible behind the first tile's barrier)
+    const FindSlot *slots = LDS_TABLE ? slotsLds : slotsGlobal;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
+        const uint32_t r = find_tile_record(tileStart, nrec, tile);
+        const FindRec rec = recs[r];
+        const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * FIND_TILE;
+        find_stage_step(seq, seqBytes, tileAddr, lane, stage);
+        if (lane == 0) find_stage_step(seq, seqBytes, tileAddr, FIND_VECS - 1, stage);
+        __syncthreads();
+        find_lane_step(seq, rec, tileAddr, lane, stage, slots, bits, seeds, pats, patBytes, K, [&](uint64_t pos, uint32_t pat, uint32_t d) {
+            const unsigned long long at = atomicAdd(cursor, 1ull);
+            if (at < hitCap) hits[at] = mbgc_fasta_hit_t{pos, r, pat, d, 0u};
+        });
+        __syncthreads();                                                     // (the next tile's stores wait for this tile's reads)
     }
 }
 
@@ -1000,6 +1030,14 @@ struct mbgc_fasta {
     fa::Buf<fa::SelPat> dSelPats;
     fa::Buf<uint8_t> dSelBytes;
     fa::Buf<uint32_t> dSelChosen;
+    fa::Buf<fa::FindRec> dFindRecs;             // mbgc_fasta_find_dev: the records, their tiles' prefix sum, the gram table, the hit rows and their cursor
+    fa::Buf<uint64_t> dFindTiles;
+    fa::Buf<fa::FindSlot> dFindSlots;
+    fa::Buf<fa::FindSeed> dFindSeeds;
+    fa::Buf<fa::FindPat> dFindPats;
+    fa::Buf<uint8_t> dFindBytes;
+    fa::Buf<mbgc_fasta_hit_t> dFindHits;
+    fa::Buf<unsigned long long> dFindCursor;
     fa::Buf<fa::CrcRow> dCrcRows;               // mbgc_fasta_crc_dev: the rows, the bytes behind the cut ranges' pieces, the ranges' words, the constants
     fa::Buf<uint64_t> dCrcBehind;
     fa::Buf<uint32_t> dCrcOut;
@@ -1050,6 +1088,8 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
     p->dPackPieces.release(); p->dPackOwner.release();
     p->dSelRecs.release(); p->dSelSlots.release(); p->dSelPats.release(); p->dSelBytes.release(); p->dSelChosen.release();
+    p->dFindRecs.release(); p->dFindTiles.release(); p->dFindSlots.release(); p->dFindSeeds.release(); p->dFindPats.release(); p->dFindBytes.release();
+    p->dFindHits.release(); p->dFindCursor.release();
     p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
@@ -1435,6 +1475,75 @@ int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, ui
     FCHK(hipStreamSynchronize(p->stream));
     if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
     memcpy(chosen, out.data(), words * sizeof(uint32_t));
+    return 0;
+}
+
+int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                        const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
+                        mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(FindRec) == sizeof(mbgc_fasta_crc_rec_t), "the kernel reads the ABI's ranges");
+    if (kernelMs) *kernelMs = 0;
+    const uint32_t K = maxMismatches;
+    if (K > FIND_MAX_K) return fail(-103, "find: %u mismatches (at most %u)", K, FIND_MAX_K);
+    if (n >= 0xffffffffull || npat >= 0xffffffffull / (FIND_MAX_K + 1)) return fail(-103, "find: %llu records, %llu patterns in one call", (unsigned long long) n, (unsigned long long) npat);
+    for (uint64_t q = 0; q < npat; q++) {
+        if (patOff[q + 1] < patOff[q]) return fail(-103, "find: pattern %llu ends in front of its start", (unsigned long long) q);
+        const uint64_t len = patOff[q + 1] - patOff[q];
+        if (len < (uint64_t) FIND_GRAM * (K + 1)) return fail(-103, "find: pattern %llu has %llu bytes, %u mismatches need at least %u", (unsigned long long) q, (unsigned long long) len, K, FIND_GRAM * (K + 1));
+        if (len > FIND_MAX_LEN) return fail(-103, "find: pattern %llu has %llu bytes (at most %u)", (unsigned long long) q, (unsigned long long) len, FIND_MAX_LEN);
+        for (uint64_t i = patOff[q]; i < patOff[q + 1]; i++)
+            if ((uint8_t) ((patterns_host[i] | 0x20) - 'a') >= 26) return fail(-103, "find: pattern %llu holds a byte that is no letter (0x%02x at %llu)", (unsigned long long) q, patterns_host[i], (unsigned long long) (i - patOff[q]));
+    }
+    for (uint64_t r = 0; r < n; r++)
+        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "find: record %llu lies outside the buffer", (unsigned long long) r);
+    if (n == 0 || npat == 0) { *nHits = 0; return 0; }
+    FindTable T;
+    find_build_table(patterns_host, patOff, npat, K, T);
+    std::vector<uint64_t> tileStart(n + 1, 0);
+    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + find_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len, T.shortest);
+    const uint64_t ntiles = tileStart[n];
+    if (ntiles == 0) { *nHits = 0; return 0; }                       // (no record is as long as the shortest pattern)
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dFindSlots.reserve(T.slots.size())) || (rc = p->dFindSeeds.reserve(T.seeds.size())) ||
+        (rc = p->dFindPats.reserve(T.pats.size())) || (rc = p->dFindBytes.reserve(T.bytes.size())) || (rc = p->dFindHits.reserve(std::max<uint64_t>(hitCap, 1))) ||
+        (rc = p->dFindCursor.reserve(1))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindSlots.p, T.slots.data(), T.slots.size() * sizeof(FindSlot), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindSeeds.p, T.seeds.data(), T.seeds.size() * sizeof(FindSeed), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindPats.p, T.pats.data(), T.pats.size() * sizeof(FindPat), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindBytes.p, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemsetAsync(p->dFindCursor.p, 0, sizeof(unsigned long long), p->stream));
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    // one launch whatever n is: the blocks stride over the tiles, four blocks of four waves to a CU
+    const dim3 grid((uint32_t) std::min<uint64_t>(ntiles, 1024));
+    if (T.bits <= FIND_LDS_BITS)
+        k_fa_find<true><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
+                                                                    p->dFindPats.p, p->dFindBytes.p, K, p->dFindHits.p, hitCap, p->dFindCursor.p);
+    else
+        k_fa_find<false><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
+                                                                     p->dFindPats.p, p->dFindBytes.p, K, p->dFindHits.p, hitCap, p->dFindCursor.p);
+    FCHK(hipGetLastError());
+    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    unsigned long long count = 0;
+    FCHK(hipMemcpyAsync(&count, p->dFindCursor.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    *nHits = count;
+    if (count > hitCap) return fail(-104, "find: %llu hits, the buffer holds %llu", count, (unsigned long long) hitCap);
+    if (count == 0) return 0;
+    std::vector<mbgc_fasta_hit_t> out(count);                        // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(out.data(), p->dFindHits.p, count * sizeof(mbgc_fasta_hit_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    std::sort(out.begin(), out.end(), [](const mbgc_fasta_hit_t &a, const mbgc_fasta_hit_t &b) {
+        if (a.rec != b.rec) return a.rec < b.rec;
+        if (a.pos != b.pos) return a.pos < b.pos;
+        return a.pattern < b.pattern;
+    });
+    memcpy(hits_host, out.data(), count * sizeof(mbgc_fasta_hit_t));
     return 0;
 }
 

@@ -8,7 +8,7 @@ from . import binding
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
-           mbgc_fasta_crc_dev mbgc_fasta_crc_combine""".split()
+           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -34,6 +34,24 @@ class PackPiece(C.Structure):
 
 class CrcRec(C.Structure):
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+FIND_TILE = 4096                     # MBGC_FASTA_FIND_TILE: text positions per tile of find_dev
+FIND_MAX_MISMATCHES, FIND_MAX_PATTERN = 3, 65535
+
+
+class Hit(C.Structure):
+    _fields_ = [("pos", C.c_uint64), ("rec", C.c_uint32), ("pattern", C.c_uint32), ("mismatches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+HIT_DTYPE = np.dtype([("pos", "<u8"), ("rec", "<u4"), ("pattern", "<u4"), ("mismatches", "<u4"), ("reserved", "<u4")])
+
+
+class HitsTooMany(binding.SwsemError):
+    """find_dev: the hits do not fit the buffer; .needed = their exact count"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
 
 
 class PackTooSmall(binding.SwsemError):
@@ -140,6 +158,8 @@ def _lib():
         L.mbgc_fasta_match_headers_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p,
                                                    C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L.mbgc_fasta_crc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        L.mbgc_fasta_find_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64,
+                                          C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
@@ -361,6 +381,33 @@ class FastaParser:
                                      C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out[:n], ms.value
+
+    def find_dev(self, seq_ptr, seq_bytes, ranges, patterns, max_mismatches=0, hit_cap=None):
+        """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes; patterns: bytes objects,
+        ASCII letters only. Where does a pattern stand in a record with at most max_mismatches substitutions, letters compared
+        without case -> (structured array of HIT_DTYPE: pos, rec, pattern, mismatches — every hit once, sorted by (rec, pos, pattern);
+        the kernel's ms). hit_cap=None: the call is made again with the capacity it asks for when the hits do not fit; a given
+        hit_cap: HitsTooMany (.needed = the exact count) when they do not. A refused call (a pattern that is too short for
+        max_mismatches, too long or holds a non-letter, max_mismatches > 3, a record outside the buffer) raises and launches nothing."""
+        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        pats = [bytes(x) for x in patterns]
+        blob = np.frombuffer(b"".join(pats) + b"\0", dtype=np.uint8)      # (one byte more: an empty list still has an address)
+        pat_off = np.concatenate([[0], np.cumsum([len(x) for x in pats], dtype=np.uint64)]).astype(np.uint64)
+        cap = 4096 if hit_cap is None else int(hit_cap)
+        n, ms = C.c_uint64(0), C.c_double(0)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            r = _lib().mbgc_fasta_find_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0],
+                                           blob.ctypes.data_as(C.c_void_p), pat_off.ctypes.data_as(C.POINTER(C.c_uint64)), len(pats), int(max_mismatches),
+                                           out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
+            if r == -104 and hit_cap is None:
+                cap = int(n.value)
+                continue
+            if r == -104:
+                raise HitsTooMany(_lib().mbgc_fasta_last_error().decode(), int(n.value))
+            if r:
+                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+            return out[: n.value].copy(), ms.value
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

@@ -11,6 +11,7 @@
 #include <fstream>
 #include <future>
 #include <set>
+#include <thread>
 #include <tuple>
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -197,6 +198,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_region.h"     // d --region: the specs, the pieces, their outputs
 #include "mbgc_decoder_validate.h"   // v: Validation
 #include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
+#include "mbgc_decoder_find.h"       // f: query sequences searched in the chosen contigs
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -358,7 +360,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     mbgc_checksums::Manifest manifest;
     if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
     // (--check names a differing contig by its file and header: the whole layout)
-    const bool wantLayout = wantFasta || opt.check;
+    const bool wantLayout = wantFasta || opt.check || opt.find;      // (`f` names a hit by its file and record)
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
     if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
@@ -387,6 +389,14 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         ValidateResult vres;
         CheckResult chk;
         if (opt.check && last && !checkChecksums(prefix, D, S, layout, chosen, manifest, opt.device, chk, msg)) return failed();
+        // `f`: the search is the sink — its lines, its summary, and 3 when nothing was found
+        if (opt.find) {
+            if (!last) continue;
+            FindResult found;
+            if (!findQueries(D, S, layout, chosen, opt, opt.bench, found, msg) ||
+                !reportFind(opt, layout, found, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
+            return found.lines.empty() ? 3 : 0;
+        }
         if (wantFasta) {
             const FastaPlan plan = sel.selectingRegion ? planFasta(pieces.rows, S.meta, pieces.layout, pieces.len, opt.batchText, opt.gzip, true)
                                                        : planFasta(chosen, S.meta, layout, D.contigLen, opt.batchText, opt.gzip, sel.selectingSeq);
@@ -617,6 +627,98 @@ int mbgc_hip_test_main(int argc, char **argv) {
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
     if (r == 1) { fprintf(stderr, "mbgc-hip t: %s\n", error.c_str()); return EXIT_FAILURE; }
     return r;
+}
+
+const char *const MBGC_HIP_F_USAGE =
+    "mbgc-hip f [--seq ACGT...]... [--seq-file queries.fa] [--mismatches K] [--forward-only] [--hits file] [--regions-out file [--flank N]]\n"
+    "                  [--hit-capacity N] [--find-host] [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file]\n"
+    "                  [--select-seq pattern]... [--select-seq-list file] [-d device] [--bench] <streamsPrefix>\n"
+    "  finds query sequences in the collection without unpacking it: the chosen contigs are decoded as mbgc-hip d decodes them (--serial,\n"
+    "  --no-index, --restore-rc, --select, --select-list, --select-seq, --select-seq-list: as there; contigs decoded only as dependencies are\n"
+    "  not searched) and scanned where they lie, on the device; no sequence file is written. --seq: a query, named q1, q2, ... in command-line\n"
+    "  order; --seq-file: a FASTA file of queries, each named by the first word of its header. Letters only, compared without case; with\n"
+    "  --mismatches K (0..3, substitutions only) a query holds 8 (K + 1) to 65535 bases. The reverse complement of every query is searched\n"
+    "  too (--forward-only: not); a query that is its own reverse complement is reported once, as +\n"
+    "  One line per hit on stdout (--hits file: there): query, file (its line of <streamsPrefix>.names), record (the first word of its header),\n"
+    "  start, end (1-based, inclusive, forward-strand coordinates also for a - hit), strand, mismatches, tab-separated; sorted by file, record,\n"
+    "  start, query, + before -. Then `hits: <n> in <records> records of <files> files; <bases> bases searched, <patterns> patterns` (the\n"
+    "  records and files that hold a hit). Exit status 0: at least one hit; 3: none; 1: malformed streams or a refused option\n"
+    "  --regions-out file [--flank N]: a line RECORD:FROM-TO per hit, FROM = max(1, start - N), TO = end + N, identical lines once; mbgc-hip d\n"
+    "  --region-list file then fetches those pieces (d clamps TO). d matches RECORD as a SUBSTRING of the header line: a record whose first\n"
+    "  word is part of another record's header brings that one's piece along\n"
+    "  --hit-capacity N: the first size of the hit buffer (a knob of the tests; the search is made again with the size it needs). --find-host:\n"
+    "  a developer switch, the chosen contigs are downloaded and searched by a plain loop on the host, timed, and the two results must agree\n"
+    "  --bench: two decodes, the second one timed, the search run six times (the median of the last five); one JSON line (find_kernel_ms,\n"
+    "  bases_searched, patterns, hits, retries, decode_ms, find_gb_per_s; --find-host: find_host_ms). Not with --region or --check\n";
+
+// --seq-file: the records of a FASTA file as queries — the header's first word, the sequence lines joined
+static bool readQueryFile(const char *path, std::vector<MBGC_Decoder::FindQuery> &out) {
+    std::ifstream f(path);
+    if (!f) return false;
+    for (std::string line; std::getline(f, line);) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (!line.empty() && line[0] == '>') { const std::string h = line.substr(1); out.push_back({h.substr(0, h.find_first_of(" \t")), std::string()}); }
+        else if (!line.empty() && !out.empty()) out.back().seq += line;
+        else if (!line.empty()) out.push_back({"?", line});             // (bases in front of the first header: refused below, by this name)
+    }
+    return true;
+}
+
+// `mbgc-hip f`: the decode of `t` — nothing is written —, then the search in place of the check
+int mbgc_hip_find_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.find = opt.writeNothing = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    int inlineQueries = 0;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (const int r = mbgc_hip_decode_option('f', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "--seq" && i + 1 < argc) opt.findQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]});
+        else if (a == "--seq-file" && i + 1 < argc) {
+            if (!readQueryFile(argv[++i], opt.findQueries)) { fprintf(stderr, "mbgc-hip f: cannot open the query file %s\n", argv[i]); return EXIT_FAILURE; }
+        }
+        else if (a == "--mismatches" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            if (v.size() != 1 || v[0] < '0' || v[0] > '3') { fprintf(stderr, "mbgc-hip f: --mismatches takes 0, 1, 2 or 3\n"); return EXIT_FAILURE; }
+            opt.findMismatches = (uint32_t) (v[0] - '0');
+        }
+        else if (a == "--forward-only") opt.findForwardOnly = true;
+        else if (a == "--hits" && i + 1 < argc) opt.findHitsFile = argv[++i];
+        else if (a == "--regions-out" && i + 1 < argc) opt.findRegionsOut = argv[++i];
+        else if (a == "--flank" && i + 1 < argc) opt.findFlank = strtoull(argv[++i], nullptr, 10);
+        else if (a == "--hit-capacity" && i + 1 < argc) {
+            opt.findHitCapacity = strtoull(argv[++i], nullptr, 10);
+            if (!opt.findHitCapacity) { fprintf(stderr, "mbgc-hip f: --hit-capacity takes a positive number of hits\n"); return EXIT_FAILURE; }
+        }
+        else if (a == "--find-host") opt.findHost = true;
+        else if (a == "--check") { fprintf(stderr, "mbgc-hip f: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
+        else pos.push_back(a);
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip f: --region / --region-list select parts of records, and a search looks at whole records (an option of mbgc-hip d; f --regions-out writes such a list)\n");
+        return EXIT_FAILURE;
+    }
+    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0 || opt.findQueries.empty()) { fprintf(stderr, "usage: %s", MBGC_HIP_F_USAGE); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('f', opt, selectAsked)) return EXIT_FAILURE;
+    // the queries, held to the search's limits before anything is decoded
+    const uint64_t shortest = 8ull * (opt.findMismatches + 1);
+    for (MBGC_Decoder::FindQuery &q : opt.findQueries) {
+        for (char &c : q.seq) {
+            if (!((c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'))) { fprintf(stderr, "mbgc-hip f: query %s holds a byte that is no letter\n", q.name.c_str()); return EXIT_FAILURE; }
+            c &= (char) 0xDF;
+        }
+        if (q.seq.size() < shortest) {
+            fprintf(stderr, "mbgc-hip f: query %s has %zu bases: --mismatches %u needs at least %llu\n", q.name.c_str(), q.seq.size(), opt.findMismatches, (unsigned long long) shortest);
+            return EXIT_FAILURE;
+        }
+        if (q.seq.size() > 65535) { fprintf(stderr, "mbgc-hip f: query %s has %zu bases (at most 65535)\n", q.name.c_str(), q.seq.size()); return EXIT_FAILURE; }
+    }
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r == 1) { fprintf(stderr, "mbgc-hip f: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return r;                                                                                   // (0: a hit, 3: none)
 }
 
 // `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device

@@ -15,6 +15,7 @@
 //                             and `v`), FastaStage (device buffers, formatBatch), writeFastaFiles (--gzip: deflateBatch)
 //   mbgc_decoder_region.h     `d --region`: the specs held to the headers and the records' lengths, the pieces as outputs
 //   mbgc_decoder_validate.h   `v`: Validation (read-ahead, originals to the device, compare, verdicts, --dump)
+//   mbgc_decoder_find.h       `f`: the queries and their reverse complements searched in the chosen contigs, the hits named and sorted
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
@@ -94,6 +95,7 @@ public:
     struct RegionSpec { std::string pattern; uint64_t from = 0, to = 0; };
     // the spec is split at its last ':'; false: *why says what is wrong with it
     static bool parseRegionSpec(const std::string &text, RegionSpec &out, std::string *why);
+    struct FindQuery { std::string name, seq; };
     struct Options {
         // regions: --region / --region-list, parts of records to bring back (mbgc_decoder_region.h); regionAsked: one of the two
         // options stood on the command line; regionGranule: --region-granule, bytes per granule of the closure (a power of two; a
@@ -112,6 +114,13 @@ public:
         // `d --check` / `mbgc-hip t`: the chosen contigs' CRC-32s, taken on the device, are held against <prefix>.checksums before
         // anything is written (2 = a contig or a side file differs); writeNothing: `t`, no sequence files
         bool check = false, writeNothing = false;
+        // `mbgc-hip f` (mbgc_decoder_find.h): the queries (name; bases, upper case, letters only, held to the limits by the command line) are
+        // searched in the chosen contigs on the device with at most findMismatches substitutions, their reverse complements too unless
+        // findForwardOnly. findHitsFile: --hits (empty: stdout); findRegionsOut / findFlank: --regions-out, --flank; findHitCapacity:
+        // --hit-capacity, the first size of the hit buffer (0: sized from the bases searched); findHost: --find-host, a developer switch —
+        // the search is made again by the host, timed, and held against the device's. decode() then returns 0 (a hit) or 3 (none)
+        bool find = false, findForwardOnly = false, findHost = false; uint32_t findMismatches = 0; uint64_t findHitCapacity = 0, findFlank = 0;
+        std::vector<FindQuery> findQueries; std::string findHitsFile, findRegionsOut;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -136,8 +145,9 @@ public:
 int mbgc_hip_decompress_main(int argc, char **argv);
 int mbgc_hip_validate_main(int argc, char **argv);
 int mbgc_hip_test_main(int argc, char **argv);
+int mbgc_hip_find_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
-extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE;
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.

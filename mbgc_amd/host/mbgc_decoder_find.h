@@ -1,0 +1,172 @@
+// Part of mbgc_decoder.cpp (included there once, behind mbgc_decoder_check.h): `mbgc-hip f` — query sequences searched in the decoded
+// collection where it lies. The CHOSEN contigs are the records of one mbgc_fasta_find_dev call over the decoder's
+// sequence buffer (contigs that were decoded only because a chosen one depends on them are not searched, as in `d --check`); the
+// patterns are the queries and, unless --forward-only, their reverse complements — made on the device by the loader's own kernel
+// (swsem_revcomp_dev: the reference's complement table), so a base is complemented here exactly as the decoder complements one. A
+// few rows come back; the host names them (query, file, record, 1-based forward-strand coordinates, strand) and sorts them.
+#pragma once
+
+namespace {
+struct FindLine { uint64_t contig, start, end; uint32_t query; char strand; uint32_t mismatches; size_t unit; };
+struct FindResult {
+    std::vector<FindLine> lines;
+    uint64_t records = 0, files = 0, bases = 0, patterns = 0, retries = 0;
+    double kernelMs = 0, hostMs = 0;
+};
+
+// the first word of contig k's header: what `d --region` is given to find the record again
+std::string recordName(const FastaLayout &layout, uint64_t k) {
+    const std::string h(layout.headers, layout.hdrOff[k], layout.hdrLen[k]);
+    return h.substr(0, h.find_first_of(" \t"));
+}
+
+// --find-host: the obvious loop over the downloaded contigs — every pattern at every position, the mismatches counted byte by byte —,
+// the patterns shared among a few threads; rows as the device reports them, in its order
+struct HostHit { uint64_t pos; uint32_t rec, pattern, mismatches; };
+std::vector<HostHit> findOnHost(const std::vector<std::string> &text, const std::vector<std::string> &patterns, uint32_t K) {
+    const auto fold = [](uint8_t b) { return (uint8_t) (((b >= 'a' && b <= 'z') || (b >= 'A' && b <= 'Z')) ? b & 0xDF : b); };
+    const size_t threads = std::max<size_t>(1, std::min<size_t>({(size_t) 16, (size_t) std::thread::hardware_concurrency(), patterns.size()}));
+    std::vector<std::future<std::vector<HostHit>>> parts;
+    for (size_t w = 0; w < threads; w++)
+        parts.push_back(std::async(std::launch::async, [&, w] {
+            std::vector<HostHit> out;
+            for (size_t q = w; q < patterns.size(); q += threads)
+                for (size_t r = 0; r < text.size(); r++)
+                    for (uint64_t p = 0; p + patterns[q].size() <= text[r].size(); p++) {
+                        uint32_t d = 0;
+                        for (size_t j = 0; j < patterns[q].size() && d <= K; j++) d += fold((uint8_t) text[r][p + j]) != fold((uint8_t) patterns[q][j]);
+                        if (d <= K) out.push_back({p, (uint32_t) r, (uint32_t) q, d});
+                    }
+            return out;
+        }));
+    std::vector<HostHit> all;
+    for (auto &f : parts) { const std::vector<HostHit> part = f.get(); all.insert(all.end(), part.begin(), part.end()); }
+    std::sort(all.begin(), all.end(), [](const HostHit &a, const HostHit &b) { return std::tie(a.rec, a.pos, a.pattern) < std::tie(b.rec, b.pos, b.pattern); });
+    return all;
+}
+
+bool findQueries(const DecodedCollection &D, const StreamSet &S, const FastaLayout &layout, const std::vector<ChosenUnit> &chosen, const MBGC_Decoder::Options &opt,
+                 bool timed, FindResult &R, std::string &msg) {
+    R = FindResult();
+    const std::vector<MBGC_Decoder::FindQuery> &Q = opt.findQueries;
+    // ---- the patterns: every query, then (unless --forward-only) every reverse complement that is not its own query
+    struct Pattern { uint32_t query; char strand; };
+    std::vector<Pattern> what;
+    std::vector<std::string> patterns;
+    for (size_t q = 0; q < Q.size(); q++) { what.push_back({(uint32_t) q, '+'}); patterns.push_back(Q[q].seq); }
+    if (!opt.findForwardOnly) {
+        // rc(q0 q1 .. qn) = rc(qn) .. rc(q1) rc(q0): one launch over the queries back to back
+        std::string all;
+        std::vector<uint64_t> at(1, 0);
+        for (const MBGC_Decoder::FindQuery &q : Q) { all += q.seq; at.push_back(all.size()); }
+        void *src = nullptr, *dst = nullptr;
+        std::string rc(all.size(), '\0');
+        const bool ok = !swsem_dev_malloc(D.h, all.size() + 64, &src) && !swsem_dev_malloc(D.h, all.size() + 64, &dst) && !swsem_dev_upload(D.h, src, all.data(), all.size()) &&
+                        !swsem_revcomp_dev(D.h, (const uint8_t *) src, all.size(), (uint8_t *) dst) && !swsem_synchronize(D.h) && !swsem_dev_download(D.h, &rc[0], dst, all.size());
+        if (!ok) hipFail(msg, "the queries' reverse complements");
+        if (src) swsem_dev_free(D.h, src);
+        if (dst) swsem_dev_free(D.h, dst);
+        if (!ok) return false;
+        for (size_t q = 0; q < Q.size(); q++) {
+            const std::string r = rc.substr(all.size() - at[q + 1], Q[q].seq.size());
+            if (r == Q[q].seq) continue;                             // its own reverse complement: searched and reported once, as +
+            what.push_back({(uint32_t) q, '-'}); patterns.push_back(r);
+        }
+    }
+    R.patterns = patterns.size();
+    std::string blob;
+    std::vector<uint64_t> patOff(1, 0);
+    for (const std::string &p : patterns) { blob += p; patOff.push_back(blob.size()); }
+    // ---- the records: the chosen contigs, in collection order
+    std::vector<mbgc_fasta_crc_rec_t> recs;
+    struct Where { uint64_t contig; size_t unit; };
+    std::vector<Where> where;
+    for (const ChosenUnit &x : chosen)
+        for (uint64_t k = x.c0; k < x.c1; k++) {
+            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[k], D.contigLen[k]});
+            where.push_back({k, S.meta.singleFastaFile ? 0 : x.unit});
+            R.bases += D.contigLen[k];
+        }
+    // ---- the search; the buffer is sized from the bases searched (--hit-capacity: the first size), and the call is made again with
+    // the count it states when the hits do not fit
+    std::vector<mbgc_fasta_hit_t> hits;
+    uint64_t nHits = 0;
+    mbgc_fasta_t *fa = nullptr;
+    if (mbgc_fasta_create(&fa, opt.device)) return faFail(msg, "input stage");
+    uint64_t cap = opt.findHitCapacity ? opt.findHitCapacity : 4096 + R.bases / 256;
+    int rc = 0;
+    std::vector<double> runs;
+    for (int rep = 0; rep < (timed ? 6 : 1) && !rc; rep++)          // (--bench: one run to warm up, the median of five)
+        for (;;) {
+            hits.assign(cap, mbgc_fasta_hit_t());
+            double ms = 0;
+            rc = mbgc_fasta_find_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), (const uint8_t *) blob.data(), patOff.data(), patterns.size(), opt.findMismatches,
+                                     hits.data(), cap, &nHits, &ms);
+            if (rc == -104 && nHits > cap) { cap = nHits; R.retries++; continue; }
+            if (rep) runs.push_back(ms); else R.kernelMs = ms;
+            break;
+        }
+    if (rc) faFail(msg, "find");
+    mbgc_fasta_destroy(fa);
+    if (rc) return false;
+    if (!runs.empty()) { std::sort(runs.begin(), runs.end()); R.kernelMs = runs[runs.size() / 2]; }
+    hits.resize(nHits);
+    // ---- --find-host: the same question put to the host, over the downloaded contigs; the two tables must be equal
+    if (opt.findHost) {
+        std::vector<std::string> text(recs.size());
+        for (size_t r = 0; r < recs.size(); r++) {
+            text[r].resize(recs[r].len);
+            if (recs[r].len && swsem_dev_download(D.h, &text[r][0], D.seqDev + recs[r].off, recs[r].len)) return hipFail(msg, "download");
+        }
+        const double t0 = nowMs();
+        const std::vector<HostHit> host = findOnHost(text, patterns, opt.findMismatches);
+        R.hostMs = nowMs() - t0;
+        bool same = host.size() == hits.size();
+        for (size_t i = 0; same && i < host.size(); i++)
+            same = host[i].pos == hits[i].pos && host[i].rec == hits[i].rec && host[i].pattern == hits[i].pattern && host[i].mismatches == hits[i].mismatches;
+        if (!same) { msg = "internal error: --find-host: the host's loop finds " + std::to_string(host.size()) + " hits, the device " + std::to_string(hits.size()) + ", or other ones"; return false; }
+    }
+    // ---- the lines: by file, record, start, query, + before -
+    std::set<uint64_t> hitContigs;
+    std::set<size_t> hitUnits;
+    for (const mbgc_fasta_hit_t &h : hits) {
+        const Where &w = where[h.rec];
+        R.lines.push_back({w.contig, h.pos + 1, h.pos + patterns[h.pattern].size(), what[h.pattern].query, what[h.pattern].strand, h.mismatches, w.unit});
+        hitContigs.insert(w.contig); hitUnits.insert(w.unit);
+    }
+    std::sort(R.lines.begin(), R.lines.end(), [](const FindLine &a, const FindLine &b) {
+        return std::make_tuple(a.contig, a.start, a.query, a.strand == '-') < std::make_tuple(b.contig, b.start, b.query, b.strand == '-');
+    });
+    R.records = hitContigs.size(); R.files = hitUnits.size();
+    return true;
+}
+
+// the TSV (stdout, or --hits file), --regions-out, the summary and the JSON line of --bench
+bool reportFind(const MBGC_Decoder::Options &opt, const FastaLayout &layout, const FindResult &R, double decodeMs, std::string &msg) {
+    FILE *out = stdout;
+    if (!opt.findHitsFile.empty() && !(out = fopen(opt.findHitsFile.c_str(), "w"))) { msg = "cannot write " + opt.findHitsFile; return false; }
+    for (const FindLine &l : R.lines)
+        fprintf(out, "%s\t%s\t%s\t%llu\t%llu\t%c\t%u\n", opt.findQueries[l.query].name.c_str(), layout.names[l.unit].c_str(), recordName(layout, l.contig).c_str(),
+                (unsigned long long) l.start, (unsigned long long) l.end, l.strand, l.mismatches);
+    if (out != stdout && fclose(out) != 0) { msg = "cannot write " + opt.findHitsFile; return false; }
+    if (!opt.findRegionsOut.empty()) {
+        std::string text;
+        std::set<std::string> seen;
+        for (const FindLine &l : R.lines) {
+            const std::string line = recordName(layout, l.contig) + ":" + std::to_string(l.start > opt.findFlank ? l.start - opt.findFlank : 1) + "-" + std::to_string(l.end + opt.findFlank) + "\n";
+            if (seen.insert(line).second) text += line;
+        }
+        if (!writeFile(opt.findRegionsOut, text.data(), text.size())) { msg = "cannot write " + opt.findRegionsOut; return false; }
+    }
+    printf("hits: %zu in %llu records of %llu files; %llu bases searched, %llu patterns\n", R.lines.size(), (unsigned long long) R.records, (unsigned long long) R.files,
+           (unsigned long long) R.bases, (unsigned long long) R.patterns);
+    if (opt.bench) {
+        char hostJson[64] = "";
+        if (opt.findHost) snprintf(hostJson, sizeof hostJson, ", \"find_host_ms\": %.3f", R.hostMs);
+        printf("{\"find_kernel_ms\": %.3f, \"bases_searched\": %llu, \"patterns\": %llu, \"hits\": %zu, \"retries\": %llu, \"decode_ms\": %.3f, \"find_gb_per_s\": %.3f%s}\n",
+               R.kernelMs, (unsigned long long) R.bases, (unsigned long long) R.patterns, R.lines.size(), (unsigned long long) R.retries, decodeMs,
+               R.kernelMs > 0 ? R.bases / (R.kernelMs * 1e-3) / 1e9 : 0.0, hostJson);
+    }
+    return true;
+}
+}  // namespace
