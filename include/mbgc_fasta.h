@@ -248,6 +248,39 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
                         const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
                         mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs);
 
+/* The scan of `mbgc-hip s`: what do byte ranges of a device buffer hold, and where are their runs of N and of lower case. Record r is
+ * seq_dev[recs[r].off, recs[r].off + recs[r].len), as in mbgc_fasta_find_dev: the records may overlap, touch, repeat, be empty and
+ * stand at any offset. A record that does not lie inside [0, seqBytes) is refused before anything is launched (-103, message in
+ * mbgc_fasta_last_error; counts_host, runs_host, *nRuns and *kernelMs are left as they were).
+ * flags & MBGC_FASTA_STATS_COUNTS: counts_host[r] is filled (not touched otherwise): a, c, g, t, n counted without case, U / u as t
+ * (the probe of `c` takes acgtuACGTUN for nucleotides in the same way); other = every other byte; lower = the bytes in 'a'..'z'
+ * whatever the letter, so it is orthogonal to the first six; a + c + g + t + n + other == recs[r].len; reserved = 0.
+ * Runs: class 0 is N / n (asked for with MBGC_FASTA_STATS_NRUNS), class 1 any byte in 'a'..'z' (MBGC_FASTA_STATS_LOWER), so n is in
+ * both. A run is a MAXIMAL stretch of one class inside one record: a byte outside the record never lengthens, shortens, starts or
+ * ends one, whatever its class, also where the record ends with the buffer. A run (start = its first position in the record, len,
+ * rec, cls) is returned when len >= minRunN (class 0) / minRunLower (class 1); a minimum of 0 is read as 1. *nRuns is always the
+ * exact number of rows that qualify. When it exceeds runCap the call returns -104 and has written nothing to runs_host (the counts
+ * are filled all the same): call again with that capacity. Otherwise runs_host[0, *nRuns) holds the rows sorted by (rec, cls,
+ * start), each once. -105: internal, the edges do not pair.
+ * One pass of k_fa_stats over the tiles of mbgc_fasta_find_dev's kind (MBGC_FASTA_FIND_TILE positions on the 16-byte grid of the
+ * buffer's addresses, one list over all records; every record with a byte has tiles). A lane reads its 16 positions as one aligned
+ * vector — nothing is staged in LDS — and no byte outside seq_dev[0, seqBytes) is read. The counts are summed over the wave by
+ * shuffles, over the block in LDS, and added to the record's row with at most seven 64-bit atomic adds per tile. A run is found by
+ * its two edges (a position in the class whose neighbour inside the record is not) and never walked; the edges go to a device buffer
+ * of the call's own through one atomic cursor, which counts the ones past its end too: the call then grows the buffer and runs the
+ * kernel again. The host pairs the i-th start of a (record, class) with its i-th end and applies the minimum lengths.
+ * kernelMs (may be NULL): the last run of the kernel, from events on the stream. Runs on the input stage's stream; synchronous.
+ * mbgc_fasta_stats_last: the edges the last call's kernel reported and how often the kernel was run again for a larger buffer. */
+#define MBGC_FASTA_STATS_COUNTS 1u   /* fill counts            */
+#define MBGC_FASTA_STATS_NRUNS  2u   /* report runs of class 0 */
+#define MBGC_FASTA_STATS_LOWER  4u   /* report runs of class 1 */
+typedef struct { uint64_t a, c, g, t, n, other, lower, reserved; } mbgc_fasta_counts_t;
+typedef struct { uint64_t start, len; uint32_t rec, cls; } mbgc_fasta_run_t;
+int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t flags,
+                         uint64_t minRunN, uint64_t minRunLower, mbgc_fasta_counts_t *counts_host, mbgc_fasta_run_t *runs_host, uint64_t runCap,
+                         uint64_t *nRuns, double *kernelMs);
+void mbgc_fasta_stats_last(const mbgc_fasta_t *p, uint64_t *edges, uint64_t *reruns);
+
 /* gzip files that lie compressed in HBM, inflated there(mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

@@ -721,6 +721,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_pack.h"
 #include "fasta_select.h"
 #include "fasta_find.h"
+#include "fasta_stats.h"
 #include "fasta_crc.h"
 
 #define INF_CONST static __device__
@@ -862,6 +863,51 @@ __global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restr
         });
         __syncthreads();                                                     // (the next tile's stores wait for this tile's reads)
     }
+}
+
+// mbgc_fasta_stats_dev: a block takes tile after tile of the flat list over all records, as k_fa_find does (the lane steps: fasta_stats.h).
+// Nothing is staged in LDS: every byte is looked at by one lane, which has it in its own vector, and the one bit a lane needs from each
+// neighbour comes by a shuffle (the first and last lane of a wave: one guarded byte load). Counts: the lanes' two packed words are
+// summed over the wave by shuffles and over the block through 64 bytes of LDS; lanes 0..6 keep one counter each in a register while
+// the block's tiles stay in one record and add it to the record's row when the record changes — at most seven atomic adds per tile.
+// Edges: a lane takes as many rows as it has edges through the one cursor; rows at or past the capacity are counted and not written.
+__global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+                                                            uint32_t nrec, uint64_t ntiles, uint32_t counting, uint32_t want, unsigned long long *__restrict__ counts,
+                                                            StatsEdge *__restrict__ edges, uint64_t edgeCap, unsigned long long *__restrict__ cursor) {
+    __shared__ uint64_t sums[2][STATS_THREADS / WAVE][2];
+    const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1), wave = lane / WAVE;
+    uint64_t mine = 0;                                                       // lanes 0..6: counter `lane` of record `held`, not yet added to its row
+    uint32_t held = 0, parity = 0;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, parity ^= 1) {     // (uniform over the block)
+        const uint32_t r = find_tile_record(tileStart, nrec, tile);
+        const FindRec rec = recs[r];
+        const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * STATS_TILE;
+        const StatsLane L = stats_lane_step(seq, seqBytes, rec, tileAddr, lane);
+        const int64_t t0 = (int64_t) (tileAddr + 16u * lane) - (int64_t) ((uintptr_t) seq + rec.off);
+        if (want) {
+            uint32_t prevLast = stats_last_of(__shfl_up(L.masks, 1)), nextFirst = stats_first_of(__shfl_down(L.masks, 1));
+            if (wl == 0) prevLast = stats_class_at(seq, rec, t0 - 1);
+            if (wl == WAVE - 1) nextFirst = stats_class_at(seq, rec, t0 + STATS_PER);
+            const StatsEdges E = stats_edges(L.masks, prevLast, nextFirst, want);
+            const uint32_t cnt = stats_edge_count(E);
+            if (cnt) stats_edges_write(E, t0, r, atomicAdd(cursor, (unsigned long long) cnt), edgeCap, edges);
+        }
+        if (counting) {
+            uint64_t a = L.sumA, b = L.sumB;
+#pragma unroll
+            for (int d = WAVE / 2; d; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
+            if (wl == 0) { sums[parity][wave][0] = a; sums[parity][wave][1] = b; }
+            __syncthreads();                                                 // (the other buffer is the next tile's: one barrier per tile)
+            if (lane < 7) {
+                if (r != held) { if (mine) atomicAdd(counts + 8ull * held + lane, (unsigned long long) mine); mine = 0; held = r; }
+                a = b = 0;
+#pragma unroll
+                for (uint32_t w = 0; w < STATS_THREADS / WAVE; w++) { a += sums[parity][w][0]; b += sums[parity][w][1]; }
+                mine += stats_counter(a, b, lane);
+            }
+        }
+    }
+    if (counting && lane < 7 && mine) atomicAdd(counts + 8ull * held + lane, (unsigned long long) mine);
 }
 
 // mbgc_fasta_crc_dev: a wave per 64 / G rows of one class (the lane step, the classes and the tables: fasta_crc.h). The lanes of a group
@@ -1038,6 +1084,11 @@ struct mbgc_fasta {
     fa::Buf<uint8_t> dFindBytes;
     fa::Buf<mbgc_fasta_hit_t> dFindHits;
     fa::Buf<unsigned long long> dFindCursor;
+    fa::Buf<unsigned long long> dStatsCounts;   // mbgc_fasta_stats_dev (records and tiles: dFindRecs, dFindTiles): the records' rows, the edges and their cursor
+    fa::Buf<fa::StatsEdge> dStatsEdges;
+    fa::Buf<unsigned long long> dStatsCursor;
+    uint64_t statsEdgeCap = 0;                  // rows of dStatsEdges the kernel may write: STATS_EDGES_FIRST, then the largest count seen
+    uint64_t statsEdges = 0, statsReruns = 0;   // the last call's: mbgc_fasta_stats_last
     fa::Buf<fa::CrcRow> dCrcRows;               // mbgc_fasta_crc_dev: the rows, the bytes behind the cut ranges' pieces, the ranges' words, the constants
     fa::Buf<uint64_t> dCrcBehind;
     fa::Buf<uint32_t> dCrcOut;
@@ -1090,6 +1141,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dSelRecs.release(); p->dSelSlots.release(); p->dSelPats.release(); p->dSelBytes.release(); p->dSelChosen.release();
     p->dFindRecs.release(); p->dFindTiles.release(); p->dFindSlots.release(); p->dFindSeeds.release(); p->dFindPats.release(); p->dFindBytes.release();
     p->dFindHits.release(); p->dFindCursor.release();
+    p->dStatsCounts.release(); p->dStatsEdges.release(); p->dStatsCursor.release();
     p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
@@ -1545,6 +1597,92 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
     });
     memcpy(hits_host, out.data(), count * sizeof(mbgc_fasta_hit_t));
     return 0;
+}
+
+int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t flags,
+                         uint64_t minRunN, uint64_t minRunLower, mbgc_fasta_counts_t *counts_host, mbgc_fasta_run_t *runs_host, uint64_t runCap,
+                         uint64_t *nRuns, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(mbgc_fasta_counts_t) == 8 * sizeof(uint64_t) && sizeof(StatsEdge) == 16, "a record's row is eight words; an edge is sixteen bytes");
+    if (n >= 0xffffffffull) return fail(-103, "stats: %llu records in one call", (unsigned long long) n);
+    for (uint64_t r = 0; r < n; r++)
+        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "stats: record %llu lies outside the buffer", (unsigned long long) r);
+    if (kernelMs) *kernelMs = 0;
+    p->statsEdges = p->statsReruns = 0;
+    const bool counting = (flags & MBGC_FASTA_STATS_COUNTS) != 0;
+    const uint32_t want = (flags & MBGC_FASTA_STATS_NRUNS ? STATS_CLS_N : 0u) | (flags & MBGC_FASTA_STATS_LOWER ? STATS_CLS_LOWER : 0u);
+    std::vector<uint64_t> tileStart(n + 1, 0);
+    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + stats_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len);
+    const uint64_t ntiles = tileStart[n];
+    if (ntiles == 0 || (!counting && !want)) {                       // (no byte to look at, or nothing asked)
+        if (counting && n) memset(counts_host, 0, n * sizeof(mbgc_fasta_counts_t));
+        *nRuns = 0;
+        return 0;
+    }
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dStatsCounts.reserve(8 * n)) || (rc = p->dStatsCursor.reserve(1)) ||
+        (rc = p->dStatsEdges.reserve(std::max<uint64_t>(STATS_EDGES_FIRST, p->statsEdgeCap)))) return rc;
+    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    // the edge buffer is this call's own: when the cursor passed it, it grows to the cursor's count and the kernel runs again
+    uint64_t edgeCap = std::max<uint64_t>(STATS_EDGES_FIRST, p->statsEdgeCap);
+    unsigned long long count = 0;
+    for (;;) {
+        if (counting) FCHK(hipMemsetAsync(p->dStatsCounts.p, 0, 8 * n * sizeof(unsigned long long), p->stream));
+        FCHK(hipMemsetAsync(p->dStatsCursor.p, 0, sizeof(unsigned long long), p->stream));
+        if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+        // one launch whatever n is: the blocks stride over the tiles, eight blocks of four waves to a CU (a wave has one load in flight)
+        k_fa_stats<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(STATS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles,
+                                                                                                              counting, want, p->dStatsCounts.p, p->dStatsEdges.p, edgeCap, p->dStatsCursor.p);
+        FCHK(hipGetLastError());
+        if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+        FCHK(hipMemcpyAsync(&count, p->dStatsCursor.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+        if (count <= edgeCap) break;
+        if ((rc = p->dStatsEdges.reserve(count))) return rc;
+        edgeCap = p->statsEdgeCap = count;
+        p->statsReruns++;
+    }
+    p->statsEdges = count;
+    // the edges of a (record, class) sorted by position: its starts, then its ends — the i-th start pairs with the i-th end
+    std::vector<StatsEdge> e(count);
+    if (count) FCHK(hipMemcpyAsync(e.data(), p->dStatsEdges.p, count * sizeof(StatsEdge), hipMemcpyDeviceToHost, p->stream));
+    std::vector<mbgc_fasta_counts_t> rows(counting ? n : 0);         // (the caller's arrays stay as they are unless the call gets this far)
+    if (counting) FCHK(hipMemcpyAsync(rows.data(), p->dStatsCounts.p, n * sizeof(mbgc_fasta_counts_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    std::sort(e.begin(), e.end(), [](const StatsEdge &a, const StatsEdge &b) {
+        if (a.rec != b.rec) return a.rec < b.rec;
+        if ((a.kind & 1) != (b.kind & 1)) return (a.kind & 1) < (b.kind & 1);
+        if (a.kind != b.kind) return a.kind < b.kind;
+        return a.pos < b.pos;
+    });
+    std::vector<mbgc_fasta_run_t> out;
+    const uint64_t least[2] = {std::max<uint64_t>(minRunN, 1), std::max<uint64_t>(minRunLower, 1)};
+    for (size_t at = 0; at < e.size();) {
+        size_t ends = at, next;
+        while (ends < e.size() && e[ends].rec == e[at].rec && e[ends].kind == e[at].kind) ends++;
+        for (next = ends; next < e.size() && e[next].rec == e[at].rec && e[next].kind == (e[at].kind | 2u); next++) {}
+        if ((e[at].kind & 2u) || next - ends != ends - at) return fail(-105, "stats: internal: edges do not pair (record %u, class %u)", e[at].rec, e[at].kind & 1u);
+        for (size_t i = 0; i < ends - at; i++) {
+            if (e[ends + i].pos < e[at + i].pos) return fail(-105, "stats: internal: edges do not pair (record %u, class %u)", e[at].rec, e[at].kind & 1u);
+            const uint64_t len = e[ends + i].pos - e[at + i].pos + 1;
+            if (len >= least[e[at].kind & 1u]) out.push_back(mbgc_fasta_run_t{e[at + i].pos, len, e[at].rec, e[at].kind & 1u});
+        }
+        at = next;
+    }
+    if (counting) memcpy(counts_host, rows.data(), n * sizeof(mbgc_fasta_counts_t));
+    *nRuns = out.size();
+    if (out.size() > runCap) return fail(-104, "stats: %zu runs, the buffer holds %llu", out.size(), (unsigned long long) runCap);
+    if (!out.empty()) memcpy(runs_host, out.data(), out.size() * sizeof(mbgc_fasta_run_t));
+    return 0;
+}
+
+void mbgc_fasta_stats_last(const mbgc_fasta_t *p, uint64_t *edges, uint64_t *reruns) {
+    if (edges) *edges = p->statsEdges;
+    if (reruns) *reruns = p->statsReruns;
 }
 
 int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t *crc_out_host,

@@ -8,7 +8,7 @@ from . import binding
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
-           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev""".split()
+           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_stats_dev mbgc_fasta_stats_last""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -49,6 +49,18 @@ HIT_DTYPE = np.dtype([("pos", "<u8"), ("rec", "<u4"), ("pattern", "<u4"), ("mism
 
 class HitsTooMany(binding.SwsemError):
     """find_dev: the hits do not fit the buffer; .needed = their exact count"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
+STATS_COUNTS, STATS_NRUNS, STATS_LOWER = 1, 2, 4     # MBGC_FASTA_STATS_*
+COUNTS_COLUMNS = ("a", "c", "g", "t", "n", "other", "lower", "reserved")     # mbgc_fasta_counts_t
+RUN_DTYPE = np.dtype([("start", "<u8"), ("len", "<u8"), ("rec", "<u4"), ("cls", "<u4")])     # mbgc_fasta_run_t
+
+
+class RunsTooMany(binding.SwsemError):
+    """stats_dev: the runs do not fit the buffer; .needed = their exact count"""
     def __init__(self, msg, needed):
         super().__init__(msg)
         self.needed = needed
@@ -160,6 +172,10 @@ def _lib():
         L.mbgc_fasta_crc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L.mbgc_fasta_find_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_stats_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mbgc_fasta_stats_last.restype = None
         L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
@@ -408,6 +424,36 @@ class FastaParser:
             if r:
                 raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
             return out[: n.value].copy(), ms.value
+
+    def stats_dev(self, seq_ptr, seq_bytes, ranges, flags=STATS_COUNTS | STATS_NRUNS | STATS_LOWER, min_run_n=1, min_run_lower=1, run_cap=None):
+        """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes -> (counts: an (n, 8)
+        uint64 array, columns COUNTS_COLUMNS — zeros without STATS_COUNTS; runs: a structured array of RUN_DTYPE (start, len, rec,
+        cls: 0 = N / n with STATS_NRUNS, 1 = 'a'..'z' with STATS_LOWER), the maximal runs inside a record of at least min_run_n /
+        min_run_lower bytes (0 is read as 1), sorted by (rec, cls, start); the kernel's ms). run_cap=None: the call is made once more
+        with the count it states when the runs do not fit; a given run_cap: RunsTooMany (.needed = the exact count) when they do
+        not. A record outside the buffer raises and launches nothing. last_stats(): the edges and the kernel's reruns of this call."""
+        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        counts = np.zeros((max(rows.shape[0], 1), 8), dtype=np.uint64)
+        cap = 4096 if run_cap is None else int(run_cap)
+        n, ms = C.c_uint64(0), C.c_double(0)
+        for attempt in range(2):
+            out = np.zeros(max(cap, 1), dtype=RUN_DTYPE)
+            r = _lib().mbgc_fasta_stats_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0], int(flags), int(min_run_n),
+                                            int(min_run_lower), counts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
+            if r == -104 and run_cap is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            if r == -104:
+                raise RunsTooMany(_lib().mbgc_fasta_last_error().decode(), int(n.value))
+            if r:
+                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+            return counts[: rows.shape[0]].copy(), out[: n.value].copy(), ms.value
+
+    def last_stats(self):
+        """(edges, reruns) of the last stats_dev call: the edges its kernel reported, and how often it ran again for a larger buffer"""
+        e, k = C.c_uint64(0), C.c_uint64(0)
+        _lib().mbgc_fasta_stats_last(self.h, C.byref(e), C.byref(k))
+        return int(e.value), int(k.value)
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

@@ -199,6 +199,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_validate.h"   // v: Validation
 #include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
 #include "mbgc_decoder_find.h"       // f: query sequences searched in the chosen contigs
+#include "mbgc_decoder_stats.h"      // s: composition, N50 and the runs of N / lower case of the chosen contigs
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -360,7 +361,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     mbgc_checksums::Manifest manifest;
     if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
     // (--check names a differing contig by its file and header: the whole layout)
-    const bool wantLayout = wantFasta || opt.check || opt.find;      // (`f` names a hit by its file and record)
+    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats;      // (`f` and `s` name a record by its file and header)
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
     if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
@@ -396,6 +397,14 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             if (!findQueries(D, S, layout, chosen, opt, opt.bench, found, msg) ||
                 !reportFind(opt, layout, found, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
             return found.lines.empty() ? 3 : 0;
+        }
+        // `s`: the statistics are the sink
+        if (opt.stats) {
+            if (!last) continue;
+            StatsResult stats;
+            if (!collectStats(D, S, chosen, opt, opt.bench, stats, msg) ||
+                !reportStats(opt, layout, stats, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
+            return 0;
         }
         if (wantFasta) {
             const FastaPlan plan = sel.selectingRegion ? planFasta(pieces.rows, S.meta, pieces.layout, pieces.len, opt.batchText, opt.gzip, true)
@@ -719,6 +728,66 @@ int mbgc_hip_find_main(int argc, char **argv) {
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
     if (r == 1) { fprintf(stderr, "mbgc-hip f: %s\n", error.c_str()); return EXIT_FAILURE; }
     return r;                                                                                   // (0: a hit, 3: none)
+}
+
+const char *const MBGC_HIP_S_USAGE =
+    "mbgc-hip s [--records file] [--gaps-out file [--min-gap N]] [--masked-out file [--min-masked N]] [--stats-host] [--serial] [--no-index]\n"
+    "                  [--restore-rc] [--select pattern]... [--select-list file] [--select-seq pattern]... [--select-seq-list file] [-d device] [--bench]\n"
+    "                  <streamsPrefix>\n"
+    "  describes the collection without unpacking it: the chosen contigs are decoded as mbgc-hip d decodes them (--serial, --no-index,\n"
+    "  --restore-rc, --select, --select-list, --select-seq, --select-seq-list: as there; contigs decoded only as dependencies are not counted)\n"
+    "  and scanned where they lie, on the device; no sequence file is written. One tab-separated line per file on stdout, in collection order:\n"
+    "  file, records, bases, min, max, N50, L50, A, C, G, T, N, other, lower, GC. A, C, G, T (with U) and N are counted without case, other is\n"
+    "  every other byte, lower the bytes in a..z whatever the letter; GC = (G + C) / (A + C + G + T), 0.000000 without one of them; N50 / L50\n"
+    "  over the file's chosen records, longest first: L50 = the fewest records that hold half the file's bases, N50 = the length of the last of\n"
+    "  them. Then `stats: <files> files, <records> records, <bases> bases; GC <gc>, N <n> in <runs> runs, lower-case <n>, other <n>`. A protein\n"
+    "  collection is counted by the same rule: most of its letters are `other`. Exit status 0; 1: malformed streams, a refused option or a\n"
+    "  file that cannot be written\n"
+    "  --records file (-: stdout, in front of the files' lines): the same columns per record, `file, record` (the first word of its header) in\n"
+    "  place of `file, records`, without min, max, N50 and L50\n"
+    "  --gaps-out file [--min-gap N]: the runs of N / n of at least N bytes (default 1) as BED lines — record, start (0-based), end (half-open) —\n"
+    "  in collection order, then by start; --masked-out file [--min-masked N]: the runs of lower case in the same way. A run never reaches\n"
+    "  over a record's end\n"
+    "  --stats-host: a developer switch, the chosen contigs are downloaded and counted by a plain loop on the host, and the two results must\n"
+    "  agree. --bench: two decodes, the second one timed, the scan run six times (the median of the last five); one JSON line\n"
+    "  (stats_kernel_ms, bases, records, edges, edge_reruns, decode_ms, stats_gb_per_s). Not with --region, --check or --fasta\n";
+
+// `mbgc-hip s`: the decode of `t` — nothing is written —, then the statistics in place of the check
+int mbgc_hip_stats_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.stats = opt.writeNothing = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    const auto number = [&](const char *name, int &i, uint64_t &v) {
+        const std::string text = argv[++i];
+        if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip s: %s takes a number of bytes\n", name); return false; }
+        v = strtoull(text.c_str(), nullptr, 10);
+        return true;
+    };
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (const int r = mbgc_hip_decode_option('s', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "--records" && i + 1 < argc) opt.statsRecordsFile = argv[++i];
+        else if (a == "--gaps-out" && i + 1 < argc) opt.statsGapsOut = argv[++i];
+        else if (a == "--masked-out" && i + 1 < argc) opt.statsMaskedOut = argv[++i];
+        else if (a == "--min-gap" && i + 1 < argc) { if (!number("--min-gap", i, opt.statsMinGap)) return EXIT_FAILURE; }
+        else if (a == "--min-masked" && i + 1 < argc) { if (!number("--min-masked", i, opt.statsMinMasked)) return EXIT_FAILURE; }
+        else if (a == "--stats-host") opt.statsHost = true;
+        else if (a == "--check") { fprintf(stderr, "mbgc-hip s: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
+        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip s: --fasta is an option of mbgc-hip d: s writes no sequence, it describes the set where it lies\n"); return EXIT_FAILURE; }
+        else pos.push_back(a);
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip s: --region / --region-list select parts of records, and the statistics are taken over whole records (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
+    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_S_USAGE); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('s', opt, selectAsked)) return EXIT_FAILURE;
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r) { fprintf(stderr, "mbgc-hip s: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return 0;
 }
 
 // `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device

@@ -16,6 +16,7 @@
 //   mbgc_decoder_region.h     `d --region`: the specs held to the headers and the records' lengths, the pieces as outputs
 //   mbgc_decoder_validate.h   `v`: Validation (read-ahead, originals to the device, compare, verdicts, --dump)
 //   mbgc_decoder_find.h       `f`: the queries and their reverse complements searched in the chosen contigs, the hits named and sorted
+//   mbgc_decoder_stats.h      `s`: the chosen contigs' counters and runs of N / lower case taken on the device, summed per file, N50 / L50
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
@@ -121,6 +122,12 @@ public:
         // the search is made again by the host, timed, and held against the device's. decode() then returns 0 (a hit) or 3 (none)
         bool find = false, findForwardOnly = false, findHost = false; uint32_t findMismatches = 0; uint64_t findHitCapacity = 0, findFlank = 0;
         std::vector<FindQuery> findQueries; std::string findHitsFile, findRegionsOut;
+        // `mbgc-hip s` (mbgc_decoder_stats.h): the chosen contigs are counted on the device and nothing else happens to them.
+        // statsRecordsFile: --records ("-": stdout); statsGapsOut / statsMinGap: --gaps-out, --min-gap; statsMaskedOut / statsMinMasked:
+        // --masked-out, --min-masked (a minimum of 0 is read as 1); statsHost: --stats-host, a developer switch — everything is
+        // computed again by the host and held against the device's
+        bool stats = false, statsHost = false; uint64_t statsMinGap = 1, statsMinMasked = 1;
+        std::string statsRecordsFile, statsGapsOut, statsMaskedOut;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -146,8 +153,9 @@ int mbgc_hip_decompress_main(int argc, char **argv);
 int mbgc_hip_validate_main(int argc, char **argv);
 int mbgc_hip_test_main(int argc, char **argv);
 int mbgc_hip_find_main(int argc, char **argv);
+int mbgc_hip_stats_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
-extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE;
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.
