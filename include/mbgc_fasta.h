@@ -281,6 +281,42 @@ int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBy
                          uint64_t *nRuns, double *kernelMs);
 void mbgc_fasta_stats_last(const mbgc_fasta_t *p, uint64_t *edges, uint64_t *reruns);
 
+/* The two scans of `mbgc-hip k`: FracMinHash sketches of groups of records of a device buffer, and the sizes of the sketches'
+ * intersections. Everything returned is an integer.
+ * The hash: k is 1..32 (anything else: -103). A/a = 0, C/c = 1, G/g = 2, T/t/U/u = 3, every other byte is invalid. A k-mer is the k bytes
+ * at positions i .. i + k - 1 of ONE record, 0 <= i <= len - k; one that holds an invalid byte is skipped. fw = sum of code[i + j] <<
+ * 2 (k - 1 - j), rc = sum of (3 - code[i + j]) << 2 j, h = fmix64(min(fw, rc) ^ 0x9E3779B97F4A7C15), fmix64 being MurmurHash3's 64-bit
+ * finaliser. This is NOT the hash of Mash or of sourmash: the sketches cannot be exchanged with theirs. h is kept when h <= maxHash
+ * (maxHash = (2^64 - 1) / scale; ~0: every hash).
+ * mbgc_fasta_sketch_dev: record r is seq_dev[recs[r].off, recs[r].off + recs[r].len), as in mbgc_fasta_stats_dev — the records may
+ * overlap, touch, repeat, be empty or shorter than k —, and belongs to group group_host[r] < ngroups (any values, in any order; a
+ * record outside the buffer or a group >= ngroups: -103, nothing launched). kmers_host[g] = the valid k-mer positions of group g's
+ * records (a record listed twice counts twice). The sketch of group g = the strictly ascending list of the DISTINCT kept hashes of all
+ * its records = hashes_host[groupStart_host[g], groupStart_host[g + 1]); groupStart_host has ngroups + 1 entries. *total is always the
+ * exact number of hashes over all groups, = groupStart_host[ngroups]. When it exceeds cap the call returns -104: nothing in
+ * hashes_host is promised, groupStart_host and kmers_host are filled — call again with that capacity.
+ * One pass of k_fa_sketch over the tiles of mbgc_fasta_find_dev's kind (MBGC_FASTA_FIND_TILE k-mer starts on the 16-byte grid of the
+ * buffer's addresses). A lane packs its aligned 16-byte vector into a 32-bit code word and a 16-bit invalid mask and takes those of the
+ * two vectors behind it from its neighbours; no byte outside seq_dev[0, seqBytes) is read and none outside the record reaches a
+ * result. The kept (hash, group) rows go to a device buffer of the call's own through one atomic cursor, taken once per wave and tile,
+ * which counts the rows past the buffer's end too: the call then grows the buffer and runs the kernel again. The rows are sorted to
+ * (group, hash) order by two stable radix sorts, the first of each (group, hash) is kept, and the groups' starts are read off the
+ * kept rows — all on the device. kernelMs (may be NULL): the last run of k_fa_sketch. Runs on the input stage's stream; synchronous.
+ * mbgc_fasta_sketch_last: the rows the last call's kernel reported and how often it was run again for a larger buffer;
+ * mbgc_fasta_sketch_sort_ms: the last call's sorts, flagging and compaction, from events on the stream.
+ * mbgc_fasta_sketch_pairs_dev: shared_host[q] = the number of hashes the sketches of groups pairs_host[2 q] and pairs_host[2 q + 1]
+ * have in common (any ids < ngroups, repeats and (i, i) too); pairs_host == NULL: all i < j in row-major order, npairs must be ngroups
+ * (ngroups - 1) / 2. The sketches (small) are uploaded; a list that does not ascend strictly, an id >= ngroups or a wrong npairs is
+ * refused on the host (-103). k_fa_sketch_pairs: a wave per pair, the lanes stride over the shorter list and look each hash up in the
+ * longer one by bisection; a pair with an empty side answers 0 without a search. */
+int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, const uint32_t *group_host,
+                          uint32_t ngroups, uint32_t k, uint64_t maxHash, uint64_t *hashes_host, uint64_t cap, uint64_t *groupStart_host, uint64_t *kmers_host,
+                          uint64_t *total, double *kernelMs);
+void mbgc_fasta_sketch_last(const mbgc_fasta_t *p, uint64_t *rows, uint64_t *reruns);
+double mbgc_fasta_sketch_sort_ms(const mbgc_fasta_t *p);
+int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, const uint64_t *groupStart_host, uint32_t ngroups, const uint32_t *pairs_host,
+                                uint64_t npairs, uint32_t *shared_host, double *kernelMs);
+
 /* gzip files that lie compressed in HBM, inflated there(mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

@@ -17,6 +17,8 @@
 // decided inside the chunk (the one behind the chunk's leading run of newlines): the summary names what it depends on,
 // the scan counts it, the emit pass keeps or drops it by the same two flags.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstdarg>
@@ -722,6 +724,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_select.h"
 #include "fasta_find.h"
 #include "fasta_stats.h"
+#include "fasta_sketch.h"
 #include "fasta_crc.h"
 
 #define INF_CONST static __device__
@@ -910,6 +913,96 @@ __global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__res
     if (counting && lane < 7 && mine) atomicAdd(counts + 8ull * held + lane, (unsigned long long) mine);
 }
 
+// mbgc_fasta_sketch_dev: a block takes tile after tile of the flat list over all records, as k_fa_stats does (the lane steps:
+// fasta_sketch.h). A lane packs its own aligned vector into a code word and an invalid mask and takes the same of the two vectors
+// behind it by shuffles; the last two lanes of a wave pack what lies behind the wave themselves (guarded: a vector outside the record is
+// not read). Rows: a lane keeps the hashes <= maxHash among its 16, the wave sums the lanes' counts by a scan of shuffles and takes its
+// rows from the one cursor with ONE atomic add per wave and tile, none when the ballot says no lane keeps one; rows at or past the
+// capacity are counted and not written. kmers: the valid positions summed over the wave, held in a register while the block's tiles
+// stay in one group, one atomic add per wave when the group changes.
+__global__ void __launch_bounds__(SKETCH_THREADS) k_fa_sketch(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint32_t *__restrict__ groups,
+                                                              const uint64_t *__restrict__ tileStart, uint32_t nrec, uint64_t ntiles, uint32_t k, uint64_t maxHash,
+                                                              unsigned long long *__restrict__ kmers, uint64_t *__restrict__ rowHash, uint32_t *__restrict__ rowGroup, uint64_t rowCap,
+                                                              unsigned long long *__restrict__ cursor) {
+    const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1);
+    uint64_t mine = 0;                                                       // the wave's valid positions of group `held`, not yet added (the same in every lane)
+    uint32_t held = 0;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
+        const uint32_t r = find_tile_record(tileStart, nrec, tile);
+        const FindRec rec = recs[r];
+        const uint32_t g = groups[r];
+        const uintptr_t v = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * SKETCH_TILE + 16u * lane;
+        const uint64_t own = sketch_pack(seq, seqBytes, rec, v);
+        uint64_t next1 = __shfl_down(own, 1), next2 = __shfl_down(own, 2);
+        if (wl == WAVE - 1) next1 = sketch_pack(seq, seqBytes, rec, v + 16);
+        if (wl >= WAVE - 2) next2 = sketch_pack(seq, seqBytes, rec, v + 32);
+        uint64_t h[SKETCH_PER];
+        const uint32_t valid = sketch_lane_hashes(own, next1, next2, k, h);
+        uint32_t keep = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SKETCH_PER; j++) if (((valid >> j) & 1u) && h[j] <= maxHash) keep |= 1u << j;
+        uint32_t nv = (uint32_t) __builtin_popcount(valid);
+#pragma unroll
+        for (int d = WAVE / 2; d; d >>= 1) nv += __shfl_xor(nv, d);
+        if (g != held) { if (wl == 0 && mine) atomicAdd(kmers + held, (unsigned long long) mine); mine = 0; held = g; }
+        mine += nv;
+        const uint32_t cnt = (uint32_t) __builtin_popcount(keep);
+        if (__ballot(cnt != 0) == 0) continue;                               // (uniform over the wave)
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) { const uint32_t up = __shfl_up(incl, d); if (wl >= (uint32_t) d) incl += up; }
+        unsigned long long base = 0;
+        if (wl == WAVE - 1) base = atomicAdd(cursor, (unsigned long long) incl);
+        uint64_t at = __shfl(base, WAVE - 1) + incl - cnt;
+#pragma unroll
+        for (uint32_t j = 0; j < SKETCH_PER; j++)
+            if ((keep >> j) & 1u) {
+                if (at < rowCap) { rowHash[at] = h[j]; rowGroup[at] = g; }
+                at++;
+            }
+    }
+    if (wl == 0 && mine) atomicAdd(kmers + held, (unsigned long long) mine);
+}
+
+// the rows sorted by (group, hash): flag[i] = row i is the first of its (group, hash)
+__global__ void __launch_bounds__(256) k_fa_sketch_flag(const uint64_t *__restrict__ hash, const uint32_t *__restrict__ group, uint64_t n, uint32_t *__restrict__ flag) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
+        flag[i] = i == 0 || group[i] != group[i - 1] || hash[i] != hash[i - 1];
+}
+
+// pos = the exclusive sum of the flags: a flagged row goes to out[pos]; the first row of a group leaves its place in groupStart (the
+// groups without a row keep the host's filling); the last row leaves the number of distinct rows
+__global__ void __launch_bounds__(256) k_fa_sketch_compact(const uint64_t *__restrict__ hash, const uint32_t *__restrict__ group, const uint32_t *__restrict__ flag,
+                                                           const uint32_t *__restrict__ pos, uint64_t n, uint64_t *__restrict__ out, unsigned long long *__restrict__ groupStart,
+                                                           unsigned long long *__restrict__ total) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
+        if (flag[i]) {
+            out[pos[i]] = hash[i];
+            if (i == 0 || group[i] != group[i - 1]) groupStart[group[i]] = pos[i];
+        }
+        if (i == n - 1) *total = (unsigned long long) pos[i] + flag[i];
+    }
+}
+
+// mbgc_fasta_sketch_pairs_dev: a wave per pair. The lanes stride over the shorter of the two strictly ascending lists, each lane looks
+// its hash up in the longer one by bisection; the finds are counted by ballot and popcount — no atomics, the count is the wave's own.
+__global__ void __launch_bounds__(256) k_fa_sketch_pairs(const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ start, uint32_t ngroups, const uint32_t *__restrict__ pairs,
+                                                         uint64_t npairs, uint32_t *__restrict__ shared) {
+    const uint32_t wl = threadIdx.x & (WAVE - 1), waves = blockDim.x / WAVE;
+    for (uint64_t q = (uint64_t) blockIdx.x * waves + threadIdx.x / WAVE; q < npairs; q += (uint64_t) gridDim.x * waves) {      // (uniform over the wave)
+        uint32_t i, j;
+        if (pairs) { i = pairs[2 * q]; j = pairs[2 * q + 1]; } else sketch_pair_of(q, ngroups, i, j);
+        uint64_t a0 = start[i], na = start[i + 1] - a0, b0 = start[j], nb = start[j + 1] - b0;
+        if (na > nb) { const uint64_t t0 = a0, tn = na; a0 = b0; na = nb; b0 = t0; nb = tn; }
+        uint32_t cnt = 0;
+        for (uint64_t at = 0; at < na; at += WAVE) {                         // (na == 0: an empty side, nothing is searched)
+            const bool found = at + wl < na && sketch_holds(hashes + b0, nb, hashes[a0 + at + wl]);
+            cnt += (uint32_t) __popcll(__ballot(found));
+        }
+        if (wl == 0) shared[q] = cnt;
+    }
+}
+
 // mbgc_fasta_crc_dev: a wave per 64 / G rows of one class (the lane step, the classes and the tables: fasta_crc.h). The lanes of a group
 // fold their values by shuffles; a row that is a whole range stores its word, a piece of a cut range moves its value over the bytes
 // behind it (the lanes' factors multiplied by shuffles) and XORs it into the range's word.
@@ -1089,6 +1182,17 @@ struct mbgc_fasta {
     fa::Buf<unsigned long long> dStatsCursor;
     uint64_t statsEdgeCap = 0;                  // rows of dStatsEdges the kernel may write: STATS_EDGES_FIRST, then the largest count seen
     uint64_t statsEdges = 0, statsReruns = 0;   // the last call's: mbgc_fasta_stats_last
+    fa::Buf<uint32_t> dSkGroups;                // mbgc_fasta_sketch_dev (records and tiles: dFindRecs, dFindTiles): the records' groups, the groups' k-mers and starts,
+    fa::Buf<unsigned long long> dSkKmers, dSkStart, dSkWords;     // the cursor and the distinct total (dSkWords), the rows twice over (the sort's two sides),
+    fa::Buf<uint64_t> dSkHash, dSkHash2;        // the flags, their sums and the sort's scratch
+    fa::Buf<uint32_t> dSkGroup, dSkGroup2, dSkFlag, dSkPos;
+    fa::Buf<uint8_t> dSkTmp;
+    uint64_t sketchRowCap = 0;                  // rows the kernel may write: SKETCH_ROWS_FIRST, then the largest count seen
+    uint64_t sketchRows = 0, sketchReruns = 0;  // the last call's: mbgc_fasta_sketch_last
+    double sketchSortMs = 0;
+    hipEvent_t skEv[4] = {nullptr, nullptr, nullptr, nullptr};    // around the scan, around the sort and the compaction
+    fa::Buf<uint64_t> dPairHashes, dPairStart;  // mbgc_fasta_sketch_pairs_dev: the sketches, their starts, the pair list, the answers
+    fa::Buf<uint32_t> dPairList, dPairShared;
     fa::Buf<fa::CrcRow> dCrcRows;               // mbgc_fasta_crc_dev: the rows, the bytes behind the cut ranges' pieces, the ranges' words, the constants
     fa::Buf<uint64_t> dCrcBehind;
     fa::Buf<uint32_t> dCrcOut;
@@ -1142,11 +1246,15 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dFindRecs.release(); p->dFindTiles.release(); p->dFindSlots.release(); p->dFindSeeds.release(); p->dFindPats.release(); p->dFindBytes.release();
     p->dFindHits.release(); p->dFindCursor.release();
     p->dStatsCounts.release(); p->dStatsEdges.release(); p->dStatsCursor.release();
+    p->dSkGroups.release(); p->dSkKmers.release(); p->dSkStart.release(); p->dSkWords.release(); p->dSkHash.release(); p->dSkHash2.release();
+    p->dSkGroup.release(); p->dSkGroup2.release(); p->dSkFlag.release(); p->dSkPos.release(); p->dSkTmp.release();
+    p->dPairHashes.release(); p->dPairStart.release(); p->dPairList.release(); p->dPairShared.release();
     p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
     p->dInfJobs.release(); p->dInfResults.release();
     p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
     for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : p->skEv) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
     delete p;
 }
@@ -1683,6 +1791,144 @@ int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBy
 void mbgc_fasta_stats_last(const mbgc_fasta_t *p, uint64_t *edges, uint64_t *reruns) {
     if (edges) *edges = p->statsEdges;
     if (reruns) *reruns = p->statsReruns;
+}
+
+int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, const uint32_t *group_host, uint32_t ngroups,
+                          uint32_t k, uint64_t maxHash, uint64_t *hashes_host, uint64_t cap, uint64_t *groupStart_host, uint64_t *kmers_host, uint64_t *total, double *kernelMs) {
+    using namespace fa;
+    if (k < 1 || k > 32) return fail(-103, "sketch: k = %u (1 to 32)", k);
+    if (n >= 0xffffffffull) return fail(-103, "sketch: %llu records in one call", (unsigned long long) n);
+    for (uint64_t r = 0; r < n; r++) {
+        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "sketch: record %llu lies outside the buffer", (unsigned long long) r);
+        if (group_host[r] >= ngroups) return fail(-103, "sketch: record %llu names group %u of %u", (unsigned long long) r, group_host[r], ngroups);
+    }
+    if (kernelMs) *kernelMs = 0;
+    p->sketchRows = p->sketchReruns = 0;
+    p->sketchSortMs = 0;
+    std::vector<uint64_t> tileStart(n + 1, 0);
+    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + sketch_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len, k);
+    const uint64_t ntiles = tileStart[n];
+    *total = 0;
+    for (uint32_t g = 0; g <= ngroups; g++) groupStart_host[g] = 0;
+    for (uint32_t g = 0; g < ngroups; g++) kmers_host[g] = 0;
+    if (ntiles == 0) return 0;                                       // (no record holds a k-mer)
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dSkGroups.reserve(n)) || (rc = p->dSkKmers.reserve(ngroups)) ||
+        (rc = p->dSkStart.reserve(ngroups)) || (rc = p->dSkWords.reserve(2))) return rc;
+    for (hipEvent_t &e : p->skEv) if (!e) FCHK(hipEventCreate(&e));
+    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dSkGroups.p, group_host, n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    // the row buffer is this call's own: when the cursor passed it, it grows to the cursor's count and the kernel runs again
+    uint64_t rowCap = std::max<uint64_t>(SKETCH_ROWS_FIRST, p->sketchRowCap);
+    unsigned long long count = 0;
+    for (;;) {
+        if ((rc = p->dSkHash.reserve(rowCap)) || (rc = p->dSkGroup.reserve(rowCap))) return rc;
+        FCHK(hipMemsetAsync(p->dSkKmers.p, 0, ngroups * sizeof(unsigned long long), p->stream));
+        FCHK(hipMemsetAsync(p->dSkWords.p, 0, 2 * sizeof(unsigned long long), p->stream));
+        FCHK(hipEventRecord(p->skEv[0], p->stream));
+        // one launch whatever n is: the blocks stride over the tiles, eight blocks of four waves to a CU
+        k_fa_sketch<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(SKETCH_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dSkGroups.p, p->dFindTiles.p, (uint32_t) n,
+                                                                                                                 ntiles, k, maxHash, p->dSkKmers.p, p->dSkHash.p, p->dSkGroup.p, rowCap, p->dSkWords.p);
+        FCHK(hipGetLastError());
+        FCHK(hipEventRecord(p->skEv[1], p->stream));
+        FCHK(hipMemcpyAsync(&count, p->dSkWords.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[0], p->skEv[1])); *kernelMs = ms; }
+        if (count <= rowCap) break;
+        if (count >= 0xffffffffull) return fail(-103, "sketch: %llu rows in one call (a larger scale, or fewer records)", count);
+        rowCap = p->sketchRowCap = count;
+        p->sketchReruns++;
+    }
+    p->sketchRows = count;
+    std::vector<unsigned long long> kmers(ngroups), starts(ngroups, ~0ull);
+    FCHK(hipMemcpyAsync(kmers.data(), p->dSkKmers.p, ngroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+    unsigned long long distinct = 0;
+    if (count) {
+        // a stable sort by hash, then a stable sort by group: (group, hash) order; the first row of every (group, hash) is flagged, the
+        // flags' exclusive sum is the row's place among the distinct ones
+        uint32_t gbits = 1;
+        while (gbits < 32 && ((uint64_t) 1 << gbits) < ngroups) gbits++;
+        if ((rc = p->dSkHash2.reserve(count)) || (rc = p->dSkGroup2.reserve(count)) || (rc = p->dSkFlag.reserve(count)) || (rc = p->dSkPos.reserve(count))) return rc;
+        size_t t1 = 0, t2 = 0, t3 = 0;
+        FCHK(rocprim::radix_sort_pairs(nullptr, t1, p->dSkHash.p, p->dSkHash2.p, p->dSkGroup.p, p->dSkGroup2.p, (size_t) count, 0u, 64u, p->stream));
+        FCHK(rocprim::radix_sort_pairs(nullptr, t2, p->dSkGroup2.p, p->dSkGroup.p, p->dSkHash2.p, p->dSkHash.p, (size_t) count, 0u, gbits, p->stream));
+        FCHK(rocprim::exclusive_scan(nullptr, t3, p->dSkFlag.p, p->dSkPos.p, 0u, (size_t) count, rocprim::plus<uint32_t>(), p->stream));
+        const size_t tb = std::max(t1, std::max(t2, t3));
+        if ((rc = p->dSkTmp.reserve(tb))) return rc;
+        const uint32_t blocks = (uint32_t) std::min<uint64_t>((count + 255) / 256, 4096);
+        FCHK(hipMemsetAsync(p->dSkStart.p, 0xff, ngroups * sizeof(unsigned long long), p->stream));
+        FCHK(hipEventRecord(p->skEv[2], p->stream));
+        FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t1, p->dSkHash.p, p->dSkHash2.p, p->dSkGroup.p, p->dSkGroup2.p, (size_t) count, 0u, 64u, p->stream));
+        FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t2, p->dSkGroup2.p, p->dSkGroup.p, p->dSkHash2.p, p->dSkHash.p, (size_t) count, 0u, gbits, p->stream));
+        k_fa_sketch_flag<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dSkHash.p, p->dSkGroup.p, count, p->dSkFlag.p);
+        FCHK(hipGetLastError());
+        FCHK(rocprim::exclusive_scan(p->dSkTmp.p, t3, p->dSkFlag.p, p->dSkPos.p, 0u, (size_t) count, rocprim::plus<uint32_t>(), p->stream));
+        k_fa_sketch_compact<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dSkHash.p, p->dSkGroup.p, p->dSkFlag.p, p->dSkPos.p, count, p->dSkHash2.p, p->dSkStart.p, p->dSkWords.p + 1);
+        FCHK(hipGetLastError());
+        FCHK(hipEventRecord(p->skEv[3], p->stream));
+        FCHK(hipMemcpyAsync(&distinct, p->dSkWords.p + 1, sizeof distinct, hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipMemcpyAsync(starts.data(), p->dSkStart.p, ngroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+    }
+    FCHK(hipStreamSynchronize(p->stream));
+    if (count) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[2], p->skEv[3])); p->sketchSortMs = ms; }
+    // a group without a row starts where the next one does
+    groupStart_host[ngroups] = distinct;
+    for (uint32_t g = ngroups; g-- > 0;) groupStart_host[g] = starts[g] == ~0ull ? groupStart_host[g + 1] : starts[g];
+    for (uint32_t g = 0; g < ngroups; g++) kmers_host[g] = kmers[g];
+    *total = distinct;
+    if (distinct > cap) return fail(-104, "sketch: %llu hashes, the buffer holds %llu", distinct, (unsigned long long) cap);
+    if (distinct) {
+        FCHK(hipMemcpyAsync(hashes_host, p->dSkHash2.p, distinct * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+    }
+    return 0;
+}
+
+void mbgc_fasta_sketch_last(const mbgc_fasta_t *p, uint64_t *rows, uint64_t *reruns) {
+    if (rows) *rows = p->sketchRows;
+    if (reruns) *reruns = p->sketchReruns;
+}
+
+double mbgc_fasta_sketch_sort_ms(const mbgc_fasta_t *p) { return p->sketchSortMs; }
+
+int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, const uint64_t *groupStart_host, uint32_t ngroups, const uint32_t *pairs_host, uint64_t npairs,
+                                uint32_t *shared_host, double *kernelMs) {
+    using namespace fa;
+    if (groupStart_host[0] != 0) return fail(-103, "pairs: the first group starts at %llu", (unsigned long long) groupStart_host[0]);
+    for (uint32_t g = 0; g < ngroups; g++) {
+        if (groupStart_host[g + 1] < groupStart_host[g]) return fail(-103, "pairs: group %u ends in front of its start", g);
+        for (uint64_t i = groupStart_host[g] + 1; i < groupStart_host[g + 1]; i++)
+            if (hashes_host[i] <= hashes_host[i - 1]) return fail(-103, "pairs: the hashes of group %u do not ascend strictly (at %llu)", g, (unsigned long long) (i - groupStart_host[g]));
+    }
+    const uint64_t nh = groupStart_host[ngroups];
+    if (nh >= 0xffffffffull) return fail(-103, "pairs: %llu hashes in one call", (unsigned long long) nh);
+    if (!pairs_host && npairs != (uint64_t) ngroups * (ngroups ? ngroups - 1 : 0) / 2)
+        return fail(-103, "pairs: %llu pairs asked without a list, %u groups have %llu", (unsigned long long) npairs, ngroups, (unsigned long long) ngroups * (ngroups ? ngroups - 1 : 0) / 2);
+    if (pairs_host)
+        for (uint64_t q = 0; q < 2 * npairs; q++)
+            if (pairs_host[q] >= ngroups) return fail(-103, "pairs: pair %llu names group %u of %u", (unsigned long long) (q / 2), pairs_host[q], ngroups);
+    if (kernelMs) *kernelMs = 0;
+    if (npairs == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = p->dPairHashes.reserve(std::max<uint64_t>(nh, 1))) || (rc = p->dPairStart.reserve(ngroups + 1)) || (rc = p->dPairShared.reserve(npairs)) ||
+        (pairs_host && (rc = p->dPairList.reserve(2 * npairs)))) return rc;
+    for (hipEvent_t &e : p->skEv) if (!e) FCHK(hipEventCreate(&e));
+    if (nh) FCHK(hipMemcpyAsync(p->dPairHashes.p, hashes_host, nh * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dPairStart.p, groupStart_host, (ngroups + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    if (pairs_host) FCHK(hipMemcpyAsync(p->dPairList.p, pairs_host, 2 * npairs * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipEventRecord(p->skEv[0], p->stream));
+    // a wave per pair, four to a block; the waves stride over the pairs
+    k_fa_sketch_pairs<<<dim3((uint32_t) std::min<uint64_t>((npairs + 3) / 4, 8192)), dim3(256), 0, p->stream>>>(p->dPairHashes.p, p->dPairStart.p, ngroups, pairs_host ? p->dPairList.p : nullptr,
+                                                                                                                  npairs, p->dPairShared.p);
+    FCHK(hipGetLastError());
+    FCHK(hipEventRecord(p->skEv[1], p->stream));
+    FCHK(hipMemcpyAsync(shared_host, p->dPairShared.p, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[0], p->skEv[1])); *kernelMs = ms; }
+    return 0;
 }
 
 int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t *crc_out_host,

@@ -8,7 +8,8 @@ from . import binding
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
-           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_stats_dev mbgc_fasta_stats_last""".split()
+           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_stats_dev mbgc_fasta_stats_last
+           mbgc_fasta_sketch_dev mbgc_fasta_sketch_last mbgc_fasta_sketch_sort_ms mbgc_fasta_sketch_pairs_dev""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -61,6 +62,13 @@ RUN_DTYPE = np.dtype([("start", "<u8"), ("len", "<u8"), ("rec", "<u4"), ("cls", 
 
 class RunsTooMany(binding.SwsemError):
     """stats_dev: the runs do not fit the buffer; .needed = their exact count"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
+class SketchTooLarge(binding.SwsemError):
+    """sketch_dev: the hashes do not fit the buffer; .needed = their exact count"""
     def __init__(self, msg, needed):
         super().__init__(msg)
         self.needed = needed
@@ -176,6 +184,13 @@ def _lib():
                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_stats_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mbgc_fasta_stats_last.restype = None
+        L.mbgc_fasta_sketch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p,
+                                            C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_sketch_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mbgc_fasta_sketch_last.restype = None
+        L.mbgc_fasta_sketch_sort_ms.argtypes = [C.c_void_p]
+        L.mbgc_fasta_sketch_sort_ms.restype = C.c_double
+        L.mbgc_fasta_sketch_pairs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_double)]
         L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
@@ -454,6 +469,60 @@ class FastaParser:
         e, k = C.c_uint64(0), C.c_uint64(0)
         _lib().mbgc_fasta_stats_last(self.h, C.byref(e), C.byref(k))
         return int(e.value), int(k.value)
+
+    def sketch_dev(self, seq_ptr, seq_bytes, ranges, groups, ngroups, k=21, max_hash=(2 ** 64 - 1) // 1000, cap=None):
+        """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes; groups = a group id
+        < ngroups per record -> (hashes: a uint64 array, the groups' sketches back to back, each strictly ascending; group_start: ngroups
+        + 1 offsets into it; kmers: the valid k-mer positions per group; the scan kernel's ms). The hash is the header's (fmix64 of the
+        canonical k-mer ^ a seed, kept when <= max_hash), not Mash's. cap=None: the call is made once more with the count it states
+        when the hashes do not fit; a given cap: SketchTooLarge (.needed = the exact count) when they do not. k outside 1..32, a record
+        outside the buffer or a group >= ngroups raises and launches nothing. last_sketch(): the rows, the reruns and the sort's ms."""
+        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        grp = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if grp.size != rows.shape[0]:
+            raise ValueError("sketch_dev: %d records, %d group ids" % (rows.shape[0], grp.size))
+        start, kmers = np.zeros(int(ngroups) + 1, dtype=np.uint64), np.zeros(max(int(ngroups), 1), dtype=np.uint64)
+        size = 4096 if cap is None else int(cap)
+        n, ms = C.c_uint64(0), C.c_double(0)
+        for attempt in range(2):
+            out = np.zeros(max(size, 1), dtype=np.uint64)
+            r = _lib().mbgc_fasta_sketch_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0], grp.ctypes.data_as(C.c_void_p), int(ngroups),
+                                             int(k), int(max_hash), out.ctypes.data_as(C.c_void_p), size, start.ctypes.data_as(C.c_void_p), kmers.ctypes.data_as(C.c_void_p),
+                                             C.byref(n), C.byref(ms))
+            if r == -104 and cap is None and attempt == 0:
+                size = int(n.value)
+                continue
+            if r == -104:
+                raise SketchTooLarge(_lib().mbgc_fasta_last_error().decode(), int(n.value))
+            if r:
+                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+            return out[: n.value].copy(), start, kmers[: int(ngroups)].copy(), ms.value
+
+    def last_sketch(self):
+        """(rows, reruns, sort_ms) of the last sketch_dev call: the (hash, group) rows its kernel reported, how often it ran again for a
+        larger row buffer, and the ms of the sorts and the compaction behind it"""
+        e, k = C.c_uint64(0), C.c_uint64(0)
+        _lib().mbgc_fasta_sketch_last(self.h, C.byref(e), C.byref(k))
+        return int(e.value), int(k.value), float(_lib().mbgc_fasta_sketch_sort_ms(self.h))
+
+    def sketch_pairs_dev(self, hashes, group_start, pairs=None):
+        """hashes, group_start as sketch_dev returns them; pairs = rows of (i, j), or None for all i < j in row-major order -> (shared:
+        a uint32 array, |sketch i & sketch j| per pair; the kernel's ms). A list that does not ascend strictly is refused."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1)
+        start = np.ascontiguousarray(group_start, dtype=np.uint64).reshape(-1)
+        ngroups = start.size - 1
+        if pairs is None:
+            rows, npairs, ptr = None, ngroups * (ngroups - 1) // 2, None
+        else:
+            rows = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+            npairs, ptr = rows.shape[0], rows.ctypes.data_as(C.c_void_p)
+        if start.size < 1 or int(start[-1]) > h.size:
+            raise ValueError("sketch_pairs_dev: group_start reaches past the hashes")
+        shared, ms = np.zeros(max(npairs, 1), dtype=np.uint32), C.c_double(0)
+        r = _lib().mbgc_fasta_sketch_pairs_dev(self.h, h.ctypes.data_as(C.c_void_p), start.ctypes.data_as(C.c_void_p), ngroups, ptr, npairs, shared.ctypes.data_as(C.c_void_p), C.byref(ms))
+        if r:
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return shared[:npairs].copy(), ms.value
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -200,6 +201,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
 #include "mbgc_decoder_find.h"       // f: query sequences searched in the chosen contigs
 #include "mbgc_decoder_stats.h"      // s: composition, N50 and the runs of N / lower case of the chosen contigs
+#include "mbgc_decoder_sketch.h"     // k: k-mer sketches of the chosen files or records and what every two of them share
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -361,7 +363,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     mbgc_checksums::Manifest manifest;
     if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
     // (--check names a differing contig by its file and header: the whole layout)
-    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats;      // (`f` and `s` name a record by its file and header)
+    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats || opt.sketch;      // (`f`, `s` and `k` name a record by its file and header)
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
     if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
@@ -404,6 +406,14 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             StatsResult stats;
             if (!collectStats(D, S, chosen, opt, opt.bench, stats, msg) ||
                 !reportStats(opt, layout, stats, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
+            return 0;
+        }
+        // `k`: the sketches and the pairs are the sink
+        if (opt.sketch) {
+            if (!last) continue;
+            SketchResult sketch;
+            if (!collectSketch(D, S, chosen, layout, opt, opt.bench, sketch, msg) ||
+                !reportSketch(opt, sketch, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
             return 0;
         }
         if (wantFasta) {
@@ -787,6 +797,85 @@ int mbgc_hip_stats_main(int argc, char **argv) {
     std::string error;
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
     if (r) { fprintf(stderr, "mbgc-hip s: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return 0;
+}
+
+const char *const MBGC_HIP_K_USAGE =
+    "mbgc-hip k [-k K] [--scale S] [--by-record] [--pairs-out file] [--min-shared N] [--no-pairs] [--sketches-out file] [--order-out file] [--sketch-host]\n"
+    "                  [--serial] [--no-index] [--restore-rc] [--select pattern]... [--select-list file] [--select-seq pattern]... [--select-seq-list file]\n"
+    "                  [-d device] [--bench] <streamsPrefix>\n"
+    "  which genomes of the collection are close to which, without unpacking it: the chosen contigs are decoded as mbgc-hip d decodes them\n"
+    "  (--serial, --no-index, --restore-rc, --select, --select-list, --select-seq, --select-seq-list: as there; contigs decoded only as\n"
+    "  dependencies are not sketched) and hashed where they lie, on the device. A group is a file, or a record (named by the first word of its\n"
+    "  header) under --by-record. Every k-mer (-k 1..32, default 21) of A/C/G/T/U letters, either case, inside one record is hashed in its\n"
+    "  canonical form, and a hash is kept when it is at most (2^64 - 1) / S (--scale, default 1000; 1 keeps all): a FracMinHash sketch. The\n"
+    "  hash is this project's own (fmix64 of the 2-bit packed k-mer): the sketches cannot be exchanged with Mash's or sourmash's.\n"
+    "  One tab-separated line per group on stdout, in collection order: name, records, bases, kmers (valid k-mer positions), hashes (distinct\n"
+    "  kept), hashes x S (the estimate of the distinct k-mers). Then one line per pair A < B of groups: nameA, nameB, hashesA, hashesB, shared,\n"
+    "  jaccard = shared / (hashesA + hashesB - shared), containmentA = shared / hashesA, containmentB, distance = -ln(2 J / (1 + J)) / K (1\n"
+    "  when J is 0). Then `sketch: <groups> groups, <records> records, <bases> bases; k <K>, scale <S>; <hashes> hashes of <kmers> k-mers,\n"
+    "  <pairs> pairs, <n> share a hash`. Exit status 0; 1: malformed streams, a refused option or a file that cannot be written\n"
+    "  --pairs-out file: the pair lines go there; --min-shared N: only the pairs that share at least N hashes; --no-pairs: no pair is\n"
+    "  computed (more than 2^28 pairs are refused without it)\n"
+    "  --sketches-out file: per group name, K, S, the number of hashes and the hashes as 16 hex digits, comma-separated\n"
+    "  --order-out file: a file list for mbgc-hip c — first the file that shares the most hashes with all others, then the others by what they\n"
+    "  share with it, descending; not with --by-record or --no-pairs\n"
+    "  --sketch-host: a developer switch, the chosen contigs are downloaded, hashed and intersected by plain loops on the host, and the two\n"
+    "  results must agree. --bench: two decodes, the second one timed, the scans run six times (the medians of the last five); one JSON line\n"
+    "  (sketch_kernel_ms, pairs_kernel_ms, sort_ms, bases, rows, row_reruns, hashes, pairs, decode_ms, sketch_gb_per_s). Not with --region,\n"
+    "  --check or --fasta\n";
+
+// `mbgc-hip k`: the decode of `t` — nothing is written —, then the sketches in place of the check
+int mbgc_hip_sketch_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.sketch = opt.writeNothing = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    const auto number = [&](const char *name, int &i, uint64_t &v) {
+        const std::string text = argv[++i];
+        if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip k: %s takes a number\n", name); return false; }
+        v = strtoull(text.c_str(), nullptr, 10);
+        return true;
+    };
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        uint64_t v = 0;
+        if (const int r = mbgc_hip_decode_option('k', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "-k" && i + 1 < argc) {
+            if (!number("-k", i, v)) return EXIT_FAILURE;
+            if (v < 1 || v > 32) { fprintf(stderr, "mbgc-hip k: -k %llu: a k-mer has 1 to 32 bases (2 bits each in one 64-bit word)\n", (unsigned long long) v); return EXIT_FAILURE; }
+            opt.sketchK = (uint32_t) v;
+        }
+        else if (a == "--scale" && i + 1 < argc) {
+            if (!number("--scale", i, v)) return EXIT_FAILURE;
+            if (v < 1) { fprintf(stderr, "mbgc-hip k: --scale 0: a hash is kept when it is at most (2^64 - 1) / scale, 1 keeps every hash\n"); return EXIT_FAILURE; }
+            opt.sketchScale = v;
+        }
+        else if (a == "--min-shared" && i + 1 < argc) { if (!number("--min-shared", i, opt.sketchMinShared)) return EXIT_FAILURE; }
+        else if (a == "--by-record") opt.sketchByRecord = true;
+        else if (a == "--no-pairs") opt.sketchNoPairs = true;
+        else if (a == "--sketch-host") opt.sketchHost = true;
+        else if (a == "--pairs-out" && i + 1 < argc) opt.sketchPairsOut = argv[++i];
+        else if (a == "--sketches-out" && i + 1 < argc) opt.sketchOut = argv[++i];
+        else if (a == "--order-out" && i + 1 < argc) opt.sketchOrderOut = argv[++i];
+        else if (a == "--check") { fprintf(stderr, "mbgc-hip k: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
+        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip k: --fasta is an option of mbgc-hip d: k writes no sequence, it compares the set where it lies\n"); return EXIT_FAILURE; }
+        else pos.push_back(a);
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip k: --region / --region-list select parts of records, and the sketches are taken over whole records (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
+    if (!opt.sketchOrderOut.empty() && (opt.sketchByRecord || opt.sketchNoPairs)) {
+        fprintf(stderr, "mbgc-hip k: --order-out orders files by the hashes they share: not with --by-record or --no-pairs\n");
+        return EXIT_FAILURE;
+    }
+    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_K_USAGE); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('k', opt, selectAsked)) return EXIT_FAILURE;
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r) { fprintf(stderr, "mbgc-hip k: %s\n", error.c_str()); return EXIT_FAILURE; }
     return 0;
 }
 

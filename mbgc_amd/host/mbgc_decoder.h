@@ -17,6 +17,7 @@
 //   mbgc_decoder_validate.h   `v`: Validation (read-ahead, originals to the device, compare, verdicts, --dump)
 //   mbgc_decoder_find.h       `f`: the queries and their reverse complements searched in the chosen contigs, the hits named and sorted
 //   mbgc_decoder_stats.h      `s`: the chosen contigs' counters and runs of N / lower case taken on the device, summed per file, N50 / L50
+//   mbgc_decoder_sketch.h     `k`: FracMinHash sketches of the chosen files or records and the pairs' shared hashes taken on the device, the distances
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
@@ -128,6 +129,12 @@ public:
         // computed again by the host and held against the device's
         bool stats = false, statsHost = false; uint64_t statsMinGap = 1, statsMinMasked = 1;
         std::string statsRecordsFile, statsGapsOut, statsMaskedOut;
+        // `mbgc-hip k` (mbgc_decoder_sketch.h): the chosen contigs are sketched on the device and nothing else happens to them. sketchK: -k
+        // (1..32); sketchScale: --scale (>= 1); sketchByRecord: a group per record, not per file; sketchNoPairs: --no-pairs; sketchMinShared:
+        // --min-shared; sketchPairsOut / sketchOut / sketchOrderOut: --pairs-out, --sketches-out, --order-out; sketchHost: --sketch-host, a
+        // developer switch — everything is computed again by the host and held against the device's
+        bool sketch = false, sketchByRecord = false, sketchNoPairs = false, sketchHost = false; uint32_t sketchK = 21; uint64_t sketchScale = 1000, sketchMinShared = 0;
+        std::string sketchPairsOut, sketchOut, sketchOrderOut;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -154,8 +161,9 @@ int mbgc_hip_validate_main(int argc, char **argv);
 int mbgc_hip_test_main(int argc, char **argv);
 int mbgc_hip_find_main(int argc, char **argv);
 int mbgc_hip_stats_main(int argc, char **argv);
+int mbgc_hip_sketch_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
-extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE;
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE, *const MBGC_HIP_K_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.
