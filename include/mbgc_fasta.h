@@ -317,6 +317,50 @@ double mbgc_fasta_sketch_sort_ms(const mbgc_fasta_t *p);
 int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, const uint64_t *groupStart_host, uint32_t ngroups, const uint32_t *pairs_host,
                                 uint64_t npairs, uint32_t *shared_host, double *kernelMs);
 
+/* The scan of `mbgc-hip u`: which byte ranges of a device buffer are the same sequence, read forward or as the reverse complement.
+ * Records. Record r is seq_dev[recs[r].off, recs[r].off + recs[r].len), exactly as in mbgc_fasta_stats_dev: the ranges may overlap,
+ * touch, repeat, be empty and stand at any byte offset. A range outside the buffer (or a flag that is not defined) is refused with
+ * -103 (message in mbgc_fasta_last_error): nothing is launched, out_host, *nClasses and *kernelMs are left as they were.
+ * fold. fold(b) = b & 0xDF for an ASCII letter, and b otherwise. Under MBGC_FASTA_DUPS_EXACT_CASE, fold(b) = b.
+ * comp. comp is an involution on the 256 byte values: comp[b] = b, except for the six pairs on upper case and the same pairs on lower
+ * case, which keep the case:
+ *     A <-> T   C <-> G   R <-> Y   K <-> M   B <-> V   D <-> H        a <-> t   c <-> g   r <-> y   k <-> m   b <-> v   d <-> h
+ * Every other byte — N, S, W, U, the other letters, non-letters, the bytes >= 0x80 — maps to itself. This is deliberately NOT the
+ * table of swsem_revcomp_dev (the upper reverse complement of the matcher): that one upper-cases, so it is no involution, and "is the
+ * reverse complement of" would not be symmetric under it. The table is kept in one place (dups_comp_upper, mbgc_amd/csrc/fasta_dups.h);
+ * mbgc_fasta_dups_comp_table returns its 256 entries.
+ * The relation. Records a and b are the same sequence when either of these holds:
+ *   - they have equal length and fold(a[i]) == fold(b[i]) for all i;
+ *   - unless MBGC_FASTA_DUPS_FORWARD_ONLY is set, they have equal length and fold(a[i]) == comp(fold(b[len - 1 - i])) for all i.
+ * This is an equivalence relation. All empty records are one class.
+ * Output per record: out_host[r] = { rep, strand }. rep is the lowest index in r's class. strand is 0 when the record equals rep read
+ * forward — a record that equals rep both ways, or is rep itself, also gets 0 — and 1 when it equals only the reverse complement of
+ * rep. *nClasses is the number of classes. Everything is exact: no result rests on a fingerprint alone.
+ * How. One pass of k_fa_dups over the tiles of mbgc_fasta_find_dev's kind (MBGC_FASTA_FIND_TILE positions on the 16-byte grid of the
+ * buffer's addresses, the record of a tile by bisection): a lane reads its aligned 16-byte vector, a position outside the record
+ * contributes nothing whatever memory holds there, and no byte outside seq_dev[0, seqBytes) is read. From that one read of the text a
+ * tile yields the partial sums of two strand fingerprints, forward = sum T[fold(s_j)] x^(len - 1 - j) and reverse complement = sum
+ * T[comp(fold(s_j))] x^j (T[b] = b + 1), each as four residues modulo four primes just below 2^31 (124 bits, every multiply 32 x 32 ->
+ * 64); lanes are summed by shuffles, waves through LDS, and at most eight 64-bit atomic adds of terms below 2^31 go to the record's
+ * row, which the host reduces modulo the primes. The canonical fingerprint is the smaller of (forward, reverse), the forward one
+ * under FORWARD_ONLY. Records with equal (len, canonical fingerprint) form a bucket, made by a sort on the host (n counts records,
+ * not bases). Every non-first member of a bucket is then verified against the bucket's first member by k_fa_dups_verify — the bytes
+ * are compared under fold, or under fold and comp with the second side read backwards; forward first, then reverse, a comparison the
+ * fingerprints already exclude being skipped; one ballot per step, one atomic per refuted pair —, a refuted member opens a new
+ * representative inside its bucket, and the remaining members are verified against the bucket's representatives, round by round,
+ * until every member has a class. MBGC_FASTA_DUPS_WEAK_HASH is a flag for tests: only the low 4 bits of a fingerprint are kept, so
+ * that the exactness step runs on ordinary inputs; the result is identical with and without it.
+ * kernelMs (may be NULL): k_fa_dups, from events on the stream. Runs on the input stage's stream; synchronous; n == 0 launches nothing.
+ * mbgc_fasta_dups_last: the last call's buckets, the pairs k_fa_dups_verify compared, those it refuted, and its launches' time. */
+#define MBGC_FASTA_DUPS_FORWARD_ONLY 1u   /* the reverse complement is not the same sequence */
+#define MBGC_FASTA_DUPS_EXACT_CASE   2u   /* fold(b) = b                                     */
+#define MBGC_FASTA_DUPS_WEAK_HASH    4u   /* tests: 4 bits of fingerprint                    */
+typedef struct { uint32_t rep; uint32_t strand; } mbgc_fasta_dup_t;
+int mbgc_fasta_dups_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t flags,
+                        mbgc_fasta_dup_t *out_host, uint64_t *nClasses, double *kernelMs);
+void mbgc_fasta_dups_last(const mbgc_fasta_t *p, uint64_t *buckets, uint64_t *verified, uint64_t *refuted, double *verifyMs);
+const uint8_t *mbgc_fasta_dups_comp_table(void);
+
 /* gzip files that lie compressed in HBM, inflated there(mgmpInOpen's loop over libdeflate_gzip_decompress_ex, matching/
  * input_with_libdeflate_wrapper.cpp:51-124): job k reads gz_dev[inOff, inOff + inLen) — a whole file: one or more gzip members (RFC
  * 1952: magic, CM = 8, FEXTRA / FNAME / FCOMMENT skipped, FHCRC checked, the eight-byte trailer) holding DEFLATE (RFC 1951, all three

@@ -21,6 +21,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -725,6 +726,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_find.h"
 #include "fasta_stats.h"
 #include "fasta_sketch.h"
+#include "fasta_dups.h"
 #include "fasta_crc.h"
 
 #define INF_CONST static __device__
@@ -911,6 +913,79 @@ __global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__res
         }
     }
     if (counting && lane < 7 && mine) atomicAdd(counts + 8ull * held + lane, (unsigned long long) mine);
+}
+
+// mbgc_fasta_dups_dev, the first scan: a block takes tile after tile of the flat list over all records, as k_fa_stats does (the lane steps
+// and the arithmetic: fasta_dups.h). One read of the text yields both strands' sums: a lane turns its own aligned vector into eight
+// residues (four primes, forward and reverse), multiplies them with its own power z^(16 lane) — computed once per launch —, the wave
+// adds them modulo the primes by shuffles, the block through 256 bytes of LDS; lanes 0..7 multiply one residue each with the tile's
+// power, which the first wave keeps (by squaring when the block comes to a record, by one multiplication while it stays in it), and
+// hold the sum in a register while the block's tiles stay in one record: at most eight 64-bit atomic adds per tile, of terms below
+// 2^31. The host reduces a record's row modulo the primes (dups_finish).
+__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+                                                           uint32_t nrec, uint64_t ntiles, uint32_t exactCase, unsigned long long *__restrict__ rows) {
+    __shared__ uint32_t sums[2][DUPS_THREADS / WAVE][8];
+    const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1), wave = lane / WAVE;
+    uint32_t lanePw[8], stride[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    dups_pow8(16ull * lane, lanePw);
+    if (wave == 0) dups_pow8((uint64_t) DUPS_TILE * gridDim.x, stride);
+    uint64_t mine = 0;                                                       // lanes 0..7: residue `lane` of record `held`, not yet added to its row
+    uint32_t held = 0, parity = 0, powerOf = 0;
+    bool powered = false;                                                    // pw is the power of record powerOf's tile gridDim.x in front of this one
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, parity ^= 1) {     // (uniform over the block)
+        const uint32_t r = find_tile_record(tileStart, nrec, tile);
+        const FindRec rec = recs[r];
+        const uintptr_t first = (uintptr_t) seq + rec.off, tileAddr = (first & ~(uintptr_t) 15) + (tile - tileStart[r]) * DUPS_TILE;
+        uint32_t v[8], other[8];
+        dups_lane_step(seq, seqBytes, rec, tileAddr, lane, exactCase != 0, v);
+        dups_mul8(v, lanePw);
+#pragma unroll
+        for (int d = WAVE / 2; d; d >>= 1) {
+#pragma unroll
+            for (uint32_t q = 0; q < 8; q++) other[q] = __shfl_xor(v[q], d);
+            dups_add8(v, other);
+        }
+        if (wl == 0)
+#pragma unroll
+            for (uint32_t q = 0; q < 8; q++) sums[parity][wave][q] = v[q];
+        if (wave == 0) {
+            if (powered && powerOf == r) dups_mul8(pw, stride);
+            else dups_pow8(dups_tile_exp(first, tile - tileStart[r]), pw);
+            powered = true; powerOf = r;
+        }
+        __syncthreads();                                                     // (the other buffer is the next tile's: one barrier per tile)
+        if (lane < 8) {
+            if (r != held) { if (mine) atomicAdd(rows + 8ull * held + lane, (unsigned long long) mine); mine = 0; held = r; }
+            uint64_t sum = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < DUPS_THREADS / WAVE; w++) sum += sums[parity][w][lane];
+            mine += dups_tile_term(lane, sum, pw);
+        }
+    }
+    if (lane < 8 && mine) atomicAdd(rows + 8ull * held + lane, (unsigned long long) mine);
+}
+
+// mbgc_fasta_dups_dev, the exactness step: a block per pair of the list (record, candidate representative, strand), striding. The
+// record's side is walked on the 16-byte grid with aligned vectors, the representative's side is read where the same positions lie,
+// forward or mirrored and complemented (dups_verify_step). One ballot per step; a wave stops at its first difference. A pair that
+// differs costs one atomic, a pair that is equal none.
+__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups_verify(const uint8_t *__restrict__ seq, const FindRec *__restrict__ recs, const DupsPair *__restrict__ pairs, uint32_t npairs,
+                                                                  uint32_t exactCase, uint32_t *__restrict__ refuted) {
+    __shared__ uint32_t differs[DUPS_THREADS / WAVE];
+    const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1), wave = lane / WAVE;
+    for (uint32_t pair = blockIdx.x; pair < npairs; pair += gridDim.x) {     // (uniform over the block)
+        const DupsPair P = pairs[pair];
+        const FindRec a = recs[P.rec], b = recs[P.rep];
+        const uintptr_t first = (uintptr_t) seq + a.off;
+        const uint64_t steps = stats_tiles_of(first, a.len);
+        bool differ = false;                                                 // (uniform over the wave)
+        for (uint64_t s = 0; s < steps && !differ; s++)
+            differ = __ballot(dups_verify_step(seq, a, b, P.strand, exactCase != 0, (first & ~(uintptr_t) 15) + s * DUPS_TILE, lane)) != 0;
+        if (wl == 0) differs[wave] = differ;
+        __syncthreads();
+        if (lane == 0 && (differs[0] | differs[1] | differs[2] | differs[3])) atomicOr(refuted + pair, 1u);
+        __syncthreads();                                                     // (the next pair's stores wait for this pair's read)
+    }
 }
 
 // mbgc_fasta_sketch_dev: a block takes tile after tile of the flat list over all records, as k_fa_stats does (the lane steps:
@@ -1191,6 +1266,11 @@ struct mbgc_fasta {
     uint64_t sketchRows = 0, sketchReruns = 0;  // the last call's: mbgc_fasta_sketch_last
     double sketchSortMs = 0;
     hipEvent_t skEv[4] = {nullptr, nullptr, nullptr, nullptr};    // around the scan, around the sort and the compaction
+    fa::Buf<unsigned long long> dDupRows;       // mbgc_fasta_dups_dev (records and tiles: dFindRecs, dFindTiles): the records' eight sums, the pair list, the pairs' verdicts
+    fa::Buf<fa::DupsPair> dDupPairs;
+    fa::Buf<uint32_t> dDupRefuted;
+    uint64_t dupBuckets = 0, dupVerified = 0, dupRefuted = 0;     // the last call's: mbgc_fasta_dups_last
+    double dupVerifyMs = 0;
     fa::Buf<uint64_t> dPairHashes, dPairStart;  // mbgc_fasta_sketch_pairs_dev: the sketches, their starts, the pair list, the answers
     fa::Buf<uint32_t> dPairList, dPairShared;
     fa::Buf<fa::CrcRow> dCrcRows;               // mbgc_fasta_crc_dev: the rows, the bytes behind the cut ranges' pieces, the ranges' words, the constants
@@ -1248,6 +1328,7 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     p->dStatsCounts.release(); p->dStatsEdges.release(); p->dStatsCursor.release();
     p->dSkGroups.release(); p->dSkKmers.release(); p->dSkStart.release(); p->dSkWords.release(); p->dSkHash.release(); p->dSkHash2.release();
     p->dSkGroup.release(); p->dSkGroup2.release(); p->dSkFlag.release(); p->dSkPos.release(); p->dSkTmp.release();
+    p->dDupRows.release(); p->dDupPairs.release(); p->dDupRefuted.release();
     p->dPairHashes.release(); p->dPairStart.release(); p->dPairList.release(); p->dPairShared.release();
     p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
     p->dInfJobs.release(); p->dInfResults.release();
@@ -1791,6 +1872,149 @@ int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBy
 void mbgc_fasta_stats_last(const mbgc_fasta_t *p, uint64_t *edges, uint64_t *reruns) {
     if (edges) *edges = p->statsEdges;
     if (reruns) *reruns = p->statsReruns;
+}
+
+const uint8_t *mbgc_fasta_dups_comp_table(void) {
+    static uint8_t table[256];
+    static std::once_flag once;
+    std::call_once(once, [] { for (uint32_t b = 0; b < 256; b++) table[b] = fa::dups_comp((uint8_t) b); });
+    return table;
+}
+
+int mbgc_fasta_dups_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t flags,
+                        mbgc_fasta_dup_t *out_host, uint64_t *nClasses, double *kernelMs) {
+    using namespace fa;
+    static_assert(sizeof(mbgc_fasta_dup_t) == 8 && sizeof(DupsPair) == 16, "a record's answer is two words; a pair is four");
+    static_assert(MBGC_FASTA_DUPS_FORWARD_ONLY == DUPS_FORWARD_ONLY && MBGC_FASTA_DUPS_EXACT_CASE == DUPS_EXACT_CASE && MBGC_FASTA_DUPS_WEAK_HASH == DUPS_WEAK_HASH, "the flags");
+    if (n >= 0xffffffffull) return fail(-103, "dups: %llu records in one call", (unsigned long long) n);
+    if (flags & ~(DUPS_FORWARD_ONLY | DUPS_EXACT_CASE | DUPS_WEAK_HASH)) return fail(-103, "dups: unknown flags %#x", flags);
+    for (uint64_t r = 0; r < n; r++)
+        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "dups: record %llu lies outside the buffer", (unsigned long long) r);
+    if (kernelMs) *kernelMs = 0;
+    p->dupBuckets = p->dupVerified = p->dupRefuted = 0;
+    p->dupVerifyMs = 0;
+    *nClasses = 0;
+    if (n == 0) return 0;
+    const bool forwardOnly = (flags & DUPS_FORWARD_ONLY) != 0;
+    const uint32_t exactCase = (flags & DUPS_EXACT_CASE) != 0;
+    // ---- the fingerprints: one pass over the tiles of every record with a byte
+    std::vector<uint64_t> tileStart(n + 1, 0);
+    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + stats_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len);
+    const uint64_t ntiles = tileStart[n];
+    std::vector<unsigned long long> rows(8 * n, 0);
+    if (ntiles) {
+        FCHK(hipSetDevice(p->device));
+        int rc;
+        if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dDupRows.reserve(8 * n)) || (rc = p->dDupPairs.reserve(n)) || (rc = p->dDupRefuted.reserve(n)))
+            return rc;
+        if (!p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
+        FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
+        FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        FCHK(hipMemsetAsync(p->dDupRows.p, 0, 8 * n * sizeof(unsigned long long), p->stream));
+        FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+        // one launch whatever n is: the blocks stride over the tiles, as k_fa_stats's do
+        k_fa_dups<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles,
+                                                                                                            exactCase, p->dDupRows.p);
+        FCHK(hipGetLastError());
+        FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+        FCHK(hipMemcpyAsync(rows.data(), p->dDupRows.p, 8 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    }
+    typedef std::array<uint32_t, 4> Print;
+    std::vector<Print> fw(n), rv(n), canon(n);
+    for (uint64_t r = 0; r < n; r++) {
+        DupsPrint f, b;
+        dups_finish(&rows[8 * r], recs[r].len, f, b);
+        for (int i = 0; i < 4; i++) { fw[r][i] = f.v[i]; rv[r][i] = b.v[i]; }
+        if (flags & DUPS_WEAK_HASH) { fw[r] = Print{0, 0, 0, fw[r][3] & 15u}; rv[r] = Print{0, 0, 0, rv[r][3] & 15u}; }     // (a switch of the tests: the exactness step on ordinary inputs)
+        canon[r] = forwardOnly ? fw[r] : std::min(fw[r], rv[r]);
+    }
+    // ---- the buckets: equal (length, canonical fingerprint), the members in index order. n counts records: a sort on the host
+    std::vector<uint32_t> order(n);
+    for (uint64_t r = 0; r < n; r++) order[r] = (uint32_t) r;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        if (recs[a].len != recs[b].len) return recs[a].len < recs[b].len;
+        if (canon[a] != canon[b]) return canon[a] < canon[b];
+        return a < b;
+    });
+    // ---- the exactness step. A bucket's first member is its first representative. Every other member is held against the bucket's
+    // representatives one after the other, forward first, then as the reverse complement, a comparison the fingerprints exclude being
+    // passed over; all members' next comparisons are one launch (a round). A member that no representative equals becomes one — but
+    // only as the LOWEST member of its bucket that is still open, so that a representative is the lowest index of its class; a higher
+    // one waits for the round after. The strand is the comparison's that held: forward is always tried first, so a record that equals
+    // its representative both ways gets 0.
+    struct Open { uint32_t rec, bucket, cand, phase; };
+    std::vector<std::vector<uint32_t>> reps;
+    std::vector<Open> open, still;
+    std::vector<mbgc_fasta_dup_t> out(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t r = order[i];
+        if (i == 0 || recs[r].len != recs[order[i - 1]].len || canon[r] != canon[order[i - 1]]) { reps.push_back({r}); out[r] = mbgc_fasta_dup_t{r, 0}; }
+        else open.push_back(Open{r, (uint32_t) (reps.size() - 1), 0, 0});
+    }
+    p->dupBuckets = reps.size();
+    std::vector<DupsPair> pairs;
+    std::vector<size_t> asked;                                       // pair k is open[asked[k]]'s
+    std::vector<uint32_t> verdict;
+    std::vector<char> lowerOpen(reps.size());
+    while (!open.empty()) {
+        pairs.clear(); asked.clear();
+        std::fill(lowerOpen.begin(), lowerOpen.end(), 0);
+        for (size_t k = 0; k < open.size(); k++) {                   // (a bucket's members: in index order)
+            Open &m = open[k];
+            std::vector<uint32_t> &R = reps[m.bucket];
+            while (m.cand < R.size()) {                              // the next comparison the fingerprints do not exclude
+                if (m.phase == 0) { if (fw[m.rec] == fw[R[m.cand]]) break; m.phase = 1; }
+                if (!forwardOnly && fw[m.rec] == rv[R[m.cand]]) break;
+                m.phase = 0; m.cand++;
+            }
+            if (m.cand == R.size()) {
+                if (!lowerOpen[m.bucket]) { R.push_back(m.rec); out[m.rec] = mbgc_fasta_dup_t{m.rec, 0}; m.rec = 0xffffffffu; }     // (closed: a representative)
+                else lowerOpen[m.bucket] = 1;
+                continue;
+            }
+            lowerOpen[m.bucket] = 1;
+            if (recs[m.rec].len == 0) { out[m.rec] = mbgc_fasta_dup_t{R[m.cand], 0}; m.rec = 0xffffffffu; continue; }            // (no byte to compare)
+            pairs.push_back(DupsPair{m.rec, R[m.cand], m.phase, 0});
+            asked.push_back(k);
+        }
+        if (!pairs.empty()) {
+            verdict.assign(pairs.size(), 0);
+            FCHK(hipMemcpyAsync(p->dDupPairs.p, pairs.data(), pairs.size() * sizeof(DupsPair), hipMemcpyHostToDevice, p->stream));
+            FCHK(hipMemsetAsync(p->dDupRefuted.p, 0, pairs.size() * sizeof(uint32_t), p->stream));
+            FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+            k_fa_dups_verify<<<dim3((uint32_t) std::min<size_t>(pairs.size(), 4096)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, p->dFindRecs.p, p->dDupPairs.p, (uint32_t) pairs.size(),
+                                                                                                                          exactCase, p->dDupRefuted.p);
+            FCHK(hipGetLastError());
+            FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+            FCHK(hipMemcpyAsync(verdict.data(), p->dDupRefuted.p, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+            FCHK(hipStreamSynchronize(p->stream));
+            float ms = 0;
+            FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1]));
+            p->dupVerifyMs += ms;
+            p->dupVerified += pairs.size();
+            for (size_t k = 0; k < pairs.size(); k++) {
+                Open &m = open[asked[k]];
+                if (!verdict[k]) { out[m.rec] = mbgc_fasta_dup_t{pairs[k].rep, pairs[k].strand}; m.rec = 0xffffffffu; continue; }
+                p->dupRefuted++;
+                if (m.phase == 0) m.phase = 1; else { m.phase = 0; m.cand++; }
+            }
+        }
+        still.clear();
+        for (const Open &m : open) if (m.rec != 0xffffffffu) still.push_back(m);
+        open.swap(still);
+    }
+    for (const std::vector<uint32_t> &R : reps) *nClasses += R.size();
+    memcpy(out_host, out.data(), n * sizeof(mbgc_fasta_dup_t));
+    return 0;
+}
+
+void mbgc_fasta_dups_last(const mbgc_fasta_t *p, uint64_t *buckets, uint64_t *verified, uint64_t *refuted, double *verifyMs) {
+    if (buckets) *buckets = p->dupBuckets;
+    if (verified) *verified = p->dupVerified;
+    if (refuted) *refuted = p->dupRefuted;
+    if (verifyMs) *verifyMs = p->dupVerifyMs;
 }
 
 int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, const uint32_t *group_host, uint32_t ngroups,

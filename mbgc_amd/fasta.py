@@ -9,7 +9,8 @@ EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fas
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
            mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_stats_dev mbgc_fasta_stats_last
-           mbgc_fasta_sketch_dev mbgc_fasta_sketch_last mbgc_fasta_sketch_sort_ms mbgc_fasta_sketch_pairs_dev""".split()
+           mbgc_fasta_sketch_dev mbgc_fasta_sketch_last mbgc_fasta_sketch_sort_ms mbgc_fasta_sketch_pairs_dev
+           mbgc_fasta_dups_dev mbgc_fasta_dups_last mbgc_fasta_dups_comp_table""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -65,6 +66,10 @@ class RunsTooMany(binding.SwsemError):
     def __init__(self, msg, needed):
         super().__init__(msg)
         self.needed = needed
+
+
+DUPS_FORWARD_ONLY, DUPS_EXACT_CASE, DUPS_WEAK_HASH = 1, 2, 4     # MBGC_FASTA_DUPS_*
+DUP_DTYPE = np.dtype([("rep", "<u4"), ("strand", "<u4")])        # mbgc_fasta_dup_t
 
 
 class SketchTooLarge(binding.SwsemError):
@@ -191,10 +196,20 @@ def _lib():
         L.mbgc_fasta_sketch_sort_ms.argtypes = [C.c_void_p]
         L.mbgc_fasta_sketch_sort_ms.restype = C.c_double
         L.mbgc_fasta_sketch_pairs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_double)]
+        L.mbgc_fasta_dups_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_dups_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_dups_last.restype = None
+        L.mbgc_fasta_dups_comp_table.argtypes = []
+        L.mbgc_fasta_dups_comp_table.restype = C.POINTER(C.c_uint8)
         L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
     return L
+
+
+def dups_comp_table():
+    """the 256 entries of the header's comp table (mbgc_fasta_dups_comp_table), as bytes"""
+    return bytes(_lib().mbgc_fasta_dups_comp_table()[:256])
 
 
 class FastaParser:
@@ -523,6 +538,34 @@ class FastaParser:
         if r:
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return shared[:npairs].copy(), ms.value
+
+    def dups_dev(self, seq_ptr, seq_bytes, ranges, flags=0, out=None):
+        """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes -> (a structured array of
+        DUP_DTYPE, one row per record: rep = the lowest index of the record's class, strand = 0 when the record equals rep read forward
+        (also when it equals it both ways), 1 when it equals only rep's reverse complement; the number of classes; k_fa_dups's ms).
+        Same = equal under fold (letters without case; DUPS_EXACT_CASE: as they are), forward or — unless DUPS_FORWARD_ONLY — as the
+        reverse complement under the header's comp table. Exact: every duplicate is compared byte by byte on the device.
+        DUPS_WEAK_HASH (tests) keeps 4 bits of the fingerprints; the answer does not change. out: an array of DUP_DTYPE to fill (a
+        refused call — a record outside the buffer, an unknown flag — raises, launches nothing and leaves it as it was).
+        last_dups(): the buckets, the pairs compared and refuted, the comparisons' ms."""
+        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        n = rows.shape[0]
+        if out is None:
+            out = np.zeros(max(n, 1), dtype=DUP_DTYPE)
+        if out.dtype != DUP_DTYPE or out.size < n or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("dups_dev: out must be a contiguous array of DUP_DTYPE with a row per record")
+        classes, ms = C.c_uint64(0), C.c_double(0)
+        if _lib().mbgc_fasta_dups_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), n, int(flags), out.ctypes.data_as(C.c_void_p), C.byref(classes),
+                                      C.byref(ms)):
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return out[:n], int(classes.value), ms.value
+
+    def last_dups(self):
+        """(buckets, verified, refuted, verify_ms) of the last dups_dev call: the groups of equal (length, canonical fingerprint), the
+        pairs k_fa_dups_verify compared, those it found different, and the ms of its launches"""
+        b, v, r, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        _lib().mbgc_fasta_dups_last(self.h, C.byref(b), C.byref(v), C.byref(r), C.byref(ms))
+        return int(b.value), int(v.value), int(r.value), float(ms.value)
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <fstream>
 #include <future>
 #include <set>
@@ -202,6 +203,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_find.h"       // f: query sequences searched in the chosen contigs
 #include "mbgc_decoder_stats.h"      // s: composition, N50 and the runs of N / lower case of the chosen contigs
 #include "mbgc_decoder_sketch.h"     // k: k-mer sketches of the chosen files or records and what every two of them share
+#include "mbgc_decoder_dups.h"       // u: which chosen contigs are the same sequence, forward or as the reverse complement
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -363,7 +365,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     mbgc_checksums::Manifest manifest;
     if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
     // (--check names a differing contig by its file and header: the whole layout)
-    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats || opt.sketch;      // (`f`, `s` and `k` name a record by its file and header)
+    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats || opt.sketch || opt.dups;      // (`f`, `s`, `k` and `u` name a record by its file and header)
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
     if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
@@ -414,6 +416,14 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
             SketchResult sketch;
             if (!collectSketch(D, S, chosen, layout, opt, opt.bench, sketch, msg) ||
                 !reportSketch(opt, sketch, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
+            return 0;
+        }
+        // `u`: the classes are the sink
+        if (opt.dups) {
+            if (!last) continue;
+            DupsResult dups;
+            if (!collectDups(D, S, chosen, opt, opt.bench, dups, msg) ||
+                !reportDups(opt, layout, dups, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
             return 0;
         }
         if (wantFasta) {
@@ -876,6 +886,68 @@ int mbgc_hip_sketch_main(int argc, char **argv) {
     std::string error;
     const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
     if (r) { fprintf(stderr, "mbgc-hip k: %s\n", error.c_str()); return EXIT_FAILURE; }
+    return 0;
+}
+
+const char *const MBGC_HIP_U_USAGE =
+    "mbgc-hip u [--forward-only] [--exact-case] [--min-len N] [--clusters-out file] [--unique-files-out file] [--dups-host] [--serial] [--no-index]\n"
+    "                  [--restore-rc] [--select pattern]... [--select-list file] [--select-seq pattern]... [--select-seq-list file] [-d device] [--bench]\n"
+    "                  <streamsPrefix>\n"
+    "  which records of the collection are the same sequence, without unpacking it: the chosen contigs are decoded as mbgc-hip d decodes them\n"
+    "  (--serial, --no-index, --restore-rc, --select, --select-list, --select-seq, --select-seq-list: as there; contigs decoded only as\n"
+    "  dependencies are not classed) and compared where they lie, on the device. Two records are the same when they have the same length and\n"
+    "  the same bytes, letters compared without case (--exact-case: as they are), read forward or — unless --forward-only — one as the reverse\n"
+    "  complement of the other (A-T, C-G, R-Y, K-M, B-V, D-H, either case; every other byte is its own complement). The answer is exact: a\n"
+    "  fingerprint only proposes, every duplicate is compared byte by byte. A class is represented by its first record in collection order.\n"
+    "  One tab-separated line per duplicate record — every record that is not its class's representative — on stdout, in collection order:\n"
+    "  record (the first word of its header), file, length, strand (+, or - when it equals only the representative's reverse complement),\n"
+    "  representative record, representative file. Then `dups: <records> records, <bases> bases; <classes> distinct sequences; <d> duplicate\n"
+    "  records, <db> bases (<rc> as reverse complements); <df> of <files> files duplicate`. Exit status 0; 1: malformed streams, a refused\n"
+    "  option or a file that cannot be written\n"
+    "  --min-len N: records shorter than N (default 1, so empty records) are left out of the lines and of the duplicate counts\n"
+    "  --clusters-out file: every class with more than one member, one line per member, the representative first: the same columns and the\n"
+    "  class's number (1, 2, ... in collection order of the representatives)\n"
+    "  --unique-files-out file: a file is a duplicate of an earlier one when the sorted lists of their records' classes are equal, whatever\n"
+    "  the strands; the names of the files that are no duplicates, in collection order, one per line — a list for mbgc-hip d / r\n"
+    "  --select-list. --select matches SUBSTRINGS of the names: a name that is contained in another one chooses both\n"
+    "  --dups-host: a developer switch, the chosen contigs are downloaded and classed by a map over canonical strings on the host, and the\n"
+    "  two results must agree. --bench: two decodes, the second one timed, the scan run six times (the medians of the last five); one JSON\n"
+    "  line (dups_kernel_ms, verify_ms, bases, records, buckets, verified, refuted, decode_ms, dups_gb_per_s). Not with --region, --check\n"
+    "  or --fasta\n";
+
+// `mbgc-hip u`: the decode of `t` — nothing is written —, then the classes in place of the check
+int mbgc_hip_dups_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.dups = opt.writeNothing = true;
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (const int r = mbgc_hip_decode_option('u', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else if (a == "--forward-only") opt.dupsForwardOnly = true;
+        else if (a == "--exact-case") opt.dupsExactCase = true;
+        else if (a == "--dups-host") opt.dupsHost = true;
+        else if (a == "--min-len" && i + 1 < argc) {
+            const std::string text = argv[++i];
+            if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip u: --min-len takes a number of bytes\n"); return EXIT_FAILURE; }
+            opt.dupsMinLen = strtoull(text.c_str(), nullptr, 10);
+        }
+        else if (a == "--clusters-out" && i + 1 < argc) opt.dupsClustersOut = argv[++i];
+        else if (a == "--unique-files-out" && i + 1 < argc) opt.dupsUniqueFilesOut = argv[++i];
+        else if (a == "--check") { fprintf(stderr, "mbgc-hip u: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
+        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip u: --fasta is an option of mbgc-hip d: u writes no sequence, it compares the records where they lie\n"); return EXIT_FAILURE; }
+        else pos.push_back(a);
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip u: --region / --region-list select parts of records, and whole records are compared (an option of mbgc-hip d)\n");
+        return EXIT_FAILURE;
+    }
+    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_U_USAGE); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection('u', opt, selectAsked)) return EXIT_FAILURE;
+    std::string error;
+    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
+    if (r) { fprintf(stderr, "mbgc-hip u: %s\n", error.c_str()); return EXIT_FAILURE; }
     return 0;
 }
 

@@ -18,6 +18,7 @@
 //   mbgc_decoder_find.h       `f`: the queries and their reverse complements searched in the chosen contigs, the hits named and sorted
 //   mbgc_decoder_stats.h      `s`: the chosen contigs' counters and runs of N / lower case taken on the device, summed per file, N50 / L50
 //   mbgc_decoder_sketch.h     `k`: FracMinHash sketches of the chosen files or records and the pairs' shared hashes taken on the device, the distances
+//   mbgc_decoder_dups.h       `u`: the chosen contigs classed on the device — same sequence, forward or reverse complement —, the duplicates and the files named
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
@@ -135,6 +136,12 @@ public:
         // developer switch — everything is computed again by the host and held against the device's
         bool sketch = false, sketchByRecord = false, sketchNoPairs = false, sketchHost = false; uint32_t sketchK = 21; uint64_t sketchScale = 1000, sketchMinShared = 0;
         std::string sketchPairsOut, sketchOut, sketchOrderOut;
+        // `mbgc-hip u` (mbgc_decoder_dups.h): the chosen contigs are classed on the device — which are the same sequence, forward or as the
+        // reverse complement — and nothing else happens to them. dupsForwardOnly: --forward-only; dupsExactCase: --exact-case; dupsMinLen:
+        // --min-len (0 is read as 1); dupsClustersOut / dupsUniqueFilesOut: --clusters-out, --unique-files-out; dupsHost: --dups-host, a
+        // developer switch — the classes are made again by the host and held against the device's
+        bool dups = false, dupsForwardOnly = false, dupsExactCase = false, dupsHost = false; uint64_t dupsMinLen = 1;
+        std::string dupsClustersOut, dupsUniqueFilesOut;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -162,8 +169,10 @@ int mbgc_hip_test_main(int argc, char **argv);
 int mbgc_hip_find_main(int argc, char **argv);
 int mbgc_hip_stats_main(int argc, char **argv);
 int mbgc_hip_sketch_main(int argc, char **argv);
+int mbgc_hip_dups_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
-extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE, *const MBGC_HIP_K_USAGE;
+extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE, *const MBGC_HIP_K_USAGE,
+    *const MBGC_HIP_U_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.
