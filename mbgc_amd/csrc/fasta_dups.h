@@ -1,5 +1,5 @@
-// The two scans of `mbgc-hip u` (included by fasta_input.hip, inside namespace fa, behind fasta_stats.h, whose tiles — stats_tiles_of,
-// find_tile_record, FindRec, FindVec — it shares): fold and comp of a byte, the arithmetic of the two strand fingerprints, the step of
+// The two scans of `mbgc-hip u` (included by fasta_input.hip, inside namespace fa, behind fasta_tiles.h, whose grid they scan — a
+// record's start positions are its bytes, as for fasta_stats.h): fold and comp of a byte, the arithmetic of the two strand fingerprints, the step of
 // one lane of k_fa_dups, the step of one lane of k_fa_dups_verify and the host's last step. Kept free of HIP calls so that the same text
 // compiles as plain C++: tests/fasta_dups_emu.cpp runs the steps tile by tile and lane by lane on the CPU under AddressSanitizer, the
 // wave's shuffles emulated by arrays. The shuffles, the block's sum in LDS, the atomic adds to a record's row, the ballot and the
@@ -18,9 +18,8 @@
 // z^(16 lane), which it computed once per launch; the wave adds modulo p by shuffles; lanes 0..7 of the block add the four waves' sums
 // and multiply with the tile's power z^(16 - (address & 15) + 4096 tile), which the first wave keeps: by squaring when the block
 // comes to a record, by one multiplication with z^(4096 gridDim) while it stays in it.
-constexpr uint32_t DUPS_TILE = 4096, DUPS_THREADS = 256, DUPS_PER = DUPS_TILE / DUPS_THREADS;   // 16 positions per lane
+constexpr uint32_t DUPS_TILE = SCAN_TILE, DUPS_THREADS = SCAN_THREADS, DUPS_PER = SCAN_PER;   // 16 positions per lane
 constexpr uint32_t DUPS_FORWARD_ONLY = 1u, DUPS_EXACT_CASE = 2u, DUPS_WEAK_HASH = 4u;            // MBGC_FASTA_DUPS_*
-static_assert(DUPS_PER == 16 && DUPS_TILE == STATS_TILE, "a lane reads its 16 positions as one vector; the tiles are stats_tiles_of's");
 
 struct DupsPair { uint32_t rec, rep, strand, reserved; };             // is record rec the same as record rep read forward (0) / as its reverse complement (1)?
 struct DupsPrint { uint32_t v[4]; };                                  // a strand's fingerprint: the residue modulo each prime
@@ -124,15 +123,15 @@ template <uint32_t Q> __host__ __device__ __forceinline__ uint32_t dups_lane_sum
 // the step of k_fa_dups: lane `lane` (of DUPS_THREADS) owns the DUPS_PER positions from address tileAddr + 16 lane on -> out[q] = the sum
 // over its positions t0 + k inside the record of T[.] z_q^k, reduced; zeros for a lane without one. The vector is read as stats_lane_step
 // reads it: aligned and whole where it lies inside seq[0, seqBytes), its bytes inside one by one otherwise
-__device__ __forceinline__ void dups_lane_step(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec rec, uintptr_t tileAddr, uint32_t lane, bool exactCase,
+__device__ __forceinline__ void dups_lane_step(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec rec, uintptr_t tileAddr, uint32_t lane, bool exactCase,
                                                uint32_t out[8]) {
 #pragma unroll
     for (uint32_t q = 0; q < 8; q++) out[q] = 0;
     const uintptr_t lo = (uintptr_t) seq, hi = lo + seqBytes, v = tileAddr + 16u * lane;
     const int64_t t0 = (int64_t) v - (int64_t) (lo + rec.off);
     if (t0 + (int64_t) DUPS_PER <= 0 || t0 >= (int64_t) rec.len) return;
-    FindVec x = {{0, 0, 0, 0}};
-    if (v >= lo && v + 16 <= hi) x = *(const FindVec *) v;
+    ScanVec x = {{0, 0, 0, 0}};
+    if (v >= lo && v + 16 <= hi) x = *(const ScanVec *) v;
     else
 #pragma unroll
         for (uint32_t k = 0; k < 16; k++)
@@ -154,17 +153,17 @@ __device__ __forceinline__ void dups_lane_step(const uint8_t *__restrict__ seq, 
 // the 16-byte grid, aligned); b has a's length and is read where the same positions lie — forward — or mirrored, from its end, and
 // complemented. -> does one of the lane's positions differ? A lane whose 16 positions all lie inside the record reads a vector on
 // either side (b's at any address: the bytes are inside b, so inside the buffer); the others read the positions inside, byte by byte
-__device__ __forceinline__ bool dups_verify_step(const uint8_t *__restrict__ seq, const FindRec a, const FindRec b, uint32_t strand, bool exactCase, uintptr_t tileAddr,
+__device__ __forceinline__ bool dups_verify_step(const uint8_t *__restrict__ seq, const ScanRec a, const ScanRec b, uint32_t strand, bool exactCase, uintptr_t tileAddr,
                                                  uint32_t lane) {
     const uintptr_t v = tileAddr + 16u * lane;
     const int64_t t0 = (int64_t) v - (int64_t) ((uintptr_t) seq + a.off), len = (int64_t) a.len;
     if (t0 + 16 <= 0 || t0 >= len) return false;
     bool differ = false;
     if (t0 >= 0 && t0 + 16 <= len) {
-        const FindVec x = *(const FindVec *) v;
-        FindVec y;
+        const ScanVec x = *(const ScanVec *) v;
+        ScanVec y;
         memcpy(&y, seq + b.off + (strand ? (uint64_t) (len - 16 - t0) : (uint64_t) t0), 16);
-        if (strand) y = FindVec{{__builtin_bswap32(y.w[3]), __builtin_bswap32(y.w[2]), __builtin_bswap32(y.w[1]), __builtin_bswap32(y.w[0])}};     // (mirrored)
+        if (strand) y = ScanVec{{__builtin_bswap32(y.w[3]), __builtin_bswap32(y.w[2]), __builtin_bswap32(y.w[1]), __builtin_bswap32(y.w[0])}};     // (mirrored)
 #pragma unroll
         for (uint32_t k = 0; k < 16; k++) {
             const uint8_t p = dups_fold((uint8_t) (x.w[k >> 2] >> (8 * (k & 3))), exactCase), q = dups_fold((uint8_t) (y.w[k >> 2] >> (8 * (k & 3))), exactCase);

@@ -12,51 +12,36 @@
 // t - seedOff_j; the lane counts the mismatches of the whole pattern there and reports the alignment only if no gram j' < j of q is
 // exact at its own place start + seedOff_j' — the lane that owns that place reports it. So every hit is reported exactly once, by the
 // smallest exact gram, and no pass removes duplicates afterwards.
-// ---- tiles: the records are cut on the 16-byte grid of the buffer's ADDRESSES, so that every tile is staged with aligned 16-byte
-// loads whatever the record's offset is: record r's tiles start at the address of its first byte rounded down to 16, FIND_TILE
-// positions each; the positions of the first tile that lie in front of the record are nobody's. tileStart[] is the prefix sum of the
-// records' tile counts; a block finds its tile's record by bisection. A byte outside the buffer is never read: a vector that
-// does not lie inside it whole is read byte by byte, the bytes inside only. A staged byte outside the record is never looked at: a
-// position counts only when its whole gram lies inside the record, and a proposed start only when the whole pattern does.
-constexpr uint32_t FIND_TILE = 4096, FIND_GRAM = 8, FIND_THREADS = 256, FIND_PER = FIND_TILE / FIND_THREADS;   // 16 positions per lane
+// ---- tiles: the shared grid of fasta_tiles.h (ScanRec, ScanVec, scan_tile); a record's start positions are those of its grams, none
+// when no pattern fits into it (find_positions). Every tile is staged with aligned 16-byte loads. A staged byte outside the record is
+// never looked at: a position counts only when its whole gram lies inside the record, and a proposed start only when the whole
+// pattern does.
+constexpr uint32_t FIND_TILE = SCAN_TILE, FIND_GRAM = 8, FIND_THREADS = SCAN_THREADS, FIND_PER = SCAN_PER;   // 16 positions per lane
 constexpr uint32_t FIND_VECS = FIND_TILE / 16 + 1, FIND_STAGE = FIND_VECS * 16;    // the tile and the 16 bytes behind it (FIND_GRAM - 1 are needed)
 constexpr uint32_t FIND_LDS_BITS = 11;                                             // the table lives in LDS up to 2048 slots (32 KiB)
 constexpr uint32_t FIND_MAX_K = 3, FIND_MAX_LEN = 65535;
-static_assert(FIND_PER == 16 && MBGC_FASTA_FIND_TILE == FIND_TILE, "a lane reads its 16 positions and the 16 bytes behind them as two vectors");
+static_assert(MBGC_FASTA_FIND_TILE == FIND_TILE, "the tile the public header states");
 
-struct alignas(16) FindVec { uint32_t w[4]; };
 struct FindSlot {
     uint64_t key;             // the folded gram, byte j in bits [8 j, 8 j + 8)
     uint32_t first, count;    // the chain: rows [first, first + count) of the seed table; count == 0: an empty slot
 };
 struct FindSeed { uint32_t pat; uint16_t off, j; };                   // seed j of the caller's pattern `pat`, `off` bytes into it
 struct FindPat { uint64_t off; uint32_t len, step; };                 // folded bytes [off, off + len) of the table's blob; seed j at j * step
-struct FindRec { uint64_t off, len; };                                // the ABI's mbgc_fasta_crc_rec_t
 
 __host__ __device__ __forceinline__ uint32_t find_hash(uint64_t key, uint32_t bits) { return (uint32_t) ((key * 0x9E3779B97F4A7C15ull) >> (64 - bits)); }
 __host__ __device__ __forceinline__ uint8_t find_fold(uint8_t b) { return (uint8_t) ((uint8_t) ((b | 0x20) - 'a') < 26 ? b & 0xDF : b); }
 
-// the tiles of a record whose first byte has address `first`: none when no pattern fits into it
-__host__ __device__ __forceinline__ uint64_t find_tiles_of(uintptr_t first, uint64_t len, uint32_t shortest) {
-    if (len < shortest || len < FIND_GRAM) return 0;
-    return ((first & 15) + (len - FIND_GRAM + 1) + FIND_TILE - 1) / FIND_TILE;
-}
-
-// the record of tile `tile`: the last r of [0, n) with tileStart[r] <= tile (records without a tile are passed over)
-__device__ __forceinline__ uint32_t find_tile_record(const uint64_t *__restrict__ tileStart, uint32_t n, uint64_t tile) {
-    uint32_t lo = 0, hi = n;                                         // tileStart[lo] <= tile < tileStart[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (tileStart[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
+// the start positions of a record of `len` bytes (scan_tiles_of): its grams, none when no pattern fits into it
+__host__ __device__ __forceinline__ uint64_t find_positions(uint64_t len, uint32_t shortest) {
+    return len < shortest || len < FIND_GRAM ? 0 : len - FIND_GRAM + 1;
 }
 
 // the first step: vector `vec` (of FIND_VECS) of the tile whose first byte has address `tileAddr` (a multiple of 16) goes to
 // stage[16 vec, 16 vec + 16) — one aligned 16-byte load when the vector lies inside seq[0, seqBytes), else its bytes inside, one by one
 __device__ __forceinline__ void find_stage_step(const uint8_t *__restrict__ seq, uint64_t seqBytes, uintptr_t tileAddr, uint32_t vec, uint8_t *stage) {
     const uintptr_t lo = (uintptr_t) seq, hi = lo + seqBytes, v = tileAddr + 16u * vec;
-    if (v >= lo && v + 16 <= hi) { *(FindVec *) (stage + 16u * vec) = *(const FindVec *) v; return; }
+    if (v >= lo && v + 16 <= hi) { *(ScanVec *) (stage + 16u * vec) = *(const ScanVec *) v; return; }
     for (uint32_t k = 0; k < 16; k++)
         if (v + k >= lo && v + k < hi) stage[16u * vec + k] = *(const uint8_t *) (v + k);
 }
@@ -71,14 +56,14 @@ __device__ __forceinline__ uint32_t find_count(const uint8_t *__restrict__ txt, 
 // the second step, behind a barrier: lane `lane` (of FIND_THREADS) owns the FIND_PER positions from address tileAddr + 16 lane on;
 // emit(pos, pattern, mismatches) is called once per hit of record `rec` this lane reports
 template <class Emit>
-__device__ __forceinline__ void find_lane_step(const uint8_t *__restrict__ seq, const FindRec rec, uintptr_t tileAddr, uint32_t lane, const uint8_t *stage,
+__device__ __forceinline__ void find_lane_step(const uint8_t *__restrict__ seq, const ScanRec rec, uintptr_t tileAddr, uint32_t lane, const uint8_t *stage,
                                                const FindSlot *slots, uint32_t bits, const FindSeed *__restrict__ seeds, const FindPat *__restrict__ pats,
                                                const uint8_t *__restrict__ patBytes, uint32_t K, Emit &&emit) {
     const uint8_t *text = seq + rec.off;
     // the lane's first position in the record; in front of the record in its first tile only
     const int64_t t0 = (int64_t) (tileAddr + 16u * lane) - (int64_t) (uintptr_t) text;
     if (t0 + (int64_t) FIND_PER <= 0 || t0 + (int64_t) FIND_GRAM > (int64_t) rec.len) return;
-    const FindVec a = *(const FindVec *) (stage + 16u * lane), b = *(const FindVec *) (stage + 16u * lane + 16);
+    const ScanVec a = *(const ScanVec *) (stage + 16u * lane), b = *(const ScanVec *) (stage + 16u * lane + 16);
     const uint32_t w[8] = {a.w[0], a.w[1], a.w[2], a.w[3], b.w[0], b.w[1], b.w[2], b.w[3]};
     uint64_t key = 0;
 #pragma unroll

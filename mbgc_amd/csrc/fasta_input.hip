@@ -723,6 +723,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_compare.h"
 #include "fasta_pack.h"
 #include "fasta_select.h"
+#include "fasta_tiles.h"
 #include "fasta_find.h"
 #include "fasta_stats.h"
 #include "fasta_sketch.h"
@@ -846,7 +847,7 @@ __global__ void __launch_bounds__(WAVE) k_fa_match_headers(const uint8_t *__rest
 // global memory — from L2 — otherwise. A hit takes a row of the buffer through the one cursor; rows at or past the capacity are
 // counted and not written, so the cursor ends as the exact count.
 template <bool LDS_TABLE>
-__global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+__global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
                                                           uint32_t nrec, uint64_t ntiles, const FindSlot *__restrict__ slotsGlobal, uint32_t bits,
                                                           const FindSeed *__restrict__ seeds, const FindPat *__restrict__ pats, const uint8_t *__restrict__ patBytes, uint32_t K,
                                                           mbgc_fasta_hit_t *__restrict__ hits, uint64_t hitCap, unsigned long long *__restrict__ cursor) {
@@ -856,9 +857,10 @@ __global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restr
     if (LDS_TABLE) for (uint32_t s = lane; s < (1u << bits); s += FIND_THREADS) slotsLds[s] = slotsGlobal[s];   // (visible behind the first tile's barrier)
     const FindSlot *slots = LDS_TABLE ? slotsLds : slotsGlobal;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
-        const uint32_t r = find_tile_record(tileStart, nrec, tile);
-        const FindRec rec = recs[r];
-        const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * FIND_TILE;
+        const ScanTile T = scan_tile(seq, recs, tileStart, nrec, tile);
+        const uint32_t r = T.r;
+        const ScanRec rec = T.rec;
+        const uintptr_t tileAddr = T.addr;
         find_stage_step(seq, seqBytes, tileAddr, lane, stage);
         if (lane == 0) find_stage_step(seq, seqBytes, tileAddr, FIND_VECS - 1, stage);
         __syncthreads();
@@ -876,7 +878,7 @@ __global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restr
 // summed over the wave by shuffles and over the block through 64 bytes of LDS; lanes 0..6 keep one counter each in a register while
 // the block's tiles stay in one record and add it to the record's row when the record changes — at most seven atomic adds per tile.
 // Edges: a lane takes as many rows as it has edges through the one cursor; rows at or past the capacity are counted and not written.
-__global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+__global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
                                                             uint32_t nrec, uint64_t ntiles, uint32_t counting, uint32_t want, unsigned long long *__restrict__ counts,
                                                             StatsEdge *__restrict__ edges, uint64_t edgeCap, unsigned long long *__restrict__ cursor) {
     __shared__ uint64_t sums[2][STATS_THREADS / WAVE][2];
@@ -884,9 +886,10 @@ __global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__res
     uint64_t mine = 0;                                                       // lanes 0..6: counter `lane` of record `held`, not yet added to its row
     uint32_t held = 0, parity = 0;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, parity ^= 1) {     // (uniform over the block)
-        const uint32_t r = find_tile_record(tileStart, nrec, tile);
-        const FindRec rec = recs[r];
-        const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * STATS_TILE;
+        const ScanTile T = scan_tile(seq, recs, tileStart, nrec, tile);
+        const uint32_t r = T.r;
+        const ScanRec rec = T.rec;
+        const uintptr_t tileAddr = T.addr;
         const StatsLane L = stats_lane_step(seq, seqBytes, rec, tileAddr, lane);
         const int64_t t0 = (int64_t) (tileAddr + 16u * lane) - (int64_t) ((uintptr_t) seq + rec.off);
         if (want) {
@@ -922,7 +925,7 @@ __global__ void __launch_bounds__(STATS_THREADS) k_fa_stats(const uint8_t *__res
 // power, which the first wave keeps (by squaring when the block comes to a record, by one multiplication while it stays in it), and
 // hold the sum in a register while the block's tiles stay in one record: at most eight 64-bit atomic adds per tile, of terms below
 // 2^31. The host reduces a record's row modulo the primes (dups_finish).
-__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
                                                            uint32_t nrec, uint64_t ntiles, uint32_t exactCase, unsigned long long *__restrict__ rows) {
     __shared__ uint32_t sums[2][DUPS_THREADS / WAVE][8];
     const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1), wave = lane / WAVE;
@@ -933,9 +936,10 @@ __global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups(const uint8_t *__restr
     uint32_t held = 0, parity = 0, powerOf = 0;
     bool powered = false;                                                    // pw is the power of record powerOf's tile gridDim.x in front of this one
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, parity ^= 1) {     // (uniform over the block)
-        const uint32_t r = find_tile_record(tileStart, nrec, tile);
-        const FindRec rec = recs[r];
-        const uintptr_t first = (uintptr_t) seq + rec.off, tileAddr = (first & ~(uintptr_t) 15) + (tile - tileStart[r]) * DUPS_TILE;
+        const ScanTile T = scan_tile(seq, recs, tileStart, nrec, tile);
+        const uint32_t r = T.r;
+        const ScanRec rec = T.rec;
+        const uintptr_t first = (uintptr_t) seq + rec.off, tileAddr = T.addr;
         uint32_t v[8], other[8];
         dups_lane_step(seq, seqBytes, rec, tileAddr, lane, exactCase != 0, v);
         dups_mul8(v, lanePw);
@@ -969,15 +973,15 @@ __global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups(const uint8_t *__restr
 // record's side is walked on the 16-byte grid with aligned vectors, the representative's side is read where the same positions lie,
 // forward or mirrored and complemented (dups_verify_step). One ballot per step; a wave stops at its first difference. A pair that
 // differs costs one atomic, a pair that is equal none.
-__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups_verify(const uint8_t *__restrict__ seq, const FindRec *__restrict__ recs, const DupsPair *__restrict__ pairs, uint32_t npairs,
+__global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups_verify(const uint8_t *__restrict__ seq, const ScanRec *__restrict__ recs, const DupsPair *__restrict__ pairs, uint32_t npairs,
                                                                   uint32_t exactCase, uint32_t *__restrict__ refuted) {
     __shared__ uint32_t differs[DUPS_THREADS / WAVE];
     const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1), wave = lane / WAVE;
     for (uint32_t pair = blockIdx.x; pair < npairs; pair += gridDim.x) {     // (uniform over the block)
         const DupsPair P = pairs[pair];
-        const FindRec a = recs[P.rec], b = recs[P.rep];
+        const ScanRec a = recs[P.rec], b = recs[P.rep];
         const uintptr_t first = (uintptr_t) seq + a.off;
-        const uint64_t steps = stats_tiles_of(first, a.len);
+        const uint64_t steps = scan_tiles_of(first, a.len);
         bool differ = false;                                                 // (uniform over the wave)
         for (uint64_t s = 0; s < steps && !differ; s++)
             differ = __ballot(dups_verify_step(seq, a, b, P.strand, exactCase != 0, (first & ~(uintptr_t) 15) + s * DUPS_TILE, lane)) != 0;
@@ -995,7 +999,7 @@ __global__ void __launch_bounds__(DUPS_THREADS) k_fa_dups_verify(const uint8_t *
 // rows from the one cursor with ONE atomic add per wave and tile, none when the ballot says no lane keeps one; rows at or past the
 // capacity are counted and not written. kmers: the valid positions summed over the wave, held in a register while the block's tiles
 // stay in one group, one atomic add per wave when the group changes.
-__global__ void __launch_bounds__(SKETCH_THREADS) k_fa_sketch(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec *__restrict__ recs, const uint32_t *__restrict__ groups,
+__global__ void __launch_bounds__(SKETCH_THREADS) k_fa_sketch(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint32_t *__restrict__ groups,
                                                               const uint64_t *__restrict__ tileStart, uint32_t nrec, uint64_t ntiles, uint32_t k, uint64_t maxHash,
                                                               unsigned long long *__restrict__ kmers, uint64_t *__restrict__ rowHash, uint32_t *__restrict__ rowGroup, uint64_t rowCap,
                                                               unsigned long long *__restrict__ cursor) {
@@ -1003,10 +1007,11 @@ __global__ void __launch_bounds__(SKETCH_THREADS) k_fa_sketch(const uint8_t *__r
     uint64_t mine = 0;                                                       // the wave's valid positions of group `held`, not yet added (the same in every lane)
     uint32_t held = 0;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
-        const uint32_t r = find_tile_record(tileStart, nrec, tile);
-        const FindRec rec = recs[r];
+        const uint32_t r = scan_tile_record(tileStart, nrec, tile);
         const uint32_t g = groups[r];
-        const uintptr_t v = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * SKETCH_TILE + 16u * lane;
+        const ScanTile T = scan_tile_of(seq, recs, tileStart, r, tile);
+        const ScanRec rec = T.rec;
+        const uintptr_t v = T.addr + 16u * lane;
         const uint64_t own = sketch_pack(seq, seqBytes, rec, v);
         uint64_t next1 = __shfl_down(own, 1), next2 = __shfl_down(own, 2);
         if (wl == WAVE - 1) next1 = sketch_pack(seq, seqBytes, rec, v + 16);
@@ -1198,10 +1203,16 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 #define FCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fa::fail(-100, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+#define FTRY(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)      // a step that has said itself what failed
 
+// a device array of the handle's: it grows and is never shrunk, and is freed with the handle (mbgc_fasta_destroy deletes it)
 template <class T>
 struct Buf {
     T *p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { if (p) (void) hipFree(p); }
     int reserve(size_t n) {
         if (n <= cap) return 0;
         if (p) (void) hipFree(p);
@@ -1211,7 +1222,30 @@ struct Buf {
         cap = want;
         return 0;
     }
-    void release() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
+};
+
+// the time of a stretch of a stream, by a pair of events made at the first start that wants it: start() in front of the launches,
+// stop() behind them, read() behind the synchronise. A start that does not want the time makes the other two do nothing.
+struct Timer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool on = false;
+    int start(hipStream_t stream, bool wanted = true) {
+        on = wanted;
+        if (!on) return 0;
+        for (hipEvent_t &e : ev) if (!e) FCHK(hipEventCreate(&e));
+        FCHK(hipEventRecord(ev[0], stream));
+        return 0;
+    }
+    int stop(hipStream_t stream) {
+        if (on) FCHK(hipEventRecord(ev[1], stream));
+        return 0;
+    }
+    int read(double *ms) {                                             // (ms == nullptr: the caller does not ask)
+        float t = 0;
+        if (on && ms) { FCHK(hipEventElapsedTime(&t, ev[0], ev[1])); *ms = t; }
+        return 0;
+    }
+    void destroy() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
 };
 
 }  // namespace fa
@@ -1233,7 +1267,7 @@ struct mbgc_fasta {
     uint32_t tileFlags = 0;                     // the flags dTileFirst was made with
     fa::Buf<fa::FmtRec> dFmtRecs;               // mbgc_fasta_format_dev: the record table and the tiles' owners
     fa::Buf<uint32_t> dFmtOwner;
-    hipEvent_t fmtEv[2] = {nullptr, nullptr};   // around the format launches (made at the first call that asks for the time)
+    fa::Timer timer;                            // around the launches of whichever entry point runs (one call at a time uses the handle)
     fa::Buf<fa::CmpPiece> dCmpPieces;           // mbgc_fasta_compare_dev: the piece table, the tiles' owners, the slots' results
     fa::Buf<uint32_t> dCmpOwner;
     fa::Buf<unsigned long long> dCmpOut;
@@ -1244,20 +1278,21 @@ struct mbgc_fasta {
     fa::Buf<fa::SelPat> dSelPats;
     fa::Buf<uint8_t> dSelBytes;
     fa::Buf<uint32_t> dSelChosen;
-    fa::Buf<fa::FindRec> dFindRecs;             // mbgc_fasta_find_dev: the records, their tiles' prefix sum, the gram table, the hit rows and their cursor
-    fa::Buf<uint64_t> dFindTiles;
-    fa::Buf<fa::FindSlot> dFindSlots;
+    fa::Buf<fa::ScanRec> dScanRecs;             // scan_prepare, for find, stats, sketch and dups: the last call's records and their tiles' prefix sum
+    fa::Buf<uint64_t> dScanTiles;
+    std::vector<uint64_t> scanTileStart;        // the host's side of dScanTiles
+    fa::Buf<fa::FindSlot> dFindSlots;           // mbgc_fasta_find_dev: the gram table, the hit rows and their cursor
     fa::Buf<fa::FindSeed> dFindSeeds;
     fa::Buf<fa::FindPat> dFindPats;
     fa::Buf<uint8_t> dFindBytes;
     fa::Buf<mbgc_fasta_hit_t> dFindHits;
     fa::Buf<unsigned long long> dFindCursor;
-    fa::Buf<unsigned long long> dStatsCounts;   // mbgc_fasta_stats_dev (records and tiles: dFindRecs, dFindTiles): the records' rows, the edges and their cursor
+    fa::Buf<unsigned long long> dStatsCounts;   // mbgc_fasta_stats_dev: the records' rows, the edges and their cursor
     fa::Buf<fa::StatsEdge> dStatsEdges;
     fa::Buf<unsigned long long> dStatsCursor;
     uint64_t statsEdgeCap = 0;                  // rows of dStatsEdges the kernel may write: STATS_EDGES_FIRST, then the largest count seen
     uint64_t statsEdges = 0, statsReruns = 0;   // the last call's: mbgc_fasta_stats_last
-    fa::Buf<uint32_t> dSkGroups;                // mbgc_fasta_sketch_dev (records and tiles: dFindRecs, dFindTiles): the records' groups, the groups' k-mers and starts,
+    fa::Buf<uint32_t> dSkGroups;                // mbgc_fasta_sketch_dev: the records' groups, the groups' k-mers and starts,
     fa::Buf<unsigned long long> dSkKmers, dSkStart, dSkWords;     // the cursor and the distinct total (dSkWords), the rows twice over (the sort's two sides),
     fa::Buf<uint64_t> dSkHash, dSkHash2;        // the flags, their sums and the sort's scratch
     fa::Buf<uint32_t> dSkGroup, dSkGroup2, dSkFlag, dSkPos;
@@ -1265,8 +1300,8 @@ struct mbgc_fasta {
     uint64_t sketchRowCap = 0;                  // rows the kernel may write: SKETCH_ROWS_FIRST, then the largest count seen
     uint64_t sketchRows = 0, sketchReruns = 0;  // the last call's: mbgc_fasta_sketch_last
     double sketchSortMs = 0;
-    hipEvent_t skEv[4] = {nullptr, nullptr, nullptr, nullptr};    // around the scan, around the sort and the compaction
-    fa::Buf<unsigned long long> dDupRows;       // mbgc_fasta_dups_dev (records and tiles: dFindRecs, dFindTiles): the records' eight sums, the pair list, the pairs' verdicts
+    fa::Timer sortTimer;                        // around the sort and the compaction (the scan: `timer`)
+    fa::Buf<unsigned long long> dDupRows;       // mbgc_fasta_dups_dev: the records' eight sums, the pair list, the pairs' verdicts
     fa::Buf<fa::DupsPair> dDupPairs;
     fa::Buf<uint32_t> dDupRefuted;
     uint64_t dupBuckets = 0, dupVerified = 0, dupRefuted = 0;     // the last call's: mbgc_fasta_dups_last
@@ -1296,6 +1331,39 @@ struct mbgc_fasta {
     uint64_t hostParsedBytes = 0;               // sequence bytes mbgc_fasta_parse_host2 left in dHostOut (mbgc_fasta_probe_host)
 };
 
+namespace fa {
+
+// the first of recs[0, n) that does not lie inside a buffer of seqBytes bytes; n when all do
+static uint64_t first_outside(const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint64_t seqBytes) {
+    uint64_t r = 0;
+    while (r < n && recs[r].off <= seqBytes && recs[r].len <= seqBytes - recs[r].off) r++;
+    return r;
+}
+
+// How find, stats, dups and sketch (`what`) open: the records are counted and held to the buffer — a refusal touches nothing —, cut
+// into the tiles of fasta_tiles.h, positionsOf(r) being the start positions the scan has in record r, and, when there is a tile at all,
+// uploaded with the tiles' prefix sum to dScanRecs / dScanTiles on the handle's stream. -> 0 and the number of tiles, or the refusal
+template <class Positions>
+static int scan_prepare(mbgc_fasta *p, const char *what, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                        Positions positionsOf, uint64_t &ntiles) {
+    static_assert(sizeof(ScanRec) == sizeof(mbgc_fasta_crc_rec_t), "the kernels read the ABI's ranges");
+    if (n >= 0xffffffffull) return fail(-103, "%s: %llu records in one call", what, (unsigned long long) n);
+    if (const uint64_t r = first_outside(recs, n, seqBytes); r < n) return fail(-103, "%s: record %llu lies outside the buffer", what, (unsigned long long) r);
+    std::vector<uint64_t> &tileStart = p->scanTileStart;             // (the handle's: the copy below may read it until the entry point synchronises)
+    tileStart.assign(n + 1, 0);
+    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + scan_tiles_of((uintptr_t) seq_dev + recs[r].off, positionsOf(r));
+    ntiles = tileStart[n];
+    if (ntiles == 0) return 0;
+    FCHK(hipSetDevice(p->device));
+    FTRY(p->dScanRecs.reserve(n));
+    FTRY(p->dScanTiles.reserve(n + 1));
+    FCHK(hipMemcpyAsync(p->dScanRecs.p, recs, n * sizeof(ScanRec), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dScanTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    return 0;
+}
+
+}  // namespace fa
+
 extern "C" {
 
 const char *mbgc_fasta_last_error(void) { return fa::g_err.c_str(); }
@@ -1317,27 +1385,11 @@ void mbgc_fasta_destroy(mbgc_fasta_t *p) {
     if (!p) return;
     (void) hipSetDevice(p->device);
     if (p->stream) { (void) hipStreamSynchronize(p->stream); (void) hipStreamDestroy(p->stream); }
-    p->dFiles.release(); p->dOwner.release(); p->dSums.release(); p->dIns.release(); p->dOut.release(); p->dBases.release(); p->dRecs.release(); p->dShift.release(); p->dHostIn.release(); p->dHostOut.release();
-    p->dTileFirst.release(); p->dSplit.release(); p->dFmtRecs.release(); p->dFmtOwner.release(); p->dGatherTab.release(); p->dGatherOut.release();
-    p->dProbeRecs.release(); p->dProbeCounts.release(); p->dProbeOut.release();
-    p->dCmpPieces.release(); p->dCmpOwner.release(); p->dCmpOut.release();
-    p->dPackPieces.release(); p->dPackOwner.release();
-    p->dSelRecs.release(); p->dSelSlots.release(); p->dSelPats.release(); p->dSelBytes.release(); p->dSelChosen.release();
-    p->dFindRecs.release(); p->dFindTiles.release(); p->dFindSlots.release(); p->dFindSeeds.release(); p->dFindPats.release(); p->dFindBytes.release();
-    p->dFindHits.release(); p->dFindCursor.release();
-    p->dStatsCounts.release(); p->dStatsEdges.release(); p->dStatsCursor.release();
-    p->dSkGroups.release(); p->dSkKmers.release(); p->dSkStart.release(); p->dSkWords.release(); p->dSkHash.release(); p->dSkHash2.release();
-    p->dSkGroup.release(); p->dSkGroup2.release(); p->dSkFlag.release(); p->dSkPos.release(); p->dSkTmp.release();
-    p->dDupRows.release(); p->dDupPairs.release(); p->dDupRefuted.release();
-    p->dPairHashes.release(); p->dPairStart.release(); p->dPairList.release(); p->dPairShared.release();
-    p->dCrcRows.release(); p->dCrcBehind.release(); p->dCrcOut.release(); p->dCrcConsts.release();
-    p->dInfJobs.release(); p->dInfResults.release();
-    p->dDefChunks.release(); p->dDefSlots.release(); p->dDefOuts.release(); p->dDefPack.release(); p->dDefJobs.release(); p->dDefCrc.release();
     if (p->copyStream) { (void) hipStreamSynchronize(p->copyStream); (void) hipStreamDestroy(p->copyStream); }
-    for (hipEvent_t e : p->fmtEv) if (e) (void) hipEventDestroy(e);
-    for (hipEvent_t e : p->skEv) if (e) (void) hipEventDestroy(e);
+    p->timer.destroy();
+    p->sortTimer.destroy();
     for (hipEvent_t e : p->copyEv) if (e) (void) hipEventDestroy(e);
-    delete p;
+    delete p;                                                         // (every fa::Buf frees itself)
 }
 
 int mbgc_fasta_parse_batch_dev2(mbgc_fasta_t *p, const uint8_t *files_dev, const uint64_t *fileOff, int nf, uint32_t flags,
@@ -1581,17 +1633,16 @@ int mbgc_fasta_format_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
     fmt_build_owner(table, nrec, mis, ntiles, owner);
     int rc;
     if ((rc = p->dFmtRecs.reserve(nrec + 1)) || (rc = p->dFmtOwner.reserve((size_t) ntiles + 1))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }   // (the handle's: freed with it)
     FCHK(hipMemcpyAsync(p->dFmtRecs.p, table.data(), (nrec + 1) * sizeof(FmtRec), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dFmtOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
         k_fa_format<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(seq_dev, seqBytes, headers_dev, p->dFmtRecs.p, p->dFmtOwner.p,
                                                                                             t0, ntiles, mis, total, text_dev);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     return 0;
 }
 
@@ -1621,20 +1672,19 @@ int mbgc_fasta_compare_dev(mbgc_fasta_t *p, const uint8_t *a_dev, uint64_t aByte
     cmp_build_owner(table, ntiles, owner);
     int rc;
     if ((rc = p->dCmpPieces.reserve(table.size())) || (rc = p->dCmpOwner.reserve((size_t) ntiles + 1)) || (rc = p->dCmpOut.reserve(nslots))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dCmpPieces.p, table.data(), table.size() * sizeof(CmpPiece), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dCmpOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemsetAsync(p->dCmpOut.p, 0xff, (size_t) nslots * sizeof(unsigned long long), p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
         k_fa_compare<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(a_dev, b_dev, p->dCmpPieces.p, p->dCmpOwner.p, t0, ntiles, total,
                                                                                              p->dCmpOut.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     std::vector<unsigned long long> out(nslots);                     // (the caller's array stays as it is unless the whole call succeeds)
     FCHK(hipMemcpyAsync(out.data(), p->dCmpOut.p, (size_t) nslots * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     for (uint32_t s = 0; s < nslots; s++) firstDiff[s] = out[s];
     return 0;
 }
@@ -1664,17 +1714,16 @@ int mbgc_fasta_pack_dev(mbgc_fasta_t *p, const uint8_t *src_dev, uint64_t srcByt
     pack_build_owner(table, mis, ntiles, owner);
     int rc;
     if ((rc = p->dPackPieces.reserve(table.size())) || (rc = p->dPackOwner.reserve((size_t) ntiles + 1))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dPackPieces.p, table.data(), table.size() * sizeof(PackPiece), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dPackOwner.p, owner.data(), ((size_t) ntiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint32_t t0 = 0; t0 < ntiles; t0 += FMT_SLICE)
         k_fa_pack<<<dim3(std::min(FMT_SLICE, ntiles - t0)), dim3(THREADS), 0, p->stream>>>(src_dev, p->dPackPieces.p, p->dPackOwner.p, t0, ntiles, mis, total,
                                                                                           (flags & MBGC_FASTA_UPPERCASE) ? 1 : 0, dst_dev);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     return 0;
 }
 
@@ -1699,22 +1748,21 @@ int mbgc_fasta_match_headers_dev(mbgc_fasta_t *p, const uint8_t *headers_dev, ui
     int rc;
     if ((rc = p->dSelRecs.reserve(2 * nrec)) || (rc = p->dSelSlots.reserve(T.slots.size())) || (rc = p->dSelPats.reserve(T.pats.size())) ||
         (rc = p->dSelBytes.reserve(patBytes)) || (rc = p->dSelChosen.reserve(words))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dSelRecs.p, hdrOff, nrec * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dSelRecs.p + nrec, hdrLen, nrec * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dSelSlots.p, T.slots.data(), T.slots.size() * sizeof(SelSlot), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dSelPats.p, T.pats.data(), T.pats.size() * sizeof(SelPat), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dSelBytes.p, patterns, patBytes, hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemsetAsync(p->dSelChosen.p, 0, words * sizeof(uint32_t), p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     k_fa_match_headers<<<dim3((uint32_t) std::min<uint64_t>(nrec, 1u << 16)), dim3(WAVE), 0, p->stream>>>(headers_dev, p->dSelRecs.p, p->dSelRecs.p + nrec, nrec, T.m,
                                                                                                         p->dSelSlots.p, T.bits, p->dSelPats.p, p->dSelBytes.p, p->dSelChosen.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     std::vector<uint32_t> out(words);                                // (the caller's array stays as it is unless the whole call succeeds)
     FCHK(hipMemcpyAsync(out.data(), p->dSelChosen.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     memcpy(chosen, out.data(), words * sizeof(uint32_t));
     return 0;
 }
@@ -1723,7 +1771,6 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
                         const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
                         mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs) {
     using namespace fa;
-    static_assert(sizeof(FindRec) == sizeof(mbgc_fasta_crc_rec_t), "the kernel reads the ABI's ranges");
     if (kernelMs) *kernelMs = 0;
     const uint32_t K = maxMismatches;
     if (K > FIND_MAX_K) return fail(-103, "find: %u mismatches (at most %u)", K, FIND_MAX_K);
@@ -1736,43 +1783,35 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
         for (uint64_t i = patOff[q]; i < patOff[q + 1]; i++)
             if ((uint8_t) ((patterns_host[i] | 0x20) - 'a') >= 26) return fail(-103, "find: pattern %llu holds a byte that is no letter (0x%02x at %llu)", (unsigned long long) q, patterns_host[i], (unsigned long long) (i - patOff[q]));
     }
-    for (uint64_t r = 0; r < n; r++)
-        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "find: record %llu lies outside the buffer", (unsigned long long) r);
-    if (n == 0 || npat == 0) { *nHits = 0; return 0; }
-    FindTable T;
-    find_build_table(patterns_host, patOff, npat, K, T);
-    std::vector<uint64_t> tileStart(n + 1, 0);
-    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + find_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len, T.shortest);
-    const uint64_t ntiles = tileStart[n];
-    if (ntiles == 0) { *nHits = 0; return 0; }                       // (no record is as long as the shortest pattern)
-    FCHK(hipSetDevice(p->device));
+    FindTable T;                                                     // (made only when there is something to search with and in)
+    if (n && npat) find_build_table(patterns_host, patOff, npat, K, T);
+    uint64_t ntiles = 0;
+    FTRY(scan_prepare(p, "find", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return npat ? find_positions(recs[r].len, T.shortest) : 0; }, ntiles));
+    if (ntiles == 0) { *nHits = 0; return 0; }                       // (no record, no pattern, or no record as long as the shortest pattern)
     int rc;
-    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dFindSlots.reserve(T.slots.size())) || (rc = p->dFindSeeds.reserve(T.seeds.size())) ||
+    if ((rc = p->dFindSlots.reserve(T.slots.size())) || (rc = p->dFindSeeds.reserve(T.seeds.size())) ||
         (rc = p->dFindPats.reserve(T.pats.size())) || (rc = p->dFindBytes.reserve(T.bytes.size())) || (rc = p->dFindHits.reserve(std::max<uint64_t>(hitCap, 1))) ||
         (rc = p->dFindCursor.reserve(1))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
-    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
-    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dFindSlots.p, T.slots.data(), T.slots.size() * sizeof(FindSlot), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dFindSeeds.p, T.seeds.data(), T.seeds.size() * sizeof(FindSeed), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dFindPats.p, T.pats.data(), T.pats.size() * sizeof(FindPat), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dFindBytes.p, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemsetAsync(p->dFindCursor.p, 0, sizeof(unsigned long long), p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     // one launch whatever n is: the blocks stride over the tiles, four blocks of four waves to a CU
     const dim3 grid((uint32_t) std::min<uint64_t>(ntiles, 1024));
     if (T.bits <= FIND_LDS_BITS)
-        k_fa_find<true><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
+        k_fa_find<true><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScanTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
                                                                     p->dFindPats.p, p->dFindBytes.p, K, p->dFindHits.p, hitCap, p->dFindCursor.p);
     else
-        k_fa_find<false><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
+        k_fa_find<false><<<grid, dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScanTiles.p, (uint32_t) n, ntiles, p->dFindSlots.p, T.bits, p->dFindSeeds.p,
                                                                      p->dFindPats.p, p->dFindBytes.p, K, p->dFindHits.p, hitCap, p->dFindCursor.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     unsigned long long count = 0;
     FCHK(hipMemcpyAsync(&count, p->dFindCursor.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     *nHits = count;
     if (count > hitCap) return fail(-104, "find: %llu hits, the buffer holds %llu", count, (unsigned long long) hitCap);
     if (count == 0) return 0;
@@ -1793,43 +1832,35 @@ int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBy
                          uint64_t *nRuns, double *kernelMs) {
     using namespace fa;
     static_assert(sizeof(mbgc_fasta_counts_t) == 8 * sizeof(uint64_t) && sizeof(StatsEdge) == 16, "a record's row is eight words; an edge is sixteen bytes");
-    if (n >= 0xffffffffull) return fail(-103, "stats: %llu records in one call", (unsigned long long) n);
-    for (uint64_t r = 0; r < n; r++)
-        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "stats: record %llu lies outside the buffer", (unsigned long long) r);
-    if (kernelMs) *kernelMs = 0;
-    p->statsEdges = p->statsReruns = 0;
     const bool counting = (flags & MBGC_FASTA_STATS_COUNTS) != 0;
     const uint32_t want = (flags & MBGC_FASTA_STATS_NRUNS ? STATS_CLS_N : 0u) | (flags & MBGC_FASTA_STATS_LOWER ? STATS_CLS_LOWER : 0u);
-    std::vector<uint64_t> tileStart(n + 1, 0);
-    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + stats_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len);
-    const uint64_t ntiles = tileStart[n];
-    if (ntiles == 0 || (!counting && !want)) {                       // (no byte to look at, or nothing asked)
+    uint64_t ntiles = 0;                                             // (nothing asked: no position is looked at)
+    FTRY(scan_prepare(p, "stats", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return counting || want ? recs[r].len : 0; }, ntiles));
+    if (kernelMs) *kernelMs = 0;
+    p->statsEdges = p->statsReruns = 0;
+    if (ntiles == 0) {                                               // (no byte to look at, or nothing asked)
         if (counting && n) memset(counts_host, 0, n * sizeof(mbgc_fasta_counts_t));
         *nRuns = 0;
         return 0;
     }
-    FCHK(hipSetDevice(p->device));
     int rc;
-    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dStatsCounts.reserve(8 * n)) || (rc = p->dStatsCursor.reserve(1)) ||
+    if ((rc = p->dStatsCounts.reserve(8 * n)) || (rc = p->dStatsCursor.reserve(1)) ||
         (rc = p->dStatsEdges.reserve(std::max<uint64_t>(STATS_EDGES_FIRST, p->statsEdgeCap)))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
-    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
-    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     // the edge buffer is this call's own: when the cursor passed it, it grows to the cursor's count and the kernel runs again
     uint64_t edgeCap = std::max<uint64_t>(STATS_EDGES_FIRST, p->statsEdgeCap);
     unsigned long long count = 0;
     for (;;) {
         if (counting) FCHK(hipMemsetAsync(p->dStatsCounts.p, 0, 8 * n * sizeof(unsigned long long), p->stream));
         FCHK(hipMemsetAsync(p->dStatsCursor.p, 0, sizeof(unsigned long long), p->stream));
-        if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+        FTRY(p->timer.start(p->stream, kernelMs != nullptr));
         // one launch whatever n is: the blocks stride over the tiles, eight blocks of four waves to a CU (a wave has one load in flight)
-        k_fa_stats<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(STATS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles,
+        k_fa_stats<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(STATS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScanTiles.p, (uint32_t) n, ntiles,
                                                                                                               counting, want, p->dStatsCounts.p, p->dStatsEdges.p, edgeCap, p->dStatsCursor.p);
         FCHK(hipGetLastError());
-        if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+        FTRY(p->timer.stop(p->stream));
         FCHK(hipMemcpyAsync(&count, p->dStatsCursor.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
         FCHK(hipStreamSynchronize(p->stream));
-        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+        FTRY(p->timer.read(kernelMs));
         if (count <= edgeCap) break;
         if ((rc = p->dStatsEdges.reserve(count))) return rc;
         edgeCap = p->statsEdgeCap = count;
@@ -1886,10 +1917,12 @@ int mbgc_fasta_dups_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
     using namespace fa;
     static_assert(sizeof(mbgc_fasta_dup_t) == 8 && sizeof(DupsPair) == 16, "a record's answer is two words; a pair is four");
     static_assert(MBGC_FASTA_DUPS_FORWARD_ONLY == DUPS_FORWARD_ONLY && MBGC_FASTA_DUPS_EXACT_CASE == DUPS_EXACT_CASE && MBGC_FASTA_DUPS_WEAK_HASH == DUPS_WEAK_HASH, "the flags");
-    if (n >= 0xffffffffull) return fail(-103, "dups: %llu records in one call", (unsigned long long) n);
-    if (flags & ~(DUPS_FORWARD_ONLY | DUPS_EXACT_CASE | DUPS_WEAK_HASH)) return fail(-103, "dups: unknown flags %#x", flags);
-    for (uint64_t r = 0; r < n; r++)
-        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "dups: record %llu lies outside the buffer", (unsigned long long) r);
+    // an unknown flag is reported in front of a record outside the buffer, and behind too many records (scan_prepare reports those two)
+    const bool unknownFlags = (flags & ~(DUPS_FORWARD_ONLY | DUPS_EXACT_CASE | DUPS_WEAK_HASH)) != 0;
+    if (unknownFlags && n < 0xffffffffull) return fail(-103, "dups: unknown flags %#x", flags);
+    // ---- the fingerprints: one pass over the tiles of every record with a byte
+    uint64_t ntiles = 0;
+    FTRY(scan_prepare(p, "dups", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return recs[r].len; }, ntiles));
     if (kernelMs) *kernelMs = 0;
     p->dupBuckets = p->dupVerified = p->dupRefuted = 0;
     p->dupVerifyMs = 0;
@@ -1897,29 +1930,20 @@ int mbgc_fasta_dups_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
     if (n == 0) return 0;
     const bool forwardOnly = (flags & DUPS_FORWARD_ONLY) != 0;
     const uint32_t exactCase = (flags & DUPS_EXACT_CASE) != 0;
-    // ---- the fingerprints: one pass over the tiles of every record with a byte
-    std::vector<uint64_t> tileStart(n + 1, 0);
-    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + stats_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len);
-    const uint64_t ntiles = tileStart[n];
     std::vector<unsigned long long> rows(8 * n, 0);
     if (ntiles) {
-        FCHK(hipSetDevice(p->device));
         int rc;
-        if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dDupRows.reserve(8 * n)) || (rc = p->dDupPairs.reserve(n)) || (rc = p->dDupRefuted.reserve(n)))
-            return rc;
-        if (!p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
-        FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
-        FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        if ((rc = p->dDupRows.reserve(8 * n)) || (rc = p->dDupPairs.reserve(n)) || (rc = p->dDupRefuted.reserve(n))) return rc;
         FCHK(hipMemsetAsync(p->dDupRows.p, 0, 8 * n * sizeof(unsigned long long), p->stream));
-        FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+        FTRY(p->timer.start(p->stream));
         // one launch whatever n is: the blocks stride over the tiles, as k_fa_stats's do
-        k_fa_dups<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dFindTiles.p, (uint32_t) n, ntiles,
+        k_fa_dups<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScanTiles.p, (uint32_t) n, ntiles,
                                                                                                             exactCase, p->dDupRows.p);
         FCHK(hipGetLastError());
-        FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+        FTRY(p->timer.stop(p->stream));
         FCHK(hipMemcpyAsync(rows.data(), p->dDupRows.p, 8 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
         FCHK(hipStreamSynchronize(p->stream));
-        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+        FTRY(p->timer.read(kernelMs));
     }
     typedef std::array<uint32_t, 4> Print;
     std::vector<Print> fw(n), rv(n), canon(n);
@@ -1983,15 +2007,15 @@ int mbgc_fasta_dups_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
             verdict.assign(pairs.size(), 0);
             FCHK(hipMemcpyAsync(p->dDupPairs.p, pairs.data(), pairs.size() * sizeof(DupsPair), hipMemcpyHostToDevice, p->stream));
             FCHK(hipMemsetAsync(p->dDupRefuted.p, 0, pairs.size() * sizeof(uint32_t), p->stream));
-            FCHK(hipEventRecord(p->fmtEv[0], p->stream));
-            k_fa_dups_verify<<<dim3((uint32_t) std::min<size_t>(pairs.size(), 4096)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, p->dFindRecs.p, p->dDupPairs.p, (uint32_t) pairs.size(),
+            FTRY(p->timer.start(p->stream));
+            k_fa_dups_verify<<<dim3((uint32_t) std::min<size_t>(pairs.size(), 4096)), dim3(DUPS_THREADS), 0, p->stream>>>(seq_dev, p->dScanRecs.p, p->dDupPairs.p, (uint32_t) pairs.size(),
                                                                                                                           exactCase, p->dDupRefuted.p);
             FCHK(hipGetLastError());
-            FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+            FTRY(p->timer.stop(p->stream));
             FCHK(hipMemcpyAsync(verdict.data(), p->dDupRefuted.p, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
             FCHK(hipStreamSynchronize(p->stream));
-            float ms = 0;
-            FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1]));
+            double ms = 0;
+            FTRY(p->timer.read(&ms));
             p->dupVerifyMs += ms;
             p->dupVerified += pairs.size();
             for (size_t k = 0; k < pairs.size(); k++) {
@@ -2021,28 +2045,22 @@ int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
                           uint32_t k, uint64_t maxHash, uint64_t *hashes_host, uint64_t cap, uint64_t *groupStart_host, uint64_t *kmers_host, uint64_t *total, double *kernelMs) {
     using namespace fa;
     if (k < 1 || k > 32) return fail(-103, "sketch: k = %u (1 to 32)", k);
-    if (n >= 0xffffffffull) return fail(-103, "sketch: %llu records in one call", (unsigned long long) n);
-    for (uint64_t r = 0; r < n; r++) {
-        if (recs[r].off > seqBytes || recs[r].len > seqBytes - recs[r].off) return fail(-103, "sketch: record %llu lies outside the buffer", (unsigned long long) r);
+    // the faults are reported in record order, a record outside the buffer in front of its own group: a group is looked at only in
+    // front of the first such record, which scan_prepare reports (as it does too many records, in front of both)
+    const uint64_t inside = n < 0xffffffffull ? first_outside(recs, n, seqBytes) : 0;
+    for (uint64_t r = 0; r < inside; r++)
         if (group_host[r] >= ngroups) return fail(-103, "sketch: record %llu names group %u of %u", (unsigned long long) r, group_host[r], ngroups);
-    }
+    uint64_t ntiles = 0;
+    FTRY(scan_prepare(p, "sketch", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return sketch_positions(recs[r].len, k); }, ntiles));
     if (kernelMs) *kernelMs = 0;
     p->sketchRows = p->sketchReruns = 0;
     p->sketchSortMs = 0;
-    std::vector<uint64_t> tileStart(n + 1, 0);
-    for (uint64_t r = 0; r < n; r++) tileStart[r + 1] = tileStart[r] + sketch_tiles_of((uintptr_t) seq_dev + recs[r].off, recs[r].len, k);
-    const uint64_t ntiles = tileStart[n];
     *total = 0;
     for (uint32_t g = 0; g <= ngroups; g++) groupStart_host[g] = 0;
     for (uint32_t g = 0; g < ngroups; g++) kmers_host[g] = 0;
     if (ntiles == 0) return 0;                                       // (no record holds a k-mer)
-    FCHK(hipSetDevice(p->device));
     int rc;
-    if ((rc = p->dFindRecs.reserve(n)) || (rc = p->dFindTiles.reserve(n + 1)) || (rc = p->dSkGroups.reserve(n)) || (rc = p->dSkKmers.reserve(ngroups)) ||
-        (rc = p->dSkStart.reserve(ngroups)) || (rc = p->dSkWords.reserve(2))) return rc;
-    for (hipEvent_t &e : p->skEv) if (!e) FCHK(hipEventCreate(&e));
-    FCHK(hipMemcpyAsync(p->dFindRecs.p, recs, n * sizeof(FindRec), hipMemcpyHostToDevice, p->stream));
-    FCHK(hipMemcpyAsync(p->dFindTiles.p, tileStart.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    if ((rc = p->dSkGroups.reserve(n)) || (rc = p->dSkKmers.reserve(ngroups)) || (rc = p->dSkStart.reserve(ngroups)) || (rc = p->dSkWords.reserve(2))) return rc;
     FCHK(hipMemcpyAsync(p->dSkGroups.p, group_host, n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
     // the row buffer is this call's own: when the cursor passed it, it grows to the cursor's count and the kernel runs again
     uint64_t rowCap = std::max<uint64_t>(SKETCH_ROWS_FIRST, p->sketchRowCap);
@@ -2051,15 +2069,15 @@ int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
         if ((rc = p->dSkHash.reserve(rowCap)) || (rc = p->dSkGroup.reserve(rowCap))) return rc;
         FCHK(hipMemsetAsync(p->dSkKmers.p, 0, ngroups * sizeof(unsigned long long), p->stream));
         FCHK(hipMemsetAsync(p->dSkWords.p, 0, 2 * sizeof(unsigned long long), p->stream));
-        FCHK(hipEventRecord(p->skEv[0], p->stream));
+        FTRY(p->timer.start(p->stream));
         // one launch whatever n is: the blocks stride over the tiles, eight blocks of four waves to a CU
-        k_fa_sketch<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(SKETCH_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dFindRecs.p, p->dSkGroups.p, p->dFindTiles.p, (uint32_t) n,
+        k_fa_sketch<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(SKETCH_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dSkGroups.p, p->dScanTiles.p, (uint32_t) n,
                                                                                                                  ntiles, k, maxHash, p->dSkKmers.p, p->dSkHash.p, p->dSkGroup.p, rowCap, p->dSkWords.p);
         FCHK(hipGetLastError());
-        FCHK(hipEventRecord(p->skEv[1], p->stream));
+        FTRY(p->timer.stop(p->stream));
         FCHK(hipMemcpyAsync(&count, p->dSkWords.p, sizeof count, hipMemcpyDeviceToHost, p->stream));
         FCHK(hipStreamSynchronize(p->stream));
-        if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[0], p->skEv[1])); *kernelMs = ms; }
+        FTRY(p->timer.read(kernelMs));
         if (count <= rowCap) break;
         if (count >= 0xffffffffull) return fail(-103, "sketch: %llu rows in one call (a larger scale, or fewer records)", count);
         rowCap = p->sketchRowCap = count;
@@ -2083,7 +2101,7 @@ int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
         if ((rc = p->dSkTmp.reserve(tb))) return rc;
         const uint32_t blocks = (uint32_t) std::min<uint64_t>((count + 255) / 256, 4096);
         FCHK(hipMemsetAsync(p->dSkStart.p, 0xff, ngroups * sizeof(unsigned long long), p->stream));
-        FCHK(hipEventRecord(p->skEv[2], p->stream));
+        FTRY(p->sortTimer.start(p->stream));
         FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t1, p->dSkHash.p, p->dSkHash2.p, p->dSkGroup.p, p->dSkGroup2.p, (size_t) count, 0u, 64u, p->stream));
         FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t2, p->dSkGroup2.p, p->dSkGroup.p, p->dSkHash2.p, p->dSkHash.p, (size_t) count, 0u, gbits, p->stream));
         k_fa_sketch_flag<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dSkHash.p, p->dSkGroup.p, count, p->dSkFlag.p);
@@ -2091,12 +2109,12 @@ int mbgc_fasta_sketch_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqB
         FCHK(rocprim::exclusive_scan(p->dSkTmp.p, t3, p->dSkFlag.p, p->dSkPos.p, 0u, (size_t) count, rocprim::plus<uint32_t>(), p->stream));
         k_fa_sketch_compact<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dSkHash.p, p->dSkGroup.p, p->dSkFlag.p, p->dSkPos.p, count, p->dSkHash2.p, p->dSkStart.p, p->dSkWords.p + 1);
         FCHK(hipGetLastError());
-        FCHK(hipEventRecord(p->skEv[3], p->stream));
+        FTRY(p->sortTimer.stop(p->stream));
         FCHK(hipMemcpyAsync(&distinct, p->dSkWords.p + 1, sizeof distinct, hipMemcpyDeviceToHost, p->stream));
         FCHK(hipMemcpyAsync(starts.data(), p->dSkStart.p, ngroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
     }
     FCHK(hipStreamSynchronize(p->stream));
-    if (count) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[2], p->skEv[3])); p->sketchSortMs = ms; }
+    if (count) FTRY(p->sortTimer.read(&p->sketchSortMs));
     // a group without a row starts where the next one does
     groupStart_host[ngroups] = distinct;
     for (uint32_t g = ngroups; g-- > 0;) groupStart_host[g] = starts[g] == ~0ull ? groupStart_host[g + 1] : starts[g];
@@ -2139,19 +2157,18 @@ int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, co
     int rc;
     if ((rc = p->dPairHashes.reserve(std::max<uint64_t>(nh, 1))) || (rc = p->dPairStart.reserve(ngroups + 1)) || (rc = p->dPairShared.reserve(npairs)) ||
         (pairs_host && (rc = p->dPairList.reserve(2 * npairs)))) return rc;
-    for (hipEvent_t &e : p->skEv) if (!e) FCHK(hipEventCreate(&e));
     if (nh) FCHK(hipMemcpyAsync(p->dPairHashes.p, hashes_host, nh * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dPairStart.p, groupStart_host, (ngroups + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     if (pairs_host) FCHK(hipMemcpyAsync(p->dPairList.p, pairs_host, 2 * npairs * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-    FCHK(hipEventRecord(p->skEv[0], p->stream));
+    FTRY(p->timer.start(p->stream));
     // a wave per pair, four to a block; the waves stride over the pairs
     k_fa_sketch_pairs<<<dim3((uint32_t) std::min<uint64_t>((npairs + 3) / 4, 8192)), dim3(256), 0, p->stream>>>(p->dPairHashes.p, p->dPairStart.p, ngroups, pairs_host ? p->dPairList.p : nullptr,
                                                                                                                   npairs, p->dPairShared.p);
     FCHK(hipGetLastError());
-    FCHK(hipEventRecord(p->skEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     FCHK(hipMemcpyAsync(shared_host, p->dPairShared.p, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->skEv[0], p->skEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     return 0;
 }
 
@@ -2161,11 +2178,9 @@ int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByte
     static_assert(sizeof(CrcIn) == sizeof(mbgc_fasta_crc_rec_t), "the table builder reads the ABI's ranges");
     if (kernelMs) *kernelMs = 0;
     if (n >= CRC_FIRST) return fail(-103, "crc: %llu ranges in one call", (unsigned long long) n);
+    if (const uint64_t k = first_outside(recs, n, seqBytes); k < n) return fail(-103, "crc: range %llu lies outside the buffer", (unsigned long long) k);
     uint64_t nrows = 0;
-    for (uint64_t k = 0; k < n; k++) {
-        if (recs[k].off > seqBytes || recs[k].len > seqBytes - recs[k].off) return fail(-103, "crc: range %llu lies outside the buffer", (unsigned long long) k);
-        nrows += recs[k].len ? (recs[k].len + CRC_PIECE - 1) / CRC_PIECE : 0;
-    }
+    for (uint64_t k = 0; k < n; k++) nrows += (recs[k].len + CRC_PIECE - 1) / CRC_PIECE;
     if (nrows >= 0xffffffffull) return fail(-103, "crc: %llu rows in one call", (unsigned long long) nrows);
     if (nrows == 0) {
         for (uint64_t k = 0; k < n; k++) crc_out_host[k] = 0;
@@ -2183,11 +2198,10 @@ int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByte
         if ((rc = p->dCrcConsts.reserve(1))) return rc;
         FCHK(hipMemcpyAsync(p->dCrcConsts.p, &consts, sizeof consts, hipMemcpyHostToDevice, p->stream));
     }
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dCrcRows.p, rows.data(), rows.size() * sizeof(CrcRow), hipMemcpyHostToDevice, p->stream));
     if (!behind.empty()) FCHK(hipMemcpyAsync(p->dCrcBehind.p, behind.data(), behind.size() * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemsetAsync(p->dCrcOut.p, 0, n * sizeof(uint32_t), p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     // one launch whatever n is: the waves stride over the rows. MBGC_HIP_CRC_LOOKUP=nibble: the per-bank nibble tables, the alternative
     // profiles/crc_bench.py measures the byte table against
     static const bool byteTable = !(getenv("MBGC_HIP_CRC_LOOKUP") && strcmp(getenv("MBGC_HIP_CRC_LOOKUP"), "nibble") == 0);
@@ -2195,11 +2209,11 @@ int mbgc_fasta_crc_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByte
     if (byteTable) k_fa_crc<CRC_LOOKUP_BYTE><<<grid, dim3(CRC_THREADS), 0, p->stream>>>(seq_dev, p->dCrcRows.p, p->dCrcBehind.p, plan, p->dCrcConsts.p, p->dCrcOut.p);
     else k_fa_crc<CRC_LOOKUP_NIBBLE><<<grid, dim3(CRC_THREADS), 0, p->stream>>>(seq_dev, p->dCrcRows.p, p->dCrcBehind.p, plan, p->dCrcConsts.p, p->dCrcOut.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     std::vector<uint32_t> out(n);                                    // (the caller's array stays as it is unless the whole call succeeds)
     FCHK(hipMemcpyAsync(out.data(), p->dCrcOut.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     for (uint64_t k = 0; k < n; k++) crc_out_host[k] = recs[k].len ? ~out[k] : 0u;      // the final XOR, once per range
     return 0;
 }
@@ -2244,18 +2258,17 @@ int mbgc_fasta_inflate_dev(mbgc_fasta_t *p, const uint8_t *gz_dev, uint64_t gzBy
     FCHK(hipSetDevice(p->device));
     int rc;
     if ((rc = p->dInfJobs.reserve(njobs)) || (rc = p->dInfResults.reserve(njobs))) return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dInfJobs.p, jobs, njobs * sizeof(InfJob), hipMemcpyHostToDevice, p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint64_t k0 = 0; k0 < njobs; k0 += FMT_SLICE)
         k_fa_inflate<<<dim3((uint32_t) std::min<uint64_t>(FMT_SLICE, njobs - k0)), dim3(INF_WAVE), 0, p->stream>>>(gz_dev, out_dev, p->dInfJobs.p, (uint32_t) k0, (uint32_t) njobs,
                                                                                                                   p->dInfResults.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     std::vector<InfResult> got(njobs);                               // (the caller's array stays as it is unless the whole call succeeds)
     FCHK(hipMemcpyAsync(got.data(), p->dInfResults.p, njobs * sizeof(InfResult), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float ms = 0; FCHK(hipEventElapsedTime(&ms, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms; }
+    FTRY(p->timer.read(kernelMs));
     memcpy(results, got.data(), njobs * sizeof(InfResult));
     return 0;
 }
@@ -2296,19 +2309,18 @@ int mbgc_fasta_deflate_dev(mbgc_fasta_t *p, const uint8_t *text_dev, uint64_t te
     if ((rc = p->dDefChunks.reserve(nc)) || (rc = p->dDefSlots.reserve((size_t) nc * DEF_SLOT)) || (rc = p->dDefOuts.reserve(nc)) || (rc = p->dDefPack.reserve(nc)) ||
         (rc = p->dDefJobs.reserve(njobs)) || (rc = p->dDefCrc.reserve(njobs)))
         return rc;
-    if (kernelMs && !p->fmtEv[0]) { FCHK(hipEventCreate(&p->fmtEv[0])); FCHK(hipEventCreate(&p->fmtEv[1])); }
     FCHK(hipMemcpyAsync(p->dDefChunks.p, chunks.data(), nc * sizeof(DefChunk), hipMemcpyHostToDevice, p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint32_t c0 = 0; c0 < nc; c0 += FMT_SLICE)
         k_fa_deflate<<<dim3(std::min(FMT_SLICE, nc - c0)), dim3(DEF_WAVE), 0, p->stream>>>(text_dev, p->dDefChunks.p, c0, nc, p->dDefSlots.p, p->dDefOuts.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     // the chunks' sizes come back (8 bytes per chunk with their CRCs); the scan that places them runs here
     std::vector<DefChunkOut> outs(nc);
     FCHK(hipMemcpyAsync(outs.data(), p->dDefOuts.p, nc * sizeof(DefChunkOut), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
     double ms = 0;
-    if (kernelMs) { float t = 0; FCHK(hipEventElapsedTime(&t, p->fmtEv[0], p->fmtEv[1])); ms = t; }
+    FTRY(p->timer.read(&ms));
     std::vector<mbgc_fasta_deflate_result_t> res(njobs);
     uint64_t at = 0;
     for (uint64_t k = 0; k < njobs; k++) {
@@ -2328,16 +2340,18 @@ int mbgc_fasta_deflate_dev(mbgc_fasta_t *p, const uint8_t *text_dev, uint64_t te
     if (at > gzCap) return fail(-104, "gzip output needs %llu bytes, capacity %llu", (unsigned long long) at, (unsigned long long) gzCap);
     FCHK(hipMemcpyAsync(p->dDefPack.p, pack.data(), nc * sizeof(DefPackIn), hipMemcpyHostToDevice, p->stream));
     FCHK(hipMemcpyAsync(p->dDefJobs.p, jtab.data(), njobs * sizeof(DefJobIn), hipMemcpyHostToDevice, p->stream));
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[0], p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
     for (uint32_t c0 = 0; c0 < nc; c0 += FMT_SLICE)
         k_fa_deflate_pack<<<dim3(std::min(FMT_SLICE, nc - c0)), dim3(DEF_WAVE), 0, p->stream>>>(p->dDefSlots.p, p->dDefOuts.p, p->dDefPack.p, p->dDefJobs.p, c0, nc, gz_dev,
                                                                                                p->dDefCrc.p);
     FCHK(hipGetLastError());
-    if (kernelMs) FCHK(hipEventRecord(p->fmtEv[1], p->stream));
+    FTRY(p->timer.stop(p->stream));
     std::vector<uint32_t> crcs(njobs);
     FCHK(hipMemcpyAsync(crcs.data(), p->dDefCrc.p, njobs * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
     FCHK(hipStreamSynchronize(p->stream));
-    if (kernelMs) { float t = 0; FCHK(hipEventElapsedTime(&t, p->fmtEv[0], p->fmtEv[1])); *kernelMs = ms + t; }
+    double packMs = 0;
+    FTRY(p->timer.read(&packMs));
+    if (kernelMs) *kernelMs = ms + packMs;
     for (uint64_t k = 0; k < njobs; k++) res[k].crc32 = crcs[k];
     memcpy(results, res.data(), njobs * sizeof(mbgc_fasta_deflate_result_t));
     return 0;

@@ -1,5 +1,5 @@
-// The scan of `mbgc-hip k` (included by fasta_input.hip, inside namespace fa, behind fasta_find.h, whose FindRec, FindVec and
-// find_tile_record it shares): the tiles of a record, the packing of a vector and the k-mer hashes of one lane. Kept free of HIP calls so
+// The scan of `mbgc-hip k` (included by fasta_input.hip, inside namespace fa, behind fasta_tiles.h, whose grid it
+// scans): the start positions of a record, the packing of a vector and the k-mer hashes of one lane. Kept free of HIP calls so
 // that the same text compiles as plain C++: tests/fasta_sketch_emu.cpp runs the steps tile by tile and lane by lane on the CPU under
 // AddressSanitizer, the wave's shuffles emulated by arrays. The shuffles, the ballot, the atomic cursor of the row buffer, the groups'
 // k-mer counters, the sort and the pair search stay in fasta_input.hip (k_fa_sketch, k_fa_sketch_flag, k_fa_sketch_compact,
@@ -16,16 +16,13 @@
 // vectors, by shuffle inside the wave, by sketch_pack on the vector's address for the wave's last two lanes.
 // ---- a position: the 32 positions from j on are one 64-bit window W (position j on top); fw = W >> (64 - 2 k), never a shift by 64
 // as k >= 1. rc comes from fw with no second state: complement, reverse the 2-bit pairs, shift right by 64 - 2 k (0 at k = 32).
-// ---- tiles: as in fasta_find.h, SKETCH_TILE positions on the 16-byte grid of the buffer's ADDRESSES, one list over all records; a record
-// has tiles for its len - k + 1 k-mer starts, none when it is shorter than k.
-constexpr uint32_t SKETCH_TILE = 4096, SKETCH_THREADS = 256, SKETCH_PER = SKETCH_TILE / SKETCH_THREADS;   // 16 positions per lane
+// ---- tiles: the shared grid of fasta_tiles.h; a record's start positions are its len - k + 1 k-mer starts, none when it is shorter
+// than k (sketch_positions).
+constexpr uint32_t SKETCH_TILE = SCAN_TILE, SKETCH_THREADS = SCAN_THREADS, SKETCH_PER = SCAN_PER;   // 16 positions per lane: a 32-bit code word, a 16-bit invalid mask
 constexpr uint64_t SKETCH_ROWS_FIRST = 65536;                        // rows of the entry point's first row buffer; it grows to the cursor's count
 constexpr uint64_t SKETCH_SEED = 0x9E3779B97F4A7C15ull;
-static_assert(SKETCH_PER == 16, "a lane reads its 16 positions as one vector: a 32-bit code word and a 16-bit invalid mask");
 
-__host__ __device__ __forceinline__ uint64_t sketch_tiles_of(uintptr_t first, uint64_t len, uint32_t k) {
-    return len >= k ? ((first & 15) + (len - k + 1) + SKETCH_TILE - 1) / SKETCH_TILE : 0;
-}
+__host__ __device__ __forceinline__ uint64_t sketch_positions(uint64_t len, uint32_t k) { return len >= k ? len - k + 1 : 0; }
 
 // MurmurHash3's 64-bit finaliser
 __host__ __device__ __forceinline__ uint64_t sketch_fmix64(uint64_t x) {
@@ -54,12 +51,12 @@ __host__ __device__ __forceinline__ uint32_t sketch_code(uint8_t b) {
 
 // the first step: the vector at address v (a multiple of 16, anywhere) -> codes | bad << 32 for record `rec`. 0xffff << 32 — all
 // invalid, nothing read — when none of its positions lies in the record
-__device__ __forceinline__ uint64_t sketch_pack(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec rec, uintptr_t v) {
+__device__ __forceinline__ uint64_t sketch_pack(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec rec, uintptr_t v) {
     const uintptr_t lo = (uintptr_t) seq, hi = lo + seqBytes;
     const int64_t t0 = (int64_t) v - (int64_t) (lo + rec.off);     // the vector's first position in the record
     if (t0 + (int64_t) SKETCH_PER <= 0 || t0 >= (int64_t) rec.len) return (uint64_t) 0xffff << 32;
-    FindVec x = {{0, 0, 0, 0}};
-    if (v >= lo && v + 16 <= hi) x = *(const FindVec *) v;
+    ScanVec x = {{0, 0, 0, 0}};
+    if (v >= lo && v + 16 <= hi) x = *(const ScanVec *) v;
     else
 #pragma unroll
         for (uint32_t j = 0; j < 16; j++)

@@ -1,5 +1,5 @@
-// The scan of `mbgc-hip s` (included by fasta_input.hip, inside namespace fa, behind fasta_find.h, whose FindRec, FindVec and
-// find_tile_record it shares): the tiles of a record, the classes of a byte and the steps of one lane. Kept free of HIP calls so that the
+// The scan of `mbgc-hip s` (included by fasta_input.hip, inside namespace fa, behind fasta_tiles.h, whose grid it
+// scans): the classes of a byte and the steps of one lane. Kept free of HIP calls so that the
 // same text compiles as plain C++: tests/fasta_stats_emu.cpp runs the steps tile by tile and lane by lane on the CPU under
 // AddressSanitizer, the wave's shuffles emulated by arrays. The shuffles, the block's sum in LDS, the atomic adds to a record's row and
 // the atomic cursor of the edge buffer stay in fasta_input.hip (k_fa_stats).
@@ -13,14 +13,12 @@
 // position outside the record is 0 whatever memory holds there; the bit in front of the mask and the bit behind it are the
 // neighbouring lane's (a shuffle) or, for the first and last lane of a wave, one guarded byte load (stats_class_at). The edges of a
 // record and class pair up when sorted: the i-th start with the i-th end.
-// ---- tiles: as in fasta_find.h, STATS_TILE positions on the 16-byte grid of the buffer's ADDRESSES, one list over all records, a
-// prefix sum of the records' tile counts, the record of a tile by bisection (find_tile_record). Every record with a byte has tiles. A
+// ---- tiles: the shared grid of fasta_tiles.h; a record's start positions are its bytes, so every record with a byte has tiles. A
 // lane reads its 16 positions as one aligned vector; a vector that does not lie inside seq[0, seqBytes) whole is read byte by byte,
 // the bytes inside only (find_stage_step's rule), and a lane none of whose positions lie in the record reads nothing.
-constexpr uint32_t STATS_TILE = 4096, STATS_THREADS = 256, STATS_PER = STATS_TILE / STATS_THREADS;   // 16 positions per lane
+constexpr uint32_t STATS_TILE = SCAN_TILE, STATS_THREADS = SCAN_THREADS, STATS_PER = SCAN_PER;   // 16 positions per lane: a class is a 16-bit mask
 constexpr uint64_t STATS_EDGES_FIRST = 65536;                         // rows of the entry point's first edge buffer; it grows to the cursor's count
 constexpr uint32_t STATS_CLS_N = 1u, STATS_CLS_LOWER = 2u;            // the class bits of a byte
-static_assert(STATS_PER == 16, "a lane reads its 16 positions as one vector and holds a class as a 16-bit mask");
 
 struct StatsEdge { uint64_t pos; uint32_t rec, kind; };               // kind: the class (0, 1), + 2 for an end
 struct StatsLane {
@@ -29,28 +27,24 @@ struct StatsLane {
 };
 struct StatsEdges { uint32_t startN, endN, startL, endL; };          // 16-bit masks over the lane's positions
 
-__host__ __device__ __forceinline__ uint64_t stats_tiles_of(uintptr_t first, uint64_t len) {
-    return len ? ((first & 15) + len + STATS_TILE - 1) / STATS_TILE : 0;
-}
-
 __host__ __device__ __forceinline__ uint32_t stats_class(uint8_t b) {
     return ((b | 0x20) == 'n' ? STATS_CLS_N : 0u) | ((uint8_t) (b - 'a') < 26 ? STATS_CLS_LOWER : 0u);
 }
 
 // the class bits of position t of the record, 0 for a position outside it: the one guarded load of a wave's first and last lane
-__device__ __forceinline__ uint32_t stats_class_at(const uint8_t *__restrict__ seq, const FindRec rec, int64_t t) {
+__device__ __forceinline__ uint32_t stats_class_at(const uint8_t *__restrict__ seq, const ScanRec rec, int64_t t) {
     return t >= 0 && (uint64_t) t < rec.len ? stats_class(seq[rec.off + (uint64_t) t]) : 0u;
 }
 
 // the first step: lane `lane` (of STATS_THREADS) owns the STATS_PER positions from address tileAddr + 16 lane on
-__device__ __forceinline__ StatsLane stats_lane_step(const uint8_t *__restrict__ seq, uint64_t seqBytes, const FindRec rec, uintptr_t tileAddr, uint32_t lane) {
+__device__ __forceinline__ StatsLane stats_lane_step(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec rec, uintptr_t tileAddr, uint32_t lane) {
     StatsLane L = {0, 0, 0};
     const uintptr_t lo = (uintptr_t) seq, hi = lo + seqBytes, v = tileAddr + 16u * lane;
     // the lane's first position in the record; in front of the record in its first tile only
     const int64_t t0 = (int64_t) v - (int64_t) (lo + rec.off);
     if (t0 + (int64_t) STATS_PER <= 0 || t0 >= (int64_t) rec.len) return L;
-    FindVec x = {{0, 0, 0, 0}};
-    if (v >= lo && v + 16 <= hi) x = *(const FindVec *) v;
+    ScanVec x = {{0, 0, 0, 0}};
+    if (v >= lo && v + 16 <= hi) x = *(const ScanVec *) v;
     else
 #pragma unroll
         for (uint32_t k = 0; k < 16; k++)

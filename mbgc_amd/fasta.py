@@ -1,5 +1,6 @@
 """ctypes view of include/mbgc_fasta.h — the input stage (kseq_read_lossless_fasta, or kseq_read_lossy, for whole files in HBM)."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -205,6 +206,31 @@ def _lib():
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
     return L
+
+
+def _ranges(ranges):
+    """rows of (off, len) -> (the uint64 array that holds them for the call, it as mbgc_fasta_crc_rec_t *, their number)"""
+    rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+    return rows, rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0]
+
+
+def _with_capacity(call, first, given, too_many, calls):
+    """call(cap) -> (status, the count the call states, a function that makes the answer): made with the capacity `given`, or, when
+    the caller left it open, with `first` and then with the count a -104 states, `calls` times at most (math.inf: as often as it
+    takes). A -104 that is left raises too_many (.needed = the count), any other failure SwsemError"""
+    cap = first if given is None else int(given)
+    made = 0
+    while True:
+        r, needed, answer = call(cap)
+        made += 1
+        if r == -104 and given is None and made < calls:
+            cap = needed
+            continue
+        if r == -104:
+            raise too_many(_lib().mbgc_fasta_last_error().decode(), needed)
+        if r:
+            raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
+        return answer()
 
 
 def dups_comp_table():
@@ -419,12 +445,10 @@ class FastaParser:
         """ranges = rows of (off, len): zlib's crc32 of seq[off, off + len) of a device buffer of seq_bytes bytes, one per range, taken
         on the device in one launch -> (uint32 per range, the kernel's ms). The ranges may overlap, repeat and come in any order; one
         of no bytes gives 0. A refused call (a range outside the buffer) raises and launches nothing."""
-        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
-        n = rows.shape[0]
+        rows, recs, n = _ranges(ranges)                                  # (rows: held so that recs stays valid through the call)
         out = np.zeros(max(n, 1), dtype=np.uint32)
         ms = C.c_double(0)
-        if _lib().mbgc_fasta_crc_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), n, out.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                     C.byref(ms)):
+        if _lib().mbgc_fasta_crc_dev(self.h, seq_ptr, int(seq_bytes), recs, n, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out[:n], ms.value
 
@@ -435,25 +459,18 @@ class FastaParser:
         the kernel's ms). hit_cap=None: the call is made again with the capacity it asks for when the hits do not fit; a given
         hit_cap: HitsTooMany (.needed = the exact count) when they do not. A refused call (a pattern that is too short for
         max_mismatches, too long or holds a non-letter, max_mismatches > 3, a record outside the buffer) raises and launches nothing."""
-        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        rows, recs, nrec = _ranges(ranges)
         pats = [bytes(x) for x in patterns]
         blob = np.frombuffer(b"".join(pats) + b"\0", dtype=np.uint8)      # (one byte more: an empty list still has an address)
         pat_off = np.concatenate([[0], np.cumsum([len(x) for x in pats], dtype=np.uint64)]).astype(np.uint64)
-        cap = 4096 if hit_cap is None else int(hit_cap)
         n, ms = C.c_uint64(0), C.c_double(0)
-        while True:
+
+        def call(cap):
             out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
-            r = _lib().mbgc_fasta_find_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0],
-                                           blob.ctypes.data_as(C.c_void_p), pat_off.ctypes.data_as(C.POINTER(C.c_uint64)), len(pats), int(max_mismatches),
-                                           out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
-            if r == -104 and hit_cap is None:
-                cap = int(n.value)
-                continue
-            if r == -104:
-                raise HitsTooMany(_lib().mbgc_fasta_last_error().decode(), int(n.value))
-            if r:
-                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
-            return out[: n.value].copy(), ms.value
+            r = _lib().mbgc_fasta_find_dev(self.h, seq_ptr, int(seq_bytes), recs, nrec, blob.ctypes.data_as(C.c_void_p), pat_off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           len(pats), int(max_mismatches), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
+            return r, int(n.value), lambda: (out[: n.value].copy(), ms.value)
+        return _with_capacity(call, 4096, hit_cap, HitsTooMany, calls=math.inf)
 
     def stats_dev(self, seq_ptr, seq_bytes, ranges, flags=STATS_COUNTS | STATS_NRUNS | STATS_LOWER, min_run_n=1, min_run_lower=1, run_cap=None):
         """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes -> (counts: an (n, 8)
@@ -462,22 +479,16 @@ class FastaParser:
         min_run_lower bytes (0 is read as 1), sorted by (rec, cls, start); the kernel's ms). run_cap=None: the call is made once more
         with the count it states when the runs do not fit; a given run_cap: RunsTooMany (.needed = the exact count) when they do
         not. A record outside the buffer raises and launches nothing. last_stats(): the edges and the kernel's reruns of this call."""
-        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
-        counts = np.zeros((max(rows.shape[0], 1), 8), dtype=np.uint64)
-        cap = 4096 if run_cap is None else int(run_cap)
+        rows, recs, nrec = _ranges(ranges)
+        counts = np.zeros((max(nrec, 1), 8), dtype=np.uint64)
         n, ms = C.c_uint64(0), C.c_double(0)
-        for attempt in range(2):
+
+        def call(cap):
             out = np.zeros(max(cap, 1), dtype=RUN_DTYPE)
-            r = _lib().mbgc_fasta_stats_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0], int(flags), int(min_run_n),
-                                            int(min_run_lower), counts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
-            if r == -104 and run_cap is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            if r == -104:
-                raise RunsTooMany(_lib().mbgc_fasta_last_error().decode(), int(n.value))
-            if r:
-                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
-            return counts[: rows.shape[0]].copy(), out[: n.value].copy(), ms.value
+            r = _lib().mbgc_fasta_stats_dev(self.h, seq_ptr, int(seq_bytes), recs, nrec, int(flags), int(min_run_n), int(min_run_lower),
+                                            counts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
+            return r, int(n.value), lambda: (counts[:nrec].copy(), out[: n.value].copy(), ms.value)
+        return _with_capacity(call, 4096, run_cap, RunsTooMany, calls=2)
 
     def last_stats(self):
         """(edges, reruns) of the last stats_dev call: the edges its kernel reported, and how often it ran again for a larger buffer"""
@@ -492,26 +503,19 @@ class FastaParser:
         canonical k-mer ^ a seed, kept when <= max_hash), not Mash's. cap=None: the call is made once more with the count it states
         when the hashes do not fit; a given cap: SketchTooLarge (.needed = the exact count) when they do not. k outside 1..32, a record
         outside the buffer or a group >= ngroups raises and launches nothing. last_sketch(): the rows, the reruns and the sort's ms."""
-        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        rows, recs, nrec = _ranges(ranges)
         grp = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
-        if grp.size != rows.shape[0]:
-            raise ValueError("sketch_dev: %d records, %d group ids" % (rows.shape[0], grp.size))
+        if grp.size != nrec:
+            raise ValueError("sketch_dev: %d records, %d group ids" % (nrec, grp.size))
         start, kmers = np.zeros(int(ngroups) + 1, dtype=np.uint64), np.zeros(max(int(ngroups), 1), dtype=np.uint64)
-        size = 4096 if cap is None else int(cap)
         n, ms = C.c_uint64(0), C.c_double(0)
-        for attempt in range(2):
+
+        def call(size):
             out = np.zeros(max(size, 1), dtype=np.uint64)
-            r = _lib().mbgc_fasta_sketch_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), rows.shape[0], grp.ctypes.data_as(C.c_void_p), int(ngroups),
-                                             int(k), int(max_hash), out.ctypes.data_as(C.c_void_p), size, start.ctypes.data_as(C.c_void_p), kmers.ctypes.data_as(C.c_void_p),
-                                             C.byref(n), C.byref(ms))
-            if r == -104 and cap is None and attempt == 0:
-                size = int(n.value)
-                continue
-            if r == -104:
-                raise SketchTooLarge(_lib().mbgc_fasta_last_error().decode(), int(n.value))
-            if r:
-                raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
-            return out[: n.value].copy(), start, kmers[: int(ngroups)].copy(), ms.value
+            r = _lib().mbgc_fasta_sketch_dev(self.h, seq_ptr, int(seq_bytes), recs, nrec, grp.ctypes.data_as(C.c_void_p), int(ngroups), int(k), int(max_hash),
+                                             out.ctypes.data_as(C.c_void_p), size, start.ctypes.data_as(C.c_void_p), kmers.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(ms))
+            return r, int(n.value), lambda: (out[: n.value].copy(), start, kmers[: int(ngroups)].copy(), ms.value)
+        return _with_capacity(call, 4096, cap, SketchTooLarge, calls=2)
 
     def last_sketch(self):
         """(rows, reruns, sort_ms) of the last sketch_dev call: the (hash, group) rows its kernel reported, how often it ran again for a
@@ -548,15 +552,13 @@ class FastaParser:
         DUPS_WEAK_HASH (tests) keeps 4 bits of the fingerprints; the answer does not change. out: an array of DUP_DTYPE to fill (a
         refused call — a record outside the buffer, an unknown flag — raises, launches nothing and leaves it as it was).
         last_dups(): the buckets, the pairs compared and refuted, the comparisons' ms."""
-        rows = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
-        n = rows.shape[0]
+        rows, recs, n = _ranges(ranges)                                  # (rows: held so that recs stays valid through the call)
         if out is None:
             out = np.zeros(max(n, 1), dtype=DUP_DTYPE)
         if out.dtype != DUP_DTYPE or out.size < n or not out.flags["C_CONTIGUOUS"]:
             raise ValueError("dups_dev: out must be a contiguous array of DUP_DTYPE with a row per record")
         classes, ms = C.c_uint64(0), C.c_double(0)
-        if _lib().mbgc_fasta_dups_dev(self.h, seq_ptr, int(seq_bytes), rows.ctypes.data_as(C.POINTER(CrcRec)), n, int(flags), out.ctypes.data_as(C.c_void_p), C.byref(classes),
-                                      C.byref(ms)):
+        if _lib().mbgc_fasta_dups_dev(self.h, seq_ptr, int(seq_bytes), recs, n, int(flags), out.ctypes.data_as(C.c_void_p), C.byref(classes), C.byref(ms)):
             raise binding.SwsemError(_lib().mbgc_fasta_last_error().decode())
         return out[:n], int(classes.value), ms.value
 

@@ -199,6 +199,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_fasta.h"      // text out of it: FastaLayout, FastaPlan, FastaStage, the writer of d --fasta
 #include "mbgc_decoder_region.h"     // d --region: the specs, the pieces, their outputs
 #include "mbgc_decoder_validate.h"   // v: Validation
+#include "mbgc_decoder_scan.h"       // what the scans of the chosen contigs share: ChosenRecords, FastaHandle, timedCalls, downloadRecord
 #include "mbgc_decoder_check.h"      // d --check, t: the chosen contigs against <prefix>.checksums
 #include "mbgc_decoder_find.h"       // f: query sequences searched in the chosen contigs
 #include "mbgc_decoder_stats.h"      // s: composition, N50 and the runs of N / lower case of the chosen contigs
@@ -240,7 +241,7 @@ bool handOverResident(const DecodedCollection &D, const StreamSet &S, const Sele
     R.packedBytes = dstOff[pieces.size()];
     if (R.packedBytes != out.bases) { msg = "internal error: the packed units are not the chosen contigs"; return false; }
     R.contigsDecoded = S.g0n + (sel.selecting ? D.closureContigs : S.planned); R.contigsChosen = out.contigs;
-    R.decodeMs = D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs;
+    R.decodeMs = decodeMs(D, S);
     return true;
 }
 
@@ -394,37 +395,19 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         ValidateResult vres;
         CheckResult chk;
         if (opt.check && last && !checkChecksums(prefix, D, S, layout, chosen, manifest, opt.device, chk, msg)) return failed();
-        // `f`: the search is the sink — its lines, its summary, and 3 when nothing was found
-        if (opt.find) {
+        // `f`, `s`, `k`, `u`: the scan of the chosen contigs is the sink — its lines and its summary; `f` returns 3 when nothing was found
+        if (opt.find || opt.stats || opt.sketch || opt.dups) {
             if (!last) continue;
             FindResult found;
-            if (!findQueries(D, S, layout, chosen, opt, opt.bench, found, msg) ||
-                !reportFind(opt, layout, found, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
-            return found.lines.empty() ? 3 : 0;
-        }
-        // `s`: the statistics are the sink
-        if (opt.stats) {
-            if (!last) continue;
             StatsResult stats;
-            if (!collectStats(D, S, chosen, opt, opt.bench, stats, msg) ||
-                !reportStats(opt, layout, stats, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
-            return 0;
-        }
-        // `k`: the sketches and the pairs are the sink
-        if (opt.sketch) {
-            if (!last) continue;
             SketchResult sketch;
-            if (!collectSketch(D, S, chosen, layout, opt, opt.bench, sketch, msg) ||
-                !reportSketch(opt, sketch, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
-            return 0;
-        }
-        // `u`: the classes are the sink
-        if (opt.dups) {
-            if (!last) continue;
             DupsResult dups;
-            if (!collectDups(D, S, chosen, opt, opt.bench, dups, msg) ||
-                !reportDups(opt, layout, dups, D.times.plan + D.times.closure + D.times.fill + D.times.load + S.rcRestoreMs, msg)) return failed();
-            return 0;
+            const bool ok = opt.find    ? findQueries(D, S, layout, chosen, opt, opt.bench, found, msg) && reportFind(opt, layout, found, decodeMs(D, S), msg)
+                          : opt.stats   ? collectStats(D, S, chosen, opt, opt.bench, stats, msg) && reportStats(opt, layout, stats, decodeMs(D, S), msg)
+                          : opt.sketch  ? collectSketch(D, S, chosen, layout, opt, opt.bench, sketch, msg) && reportSketch(opt, sketch, decodeMs(D, S), msg)
+                                        : collectDups(D, S, chosen, opt, opt.bench, dups, msg) && reportDups(opt, layout, dups, decodeMs(D, S), msg);
+            if (!ok) return failed();
+            return opt.find && found.lines.empty() ? 3 : 0;
         }
         if (wantFasta) {
             const FastaPlan plan = sel.selectingRegion ? planFasta(pieces.rows, S.meta, pieces.layout, pieces.len, opt.batchText, opt.gzip, true)
@@ -502,6 +485,20 @@ int mbgc_hip_decode_option(char tool, int argc, char **argv, int &i, MBGC_Decode
     return 1;
 }
 
+// a decimal number of 1 to 18 digits and nothing else (it fits 64 bits) — the one parser of the command lines' counts
+static bool parseDecimal(const std::string &text, uint64_t &v) {
+    if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) return false;
+    v = strtoull(text.c_str(), nullptr, 10);
+    return true;
+}
+
+// ... as the value of option `name` of `mbgc-hip <tool>`, which "takes <takes>" when it is none
+static bool numberOption(char tool, const char *name, const char *takes, const char *text, uint64_t &v) {
+    if (parseDecimal(text, v)) return true;
+    fprintf(stderr, "mbgc-hip %c: %s takes %s\n", tool, name, takes);
+    return false;
+}
+
 bool MBGC_Decoder::parseRegionSpec(const std::string &text, RegionSpec &out, std::string *why) {
     const auto bad = [why](const char *what) { if (why) *why = what; return false; };
     const size_t colon = text.rfind(':');
@@ -514,10 +511,8 @@ bool MBGC_Decoder::parseRegionSpec(const std::string &text, RegionSpec &out, std
     if (dash == std::string::npos) return bad("a region is PATTERN:FROM-TO (no '-' behind the last ':')");
     uint64_t v[2];
     const std::string part[2] = {range.substr(0, dash), range.substr(dash + 1)};
-    for (int k = 0; k < 2; k++) {
-        if (part[k].empty() || part[k].size() > 18 || part[k].find_first_not_of("0123456789") != std::string::npos) return bad("FROM and TO are positive decimal numbers");
-        v[k] = strtoull(part[k].c_str(), nullptr, 10);
-    }
+    for (int k = 0; k < 2; k++)
+        if (!parseDecimal(part[k], v[k])) return bad("FROM and TO are positive decimal numbers");
     if (v[0] < 1) return bad("FROM is 1-based: the first base is 1");
     if (v[0] > v[1]) return bad("FROM lies behind TO");
     out.from = v[0]; out.to = v[1];
@@ -603,6 +598,14 @@ const char *const MBGC_HIP_V_USAGE =
     "  that of --inflate host (the default: zlib on the read-ahead thread). The one file of a single-FASTA collection inflates on the host\n"
     "  streams of c -U or c --lossy are compared as they are: originals that were not upper case, or not strict FASTA, differ\n";
 
+// the tail of every command that decodes: the decode, its error line, its status (1: the error; what else the command returns)
+static int decodeAndReport(char tool, const std::string &prefix, const std::string &outPrefix, const MBGC_Decoder::Options &opt) {
+    std::string error;
+    const int r = MBGC_Decoder::decode(prefix, outPrefix, opt, &error);
+    if (r == 1) { fprintf(stderr, "mbgc-hip %c: %s\n", tool, error.c_str()); return EXIT_FAILURE; }
+    return r;
+}
+
 int mbgc_hip_decompress_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     std::vector<std::string> pos;
@@ -628,10 +631,7 @@ int mbgc_hip_decompress_main(int argc, char **argv) {
     if (opt.gzip && opt.fastaDir.empty()) { fprintf(stderr, "mbgc-hip d: --gzip needs --fasta dir (it compresses the FASTA files that --fasta writes)\n"); return EXIT_FAILURE; }
     if (!mbgc_hip_check_selection('d', opt, selectAsked)) return EXIT_FAILURE;
     if (!selectAsked && !opt.selectSeqAsked && !opt.regionAsked && !opt.closureOut.empty()) { fprintf(stderr, "mbgc-hip d: --closure-out needs a selection (--select / --select-list)\n"); return EXIT_FAILURE; }
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], pos[1], opt, &error);
-    if (r == 1) { fprintf(stderr, "mbgc-hip d: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return r;                                                                                   // (2: --check found a difference)
+    return decodeAndReport('d', pos[0], pos[1], opt);                                           // (2: --check found a difference)
 }
 
 // `mbgc-hip t`: the stages of `d --check` without a sink
@@ -652,10 +652,37 @@ int mbgc_hip_test_main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     if (!mbgc_hip_check_selection('t', opt, selectAsked)) return EXIT_FAILURE;
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r == 1) { fprintf(stderr, "mbgc-hip t: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return r;
+    return decodeAndReport('t', pos[0], std::string(), opt);
+}
+
+// The command line of `f`, `s`, `k` and `u`: the decoder's options and --bench, the command's own (own(a, i): 1 taken, 0 not its, -1
+// refused with its line printed), what these commands refuse before anything is decoded, the one positional. settled(): 0, 1 for a
+// refusal whose line it printed, 2 for the usage text — asked behind the --region refusal and in front of the positional. -> the exit
+// status, or -1 with the stream set's prefix when the command can go on
+struct ScanTool { char letter; const char *usage, *regionWhy, *fastaWhy; };      // fastaWhy == nullptr: --fasta is no option of the tool's at all
+template <class Own, class Settled>
+static int scanCommandLine(const ScanTool &tool, int argc, char **argv, MBGC_Decoder::Options &opt, Own own, Settled settled, std::string &prefix) {
+    std::vector<std::string> pos;
+    bool selectAsked = false;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (const int r = mbgc_hip_decode_option(tool.letter, argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--bench") opt.bench = true;
+        else if (const int r = own(a, i)) { if (r < 0) return EXIT_FAILURE; }
+        else if (a == "--check") { fprintf(stderr, "mbgc-hip %c: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n", tool.letter); return EXIT_FAILURE; }
+        else if (a == "--fasta" && tool.fastaWhy) { fprintf(stderr, "mbgc-hip %c: --fasta is an option of mbgc-hip d: %s\n", tool.letter, tool.fastaWhy); return EXIT_FAILURE; }
+        else pos.push_back(a);
+    }
+    if (opt.regionAsked) {
+        fprintf(stderr, "mbgc-hip %c: --region / --region-list select parts of records, and %s\n", tool.letter, tool.regionWhy);
+        return EXIT_FAILURE;
+    }
+    const int s = settled();
+    if (s == 1) return EXIT_FAILURE;
+    if (s == 2 || pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", tool.usage); return EXIT_FAILURE; }
+    if (!mbgc_hip_check_selection(tool.letter, opt, selectAsked)) return EXIT_FAILURE;
+    prefix = pos[0];
+    return -1;
 }
 
 const char *const MBGC_HIP_F_USAGE =
@@ -697,20 +724,17 @@ static bool readQueryFile(const char *path, std::vector<MBGC_Decoder::FindQuery>
 int mbgc_hip_find_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     opt.find = opt.writeNothing = true;
-    std::vector<std::string> pos;
-    bool selectAsked = false;
     int inlineQueries = 0;
-    for (int i = 2; i < argc; i++) {
-        const std::string a = argv[i];
-        if (const int r = mbgc_hip_decode_option('f', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
-        else if (a == "--bench") opt.bench = true;
-        else if (a == "--seq" && i + 1 < argc) opt.findQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]});
+    std::string prefix;
+    const ScanTool tool = {'f', MBGC_HIP_F_USAGE, "a search looks at whole records (an option of mbgc-hip d; f --regions-out writes such a list)", nullptr};
+    const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
+        if (a == "--seq" && i + 1 < argc) opt.findQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]});
         else if (a == "--seq-file" && i + 1 < argc) {
-            if (!readQueryFile(argv[++i], opt.findQueries)) { fprintf(stderr, "mbgc-hip f: cannot open the query file %s\n", argv[i]); return EXIT_FAILURE; }
+            if (!readQueryFile(argv[++i], opt.findQueries)) { fprintf(stderr, "mbgc-hip f: cannot open the query file %s\n", argv[i]); return -1; }
         }
         else if (a == "--mismatches" && i + 1 < argc) {
             const std::string v = argv[++i];
-            if (v.size() != 1 || v[0] < '0' || v[0] > '3') { fprintf(stderr, "mbgc-hip f: --mismatches takes 0, 1, 2 or 3\n"); return EXIT_FAILURE; }
+            if (v.size() != 1 || v[0] < '0' || v[0] > '3') { fprintf(stderr, "mbgc-hip f: --mismatches takes 0, 1, 2 or 3\n"); return -1; }
             opt.findMismatches = (uint32_t) (v[0] - '0');
         }
         else if (a == "--forward-only") opt.findForwardOnly = true;
@@ -719,18 +743,13 @@ int mbgc_hip_find_main(int argc, char **argv) {
         else if (a == "--flank" && i + 1 < argc) opt.findFlank = strtoull(argv[++i], nullptr, 10);
         else if (a == "--hit-capacity" && i + 1 < argc) {
             opt.findHitCapacity = strtoull(argv[++i], nullptr, 10);
-            if (!opt.findHitCapacity) { fprintf(stderr, "mbgc-hip f: --hit-capacity takes a positive number of hits\n"); return EXIT_FAILURE; }
+            if (!opt.findHitCapacity) { fprintf(stderr, "mbgc-hip f: --hit-capacity takes a positive number of hits\n"); return -1; }
         }
         else if (a == "--find-host") opt.findHost = true;
-        else if (a == "--check") { fprintf(stderr, "mbgc-hip f: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
-    if (opt.regionAsked) {
-        fprintf(stderr, "mbgc-hip f: --region / --region-list select parts of records, and a search looks at whole records (an option of mbgc-hip d; f --regions-out writes such a list)\n");
-        return EXIT_FAILURE;
-    }
-    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0 || opt.findQueries.empty()) { fprintf(stderr, "usage: %s", MBGC_HIP_F_USAGE); return EXIT_FAILURE; }
-    if (!mbgc_hip_check_selection('f', opt, selectAsked)) return EXIT_FAILURE;
+        else return 0;
+        return 1;
+    }, [&] { return opt.findQueries.empty() ? 2 : 0; }, prefix);
+    if (r >= 0) return r;
     // the queries, held to the search's limits before anything is decoded
     const uint64_t shortest = 8ull * (opt.findMismatches + 1);
     for (MBGC_Decoder::FindQuery &q : opt.findQueries) {
@@ -744,10 +763,7 @@ int mbgc_hip_find_main(int argc, char **argv) {
         }
         if (q.seq.size() > 65535) { fprintf(stderr, "mbgc-hip f: query %s has %zu bases (at most 65535)\n", q.name.c_str(), q.seq.size()); return EXIT_FAILURE; }
     }
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r == 1) { fprintf(stderr, "mbgc-hip f: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return r;                                                                                   // (0: a hit, 3: none)
+    return decodeAndReport('f', prefix, std::string(), opt);                                    // (0: a hit, 3: none)
 }
 
 const char *const MBGC_HIP_S_USAGE =
@@ -776,38 +792,19 @@ const char *const MBGC_HIP_S_USAGE =
 int mbgc_hip_stats_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     opt.stats = opt.writeNothing = true;
-    std::vector<std::string> pos;
-    bool selectAsked = false;
-    const auto number = [&](const char *name, int &i, uint64_t &v) {
-        const std::string text = argv[++i];
-        if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip s: %s takes a number of bytes\n", name); return false; }
-        v = strtoull(text.c_str(), nullptr, 10);
-        return true;
-    };
-    for (int i = 2; i < argc; i++) {
-        const std::string a = argv[i];
-        if (const int r = mbgc_hip_decode_option('s', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
-        else if (a == "--bench") opt.bench = true;
-        else if (a == "--records" && i + 1 < argc) opt.statsRecordsFile = argv[++i];
+    std::string prefix;
+    const ScanTool tool = {'s', MBGC_HIP_S_USAGE, "the statistics are taken over whole records (an option of mbgc-hip d)", "s writes no sequence, it describes the set where it lies"};
+    const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
+        if (a == "--records" && i + 1 < argc) opt.statsRecordsFile = argv[++i];
         else if (a == "--gaps-out" && i + 1 < argc) opt.statsGapsOut = argv[++i];
         else if (a == "--masked-out" && i + 1 < argc) opt.statsMaskedOut = argv[++i];
-        else if (a == "--min-gap" && i + 1 < argc) { if (!number("--min-gap", i, opt.statsMinGap)) return EXIT_FAILURE; }
-        else if (a == "--min-masked" && i + 1 < argc) { if (!number("--min-masked", i, opt.statsMinMasked)) return EXIT_FAILURE; }
+        else if (a == "--min-gap" && i + 1 < argc) { if (!numberOption('s', "--min-gap", "a number of bytes", argv[++i], opt.statsMinGap)) return -1; }
+        else if (a == "--min-masked" && i + 1 < argc) { if (!numberOption('s', "--min-masked", "a number of bytes", argv[++i], opt.statsMinMasked)) return -1; }
         else if (a == "--stats-host") opt.statsHost = true;
-        else if (a == "--check") { fprintf(stderr, "mbgc-hip s: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
-        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip s: --fasta is an option of mbgc-hip d: s writes no sequence, it describes the set where it lies\n"); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
-    if (opt.regionAsked) {
-        fprintf(stderr, "mbgc-hip s: --region / --region-list select parts of records, and the statistics are taken over whole records (an option of mbgc-hip d)\n");
-        return EXIT_FAILURE;
-    }
-    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_S_USAGE); return EXIT_FAILURE; }
-    if (!mbgc_hip_check_selection('s', opt, selectAsked)) return EXIT_FAILURE;
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r) { fprintf(stderr, "mbgc-hip s: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return 0;
+        else return 0;
+        return 1;
+    }, [] { return 0; }, prefix);
+    return r >= 0 ? r : decodeAndReport('s', prefix, std::string(), opt);
 }
 
 const char *const MBGC_HIP_K_USAGE =
@@ -839,54 +836,35 @@ const char *const MBGC_HIP_K_USAGE =
 int mbgc_hip_sketch_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     opt.sketch = opt.writeNothing = true;
-    std::vector<std::string> pos;
-    bool selectAsked = false;
-    const auto number = [&](const char *name, int &i, uint64_t &v) {
-        const std::string text = argv[++i];
-        if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip k: %s takes a number\n", name); return false; }
-        v = strtoull(text.c_str(), nullptr, 10);
-        return true;
-    };
-    for (int i = 2; i < argc; i++) {
-        const std::string a = argv[i];
+    std::string prefix;
+    const ScanTool tool = {'k', MBGC_HIP_K_USAGE, "the sketches are taken over whole records (an option of mbgc-hip d)", "k writes no sequence, it compares the set where it lies"};
+    const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
         uint64_t v = 0;
-        if (const int r = mbgc_hip_decode_option('k', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
-        else if (a == "--bench") opt.bench = true;
-        else if (a == "-k" && i + 1 < argc) {
-            if (!number("-k", i, v)) return EXIT_FAILURE;
-            if (v < 1 || v > 32) { fprintf(stderr, "mbgc-hip k: -k %llu: a k-mer has 1 to 32 bases (2 bits each in one 64-bit word)\n", (unsigned long long) v); return EXIT_FAILURE; }
+        if (a == "-k" && i + 1 < argc) {
+            if (!numberOption('k', "-k", "a number", argv[++i], v)) return -1;
+            if (v < 1 || v > 32) { fprintf(stderr, "mbgc-hip k: -k %llu: a k-mer has 1 to 32 bases (2 bits each in one 64-bit word)\n", (unsigned long long) v); return -1; }
             opt.sketchK = (uint32_t) v;
         }
         else if (a == "--scale" && i + 1 < argc) {
-            if (!number("--scale", i, v)) return EXIT_FAILURE;
-            if (v < 1) { fprintf(stderr, "mbgc-hip k: --scale 0: a hash is kept when it is at most (2^64 - 1) / scale, 1 keeps every hash\n"); return EXIT_FAILURE; }
+            if (!numberOption('k', "--scale", "a number", argv[++i], v)) return -1;
+            if (v < 1) { fprintf(stderr, "mbgc-hip k: --scale 0: a hash is kept when it is at most (2^64 - 1) / scale, 1 keeps every hash\n"); return -1; }
             opt.sketchScale = v;
         }
-        else if (a == "--min-shared" && i + 1 < argc) { if (!number("--min-shared", i, opt.sketchMinShared)) return EXIT_FAILURE; }
+        else if (a == "--min-shared" && i + 1 < argc) { if (!numberOption('k', "--min-shared", "a number", argv[++i], opt.sketchMinShared)) return -1; }
         else if (a == "--by-record") opt.sketchByRecord = true;
         else if (a == "--no-pairs") opt.sketchNoPairs = true;
         else if (a == "--sketch-host") opt.sketchHost = true;
         else if (a == "--pairs-out" && i + 1 < argc) opt.sketchPairsOut = argv[++i];
         else if (a == "--sketches-out" && i + 1 < argc) opt.sketchOut = argv[++i];
         else if (a == "--order-out" && i + 1 < argc) opt.sketchOrderOut = argv[++i];
-        else if (a == "--check") { fprintf(stderr, "mbgc-hip k: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
-        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip k: --fasta is an option of mbgc-hip d: k writes no sequence, it compares the set where it lies\n"); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
-    if (opt.regionAsked) {
-        fprintf(stderr, "mbgc-hip k: --region / --region-list select parts of records, and the sketches are taken over whole records (an option of mbgc-hip d)\n");
-        return EXIT_FAILURE;
-    }
-    if (!opt.sketchOrderOut.empty() && (opt.sketchByRecord || opt.sketchNoPairs)) {
+        else return 0;
+        return 1;
+    }, [&] {
+        if (opt.sketchOrderOut.empty() || (!opt.sketchByRecord && !opt.sketchNoPairs)) return 0;
         fprintf(stderr, "mbgc-hip k: --order-out orders files by the hashes they share: not with --by-record or --no-pairs\n");
-        return EXIT_FAILURE;
-    }
-    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_K_USAGE); return EXIT_FAILURE; }
-    if (!mbgc_hip_check_selection('k', opt, selectAsked)) return EXIT_FAILURE;
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r) { fprintf(stderr, "mbgc-hip k: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return 0;
+        return 1;
+    }, prefix);
+    return r >= 0 ? r : decodeAndReport('k', prefix, std::string(), opt);
 }
 
 const char *const MBGC_HIP_U_USAGE =
@@ -919,36 +897,19 @@ const char *const MBGC_HIP_U_USAGE =
 int mbgc_hip_dups_main(int argc, char **argv) {
     MBGC_Decoder::Options opt;
     opt.dups = opt.writeNothing = true;
-    std::vector<std::string> pos;
-    bool selectAsked = false;
-    for (int i = 2; i < argc; i++) {
-        const std::string a = argv[i];
-        if (const int r = mbgc_hip_decode_option('u', argc, argv, i, opt, selectAsked)) { if (r < 0) return EXIT_FAILURE; }
-        else if (a == "--bench") opt.bench = true;
-        else if (a == "--forward-only") opt.dupsForwardOnly = true;
+    std::string prefix;
+    const ScanTool tool = {'u', MBGC_HIP_U_USAGE, "whole records are compared (an option of mbgc-hip d)", "u writes no sequence, it compares the records where they lie"};
+    const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
+        if (a == "--forward-only") opt.dupsForwardOnly = true;
         else if (a == "--exact-case") opt.dupsExactCase = true;
         else if (a == "--dups-host") opt.dupsHost = true;
-        else if (a == "--min-len" && i + 1 < argc) {
-            const std::string text = argv[++i];
-            if (text.empty() || text.size() > 18 || text.find_first_not_of("0123456789") != std::string::npos) { fprintf(stderr, "mbgc-hip u: --min-len takes a number of bytes\n"); return EXIT_FAILURE; }
-            opt.dupsMinLen = strtoull(text.c_str(), nullptr, 10);
-        }
+        else if (a == "--min-len" && i + 1 < argc) { if (!numberOption('u', "--min-len", "a number of bytes", argv[++i], opt.dupsMinLen)) return -1; }
         else if (a == "--clusters-out" && i + 1 < argc) opt.dupsClustersOut = argv[++i];
         else if (a == "--unique-files-out" && i + 1 < argc) opt.dupsUniqueFilesOut = argv[++i];
-        else if (a == "--check") { fprintf(stderr, "mbgc-hip u: --check is an option of mbgc-hip d (mbgc-hip t tests a set against its manifest)\n"); return EXIT_FAILURE; }
-        else if (a == "--fasta") { fprintf(stderr, "mbgc-hip u: --fasta is an option of mbgc-hip d: u writes no sequence, it compares the records where they lie\n"); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
-    if (opt.regionAsked) {
-        fprintf(stderr, "mbgc-hip u: --region / --region-list select parts of records, and whole records are compared (an option of mbgc-hip d)\n");
-        return EXIT_FAILURE;
-    }
-    if (pos.size() != 1 || pos[0].compare(0, 1, "-") == 0) { fprintf(stderr, "usage: %s", MBGC_HIP_U_USAGE); return EXIT_FAILURE; }
-    if (!mbgc_hip_check_selection('u', opt, selectAsked)) return EXIT_FAILURE;
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r) { fprintf(stderr, "mbgc-hip u: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return 0;
+        else return 0;
+        return 1;
+    }, [] { return 0; }, prefix);
+    return r >= 0 ? r : decodeAndReport('u', prefix, std::string(), opt);
 }
 
 // `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device
@@ -984,10 +945,7 @@ int mbgc_hip_validate_main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     if (!mbgc_hip_check_selection('v', opt, selectAsked)) return EXIT_FAILURE;
-    std::string error;
-    const int r = MBGC_Decoder::decode(pos[0], std::string(), opt, &error);
-    if (r == 1) { fprintf(stderr, "mbgc-hip v: %s\n", error.c_str()); return EXIT_FAILURE; }
-    return r;
+    return decodeAndReport('v', pos[0], std::string(), opt);
 }
 
 // ---------------------------------------------------------------- C exports for tests (host only, no device)

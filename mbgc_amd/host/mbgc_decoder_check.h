@@ -37,37 +37,29 @@ bool checkChecksums(const std::string &prefix, const DecodedCollection &D, const
             R.lines.push_back("checksum ERROR: " + prefix + "." + mbgc_checksums::SIDE_EXT[k] + " differs");
     }
     const uint64_t shift = S.meta.sequentialMatching ? S.g0n : 0;   // (-t1: the initial reference has no entry of its own and is never chosen)
-    std::vector<mbgc_fasta_crc_rec_t> recs;
-    struct Where { uint64_t contig; size_t unit; uint64_t record; };
-    std::vector<Where> where;
+    const ChosenRecords in(D, S, chosen);
+    const std::vector<mbgc_fasta_crc_rec_t> &recs = in.recs;
     std::vector<uint64_t> unitFirst(S.T() + 2, 0);
     unitFirst[1] = S.g0n;
     for (size_t t = 0; t < S.T(); t++) unitFirst[t + 2] = unitFirst[t + 1] + S.seqCount[t];
-    for (const ChosenUnit &x : chosen)
-        for (uint64_t k = x.c0; k < x.c1; k++) {
-            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[k], D.contigLen[k]});
-            where.push_back({k, x.unit, S.meta.singleFastaFile ? k - shift : k - unitFirst[x.unit]});
-            R.bytes += D.contigLen[k];
-        }
+    R.bytes = in.bases;
     R.checked = recs.size();
     std::vector<uint32_t> got(recs.size());
     if (!recs.empty()) {
-        mbgc_fasta_t *fa = nullptr;
-        if (mbgc_fasta_create(&fa, device)) return faFail(msg, "input stage");
-        const int rc = mbgc_fasta_crc_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), got.data(), &R.kernelMs);
-        if (rc) faFail(msg, "checksums");
-        mbgc_fasta_destroy(fa);
-        if (rc) return false;
+        FastaHandle fa;
+        if (!fa.open(device, msg)) return false;
+        if (mbgc_fasta_crc_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), got.data(), &R.kernelMs)) return faFail(msg, "checksums");
     }
     for (size_t i = 0; i < recs.size(); i++) {
-        const uint32_t want = M.contigs[where[i].contig - shift];
+        const uint64_t k = in.records[i].contig;
+        const uint32_t want = M.contigs[k - shift];
         if (got[i] == want) continue;
         if (R.bad++ >= 100) continue;
-        const uint64_t k = where[i].contig;
-        const std::string &name = layout.names[S.meta.singleFastaFile ? 0 : where[i].unit];
+        const size_t unit = in.records[i].unit;                      // (0 for a single-FASTA set, whose records count from the first planned contig)
+        const std::string &name = layout.names[unit];
         char hex[64];
         snprintf(hex, sizeof hex, "expected %08x got %08x", want, got[i]);
-        R.lines.push_back("checksum ERROR: contig " + std::to_string(k - shift) + " (file " + name + ", record " + std::to_string(where[i].record) + ": " +
+        R.lines.push_back("checksum ERROR: contig " + std::to_string(k - shift) + " (file " + name + ", record " + std::to_string(S.meta.singleFastaFile ? k - shift : k - unitFirst[unit]) + ": " +
                           layout.headers.substr(layout.hdrOff[k], std::min<uint64_t>(layout.hdrLen[k], 60)) + ") " + hex);
     }
     return true;

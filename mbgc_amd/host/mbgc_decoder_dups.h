@@ -6,12 +6,10 @@
 #pragma once
 
 namespace {
-struct DupsRecord { uint64_t contig; size_t unit; uint64_t len; };
 struct DupsResult {
-    std::vector<DupsRecord> records;                                 // the chosen contigs, in collection order
-    std::vector<size_t> units;                                       // the chosen files, in collection order
-    std::vector<mbgc_fasta_dup_t> dup;                               // per record: rep = an index into records
-    uint64_t bases = 0, classes = 0, buckets = 0, verified = 0, refuted = 0;
+    ChosenRecords in;                                                // the chosen contigs and files
+    std::vector<mbgc_fasta_dup_t> dup;                               // per record: rep = an index into the records
+    uint64_t classes = 0, buckets = 0, verified = 0, refuted = 0;
     double kernelMs = 0, verifyMs = 0;
 };
 
@@ -37,44 +35,24 @@ void dupsOnHost(const std::vector<std::string> &texts, bool forwardOnly, bool ex
 bool collectDups(const DecodedCollection &D, const StreamSet &S, const std::vector<ChosenUnit> &chosen, const MBGC_Decoder::Options &opt, bool timed, DupsResult &R,
                  std::string &msg) {
     R = DupsResult();
-    std::vector<mbgc_fasta_crc_rec_t> recs;
-    for (const ChosenUnit &x : chosen) {
-        const size_t unit = S.meta.singleFastaFile ? 0 : x.unit;
-        if (R.units.empty() || R.units.back() != unit) R.units.push_back(unit);
-        for (uint64_t k = x.c0; k < x.c1; k++) {
-            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[k], D.contigLen[k]});
-            R.records.push_back({k, unit, D.contigLen[k]});
-            R.bases += D.contigLen[k];
-        }
-    }
+    R.in = ChosenRecords(D, S, chosen);
+    const std::vector<mbgc_fasta_crc_rec_t> &recs = R.in.recs;
     const uint32_t flags = (opt.dupsForwardOnly ? MBGC_FASTA_DUPS_FORWARD_ONLY : 0u) | (opt.dupsExactCase ? MBGC_FASTA_DUPS_EXACT_CASE : 0u);
     R.dup.assign(std::max<size_t>(recs.size(), 1), mbgc_fasta_dup_t{0, 0});
-    mbgc_fasta_t *fa = nullptr;
-    if (mbgc_fasta_create(&fa, opt.device)) return faFail(msg, "input stage");
-    int rc = 0;
-    std::vector<double> scanMs, verifyMs;
-    for (int rep = 0; rep < (timed ? 6 : 1) && !rc; rep++) {         // (--bench: one run to warm up, the medians of five)
-        double ms = 0, vms = 0;
-        rc = mbgc_fasta_dups_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), flags, R.dup.data(), &R.classes, &ms);
-        if (rc) break;
-        mbgc_fasta_dups_last(fa, &R.buckets, &R.verified, &R.refuted, &vms);
-        if (rep) { scanMs.push_back(ms); verifyMs.push_back(vms); } else { R.kernelMs = ms; R.verifyMs = vms; }
-    }
-    if (rc) faFail(msg, "dups");
-    mbgc_fasta_destroy(fa);
-    if (rc) return false;
-    if (!scanMs.empty()) {
-        std::sort(scanMs.begin(), scanMs.end()); std::sort(verifyMs.begin(), verifyMs.end());
-        R.kernelMs = scanMs[scanMs.size() / 2]; R.verifyMs = verifyMs[verifyMs.size() / 2];
-    }
+    FastaHandle fa;
+    double median[2];                                                // the scan, the exactness step
+    if (!fa.open(opt.device, msg) || !timedCalls(timed, median, [&](double (&ms)[2]) {
+            if (mbgc_fasta_dups_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), flags, R.dup.data(), &R.classes, &ms[0])) return faFail(msg, "dups");
+            mbgc_fasta_dups_last(fa, &R.buckets, &R.verified, &R.refuted, &ms[1]);
+            return true;
+        })) return false;
+    R.kernelMs = median[0]; R.verifyMs = median[1];
     R.dup.resize(recs.size());
     // ---- --dups-host: the same question put to the host, over the downloaded contigs; every answer must be equal
     if (opt.dupsHost) {
         std::vector<std::string> texts(recs.size());
-        for (size_t r = 0; r < recs.size(); r++) {
-            texts[r].resize(recs[r].len);
-            if (recs[r].len && swsem_dev_download(D.h, &texts[r][0], D.seqDev + recs[r].off, recs[r].len)) return hipFail(msg, "download");
-        }
+        for (size_t r = 0; r < recs.size(); r++)
+            if (!downloadRecord(D, recs[r], texts[r], msg)) return false;
         std::vector<mbgc_fasta_dup_t> host;
         dupsOnHost(texts, opt.dupsForwardOnly, opt.dupsExactCase, host);
         for (size_t r = 0; r < recs.size(); r++)
@@ -90,19 +68,20 @@ bool collectDups(const DecodedCollection &D, const StreamSet &S, const std::vect
 // the duplicates' lines, --clusters-out, --unique-files-out, the summary and the JSON line of --bench
 bool reportDups(const MBGC_Decoder::Options &opt, const FastaLayout &layout, const DupsResult &R, double decodeMs, std::string &msg) {
     const uint64_t least = std::max<uint64_t>(opt.dupsMinLen, 1);
+    const std::vector<ChosenRecords::Record> &records = R.in.records;
     const auto columns = [&](size_t r) {
         const size_t rep = R.dup[r].rep;
-        return recordName(layout, R.records[r].contig) + "\t" + layout.names[R.records[r].unit] + "\t" + std::to_string(R.records[r].len) + "\t" + (R.dup[r].strand ? "-" : "+") + "\t" +
-               recordName(layout, R.records[rep].contig) + "\t" + layout.names[R.records[rep].unit];
+        return recordName(layout, records[r].contig) + "\t" + layout.names[records[r].unit] + "\t" + std::to_string(records[r].len) + "\t" + (R.dup[r].strand ? "-" : "+") + "\t" +
+               recordName(layout, records[rep].contig) + "\t" + layout.names[records[rep].unit];
     };
     uint64_t dups = 0, dupBases = 0, asRc = 0;
-    std::vector<std::vector<size_t>> members(R.records.size());     // of a class, under its representative, in collection order
-    for (size_t r = 0; r < R.records.size(); r++) {
-        if (R.records[r].len < least) continue;
+    std::vector<std::vector<size_t>> members(records.size());     // of a class, under its representative, in collection order
+    for (size_t r = 0; r < records.size(); r++) {
+        if (records[r].len < least) continue;
         members[R.dup[r].rep].push_back(r);
         if (R.dup[r].rep == r) continue;
         printf("%s\n", columns(r).c_str());
-        dups++; dupBases += R.records[r].len; asRc += R.dup[r].strand;
+        dups++; dupBases += records[r].len; asRc += R.dup[r].strand;
     }
     if (!opt.dupsClustersOut.empty()) {
         std::string text;
@@ -120,20 +99,20 @@ bool reportDups(const MBGC_Decoder::Options &opt, const FastaLayout &layout, con
     std::string unique;
     uint64_t dupFiles = 0;
     size_t at = 0;
-    for (const size_t unit : R.units) {
+    for (const size_t unit : R.in.units) {
         std::vector<uint32_t> classes;
-        for (; at < R.records.size() && R.records[at].unit == unit; at++) classes.push_back(R.dup[at].rep);
+        for (; at < records.size() && records[at].unit == unit; at++) classes.push_back(R.dup[at].rep);
         std::sort(classes.begin(), classes.end());
         if (seen.emplace(classes, unit).second) unique += layout.names[unit] + "\n"; else dupFiles++;
     }
     if (!opt.dupsUniqueFilesOut.empty() && !writeFile(opt.dupsUniqueFilesOut, unique.data(), unique.size())) { msg = "cannot write " + opt.dupsUniqueFilesOut; return false; }
-    printf("dups: %zu records, %llu bases; %llu distinct sequences; %llu duplicate records, %llu bases (%llu as reverse complements); %llu of %zu files duplicate\n", R.records.size(),
-           (unsigned long long) R.bases, (unsigned long long) R.classes, (unsigned long long) dups, (unsigned long long) dupBases, (unsigned long long) asRc, (unsigned long long) dupFiles,
-           R.units.size());
+    printf("dups: %zu records, %llu bases; %llu distinct sequences; %llu duplicate records, %llu bases (%llu as reverse complements); %llu of %zu files duplicate\n", records.size(),
+           (unsigned long long) R.in.bases, (unsigned long long) R.classes, (unsigned long long) dups, (unsigned long long) dupBases, (unsigned long long) asRc, (unsigned long long) dupFiles,
+           R.in.units.size());
     if (opt.bench)
         printf("{\"dups_kernel_ms\": %.3f, \"verify_ms\": %.3f, \"bases\": %llu, \"records\": %zu, \"buckets\": %llu, \"verified\": %llu, \"refuted\": %llu, \"decode_ms\": %.3f, "
-               "\"dups_gb_per_s\": %.3f}\n", R.kernelMs, R.verifyMs, (unsigned long long) R.bases, R.records.size(), (unsigned long long) R.buckets, (unsigned long long) R.verified,
-               (unsigned long long) R.refuted, decodeMs, R.kernelMs > 0 ? R.bases / (R.kernelMs * 1e-3) / 1e9 : 0.0);
+               "\"dups_gb_per_s\": %.3f}\n", R.kernelMs, R.verifyMs, (unsigned long long) R.in.bases, records.size(), (unsigned long long) R.buckets, (unsigned long long) R.verified,
+               (unsigned long long) R.refuted, decodeMs, R.kernelMs > 0 ? R.in.bases / (R.kernelMs * 1e-3) / 1e9 : 0.0);
     return true;
 }
 }  // namespace

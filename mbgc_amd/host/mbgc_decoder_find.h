@@ -10,7 +10,7 @@ namespace {
 struct FindLine { uint64_t contig, start, end; uint32_t query; char strand; uint32_t mismatches; size_t unit; };
 struct FindResult {
     std::vector<FindLine> lines;
-    uint64_t records = 0, files = 0, bases = 0, patterns = 0, retries = 0;
+    uint64_t records = 0, files = 0, bases = 0, patterns = 0, retries = 0;      // records, files: those with a hit; bases: those searched
     double kernelMs = 0, hostMs = 0;
 };
 
@@ -78,46 +78,32 @@ bool findQueries(const DecodedCollection &D, const StreamSet &S, const FastaLayo
     std::vector<uint64_t> patOff(1, 0);
     for (const std::string &p : patterns) { blob += p; patOff.push_back(blob.size()); }
     // ---- the records: the chosen contigs, in collection order
-    std::vector<mbgc_fasta_crc_rec_t> recs;
-    struct Where { uint64_t contig; size_t unit; };
-    std::vector<Where> where;
-    for (const ChosenUnit &x : chosen)
-        for (uint64_t k = x.c0; k < x.c1; k++) {
-            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[k], D.contigLen[k]});
-            where.push_back({k, S.meta.singleFastaFile ? 0 : x.unit});
-            R.bases += D.contigLen[k];
-        }
+    const ChosenRecords in(D, S, chosen);
+    const std::vector<mbgc_fasta_crc_rec_t> &recs = in.recs;
+    R.bases = in.bases;
     // ---- the search; the buffer is sized from the bases searched (--hit-capacity: the first size), and the call is made again with
     // the count it states when the hits do not fit
     std::vector<mbgc_fasta_hit_t> hits;
     uint64_t nHits = 0;
-    mbgc_fasta_t *fa = nullptr;
-    if (mbgc_fasta_create(&fa, opt.device)) return faFail(msg, "input stage");
+    FastaHandle fa;
     uint64_t cap = opt.findHitCapacity ? opt.findHitCapacity : 4096 + R.bases / 256;
-    int rc = 0;
-    std::vector<double> runs;
-    for (int rep = 0; rep < (timed ? 6 : 1) && !rc; rep++)          // (--bench: one run to warm up, the median of five)
-        for (;;) {
-            hits.assign(cap, mbgc_fasta_hit_t());
-            double ms = 0;
-            rc = mbgc_fasta_find_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), (const uint8_t *) blob.data(), patOff.data(), patterns.size(), opt.findMismatches,
-                                     hits.data(), cap, &nHits, &ms);
-            if (rc == -104 && nHits > cap) { cap = nHits; R.retries++; continue; }
-            if (rep) runs.push_back(ms); else R.kernelMs = ms;
-            break;
-        }
-    if (rc) faFail(msg, "find");
-    mbgc_fasta_destroy(fa);
-    if (rc) return false;
-    if (!runs.empty()) { std::sort(runs.begin(), runs.end()); R.kernelMs = runs[runs.size() / 2]; }
+    double median[1];
+    if (!fa.open(opt.device, msg) || !timedCalls(timed, median, [&](double (&ms)[1]) {
+            for (;;) {
+                hits.assign(cap, mbgc_fasta_hit_t());
+                const int rc = mbgc_fasta_find_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), (const uint8_t *) blob.data(), patOff.data(), patterns.size(),
+                                                   opt.findMismatches, hits.data(), cap, &nHits, &ms[0]);
+                if (rc == -104 && nHits > cap) { cap = nHits; R.retries++; continue; }
+                return !rc || faFail(msg, "find");
+            }
+        })) return false;
+    R.kernelMs = median[0];
     hits.resize(nHits);
     // ---- --find-host: the same question put to the host, over the downloaded contigs; the two tables must be equal
     if (opt.findHost) {
         std::vector<std::string> text(recs.size());
-        for (size_t r = 0; r < recs.size(); r++) {
-            text[r].resize(recs[r].len);
-            if (recs[r].len && swsem_dev_download(D.h, &text[r][0], D.seqDev + recs[r].off, recs[r].len)) return hipFail(msg, "download");
-        }
+        for (size_t r = 0; r < recs.size(); r++)
+            if (!downloadRecord(D, recs[r], text[r], msg)) return false;
         const double t0 = nowMs();
         const std::vector<HostHit> host = findOnHost(text, patterns, opt.findMismatches);
         R.hostMs = nowMs() - t0;
@@ -130,7 +116,7 @@ bool findQueries(const DecodedCollection &D, const StreamSet &S, const FastaLayo
     std::set<uint64_t> hitContigs;
     std::set<size_t> hitUnits;
     for (const mbgc_fasta_hit_t &h : hits) {
-        const Where &w = where[h.rec];
+        const ChosenRecords::Record &w = in.records[h.rec];
         R.lines.push_back({w.contig, h.pos + 1, h.pos + patterns[h.pattern].size(), what[h.pattern].query, what[h.pattern].strand, h.mismatches, w.unit});
         hitContigs.insert(w.contig); hitUnits.insert(w.unit);
     }

@@ -16,8 +16,6 @@ struct SketchResult {
     double kernelMs = 0, sortMs = 0, pairsMs = 0;
 };
 
-double medianOf(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
-
 // --sketch-host: the hash of every k-mer of one downloaded contig by the obvious loop — each k-mer from scratch, its reverse complement
 // by walking it backwards
 void sketchOnHost(const std::string &text, uint32_t k, uint64_t maxHash, std::set<uint64_t> &kept, uint64_t &kmers) {
@@ -44,22 +42,19 @@ bool collectSketch(const DecodedCollection &D, const StreamSet &S, const std::ve
     R = SketchResult();
     // ---- the records: the chosen contigs, in collection order; a group per file (a chosen file without a contig has its line all the
     // same) or per record
-    std::vector<mbgc_fasta_crc_rec_t> recs;
+    const ChosenRecords in(D, S, chosen);
+    const std::vector<mbgc_fasta_crc_rec_t> &recs = in.recs;
     std::vector<uint32_t> groupOf;
-    size_t lastUnit = 0;
-    for (const ChosenUnit &x : chosen) {
-        const size_t unit = S.meta.singleFastaFile ? 0 : x.unit;
-        if (!opt.sketchByRecord && (R.groups.empty() || lastUnit != unit)) { R.groups.push_back(SketchGroup{layout.names[unit]}); lastUnit = unit; }
-        for (uint64_t c = x.c0; c < x.c1; c++) {
-            if (opt.sketchByRecord) R.groups.push_back(SketchGroup{recordName(layout, c)});
-            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[c], D.contigLen[c]});
-            groupOf.push_back((uint32_t) (R.groups.size() - 1));
-            R.groups.back().records++;
-            R.groups.back().bases += D.contigLen[c];
-            R.records++;
-            R.bases += D.contigLen[c];
-        }
+    if (!opt.sketchByRecord) for (const size_t unit : in.units) R.groups.push_back(SketchGroup{layout.names[unit]});
+    size_t at = 0;
+    for (const ChosenRecords::Record &rec : in.records) {
+        if (opt.sketchByRecord) { R.groups.push_back(SketchGroup{recordName(layout, rec.contig)}); at = R.groups.size() - 1; }
+        else while (in.units[at] != rec.unit) at++;
+        groupOf.push_back((uint32_t) at);
+        R.groups[at].records++;
+        R.groups[at].bases += rec.len;
     }
+    R.records = in.size(); R.bases = in.bases;
     const uint64_t ng = R.groups.size(), npairs = opt.sketchNoPairs ? 0 : ng * (ng ? ng - 1 : 0) / 2;
     if (ng >= 0xffffffffull || npairs > ((uint64_t) 1 << 28)) {
         msg = std::to_string(ng) + " groups are " + std::to_string(npairs) + " pairs, more than 2^28: sketch without the pairs (--no-pairs) or choose fewer groups (--select)";
@@ -71,28 +66,22 @@ bool collectSketch(const DecodedCollection &D, const StreamSet &S, const std::ve
     R.start.assign(ng + 1, 0);
     R.shared.assign(npairs, 0);
     uint64_t total = 0, cap = 1 << 16;
-    mbgc_fasta_t *fa = nullptr;
-    if (mbgc_fasta_create(&fa, opt.device)) return faFail(msg, "input stage");
-    int rc = 0;
-    std::vector<double> scanMs, sortMs, pairsMs;
-    for (int rep = 0; rep < (timed ? 6 : 1) && !rc; rep++) {         // (--bench: one run to warm up, the median of five)
-        double ms = 0, pms = 0;
-        for (;;) {
-            R.hashes.assign(cap, 0);
-            rc = mbgc_fasta_sketch_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), groupOf.data(), (uint32_t) ng, opt.sketchK, maxHash, R.hashes.data(), cap, R.start.data(),
-                                       kmers.data(), &total, &ms);
-            if (!rc || rc == -104) { uint64_t rows = 0, k = 0; mbgc_fasta_sketch_last(fa, &rows, &k); R.rows = rows; R.reruns += k; }     // (reruns: of all the calls, the first one's as a rule)
-            if (rc == -104 && total > cap) { cap = total; continue; }
-            break;
-        }
-        if (rc) { faFail(msg, "sketch"); break; }
-        const double sms = mbgc_fasta_sketch_sort_ms(fa);
-        if (npairs && (rc = mbgc_fasta_sketch_pairs_dev(fa, R.hashes.data(), R.start.data(), (uint32_t) ng, nullptr, npairs, R.shared.data(), &pms))) { faFail(msg, "pairs"); break; }
-        if (rep || !timed) { scanMs.push_back(ms); sortMs.push_back(sms); pairsMs.push_back(pms); }
-    }
-    mbgc_fasta_destroy(fa);
-    if (rc) return false;
-    R.kernelMs = medianOf(scanMs); R.sortMs = medianOf(sortMs); R.pairsMs = medianOf(pairsMs);
+    FastaHandle fa;
+    double median[3];                                                // the scan, the sort, the pairs
+    if (!fa.open(opt.device, msg) || !timedCalls(timed, median, [&](double (&ms)[3]) {
+            for (;;) {
+                R.hashes.assign(cap, 0);
+                const int rc = mbgc_fasta_sketch_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), groupOf.data(), (uint32_t) ng, opt.sketchK, maxHash, R.hashes.data(), cap,
+                                                     R.start.data(), kmers.data(), &total, &ms[0]);
+                if (!rc || rc == -104) { uint64_t rows = 0, k = 0; mbgc_fasta_sketch_last(fa, &rows, &k); R.rows = rows; R.reruns += k; }     // (reruns: of all the calls, the first one's as a rule)
+                if (rc == -104 && total > cap) { cap = total; continue; }
+                if (rc) return faFail(msg, "sketch");
+                break;
+            }
+            ms[1] = mbgc_fasta_sketch_sort_ms(fa);
+            return !npairs || !mbgc_fasta_sketch_pairs_dev(fa, R.hashes.data(), R.start.data(), (uint32_t) ng, nullptr, npairs, R.shared.data(), &ms[2]) || faFail(msg, "pairs");
+        })) return false;
+    R.kernelMs = median[0]; R.sortMs = median[1]; R.pairsMs = median[2];
     R.hashes.resize(total);
     for (uint64_t g = 0; g < ng; g++) R.groups[g].kmers = kmers[g];
     // ---- --sketch-host: the same questions put to the host, over the downloaded contigs; everything must be equal
@@ -101,8 +90,7 @@ bool collectSketch(const DecodedCollection &D, const StreamSet &S, const std::ve
         std::vector<uint64_t> hostKmers(ng, 0);
         std::string text;
         for (size_t r = 0; r < recs.size(); r++) {
-            text.resize(recs[r].len);
-            if (recs[r].len && swsem_dev_download(D.h, &text[0], D.seqDev + recs[r].off, recs[r].len)) return hipFail(msg, "download");
+            if (!downloadRecord(D, recs[r], text, msg)) return false;
             sketchOnHost(text, opt.sketchK, maxHash, kept[groupOf[r]], hostKmers[groupOf[r]]);
         }
         for (uint64_t g = 0; g < ng; g++) {

@@ -6,12 +6,11 @@
 #pragma once
 
 namespace {
-struct StatsRecord { uint64_t contig; size_t unit; uint64_t len; mbgc_fasta_counts_t c; };
 struct StatsResult {
-    std::vector<StatsRecord> records;                                // the chosen contigs, in collection order
-    std::vector<size_t> units;                                       // the files that have a line, in collection order
-    std::vector<mbgc_fasta_run_t> runs;                              // rec = an index into records; class 0 from 1 byte on, class 1 from --min-masked on
-    uint64_t bases = 0, edges = 0, reruns = 0;
+    ChosenRecords in;                                                // the chosen contigs; a chosen file without one has its line all the same
+    std::vector<mbgc_fasta_counts_t> counts;                         // per record
+    std::vector<mbgc_fasta_run_t> runs;                              // rec = an index into the records; class 0 from 1 byte on, class 1 from --min-masked on
+    uint64_t edges = 0, reruns = 0;
     double kernelMs = 0;
 };
 
@@ -43,51 +42,36 @@ void statsOnHost(const std::string &text, uint32_t rec, bool lowerRuns, uint64_t
 bool collectStats(const DecodedCollection &D, const StreamSet &S, const std::vector<ChosenUnit> &chosen, const MBGC_Decoder::Options &opt, bool timed, StatsResult &R,
                   std::string &msg) {
     R = StatsResult();
-    // ---- the records: the chosen contigs, in collection order; a chosen file without a contig has its line all the same
-    std::vector<mbgc_fasta_crc_rec_t> recs;
-    for (const ChosenUnit &x : chosen) {
-        const size_t unit = S.meta.singleFastaFile ? 0 : x.unit;
-        if (R.units.empty() || R.units.back() != unit) R.units.push_back(unit);
-        for (uint64_t k = x.c0; k < x.c1; k++) {
-            recs.push_back(mbgc_fasta_crc_rec_t{D.seqOff[k], D.contigLen[k]});
-            R.records.push_back({k, unit, D.contigLen[k], mbgc_fasta_counts_t()});
-            R.bases += D.contigLen[k];
-        }
-    }
+    R.in = ChosenRecords(D, S, chosen);
+    const std::vector<mbgc_fasta_crc_rec_t> &recs = R.in.recs;
     // ---- the scan. Runs of N are few and the summary counts them, so they are always asked for, from one byte on (--min-gap is applied
     // where the BED file is written); runs of lower case only for --masked-out. The call is made again with the count it states when
     // the rows do not fit
     const bool lowerRuns = !opt.statsMaskedOut.empty();
     const uint32_t flags = MBGC_FASTA_STATS_COUNTS | MBGC_FASTA_STATS_NRUNS | (lowerRuns ? MBGC_FASTA_STATS_LOWER : 0u);
-    std::vector<mbgc_fasta_counts_t> counts(std::max<size_t>(recs.size(), 1));
+    std::vector<mbgc_fasta_counts_t> &counts = R.counts;
+    counts.resize(std::max<size_t>(recs.size(), 1));
     uint64_t nRuns = 0, cap = 4096;
-    mbgc_fasta_t *fa = nullptr;
-    if (mbgc_fasta_create(&fa, opt.device)) return faFail(msg, "input stage");
-    int rc = 0;
-    std::vector<double> timings;
-    for (int rep = 0; rep < (timed ? 6 : 1) && !rc; rep++)          // (--bench: one run to warm up, the median of five)
-        for (;;) {
-            R.runs.assign(cap, mbgc_fasta_run_t());
-            double ms = 0;
-            rc = mbgc_fasta_stats_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), flags, 1, opt.statsMinMasked, counts.data(), R.runs.data(), cap, &nRuns, &ms);
-            if (!rc || rc == -104) { uint64_t e = 0, k = 0; mbgc_fasta_stats_last(fa, &e, &k); R.edges = e; R.reruns += k; }     // (reruns: of all the calls, the first one's as a rule)
-            if (rc == -104 && nRuns > cap) { cap = nRuns; continue; }
-            if (rep) timings.push_back(ms); else R.kernelMs = ms;
-            break;
-        }
-    if (rc) faFail(msg, "stats");
-    mbgc_fasta_destroy(fa);
-    if (rc) return false;
-    if (!timings.empty()) { std::sort(timings.begin(), timings.end()); R.kernelMs = timings[timings.size() / 2]; }
+    FastaHandle fa;
+    double median[1];
+    if (!fa.open(opt.device, msg) || !timedCalls(timed, median, [&](double (&ms)[1]) {
+            for (;;) {
+                R.runs.assign(cap, mbgc_fasta_run_t());
+                const int rc = mbgc_fasta_stats_dev(fa, D.seqDev, D.totalBases, recs.data(), recs.size(), flags, 1, opt.statsMinMasked, counts.data(), R.runs.data(), cap, &nRuns, &ms[0]);
+                if (!rc || rc == -104) { uint64_t e = 0, k = 0; mbgc_fasta_stats_last(fa, &e, &k); R.edges = e; R.reruns += k; }     // (reruns: of all the calls, the first one's as a rule)
+                if (rc == -104 && nRuns > cap) { cap = nRuns; continue; }
+                return !rc || faFail(msg, "stats");
+            }
+        })) return false;
+    R.kernelMs = median[0];
     R.runs.resize(nRuns);
-    for (size_t r = 0; r < R.records.size(); r++) R.records[r].c = counts[r];
+    counts.resize(recs.size());
     // ---- --stats-host: the same questions put to the host, over the downloaded contigs; everything must be equal
     if (opt.statsHost) {
         std::vector<mbgc_fasta_run_t> hostRuns;
         std::string text;
         for (size_t r = 0; r < recs.size(); r++) {
-            text.resize(recs[r].len);
-            if (recs[r].len && swsem_dev_download(D.h, &text[0], D.seqDev + recs[r].off, recs[r].len)) return hipFail(msg, "download");
+            if (!downloadRecord(D, recs[r], text, msg)) return false;
             mbgc_fasta_counts_t c;
             statsOnHost(text, (uint32_t) r, lowerRuns, opt.statsMinMasked, c, hostRuns);
             if (memcmp(&c, &counts[r], sizeof c)) { msg = "internal error: --stats-host: the host's loop counts record " + std::to_string(r) + " otherwise than the device"; return false; }
@@ -112,20 +96,21 @@ void statsAdd(mbgc_fasta_counts_t &sum, const mbgc_fasta_counts_t &c) { sum.a +=
 
 // --records, the per-file lines, --gaps-out / --masked-out (BED), the summary and the JSON line of --bench
 bool reportStats(const MBGC_Decoder::Options &opt, const FastaLayout &layout, const StatsResult &R, double decodeMs, std::string &msg) {
+    const std::vector<ChosenRecords::Record> &records = R.in.records;
     if (!opt.statsRecordsFile.empty()) {
         std::string text;
-        for (const StatsRecord &r : R.records)
-            text += layout.names[r.unit] + "\t" + recordName(layout, r.contig) + "\t" + std::to_string(r.len) + "\t" + statsColumns(r.c) + "\n";
+        for (size_t r = 0; r < records.size(); r++)
+            text += layout.names[records[r].unit] + "\t" + recordName(layout, records[r].contig) + "\t" + std::to_string(records[r].len) + "\t" + statsColumns(R.counts[r]) + "\n";
         if (opt.statsRecordsFile == "-") fputs(text.c_str(), stdout);
         else if (!writeFile(opt.statsRecordsFile, text.data(), text.size())) { msg = "cannot write " + opt.statsRecordsFile; return false; }
     }
     mbgc_fasta_counts_t all = {0, 0, 0, 0, 0, 0, 0, 0};
     size_t at = 0;
-    for (const size_t unit : R.units) {
+    for (const size_t unit : R.in.units) {
         mbgc_fasta_counts_t sum = {0, 0, 0, 0, 0, 0, 0, 0};
         std::vector<uint64_t> lens;
         uint64_t bases = 0;
-        for (; at < R.records.size() && R.records[at].unit == unit; at++) { statsAdd(sum, R.records[at].c); lens.push_back(R.records[at].len); bases += R.records[at].len; }
+        for (; at < records.size() && records[at].unit == unit; at++) { statsAdd(sum, R.counts[at]); lens.push_back(records[at].len); bases += records[at].len; }
         // N50 / L50 over the lengths in descending order: the first record at which twice the running sum reaches the file's bases
         std::sort(lens.begin(), lens.end(), std::greater<uint64_t>());
         uint64_t n50 = 0, l50 = 0, run = 0;
@@ -141,19 +126,19 @@ bool reportStats(const MBGC_Decoder::Options &opt, const FastaLayout &layout, co
     uint64_t runsN = 0;
     std::string gaps, masked;
     for (const mbgc_fasta_run_t &r : R.runs) {
-        const std::string line = recordName(layout, R.records[r.rec].contig) + "\t" + std::to_string(r.start) + "\t" + std::to_string(r.start + r.len) + "\n";
+        const std::string line = recordName(layout, records[r.rec].contig) + "\t" + std::to_string(r.start) + "\t" + std::to_string(r.start + r.len) + "\n";
         if (r.cls == 0) { runsN++; if (r.len >= std::max<uint64_t>(opt.statsMinGap, 1)) gaps += line; }
         else masked += line;
     }
     if (!opt.statsGapsOut.empty() && !writeFile(opt.statsGapsOut, gaps.data(), gaps.size())) { msg = "cannot write " + opt.statsGapsOut; return false; }
     if (!opt.statsMaskedOut.empty() && !writeFile(opt.statsMaskedOut, masked.data(), masked.size())) { msg = "cannot write " + opt.statsMaskedOut; return false; }
     const uint64_t acgt = all.a + all.c + all.g + all.t;
-    printf("stats: %zu files, %zu records, %llu bases; GC %.6f, N %llu in %llu runs, lower-case %llu, other %llu\n", R.units.size(), R.records.size(), (unsigned long long) R.bases,
+    printf("stats: %zu files, %zu records, %llu bases; GC %.6f, N %llu in %llu runs, lower-case %llu, other %llu\n", R.in.units.size(), records.size(), (unsigned long long) R.in.bases,
            acgt ? (double) (all.g + all.c) / (double) acgt : 0.0, (unsigned long long) all.n, (unsigned long long) runsN, (unsigned long long) all.lower, (unsigned long long) all.other);
     if (opt.bench)
         printf("{\"stats_kernel_ms\": %.3f, \"bases\": %llu, \"records\": %zu, \"edges\": %llu, \"edge_reruns\": %llu, \"decode_ms\": %.3f, \"stats_gb_per_s\": %.3f}\n", R.kernelMs,
-               (unsigned long long) R.bases, R.records.size(), (unsigned long long) R.edges, (unsigned long long) R.reruns, decodeMs,
-               R.kernelMs > 0 ? R.bases / (R.kernelMs * 1e-3) / 1e9 : 0.0);
+               (unsigned long long) R.in.bases, records.size(), (unsigned long long) R.edges, (unsigned long long) R.reruns, decodeMs,
+               R.kernelMs > 0 ? R.in.bases / (R.kernelMs * 1e-3) / 1e9 : 0.0);
     return true;
 }
 }  // namespace

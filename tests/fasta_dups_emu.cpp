@@ -21,18 +21,7 @@
 #define __forceinline__ inline
 #define __restrict__
 namespace fa {
-struct alignas(16) FindVec { uint32_t w[4]; };                       // (fasta_find.h's, which fasta_dups.h shares in fasta_input.hip)
-struct FindRec { uint64_t off, len; };
-constexpr uint32_t STATS_TILE = 4096;
-inline uint64_t stats_tiles_of(uintptr_t first, uint64_t len) { return len ? ((first & 15) + len + STATS_TILE - 1) / STATS_TILE : 0; }
-inline uint32_t find_tile_record(const uint64_t *tileStart, uint32_t n, uint64_t tile) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (tileStart[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+#include "../mbgc_amd/csrc/fasta_tiles.h"
 #include "../mbgc_amd/csrc/fasta_dups.h"
 }
 using namespace fa;
@@ -87,10 +76,10 @@ int main(int argc, char **argv) {
         }
         // ---- the buffer: the records at any offset, foreign bytes between them; exactly seqBytes long, at any alignment
         std::vector<uint8_t> buf;
-        std::vector<FindRec> recs;
+        std::vector<ScanRec> recs;
         for (const std::vector<uint8_t> &t : texts) {
             for (uint64_t k = rng() % 18; k; k--) buf.push_back(alpha[rng() % sizeof alpha]);
-            recs.push_back(FindRec{buf.size(), t.size()});
+            recs.push_back(ScanRec{buf.size(), t.size()});
             buf.insert(buf.end(), t.begin(), t.end());
         }
         if (it % 2) for (uint64_t k = rng() % 18; k; k--) buf.push_back('A');                    // (else the last record ends with the buffer)
@@ -102,19 +91,20 @@ int main(int argc, char **argv) {
 
         // ---- the kernel's way: the fingerprints
         std::vector<uint64_t> tileStartV(recs.size() + 1, 0);
-        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + stats_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len);
+        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + scan_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len);
         uint64_t *tileStart = exact(tileStartV);
-        FindRec *recTab = exact(recs);
+        ScanRec *recTab = exact(recs);
         std::vector<unsigned long long> rows(8 * recs.size(), 0);
         for (uint32_t block = 0; block < grid; block++) {
             uint32_t stride[8], pw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, powerOf = 0;
             bool powered = false;
             dups_pow8((uint64_t) DUPS_TILE * grid, stride);
             for (uint64_t tile = block; tile < tileStartV.back(); tile += grid) {
-                const uint32_t r = find_tile_record(tileStart, (uint32_t) recs.size(), tile);
-                const FindRec rec = recTab[r];
+                const ScanTile open = scan_tile(seq, recTab, tileStart, (uint32_t) recs.size(), tile);
+                const uint32_t r = open.r;
+                const ScanRec rec = open.rec;
                 multiTile += tile != tileStart[r];
-                const uintptr_t first = (uintptr_t) seq + rec.off, tileAddr = (first & ~(uintptr_t) 15) + (tile - tileStart[r]) * DUPS_TILE;
+                const uintptr_t first = (uintptr_t) seq + rec.off, tileAddr = open.addr;
                 uint32_t v[DUPS_THREADS][8], lanePw[8];
                 for (uint32_t lane = 0; lane < DUPS_THREADS; lane++) {
                     dups_lane_step(seq, seqBytes, rec, tileAddr, lane, exactCase, v[lane]);
@@ -167,7 +157,7 @@ int main(int argc, char **argv) {
                     }
                     const uintptr_t first = (uintptr_t) seq + recs[a].off;
                     bool got = false;
-                    for (uint64_t s = 0; s < stats_tiles_of(first, len); s++)
+                    for (uint64_t s = 0; s < scan_tiles_of(first, len); s++)
                         for (uint32_t lane = 0; lane < DUPS_THREADS; lane++)
                             got |= dups_verify_step(seq, recTab[a], recTab[b], strand, exactCase, (first & ~(uintptr_t) 15) + s * DUPS_TILE, lane);
                     if (got != want) { printf("MISMATCH in call %d: records %zu and %zu (len %llu), strand %u: differ %d, expected %d\n", it, a, b, (unsigned long long) len, strand, (int) got, (int) want); return 1; }

@@ -21,6 +21,7 @@
 #define __restrict__
 #define MBGC_FASTA_FIND_TILE 4096
 namespace fa {
+#include "../mbgc_amd/csrc/fasta_tiles.h"
 #include "../mbgc_amd/csrc/fasta_find.h"
 }
 using namespace fa;
@@ -54,7 +55,7 @@ int main(int argc, char **argv) {
         unaligned += ((uintptr_t) seq & 15) != 0;
         const uint32_t K = (uint32_t) (rng() % 4);
         // records: anywhere, of any length — empty ones, ones of a few bytes, the whole buffer, neighbours, the same one twice, unsorted
-        std::vector<FindRec> recs;
+        std::vector<ScanRec> recs;
         const int nrec = 1 + (int) (rng() % 9);
         for (int r = 0; r < nrec; r++) {
             const uint64_t lc[] = {0, 1, 7, 8, 9, seqBytes, rng() % 40, rng() % (seqBytes + 1), rng() % (seqBytes + 1)};
@@ -62,7 +63,7 @@ int main(int argc, char **argv) {
             if (r && rng() % 4 == 0) { off = recs[r - 1].off + recs[r - 1].len; len = std::min(len, seqBytes - off); }     // right behind the one before
             if (r && rng() % 6 == 0) { off = recs[r - 1].off; len = recs[r - 1].len; }                                     // the same again
             if (rng() % 5 == 0) { off = seqBytes - len; }                                                                 // ends with the buffer
-            recs.push_back(FindRec{off, len});
+            recs.push_back(ScanRec{off, len});
         }
         // patterns: pieces of the text with up to K + 1 substitutions, in the other case, random ones, prefixes of others, the same
         // one twice, one over a record's joint, long ones that span tiles
@@ -72,7 +73,7 @@ int main(int argc, char **argv) {
         for (int q = 0; q < npat; q++) {
             std::string p;
             const unsigned kind = (unsigned) (rng() % 8);
-            const FindRec &rc = recs[rng() % recs.size()];
+            const ScanRec &rc = recs[rng() % recs.size()];
             uint32_t len = minLen + (uint32_t) (rng() % 4 == 0 ? rng() % 60 : rng() % 6);
             if (big && rng() % 9 == 0) len = FIND_TILE + (uint32_t) (rng() % (FIND_TILE + 9));
             if (kind <= 3 && rc.len >= len) {
@@ -113,15 +114,16 @@ int main(int argc, char **argv) {
         FindSlot *slots = exact(T.slots); FindSeed *seeds = exact(T.seeds); FindPat *ptab = exact(T.pats); uint8_t *folded = exact(T.bytes);
         bigTables += T.bits > 7;                                        // (more than 64 chains)
         std::vector<uint64_t> tileStartV(recs.size() + 1, 0);
-        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + find_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len, T.shortest);
+        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + scan_tiles_of((uintptr_t) seq + recs[r].off, find_positions(recs[r].len, T.shortest));
         uint64_t *tileStart = exact(tileStartV);
-        FindRec *recTab = exact(recs);
+        ScanRec *recTab = exact(recs);
         std::vector<Hit> got;
         for (uint64_t tile = 0; tile < tileStartV.back(); tile++) {
-            const uint32_t r = find_tile_record(tileStart, (uint32_t) recs.size(), tile);
-            const FindRec rec = recTab[r];
+            const ScanTile open = scan_tile(seq, recTab, tileStart, (uint32_t) recs.size(), tile);
+            const uint32_t r = open.r;
+            const ScanRec rec = open.rec;
             multiTile += tile != tileStart[r];
-            const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * FIND_TILE;
+            const uintptr_t tileAddr = open.addr;
             uint8_t *stage = (uint8_t *) operator new[](FIND_STAGE, std::align_val_t(16));
             memset(stage, 0xee, FIND_STAGE);
             for (uint32_t lane = 0; lane < FIND_THREADS; lane++) find_stage_step(seq, seqBytes, tileAddr, lane, stage);

@@ -22,16 +22,7 @@
 #define __forceinline__ inline
 #define __restrict__
 namespace fa {
-struct alignas(16) FindVec { uint32_t w[4]; };                       // (fasta_find.h's, which fasta_sketch.h shares in fasta_input.hip)
-struct FindRec { uint64_t off, len; };
-inline uint32_t find_tile_record(const uint64_t *tileStart, uint32_t n, uint64_t tile) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (tileStart[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+#include "../mbgc_amd/csrc/fasta_tiles.h"
 #include "../mbgc_amd/csrc/fasta_sketch.h"
 }
 using namespace fa;
@@ -111,7 +102,7 @@ int main(int argc, char **argv) {
                     }
                 }
             // records: a start at every offset mod 16 of the buffer's addresses; the lengths and ends the header names
-            std::vector<FindRec> recs;
+            std::vector<ScanRec> recs;
             for (uint32_t r = 0; r < 16; r++) {
                 uint64_t off = rng() % 200;
                 while (((uintptr_t) seq + off) % 16 != r) off++;
@@ -120,11 +111,11 @@ int main(int argc, char **argv) {
                 const uint64_t edge = edges[rng() % 3];
                 const uint64_t lc[] = {0, k - 1, k, k + 1, seqBytes - off, edge - k, edge + k, edge - 1, edge, edge + 1, edge + k - 1, edge - k + 1, rng() % (seqBytes - off + 1)};
                 const uint64_t len = std::min(lc[(it + r) % 13], seqBytes - off);
-                recs.push_back(FindRec{off, len});
+                recs.push_back(ScanRec{off, len});
                 atBufferEnd += off + len == seqBytes && len >= k;
             }
-            recs.push_back(FindRec{seqBytes - k, k});                    // one k-mer, the buffer's last bytes
-            recs.push_back(FindRec{seqBytes, 0});
+            recs.push_back(ScanRec{seqBytes - k, k});                    // one k-mer, the buffer's last bytes
+            recs.push_back(ScanRec{seqBytes, 0});
             recs.push_back(recs[rng() % 16]);                            // the same again
             atBufferEnd++;
 
@@ -146,15 +137,16 @@ int main(int argc, char **argv) {
 
             // ---- the kernel's way
             std::vector<uint64_t> tileStartV(recs.size() + 1, 0);
-            for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + sketch_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len, k);
+            for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + scan_tiles_of((uintptr_t) seq + recs[r].off, sketch_positions(recs[r].len, k));
             uint64_t *tileStart = exact(tileStartV);
-            FindRec *recTab = exact(recs);
+            ScanRec *recTab = exact(recs);
             std::vector<Row> got;
             std::vector<uint64_t> gotValid(recs.size(), 0);
             for (uint64_t tile = 0; tile < tileStartV.back(); tile++) {
-                const uint32_t r = find_tile_record(tileStart, (uint32_t) recs.size(), tile);
-                const FindRec rec = recTab[r];
-                const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * SKETCH_TILE;
+                const ScanTile open = scan_tile(seq, recTab, tileStart, (uint32_t) recs.size(), tile);
+                const uint32_t r = open.r;
+                const ScanRec rec = open.rec;
+                const uintptr_t tileAddr = open.addr;
                 uint64_t own[SKETCH_THREADS];
                 for (uint32_t lane = 0; lane < SKETCH_THREADS; lane++) own[lane] = sketch_pack(seq, seqBytes, rec, tileAddr + 16u * lane);
                 for (uint32_t lane = 0; lane < SKETCH_THREADS; lane++) {

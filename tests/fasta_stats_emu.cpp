@@ -20,16 +20,7 @@
 #define __forceinline__ inline
 #define __restrict__
 namespace fa {
-struct alignas(16) FindVec { uint32_t w[4]; };                       // (fasta_find.h's, which fasta_stats.h shares in fasta_input.hip)
-struct FindRec { uint64_t off, len; };
-inline uint32_t find_tile_record(const uint64_t *tileStart, uint32_t n, uint64_t tile) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (tileStart[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+#include "../mbgc_amd/csrc/fasta_tiles.h"
 #include "../mbgc_amd/csrc/fasta_stats.h"
 }
 using namespace fa;
@@ -66,7 +57,7 @@ int main(int argc, char **argv) {
         }
         unaligned += ((uintptr_t) seq & 15) != 0;
         // records: anywhere, of any length — empty ones, ones of a byte, the whole buffer, neighbours, the same one twice, overlapping
-        std::vector<FindRec> recs;
+        std::vector<ScanRec> recs;
         const int nrec = 1 + (int) (rng() % 9);
         for (int r = 0; r < nrec; r++) {
             const uint64_t lc[] = {0, 1, 15, 16, 17, seqBytes, rng() % 40, rng() % (seqBytes + 1), rng() % (seqBytes + 1)};
@@ -74,7 +65,7 @@ int main(int argc, char **argv) {
             if (r && rng() % 3 == 0) { off = recs[r - 1].off + recs[r - 1].len; len = std::min(len, seqBytes - off); }     // right behind the one before
             if (r && rng() % 6 == 0) { off = recs[r - 1].off; len = recs[r - 1].len; }                                     // the same again
             if (rng() % 5 == 0) { off = seqBytes - len; }                                                                 // ends with the buffer
-            recs.push_back(FindRec{off, len});
+            recs.push_back(ScanRec{off, len});
         }
         const uint32_t want = it % 7 == 0 ? STATS_CLS_N : (it % 7 == 1 ? STATS_CLS_LOWER : STATS_CLS_N | STATS_CLS_LOWER);
 
@@ -112,9 +103,9 @@ int main(int argc, char **argv) {
 
         // ---- the kernel's way
         std::vector<uint64_t> tileStartV(recs.size() + 1, 0);
-        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + stats_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len);
+        for (size_t r = 0; r < recs.size(); r++) tileStartV[r + 1] = tileStartV[r] + scan_tiles_of((uintptr_t) seq + recs[r].off, recs[r].len);
         uint64_t *tileStart = exact(tileStartV);
-        FindRec *recTab = exact(recs);
+        ScanRec *recTab = exact(recs);
         std::vector<Counts> gotCounts(recs.size(), Counts{{0, 0, 0, 0, 0, 0, 0}});
         // the edge buffer: exactly edgeCap rows, now and then too few — the cursor then counts on, and the pass is made again
         uint64_t edgeCap = it % 5 == 0 ? 3 : 1 << 16, cursor = 0;
@@ -124,10 +115,11 @@ int main(int argc, char **argv) {
             cursor = 0;
             for (Counts &c : gotCounts) c = Counts{{0, 0, 0, 0, 0, 0, 0}};
             for (uint64_t tile = 0; tile < tileStartV.back(); tile++) {
-                const uint32_t r = find_tile_record(tileStart, (uint32_t) recs.size(), tile);
-                const FindRec rec = recTab[r];
+                const ScanTile open = scan_tile(seq, recTab, tileStart, (uint32_t) recs.size(), tile);
+                const uint32_t r = open.r;
+                const ScanRec rec = open.rec;
                 multiTile += tile != tileStart[r];
-                const uintptr_t tileAddr = (((uintptr_t) seq + rec.off) & ~(uintptr_t) 15) + (tile - tileStart[r]) * STATS_TILE;
+                const uintptr_t tileAddr = open.addr;
                 StatsLane L[STATS_THREADS];
                 for (uint32_t lane = 0; lane < STATS_THREADS; lane++) L[lane] = stats_lane_step(seq, seqBytes, rec, tileAddr, lane);
                 uint64_t a = 0, b = 0;                                   // the wave's and the block's sums
