@@ -248,6 +248,32 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
                         const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
                         mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs);
 
+/* The search of `mbgc-hip f --iupac` and `--primers`: mbgc_fasta_find_dev's question, arguments, hit rows, order and refusals with
+ * another matching rule — a pattern letter is an IUPAC code, a SET of bases. The set of a pattern letter, either case:
+ *   A: A   C: C   G: G   T, U: T   R: AG   Y: CT   S: CG   W: AT   K: GT   M: AC   B: CGT   D: AGT   H: ACT   V: ACG   N: ACGT
+ * A text byte has a base only if it is one of acgtuACGTU, u counting as T; every other byte has none — N and the ambiguity letters IN THE
+ * TEXT included. Position j matches if and only if the text byte has a base and that base is in the pattern letter's set. So a text N is
+ * a mismatch against everything, a pattern N included; this differs from mbgc_fasta_find_dev, where letters are compared literally and
+ * an N matches an N. A hit is (rec r, pattern q, pos p, mismatches d): p + len(q) <= recs[r].len, d = the positions that do not match,
+ * d <= maxMismatches. Every hit is reported exactly once, overlapping ones included; a hit never reaches over a record's end; no byte
+ * outside seq_dev[0, seqBytes) is read.
+ * Refused before anything is launched (-103; *nHits and hits_host are left as they were): maxMismatches > 3; a pattern shorter than
+ * 8 (maxMismatches + 1) letters or longer than 65535; a letter outside the table above; a pattern with a segment that has no usable
+ * seed (below; the message names the pattern and the segment); a record that does not lie inside the buffer. -104 with the exact count
+ * in *nHits when the hits do not fit, as in mbgc_fasta_find_dev; otherwise hits_host[0, *nHits) sorted by (rec, pos, pattern).
+ * How: a pattern is cut into maxMismatches + 1 disjoint segments of len / (maxMismatches + 1) letters, one of which an alignment
+ * leaves free of mismatches. A segment's seed is the window of 8 letters inside it that stands for the fewest concrete sequences (the
+ * product of the letters' set sizes; the leftmost on a tie); the host expands it into each of them — 256 at most, which four N in a
+ * row reach exactly; a segment whose best window stands for more is the refusal above — and packs each into 16 bits. The 65536
+ * possible grams are a bitmap of 8 KiB that a block keeps in LDS whatever the patterns are; a lane tests its 16 positions against it
+ * (a text gram that holds a byte without a base is no gram) and reads the rows of a gram from global memory only on a set bit. Tiles,
+ * staging, cursor and hit buffer are mbgc_fasta_find_dev's.
+ * mbgc_fasta_find_iupac_last: the rows (pattern, segment, expansion) of the last call's table, and the rows its lanes walked. */
+int mbgc_fasta_find_iupac_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                              const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
+                              mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs);
+void mbgc_fasta_find_iupac_last(const mbgc_fasta_t *p, uint64_t *tableRows, uint64_t *rowsWalked);
+
 /* The scan of `mbgc-hip s`: what do byte ranges of a device buffer hold, and where are their runs of N and of lower case. Record r is
  * seq_dev[recs[r].off, recs[r].off + recs[r].len), as in mbgc_fasta_find_dev: the records may overlap, touch, repeat, be empty and
  * stand at any offset. A record that does not lie inside [0, seqBytes) is refused before anything is launched (-103, message in

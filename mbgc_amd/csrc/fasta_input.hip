@@ -725,6 +725,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_select.h"
 #include "fasta_tiles.h"
 #include "fasta_find.h"
+#include "fasta_find_iupac.h"
 #include "fasta_stats.h"
 #include "fasta_sketch.h"
 #include "fasta_dups.h"
@@ -868,6 +869,36 @@ __global__ void __launch_bounds__(FIND_THREADS) k_fa_find(const uint8_t *__restr
             const unsigned long long at = atomicAdd(cursor, 1ull);
             if (at < hitCap) hits[at] = mbgc_fasta_hit_t{pos, r, pat, d, 0u};
         });
+        __syncthreads();                                                     // (the next tile's stores wait for this tile's reads)
+    }
+}
+
+// mbgc_fasta_find_iupac_dev: k_fa_find's grid, staging, cursor and hit buffer with the matcher of fasta_find_iupac.h. The bitmap of the
+// grams that have a chain — 8 KiB whatever the patterns are — is copied to LDS once per block; the chains' starts and the rows are read
+// where they lie in global memory, from L2, and only behind a set bit. stats[0] is the cursor; stats[IUPAC_WALKED], a cache line of
+// its own, the rows walked: summed over the wave by shuffles, one add per wave and tile that walked any.
+__global__ void __launch_bounds__(FIND_THREADS) k_fa_find_iupac(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint64_t *__restrict__ tileStart,
+                                                                uint32_t nrec, uint64_t ntiles, const uint32_t *__restrict__ bitmapGlobal, const uint32_t *__restrict__ gramStart,
+                                                                const IupacRow *__restrict__ rows, const IupacPat *__restrict__ pats, const uint8_t *__restrict__ masks, uint32_t K,
+                                                                mbgc_fasta_hit_t *__restrict__ hits, uint64_t hitCap, unsigned long long *__restrict__ stats) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[FIND_STAGE];
+    __shared__ uint32_t bitmap[IUPAC_BITMAP_WORDS];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t s = lane; s < IUPAC_BITMAP_WORDS; s += FIND_THREADS) bitmap[s] = bitmapGlobal[s];      // (visible behind the first tile's barrier)
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
+        const ScanTile T = scan_tile(seq, recs, tileStart, nrec, tile);
+        const uint32_t r = T.r;
+        find_stage_step(seq, seqBytes, T.addr, lane, stage);
+        if (lane == 0) find_stage_step(seq, seqBytes, T.addr, FIND_VECS - 1, stage);
+        __syncthreads();
+        const uint32_t walked = iupac_lane_step(seq, T.rec, T.addr, lane, stage, bitmap, gramStart, rows, pats, masks, K, [&](uint64_t pos, uint32_t pat, uint32_t d) {
+            const unsigned long long at = atomicAdd(stats, 1ull);
+            if (at < hitCap) hits[at] = mbgc_fasta_hit_t{pos, r, pat, d, 0u};
+        });
+        uint32_t waveWalked = walked;                                        // (every lane of the block is here: the tile loop is uniform)
+#pragma unroll
+        for (uint32_t d = WAVE / 2; d; d >>= 1) waveWalked += __shfl_xor(waveWalked, d);
+        if (waveWalked && (lane & (WAVE - 1)) == 0) atomicAdd(stats + IUPAC_WALKED, (unsigned long long) waveWalked);
         __syncthreads();                                                     // (the next tile's stores wait for this tile's reads)
     }
 }
@@ -1287,6 +1318,12 @@ struct mbgc_fasta {
     fa::Buf<uint8_t> dFindBytes;
     fa::Buf<mbgc_fasta_hit_t> dFindHits;
     fa::Buf<unsigned long long> dFindCursor;
+    fa::Buf<uint32_t> dIupacBitmap, dIupacStart;                      // mbgc_fasta_find_iupac_dev: the bitmap, the chains' starts, the rows, the patterns and
+    fa::Buf<fa::IupacRow> dIupacRows;                                 // their masks, the cursor with the rows walked behind it (hits: dFindHits)
+    fa::Buf<fa::IupacPat> dIupacPats;
+    fa::Buf<uint8_t> dIupacMasks;
+    fa::Buf<unsigned long long> dIupacStats;
+    uint64_t iupacRows = 0, iupacWalked = 0;                          // the last call's: mbgc_fasta_find_iupac_last
     fa::Buf<unsigned long long> dStatsCounts;   // mbgc_fasta_stats_dev: the records' rows, the edges and their cursor
     fa::Buf<fa::StatsEdge> dStatsEdges;
     fa::Buf<unsigned long long> dStatsCursor;
@@ -1825,6 +1862,78 @@ int mbgc_fasta_find_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqByt
     });
     memcpy(hits_host, out.data(), count * sizeof(mbgc_fasta_hit_t));
     return 0;
+}
+
+int mbgc_fasta_find_iupac_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n,
+                              const uint8_t *patterns_host, const uint64_t *patOff, uint64_t npat, uint32_t maxMismatches,
+                              mbgc_fasta_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs) {
+    using namespace fa;
+    if (kernelMs) *kernelMs = 0;
+    const uint32_t K = maxMismatches;
+    if (K > FIND_MAX_K) return fail(-103, "find-iupac: %u mismatches (at most %u)", K, FIND_MAX_K);
+    // (every row is a 32-bit index: a pattern has at most (FIND_MAX_K + 1) IUPAC_MAX_EXPAND of them)
+    if (n >= 0xffffffffull || npat >= 0xffffffffull / ((FIND_MAX_K + 1) * IUPAC_MAX_EXPAND))
+        return fail(-103, "find-iupac: %llu records, %llu patterns in one call", (unsigned long long) n, (unsigned long long) npat);
+    for (uint64_t q = 0; q < npat; q++) {
+        if (patOff[q + 1] < patOff[q]) return fail(-103, "find-iupac: pattern %llu ends in front of its start", (unsigned long long) q);
+        const uint64_t len = patOff[q + 1] - patOff[q];
+        if (len < (uint64_t) IUPAC_GRAM * (K + 1)) return fail(-103, "find-iupac: pattern %llu has %llu letters, %u mismatches need at least %u", (unsigned long long) q, (unsigned long long) len, K, IUPAC_GRAM * (K + 1));
+        if (len > FIND_MAX_LEN) return fail(-103, "find-iupac: pattern %llu has %llu letters (at most %u)", (unsigned long long) q, (unsigned long long) len, FIND_MAX_LEN);
+        for (uint64_t i = patOff[q]; i < patOff[q + 1]; i++)
+            if (!iupac_mask(patterns_host[i])) return fail(-103, "find-iupac: pattern %llu holds a byte that is no IUPAC letter (0x%02x at %llu)", (unsigned long long) q, patterns_host[i], (unsigned long long) (i - patOff[q]));
+    }
+    // (the table is made whatever the records are: a pattern that cannot be searched is refused, not passed over)
+    IupacTable T;
+    uint64_t badPat = 0;
+    uint32_t badSeg = 0, badGrams = 0;
+    if (npat && !iupac_build_table(patterns_host, patOff, npat, K, T, badPat, badSeg, badGrams))
+        return fail(-103, "find-iupac: pattern %llu, segment %u (letters %u to %u): its best window of %u letters stands for %u sequences (at most %u): too many degenerate letters in a row",
+                    (unsigned long long) badPat, badSeg, badSeg * (uint32_t) ((patOff[badPat + 1] - patOff[badPat]) / (K + 1)) + 1,
+                    (badSeg + 1) * (uint32_t) ((patOff[badPat + 1] - patOff[badPat]) / (K + 1)), IUPAC_GRAM, badGrams, IUPAC_MAX_EXPAND);
+    uint64_t ntiles = 0;
+    FTRY(scan_prepare(p, "find-iupac", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return npat ? find_positions(recs[r].len, T.shortest) : 0; }, ntiles));
+    p->iupacRows = T.rows.size(); p->iupacWalked = 0;
+    if (ntiles == 0) { *nHits = 0; return 0; }                       // (no record, no pattern, or no record as long as the shortest pattern)
+    int rc;
+    if ((rc = p->dIupacBitmap.reserve(T.bitmap.size())) || (rc = p->dIupacStart.reserve(T.gramStart.size())) || (rc = p->dIupacRows.reserve(T.rows.size())) ||
+        (rc = p->dIupacPats.reserve(T.pats.size())) || (rc = p->dIupacMasks.reserve(T.masks.size())) || (rc = p->dFindHits.reserve(std::max<uint64_t>(hitCap, 1))) ||
+        (rc = p->dIupacStats.reserve(IUPAC_WALKED + 1))) return rc;
+    FCHK(hipMemcpyAsync(p->dIupacBitmap.p, T.bitmap.data(), T.bitmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dIupacStart.p, T.gramStart.data(), T.gramStart.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dIupacRows.p, T.rows.data(), T.rows.size() * sizeof(IupacRow), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dIupacPats.p, T.pats.data(), T.pats.size() * sizeof(IupacPat), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dIupacMasks.p, T.masks.data(), T.masks.size(), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemsetAsync(p->dIupacStats.p, 0, (IUPAC_WALKED + 1) * sizeof(unsigned long long), p->stream));
+    FTRY(p->timer.start(p->stream, kernelMs != nullptr));
+    // one launch whatever n is, as k_fa_find's: the blocks stride over the tiles
+    k_fa_find_iupac<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 1024)), dim3(FIND_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScanTiles.p, (uint32_t) n, ntiles,
+        p->dIupacBitmap.p, p->dIupacStart.p, p->dIupacRows.p, p->dIupacPats.p, p->dIupacMasks.p, K, p->dFindHits.p, hitCap, p->dIupacStats.p);
+    FCHK(hipGetLastError());
+    FTRY(p->timer.stop(p->stream));
+    unsigned long long stats[IUPAC_WALKED + 1] = {0};
+    FCHK(hipMemcpyAsync(stats, p->dIupacStats.p, sizeof stats, hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    FTRY(p->timer.read(kernelMs));
+    const unsigned long long count = stats[0];
+    p->iupacWalked = stats[IUPAC_WALKED];
+    *nHits = count;
+    if (count > hitCap) return fail(-104, "find-iupac: %llu hits, the buffer holds %llu", count, (unsigned long long) hitCap);
+    if (count == 0) return 0;
+    std::vector<mbgc_fasta_hit_t> out(count);                        // (the caller's array stays as it is unless the whole call succeeds)
+    FCHK(hipMemcpyAsync(out.data(), p->dFindHits.p, count * sizeof(mbgc_fasta_hit_t), hipMemcpyDeviceToHost, p->stream));
+    FCHK(hipStreamSynchronize(p->stream));
+    std::sort(out.begin(), out.end(), [](const mbgc_fasta_hit_t &a, const mbgc_fasta_hit_t &b) {
+        if (a.rec != b.rec) return a.rec < b.rec;
+        if (a.pos != b.pos) return a.pos < b.pos;
+        return a.pattern < b.pattern;
+    });
+    memcpy(hits_host, out.data(), count * sizeof(mbgc_fasta_hit_t));
+    return 0;
+}
+
+void mbgc_fasta_find_iupac_last(const mbgc_fasta_t *p, uint64_t *tableRows, uint64_t *rowsWalked) {
+    if (tableRows) *tableRows = p->iupacRows;
+    if (rowsWalked) *rowsWalked = p->iupacWalked;
 }
 
 int mbgc_fasta_stats_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, uint32_t flags,

@@ -9,7 +9,7 @@ from . import binding
 EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fasta_parse_batch_dev mbgc_fasta_parse_host mbgc_fasta_parse_batch_dev2 mbgc_fasta_parse_host2 mbgc_fasta_host_alloc mbgc_fasta_host_free mbgc_fasta_upload
            mbgc_fasta_split_dev mbgc_fasta_split_buf_dev mbgc_fasta_split_buf_dev2 mbgc_fasta_format_dev mbgc_fasta_download_begin mbgc_fasta_download_wait mbgc_fasta_gather_dev mbgc_fasta_dev_alloc mbgc_fasta_dev_free mbgc_fasta_dev_copy mbgc_fasta_download
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
-           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_stats_dev mbgc_fasta_stats_last
+           mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_find_iupac_dev mbgc_fasta_find_iupac_last mbgc_fasta_stats_dev mbgc_fasta_stats_last
            mbgc_fasta_sketch_dev mbgc_fasta_sketch_last mbgc_fasta_sketch_sort_ms mbgc_fasta_sketch_pairs_dev
            mbgc_fasta_dups_dev mbgc_fasta_dups_last mbgc_fasta_dups_comp_table""".split()
 
@@ -41,6 +41,9 @@ class CrcRec(C.Structure):
 
 FIND_TILE = 4096                     # MBGC_FASTA_FIND_TILE: text positions per tile of find_dev
 FIND_MAX_MISMATCHES, FIND_MAX_PATTERN = 3, 65535
+FIND_IUPAC_MAX_EXPAND = 256          # find_iupac_dev: the concrete sequences a segment's best window of 8 letters may stand for
+IUPAC_SETS = {"A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC",
+              "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
 
 
 class Hit(C.Structure):
@@ -186,6 +189,9 @@ def _lib():
         L.mbgc_fasta_crc_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L.mbgc_fasta_find_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_find_iupac_dev.argtypes = L.mbgc_fasta_find_dev.argtypes
+        L.mbgc_fasta_find_iupac_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mbgc_fasta_find_iupac_last.restype = None
         L.mbgc_fasta_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mbgc_fasta_stats_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -471,6 +477,31 @@ class FastaParser:
                                            len(pats), int(max_mismatches), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
             return r, int(n.value), lambda: (out[: n.value].copy(), ms.value)
         return _with_capacity(call, 4096, hit_cap, HitsTooMany, calls=math.inf)
+
+    def find_iupac_dev(self, seq_ptr, seq_bytes, ranges, patterns, max_mismatches=0, hit_cap=None):
+        """find_dev with IUPAC patterns (mbgc_fasta_find_iupac_dev): a pattern letter is a set of bases (IUPAC_SETS), a text byte has a
+        base only if it is one of acgtuACGTU, and a position matches iff the text's base is in the pattern letter's set — a text N
+        matches nothing. Same arguments, same answer, same HitsTooMany; a refused call (a letter outside the table, a segment whose
+        best window of 8 letters stands for more than FIND_IUPAC_MAX_EXPAND sequences, and find_dev's refusals) raises and launches
+        nothing."""
+        rows, recs, nrec = _ranges(ranges)
+        pats = [bytes(x) for x in patterns]
+        blob = np.frombuffer(b"".join(pats) + b"\0", dtype=np.uint8)      # (one byte more: an empty list still has an address)
+        pat_off = np.concatenate([[0], np.cumsum([len(x) for x in pats], dtype=np.uint64)]).astype(np.uint64)
+        n, ms = C.c_uint64(0), C.c_double(0)
+
+        def call(cap):
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            r = _lib().mbgc_fasta_find_iupac_dev(self.h, seq_ptr, int(seq_bytes), recs, nrec, blob.ctypes.data_as(C.c_void_p), pat_off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 len(pats), int(max_mismatches), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(ms))
+            return r, int(n.value), lambda: (out[: n.value].copy(), ms.value)
+        return _with_capacity(call, 4096, hit_cap, HitsTooMany, calls=math.inf)
+
+    def find_iupac_last(self):
+        """-> (the rows of the last find_iupac_dev call's table, the rows its lanes walked)"""
+        rows, walked = C.c_uint64(0), C.c_uint64(0)
+        _lib().mbgc_fasta_find_iupac_last(self.h, C.byref(rows), C.byref(walked))
+        return int(rows.value), int(walked.value)
 
     def stats_dev(self, seq_ptr, seq_bytes, ranges, flags=STATS_COUNTS | STATS_NRUNS | STATS_LOWER, min_run_n=1, min_run_lower=1, run_cap=None):
         """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes -> (counts: an (n, 8)

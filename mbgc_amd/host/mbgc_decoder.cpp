@@ -407,7 +407,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
                           : opt.sketch  ? collectSketch(D, S, chosen, layout, opt, opt.bench, sketch, msg) && reportSketch(opt, sketch, decodeMs(D, S), msg)
                                         : collectDups(D, S, chosen, opt, opt.bench, dups, msg) && reportDups(opt, layout, dups, decodeMs(D, S), msg);
             if (!ok) return failed();
-            return opt.find && found.lines.empty() ? 3 : 0;
+            return opt.find && (opt.findPrimers.empty() ? found.lines.empty() : found.amplicons.empty()) ? 3 : 0;
         }
         if (wantFasta) {
             const FastaPlan plan = sel.selectingRegion ? planFasta(pieces.rows, S.meta, pieces.layout, pieces.len, opt.batchText, opt.gzip, true)
@@ -707,6 +707,30 @@ const char *const MBGC_HIP_F_USAGE =
     "  --bench: two decodes, the second one timed, the search run six times (the median of the last five); one JSON line (find_kernel_ms,\n"
     "  bases_searched, patterns, hits, retries, decode_ms, find_gb_per_s; --find-host: find_host_ms). Not with --region or --check\n";
 
+// what --iupac and --primers add to `f`; printed behind MBGC_HIP_F_USAGE by the general help and when one of their options stands on a
+// command line that is answered with the usage text (MBGC_HIP_F_USAGE itself is what `f` printed before these options came)
+const char *const MBGC_HIP_F_IUPAC_USAGE =
+    "mbgc-hip f --iupac ... | f --primers NAME:FWD:REV... [--primer-file file] [--min-amplicon N] [--max-amplicon N] [--amplicons-out file] ...\n"
+    "  --iupac: the queries are IUPAC patterns, a letter stands for a set of bases: A, C, G, T (or U); R = AG, Y = CT, S = CG, W = AT, K = GT,\n"
+    "  M = AC; B = CGT, D = AGT, H = ACT, V = ACG; N = ACGT. A query with any other letter is refused. A text byte has a base only if it is one of\n"
+    "  acgtuACGTU (u is T); a position matches if the text's base is in the query letter's set. So an N or an ambiguity letter IN THE TEXT is a\n"
+    "  mismatch against everything, a query N included — unlike f without --iupac, which compares letters literally (there an N matches an N and\n"
+    "  an R only an R). The reverse complement is the IUPAC one (A-T, C-G, R-Y, K-M, B-V, D-H; S, W, N are their own). --mismatches and its length\n"
+    "  rule, the lines, the summary, the exit statuses and every other option of f stay as they are; --bench adds rows (of the seed table) and\n"
+    "  rows_walked. Every one of the K + 1 equal parts of a query needs 8 letters in a row that stand for at most 256 sequences together (ACNNNNGT\n"
+    "  does, ACNNNNNT does not): a query with a part that has no such 8 letters is refused, by name and part\n"
+    "  --primers NAME:FWD:REV (repeatable; --primer-file file: a line name<TAB>fwd<TAB>rev per pair): in-silico PCR. Implies --iupac; both primers\n"
+    "  are written 5'->3' and are subject to --mismatches K and its length rule, 8 (K + 1) letters: a 20-mer allows K <= 1, a 24-mer K <= 3. A +\n"
+    "  product is a + hit of FWD at [s1, e1] and a - hit of REV at [s2, e2] of one record with s1 <= s2, e1 <= e2 and --min-amplicon (default 0)\n"
+    "  <= e2 - s1 + 1 <= --max-amplicon (default 5000); a - product the same with REV + on the left and FWD - on the right. Every such pair of\n"
+    "  hits is a product, not only the nearest; FWD-FWD and REV-REV are none. Records are linear: a product across the origin of a circular\n"
+    "  genome is not found. One line per product on stdout: pair, file, record, start, end (1-based, inclusive, primers included), strand, length,\n"
+    "  mismatches of the left primer, mismatches of the right primer, tab-separated; sorted by file, record, start, end, pair, + before -. Then\n"
+    "  `amplicons: <n> of <pairs> primer pairs in <records> records of <files> files; <bases> bases searched` (n products; the pairs given; the\n"
+    "  records and files that hold a product). The primers' own hits (queries NAME.fwd, NAME.rev) are printed only with --hits file.\n"
+    "  --amplicons-out file: a line RECORD:START-END per product, identical lines once, for mbgc-hip d --region-list. Exit status 0: at least\n"
+    "  one product; 3: none; 1: a refusal. Not with --seq, --seq-file or --forward-only\n";
+
 // --seq-file: the records of a FASTA file as queries — the header's first word, the sequence lines joined
 static bool readQueryFile(const char *path, std::vector<MBGC_Decoder::FindQuery> &out) {
     std::ifstream f(path);
@@ -726,12 +750,55 @@ int mbgc_hip_find_main(int argc, char **argv) {
     opt.find = opt.writeNothing = true;
     int inlineQueries = 0;
     std::string prefix;
-    const ScanTool tool = {'f', MBGC_HIP_F_USAGE, "a search looks at whole records (an option of mbgc-hip d; f --regions-out writes such a list)", nullptr};
+    // The usage text grows by the new options' part only when one of them stands on the command line as a word of its own: without
+    // them `f` answers a malformed command line with the text it always printed, byte for byte (tests/golden/scan_cli_refusals.json
+    // holds it). This look at argv chooses that text and nothing else — the options themselves are read by the one parser below, which
+    // knows no --option=value form either, so the two cannot disagree on what was given; a later change may extend the one text and
+    // its recorded copy and drop this.
+    static const char *const newOptions[] = {"--iupac", "--primers", "--primer-file", "--min-amplicon", "--max-amplicon", "--amplicons-out"};
+    bool newAsked = false, plainQueries = false, ampliconOptions = false;
+    for (int i = 2; i < argc; i++) for (const char *o : newOptions) newAsked |= !strcmp(argv[i], o);
+    const std::string usage = std::string(MBGC_HIP_F_USAGE) + (newAsked ? MBGC_HIP_F_IUPAC_USAGE : "");
+    const auto addPair = [&](const std::string &name, const std::string &fwd, const std::string &rev) {
+        opt.findPrimers.push_back({name, fwd, rev});
+        opt.findQueries.push_back({name + ".fwd", fwd}); opt.findQueries.push_back({name + ".rev", rev});
+    };
+    const ScanTool tool = {'f', usage.c_str(), "a search looks at whole records (an option of mbgc-hip d; f --regions-out writes such a list)", nullptr};
     const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
-        if (a == "--seq" && i + 1 < argc) opt.findQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]});
+        if (a == "--seq" && i + 1 < argc) { opt.findQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]}); plainQueries = true; }
         else if (a == "--seq-file" && i + 1 < argc) {
             if (!readQueryFile(argv[++i], opt.findQueries)) { fprintf(stderr, "mbgc-hip f: cannot open the query file %s\n", argv[i]); return -1; }
+            plainQueries = true;
         }
+        else if (a == "--iupac") opt.findIupac = true;
+        else if (a == "--primers" && i + 1 < argc) {
+            const std::string spec = argv[++i];
+            const size_t c1 = spec.find(':'), c2 = c1 == std::string::npos ? c1 : spec.find(':', c1 + 1);
+            if (c2 == std::string::npos || spec.find(':', c2 + 1) != std::string::npos || c1 == 0 || c2 == c1 + 1 || c2 + 1 == spec.size()) {
+                fprintf(stderr, "mbgc-hip f: --primers takes NAME:FWD:REV, three parts that are not empty (got %s)\n", spec.c_str());
+                return -1;
+            }
+            addPair(spec.substr(0, c1), spec.substr(c1 + 1, c2 - c1 - 1), spec.substr(c2 + 1));
+        }
+        else if (a == "--primer-file" && i + 1 < argc) {
+            std::ifstream f(argv[++i]);
+            if (!f) { fprintf(stderr, "mbgc-hip f: cannot open the primer file %s\n", argv[i]); return -1; }
+            size_t n = 0;
+            for (std::string line; std::getline(f, line);) {
+                n++;
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                if (line.empty()) continue;
+                const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+                if (t2 == std::string::npos || line.find('\t', t2 + 1) != std::string::npos || t1 == 0 || t2 == t1 + 1 || t2 + 1 == line.size()) {
+                    fprintf(stderr, "mbgc-hip f: --primer-file %s, line %zu: a line is name<TAB>fwd<TAB>rev, three parts that are not empty\n", argv[i], n);
+                    return -1;
+                }
+                addPair(line.substr(0, t1), line.substr(t1 + 1, t2 - t1 - 1), line.substr(t2 + 1));
+            }
+        }
+        else if (a == "--min-amplicon" && i + 1 < argc) { ampliconOptions = true; if (!numberOption('f', "--min-amplicon", "a number of bases", argv[++i], opt.findMinAmplicon)) return -1; }
+        else if (a == "--max-amplicon" && i + 1 < argc) { ampliconOptions = true; if (!numberOption('f', "--max-amplicon", "a number of bases", argv[++i], opt.findMaxAmplicon)) return -1; }
+        else if (a == "--amplicons-out" && i + 1 < argc) { ampliconOptions = true; opt.findAmpliconsOut = argv[++i]; }
         else if (a == "--mismatches" && i + 1 < argc) {
             const std::string v = argv[++i];
             if (v.size() != 1 || v[0] < '0' || v[0] > '3') { fprintf(stderr, "mbgc-hip f: --mismatches takes 0, 1, 2 or 3\n"); return -1; }
@@ -748,11 +815,42 @@ int mbgc_hip_find_main(int argc, char **argv) {
         else if (a == "--find-host") opt.findHost = true;
         else return 0;
         return 1;
-    }, [&] { return opt.findQueries.empty() ? 2 : 0; }, prefix);
+    }, [&] {
+        if (opt.findQueries.empty()) return 2;
+        if (!opt.findPrimers.empty() && plainQueries) { fprintf(stderr, "mbgc-hip f: --primers / --primer-file and --seq / --seq-file: the primers are the queries of that search\n"); return 1; }
+        if (!opt.findPrimers.empty() && opt.findForwardOnly) { fprintf(stderr, "mbgc-hip f: --primers and --forward-only: a product has a primer on either strand\n"); return 1; }
+        if (opt.findPrimers.empty() && ampliconOptions) { fprintf(stderr, "mbgc-hip f: --min-amplicon, --max-amplicon and --amplicons-out go with --primers / --primer-file\n"); return 1; }
+        if (opt.findMaxAmplicon < opt.findMinAmplicon) {
+            fprintf(stderr, "mbgc-hip f: --max-amplicon %llu is below --min-amplicon %llu\n", (unsigned long long) opt.findMaxAmplicon, (unsigned long long) opt.findMinAmplicon);
+            return 1;
+        }
+        return 0;
+    }, prefix);
     if (r >= 0) return r;
+    if (!opt.findPrimers.empty()) opt.findIupac = true;
     // the queries, held to the search's limits before anything is decoded
     const uint64_t shortest = 8ull * (opt.findMismatches + 1);
+    const char *const what = opt.findPrimers.empty() ? "query" : "primer";
     for (MBGC_Decoder::FindQuery &q : opt.findQueries) {
+        if (opt.findIupac) {
+            // the letter table of --iupac; U is written as T from here on (the same set), so that a query equals its own reverse complement as text
+            for (char &c : q.seq) {
+                const char u = (char) (c & 0xDF);
+                if (!((c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z')) || !strchr("ACGTURYSWKMBDHVN", u)) {
+                    if (c > 32 && c < 127) fprintf(stderr, "mbgc-hip f: %s %s holds '%c', which is no IUPAC letter (ACGTU, RYSWKM, BDHV, N)\n", what, q.name.c_str(), c);
+                    else fprintf(stderr, "mbgc-hip f: %s %s holds the byte 0x%02x, which is no IUPAC letter (ACGTU, RYSWKM, BDHV, N)\n", what, q.name.c_str(), (unsigned) (uint8_t) c);
+                    return EXIT_FAILURE;
+                }
+                c = u == 'U' ? 'T' : u;
+            }
+            if (q.seq.size() < shortest) {
+                fprintf(stderr, "mbgc-hip f: %s %s has %zu letters: --mismatches %u needs at least 8 (%u + 1) = %llu\n", what, q.name.c_str(), q.seq.size(), opt.findMismatches,
+                        opt.findMismatches, (unsigned long long) shortest);
+                return EXIT_FAILURE;
+            }
+            if (q.seq.size() > 65535) { fprintf(stderr, "mbgc-hip f: %s %s has %zu letters (at most 65535)\n", what, q.name.c_str(), q.seq.size()); return EXIT_FAILURE; }
+            continue;
+        }
         for (char &c : q.seq) {
             if (!((c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'))) { fprintf(stderr, "mbgc-hip f: query %s holds a byte that is no letter\n", q.name.c_str()); return EXIT_FAILURE; }
             c &= (char) 0xDF;

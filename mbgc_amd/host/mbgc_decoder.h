@@ -99,6 +99,7 @@ public:
     // the spec is split at its last ':'; false: *why says what is wrong with it
     static bool parseRegionSpec(const std::string &text, RegionSpec &out, std::string *why);
     struct FindQuery { std::string name, seq; };
+    struct PrimerPair { std::string name, fwd, rev; };
     struct Options {
         // regions: --region / --region-list, parts of records to bring back (mbgc_decoder_region.h); regionAsked: one of the two
         // options stood on the command line; regionGranule: --region-granule, bytes per granule of the closure (a power of two; a
@@ -124,6 +125,11 @@ public:
         // the search is made again by the host, timed, and held against the device's. decode() then returns 0 (a hit) or 3 (none)
         bool find = false, findForwardOnly = false, findHost = false; uint32_t findMismatches = 0; uint64_t findHitCapacity = 0, findFlank = 0;
         std::vector<FindQuery> findQueries; std::string findHitsFile, findRegionsOut;
+        // findIupac: --iupac, the queries are IUPAC patterns (upper case, letters of the table, U written as T) and a letter matches the
+        // bases of its set. findPrimers: --primers / --primer-file (implies findIupac); findQueries then holds pair i's FWD at 2 i and
+        // its REV at 2 i + 1, and the hits are paired into products of findMinAmplicon .. findMaxAmplicon bases (--min-amplicon,
+        // --max-amplicon); findAmpliconsOut: --amplicons-out. decode() then returns 0 (a product) or 3 (none)
+        bool findIupac = false; std::vector<PrimerPair> findPrimers; uint64_t findMinAmplicon = 0, findMaxAmplicon = 5000; std::string findAmpliconsOut;
         // `mbgc-hip s` (mbgc_decoder_stats.h): the chosen contigs are counted on the device and nothing else happens to them.
         // statsRecordsFile: --records ("-": stdout); statsGapsOut / statsMinGap: --gaps-out, --min-gap; statsMaskedOut / statsMinMasked:
         // --masked-out, --min-masked (a minimum of 0 is read as 1); statsHost: --stats-host, a developer switch — everything is
@@ -172,7 +178,7 @@ int mbgc_hip_sketch_main(int argc, char **argv);
 int mbgc_hip_dups_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
 extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE, *const MBGC_HIP_K_USAGE,
-    *const MBGC_HIP_U_USAGE;
+    *const MBGC_HIP_U_USAGE, *const MBGC_HIP_F_IUPAC_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.

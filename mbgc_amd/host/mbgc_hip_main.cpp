@@ -295,8 +295,8 @@ int main(int argc, char **argv) {
                         "  mbgc-hip t <outputPrefix> and d --check hold the set against it without the FASTA files. One GPU, not with --bench\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       %s       %s       %s       %s       %s       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_T_USAGE, MBGC_HIP_V_USAGE, MBGC_HIP_F_USAGE, MBGC_HIP_S_USAGE, MBGC_HIP_K_USAGE,
-                MBGC_HIP_U_USAGE, REPACK_USAGE);
+        fprintf(stderr, "       %s       %s       %s       %s       %s       %s       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_T_USAGE, MBGC_HIP_V_USAGE, MBGC_HIP_F_USAGE, MBGC_HIP_F_IUPAC_USAGE,
+                MBGC_HIP_S_USAGE, MBGC_HIP_K_USAGE, MBGC_HIP_U_USAGE, REPACK_USAGE);
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
