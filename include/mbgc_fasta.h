@@ -343,6 +343,36 @@ double mbgc_fasta_sketch_sort_ms(const mbgc_fasta_t *p);
 int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, const uint64_t *groupStart_host, uint32_t ngroups, const uint32_t *pairs_host,
                                 uint64_t npairs, uint32_t *shared_host, double *kernelMs);
 
+/* The scan of `mbgc-hip m`: which of a list of k-mers occur in which groups of records of a device buffer, and where.
+ * k-mers. k, the codes, validity, fw, rc and canon = min(fw, rc) are those of mbgc_fasta_sketch_dev above; a k-mer lies inside ONE record.
+ * No hash enters a result: the key of a k-mer is canon itself. keys_host[0, nkeys) is a strictly ascending list of such words.
+ * Records and groups: as in mbgc_fasta_sketch_dev — the records may overlap, touch, repeat, be empty or shorter than k and stand at any
+ * offset; record r belongs to group group_host[r] < ngroups.
+ * A hit is (record r, position p, key index i): the k-mer at position p of record r is valid and its canon is keys_host[i].
+ * found_host[groupStart_host[g], groupStart_host[g + 1]) = the strictly ascending list of the key INDICES with a hit in a record of group
+ * g; groupStart_host has ngroups + 1 entries. *total is always the exact number over all groups; when it exceeds foundCap the call
+ * returns -104 with groupStart_host filled and nothing promised in found_host. hits_host may be NULL; otherwise it receives the hits as
+ * (pos, rec, key) rows sorted by (rec, pos), each hit once. *nHits is always their exact number; when it exceeds hitCap the call
+ * returns -104 and writes no hit (mbgc_fasta_find_dev's protocol).
+ * Refused with -103, nothing launched, every output left as it was: k outside 1..32; nkeys == 0 or > 2^24; a key with a bit at or above
+ * 2 k; keys that do not ascend strictly; a record outside the buffer; a group >= ngroups.
+ * One pass of k_fa_screen over the tiles of mbgc_fasta_sketch_dev's kind, with its packing and window, so no byte outside seq_dev[0,
+ * seqBytes) is read and none outside the record reaches a result. Membership has two levels: a filter of 2^17 bits, built here from the
+ * keys and copied into every block's LDS, is asked about every valid position (bit = the top 17 bits of fmix64(canon ^
+ * 0x9E3779B97F4A7C15)); only a set bit leads to a table in global memory — open addressing, linear probing, a power-of-two number of
+ * slots >= 2 nkeys indexed by the hash's low bits, a slot holds a key index + 1 — and a find is confirmed against the keys. The rows go
+ * to a device buffer through one atomic cursor, taken once per wave and tile, which counts the rows past the buffer's end too: the call
+ * then grows the buffer and runs the kernel again. The distinct (group, key) come from the rows on the device: one radix sort, the first
+ * of each run flagged, an exclusive sum, a compaction; the hits by a stable sort by position and one by record. kernelMs (may be NULL):
+ * the last run of k_fa_screen. Runs on the input stage's stream; synchronous.
+ * mbgc_fasta_screen_last: the last call's rows (= hits), the valid positions that passed the filter, how often the kernel was run again
+ * for a larger buffer, and the ms of the sorts and the compaction. Every pointer may be NULL. */
+typedef struct { uint64_t pos; uint32_t rec, key; } mbgc_fasta_screen_hit_t;
+int mbgc_fasta_screen_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, const uint32_t *group_host,
+                          uint32_t ngroups, uint32_t k, const uint64_t *keys_host, uint64_t nkeys, uint32_t *found_host, uint64_t foundCap, uint64_t *groupStart_host,
+                          uint64_t *total, mbgc_fasta_screen_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs);
+void mbgc_fasta_screen_last(const mbgc_fasta_t *p, uint64_t *hitRows, uint64_t *filterPasses, uint64_t *reruns, double *sortMs);
+
 /* The scan of `mbgc-hip u`: which byte ranges of a device buffer are the same sequence, read forward or as the reverse complement.
  * Records. Record r is seq_dev[recs[r].off, recs[r].off + recs[r].len), exactly as in mbgc_fasta_stats_dev: the ranges may overlap,
  * touch, repeat, be empty and stand at any byte offset. A range outside the buffer (or a flag that is not defined) is refused with

@@ -728,6 +728,7 @@ static void launch_split(hipStream_t stream, const uint8_t *buf_dev, uint64_t st
 #include "fasta_find_iupac.h"
 #include "fasta_stats.h"
 #include "fasta_sketch.h"
+#include "fasta_screen.h"
 #include "fasta_dups.h"
 #include "fasta_crc.h"
 
@@ -1095,6 +1096,97 @@ __global__ void __launch_bounds__(256) k_fa_sketch_compact(const uint64_t *__res
     }
 }
 
+// mbgc_fasta_screen_dev: k_fa_sketch's scan with another question (the lane steps: fasta_screen.h). The filter is copied into the block's
+// LDS once, in front of the block's tiles. A lane forms the canonical words of its 16 positions, asks the filter about every valid one
+// and, on a set bit, reads the word's first slot of the table — all 16 positions before one answer is looked at, then the keys behind the
+// slots, so the loads of a lane travel together —; a key that is another's sends the lane down the probe. Rows: the sketch kernel's
+// ballot, scan and ONE atomic add per wave and tile; a row is group << keyBits | key index for the found lists and, when the hits are
+// asked for (rowPos != nullptr), the position and rec << 32 | key index; rows at or past the capacity are counted and not written.
+// words[0]: the cursor; words[2]: the valid positions that passed the filter, one atomic add per wave at the end.
+__global__ void __launch_bounds__(SCREEN_THREADS) k_fa_screen(const uint8_t *__restrict__ seq, uint64_t seqBytes, const ScanRec *__restrict__ recs, const uint32_t *__restrict__ groups,
+                                                              const uint64_t *__restrict__ tileStart, uint32_t nrec, uint64_t ntiles, uint32_t k, const uint32_t *__restrict__ filterWords,
+                                                              const uint32_t *__restrict__ table, uint32_t slotMask, const uint64_t *__restrict__ keys, uint32_t keyBits,
+                                                              uint64_t *__restrict__ rowGroupKey, uint64_t *__restrict__ rowPos, uint64_t *__restrict__ rowRecKey, uint64_t rowCap,
+                                                              unsigned long long *__restrict__ words) {
+    __shared__ ScanVec filterVec[SCREEN_FILTER_WORDS / 4];
+    for (uint32_t i = threadIdx.x; i < SCREEN_FILTER_WORDS / 4; i += SCREEN_THREADS) filterVec[i] = ((const ScanVec *) filterWords)[i];
+    __syncthreads();
+    const uint32_t *filter = (const uint32_t *) filterVec;
+    const uint32_t lane = threadIdx.x, wl = lane & (WAVE - 1);
+    uint32_t passed = 0;                                                     // the lane's own
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {     // (uniform over the block)
+        const uint32_t r = scan_tile_record(tileStart, nrec, tile);
+        const uint32_t g = groups[r];
+        const ScanTile T = scan_tile_of(seq, recs, tileStart, r, tile);
+        const ScanRec rec = T.rec;
+        const uintptr_t v = T.addr + 16u * lane;
+        const uint64_t own = sketch_pack(seq, seqBytes, rec, v);
+        uint64_t next1 = __shfl_down(own, 1), next2 = __shfl_down(own, 2);
+        if (wl == WAVE - 1) next1 = sketch_pack(seq, seqBytes, rec, v + 16);
+        if (wl >= WAVE - 2) next2 = sketch_pack(seq, seqBytes, rec, v + 32);
+        uint64_t c[SCREEN_PER];
+        const uint32_t valid = screen_lane_canons(own, next1, next2, k, c);
+        uint32_t e[SCREEN_PER], pass = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SCREEN_PER; j++) {
+            e[j] = 0;
+            if (((valid >> j) & 1u) && screen_first(filter, table, slotMask, c[j], e[j])) pass |= 1u << j;
+        }
+        passed += (uint32_t) __builtin_popcount(pass);
+        uint64_t behind[SCREEN_PER];
+#pragma unroll
+        for (uint32_t j = 0; j < SCREEN_PER; j++) behind[j] = e[j] ? keys[e[j] - 1] : 0;
+        uint32_t keep = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SCREEN_PER; j++) {
+            uint32_t steps = 0;
+            if (e[j]) e[j] = screen_confirm(table, slotMask, keys, c[j], e[j], behind[j], steps);
+            if (e[j]) keep |= 1u << j;
+        }
+        const uint32_t cnt = (uint32_t) __builtin_popcount(keep);
+        if (__ballot(cnt != 0) == 0) continue;                               // (uniform over the wave)
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) { const uint32_t up = __shfl_up(incl, d); if (wl >= (uint32_t) d) incl += up; }
+        unsigned long long base = 0;
+        if (wl == WAVE - 1) base = atomicAdd(words, (unsigned long long) incl);
+        uint64_t at = __shfl(base, WAVE - 1) + incl - cnt;
+        const uint64_t t0 = (uint64_t) ((int64_t) v - (int64_t) ((uintptr_t) seq + rec.off));    // the lane's first position in the record (a kept position is inside it)
+#pragma unroll
+        for (uint32_t j = 0; j < SCREEN_PER; j++)
+            if ((keep >> j) & 1u) {
+                if (at < rowCap) {
+                    rowGroupKey[at] = (uint64_t) g << keyBits | (uint64_t) (e[j] - 1);
+                    if (rowPos) { rowPos[at] = t0 + j; rowRecKey[at] = (uint64_t) r << 32 | (uint64_t) (e[j] - 1); }
+                }
+                at++;
+            }
+    }
+#pragma unroll
+    for (int d = WAVE / 2; d; d >>= 1) passed += __shfl_xor(passed, d);
+    if (wl == 0 && passed) atomicAdd(words + 2, (unsigned long long) passed);
+}
+
+// the rows sorted by group << keyBits | key: flag[i] = row i is the first of its (group, key)
+__global__ void __launch_bounds__(256) k_fa_screen_flag(const uint64_t *__restrict__ groupKey, uint64_t n, uint32_t *__restrict__ flag) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
+        flag[i] = i == 0 || groupKey[i] != groupKey[i - 1];
+}
+
+// k_fa_sketch_compact for these rows: a flagged row's key index goes to out[pos]; the first row of a group leaves its place in
+// groupStart (the groups without a row keep the host's filling); the last row leaves the number of distinct rows
+__global__ void __launch_bounds__(256) k_fa_screen_compact(const uint64_t *__restrict__ groupKey, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, uint64_t n,
+                                                           uint32_t keyBits, uint32_t *__restrict__ out, unsigned long long *__restrict__ groupStart,
+                                                           unsigned long long *__restrict__ total) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
+        if (flag[i]) {
+            out[pos[i]] = (uint32_t) (groupKey[i] & (((uint64_t) 1 << keyBits) - 1));
+            if (i == 0 || groupKey[i] >> keyBits != groupKey[i - 1] >> keyBits) groupStart[groupKey[i] >> keyBits] = pos[i];
+        }
+        if (i == n - 1) *total = (unsigned long long) pos[i] + flag[i];
+    }
+}
+
 // mbgc_fasta_sketch_pairs_dev: a wave per pair. The lanes stride over the shorter of the two strictly ascending lists, each lane looks
 // its hash up in the longer one by bisection; the finds are counted by ballot and popcount — no atomics, the count is the wave's own.
 __global__ void __launch_bounds__(256) k_fa_sketch_pairs(const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ start, uint32_t ngroups, const uint32_t *__restrict__ pairs,
@@ -1337,6 +1429,13 @@ struct mbgc_fasta {
     uint64_t sketchRowCap = 0;                  // rows the kernel may write: SKETCH_ROWS_FIRST, then the largest count seen
     uint64_t sketchRows = 0, sketchReruns = 0;  // the last call's: mbgc_fasta_sketch_last
     double sketchSortMs = 0;
+    fa::Buf<uint32_t> dScrGroups, dScrFilter, dScrTable, dScrFound;    // mbgc_fasta_screen_dev: the records' groups, the filter, the table, the found lists;
+    fa::Buf<uint64_t> dScrKeys, dScrGK, dScrGK2, dScrPos, dScrPos2, dScrRK, dScrRK2;     // the keys, the rows twice over (the sorts' two sides);
+    fa::Buf<unsigned long long> dScrStart, dScrWords;                   // the groups' starts; the cursor, the distinct total, the filter passes
+    std::vector<uint32_t> scrFilter, scrTable;                          // the host's side of filter and table (the copies may read them until the call synchronises)
+    uint64_t screenRowCap = 0;                                          // rows the kernel may write: SCREEN_ROWS_FIRST, then the largest count seen
+    uint64_t screenRows = 0, screenPasses = 0, screenReruns = 0;        // the last call's: mbgc_fasta_screen_last
+    double screenSortMs = 0;
     fa::Timer sortTimer;                        // around the sort and the compaction (the scan: `timer`)
     fa::Buf<unsigned long long> dDupRows;       // mbgc_fasta_dups_dev: the records' eight sums, the pair list, the pairs' verdicts
     fa::Buf<fa::DupsPair> dDupPairs;
@@ -2243,6 +2342,136 @@ void mbgc_fasta_sketch_last(const mbgc_fasta_t *p, uint64_t *rows, uint64_t *rer
 }
 
 double mbgc_fasta_sketch_sort_ms(const mbgc_fasta_t *p) { return p->sketchSortMs; }
+
+int mbgc_fasta_screen_dev(mbgc_fasta_t *p, const uint8_t *seq_dev, uint64_t seqBytes, const mbgc_fasta_crc_rec_t *recs, uint64_t n, const uint32_t *group_host, uint32_t ngroups,
+                          uint32_t k, const uint64_t *keys_host, uint64_t nkeys, uint32_t *found_host, uint64_t foundCap, uint64_t *groupStart_host, uint64_t *total,
+                          mbgc_fasta_screen_hit_t *hits_host, uint64_t hitCap, uint64_t *nHits, double *kernelMs) {
+    using namespace fa;
+    if (k < 1 || k > 32) return fail(-103, "screen: k = %u (1 to 32)", k);
+    if (nkeys == 0 || nkeys > SCREEN_MAX_KEYS) return fail(-103, "screen: %llu keys in one call (1 to 2^%u)", (unsigned long long) nkeys, SCREEN_KEYS_LOG);
+    for (uint64_t i = 0; i < nkeys; i++) {
+        if (k < 32 && keys_host[i] >> (2 * k)) return fail(-103, "screen: key %llu has bits above 2 k = %u", (unsigned long long) i, 2 * k);
+        if (i && keys_host[i] <= keys_host[i - 1]) return fail(-103, "screen: the keys do not ascend strictly (at %llu)", (unsigned long long) i);
+    }
+    // (records and groups: the order of mbgc_fasta_sketch_dev's refusals)
+    const uint64_t inside = n < 0xffffffffull ? first_outside(recs, n, seqBytes) : 0;
+    uint64_t longest = 0;
+    for (uint64_t r = 0; r < inside; r++) {
+        if (group_host[r] >= ngroups) return fail(-103, "screen: record %llu names group %u of %u", (unsigned long long) r, group_host[r], ngroups);
+        longest = std::max<uint64_t>(longest, recs[r].len);
+    }
+    uint64_t ntiles = 0;
+    FTRY(scan_prepare(p, "screen", seq_dev, seqBytes, recs, n, [&](uint64_t r) { return sketch_positions(recs[r].len, k); }, ntiles));
+    if (kernelMs) *kernelMs = 0;
+    p->screenRows = p->screenPasses = p->screenReruns = 0;
+    p->screenSortMs = 0;
+    *total = *nHits = 0;
+    for (uint32_t g = 0; g <= ngroups; g++) groupStart_host[g] = 0;
+    if (ntiles == 0) return 0;                                       // (no record holds a k-mer)
+    // ---- the filter and the table, built here and uploaded
+    const uint64_t slots = screen_slots(nkeys);
+    p->scrFilter.resize(SCREEN_FILTER_WORDS);
+    p->scrTable.resize(slots);
+    screen_build_filter(keys_host, nkeys, p->scrFilter.data());
+    screen_build_table(keys_host, nkeys, p->scrTable.data(), slots);
+    uint32_t keyBits = 1, gbits = 1, rbits = 1, pbits = 1;
+    while (((uint64_t) 1 << keyBits) < nkeys) keyBits++;
+    while (gbits < 32 && ((uint64_t) 1 << gbits) < ngroups) gbits++;
+    while (rbits < 32 && ((uint64_t) 1 << rbits) < n) rbits++;
+    while (pbits < 64 && ((uint64_t) 1 << pbits) < longest) pbits++;
+    int rc;
+    if ((rc = p->dScrGroups.reserve(n)) || (rc = p->dScrFilter.reserve(SCREEN_FILTER_WORDS)) || (rc = p->dScrTable.reserve(slots)) || (rc = p->dScrKeys.reserve(nkeys)) ||
+        (rc = p->dScrStart.reserve(ngroups)) || (rc = p->dScrWords.reserve(3))) return rc;
+    FCHK(hipMemcpyAsync(p->dScrGroups.p, group_host, n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dScrFilter.p, p->scrFilter.data(), SCREEN_FILTER_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dScrTable.p, p->scrTable.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    FCHK(hipMemcpyAsync(p->dScrKeys.p, keys_host, nkeys * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    // ---- the scan. The row buffer is this call's own: when the cursor passed it, it grows to the cursor's count and the kernel runs again
+    const bool wantHits = hits_host != nullptr;
+    uint64_t rowCap = std::max<uint64_t>(SCREEN_ROWS_FIRST, p->screenRowCap);
+    unsigned long long words[3] = {0, 0, 0};
+    for (;;) {
+        if ((rc = p->dScrGK.reserve(rowCap)) || (wantHits && ((rc = p->dScrPos.reserve(rowCap)) || (rc = p->dScrRK.reserve(rowCap))))) return rc;
+        FCHK(hipMemsetAsync(p->dScrWords.p, 0, 3 * sizeof(unsigned long long), p->stream));
+        FTRY(p->timer.start(p->stream));
+        // one launch whatever n is: the blocks stride over the tiles (k_fa_sketch's grid; four of these blocks fit a CU at a time)
+        k_fa_screen<<<dim3((uint32_t) std::min<uint64_t>(ntiles, 2048)), dim3(SCREEN_THREADS), 0, p->stream>>>(seq_dev, seqBytes, p->dScanRecs.p, p->dScrGroups.p, p->dScanTiles.p, (uint32_t) n,
+                                                                                                                 ntiles, k, p->dScrFilter.p, p->dScrTable.p, (uint32_t) (slots - 1), p->dScrKeys.p, keyBits,
+                                                                                                                 p->dScrGK.p, wantHits ? p->dScrPos.p : nullptr, wantHits ? p->dScrRK.p : nullptr, rowCap,
+                                                                                                                 p->dScrWords.p);
+        FCHK(hipGetLastError());
+        FTRY(p->timer.stop(p->stream));
+        FCHK(hipMemcpyAsync(words, p->dScrWords.p, sizeof words, hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+        FTRY(p->timer.read(kernelMs));
+        if (words[0] <= rowCap) break;
+        if (words[0] >= 0xffffffffull) return fail(-103, "screen: %llu rows in one call (fewer keys, or fewer records)", words[0]);
+        rowCap = p->screenRowCap = words[0];
+        p->screenReruns++;
+    }
+    const unsigned long long count = words[0];
+    p->screenRows = count;
+    p->screenPasses = words[2];
+    *nHits = count;                                                  // (a position holds one k-mer, a k-mer is one key: every row is a hit, once)
+    std::vector<unsigned long long> starts(ngroups, ~0ull);
+    unsigned long long distinct = 0;
+    const bool sortHits = wantHits && count && count <= hitCap;
+    if (count) {
+        // one sort of group << keyBits | key; the first row of every (group, key) is flagged, the flags' exclusive sum is the row's place
+        // among the distinct ones. The hits: a stable sort by position, then a stable sort by record
+        if ((rc = p->dScrGK2.reserve(count)) || (rc = p->dSkFlag.reserve(count)) || (rc = p->dSkPos.reserve(count)) || (rc = p->dScrFound.reserve(count)) ||
+            (sortHits && ((rc = p->dScrPos2.reserve(count)) || (rc = p->dScrRK2.reserve(count))))) return rc;
+        size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+        FCHK(rocprim::radix_sort_keys(nullptr, t1, p->dScrGK.p, p->dScrGK2.p, (size_t) count, 0u, keyBits + gbits, p->stream));
+        FCHK(rocprim::exclusive_scan(nullptr, t2, p->dSkFlag.p, p->dSkPos.p, 0u, (size_t) count, rocprim::plus<uint32_t>(), p->stream));
+        if (sortHits) {
+            FCHK(rocprim::radix_sort_pairs(nullptr, t3, p->dScrPos.p, p->dScrPos2.p, p->dScrRK.p, p->dScrRK2.p, (size_t) count, 0u, pbits, p->stream));
+            FCHK(rocprim::radix_sort_pairs(nullptr, t4, p->dScrRK2.p, p->dScrRK.p, p->dScrPos2.p, p->dScrPos.p, (size_t) count, 32u, 32u + rbits, p->stream));
+        }
+        if ((rc = p->dSkTmp.reserve(std::max(std::max(t1, t2), std::max(t3, t4))))) return rc;
+        const uint32_t blocks = (uint32_t) std::min<uint64_t>((count + 255) / 256, 4096);
+        FCHK(hipMemsetAsync(p->dScrStart.p, 0xff, ngroups * sizeof(unsigned long long), p->stream));
+        FTRY(p->sortTimer.start(p->stream));
+        FCHK(rocprim::radix_sort_keys(p->dSkTmp.p, t1, p->dScrGK.p, p->dScrGK2.p, (size_t) count, 0u, keyBits + gbits, p->stream));
+        k_fa_screen_flag<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dScrGK2.p, count, p->dSkFlag.p);
+        FCHK(hipGetLastError());
+        FCHK(rocprim::exclusive_scan(p->dSkTmp.p, t2, p->dSkFlag.p, p->dSkPos.p, 0u, (size_t) count, rocprim::plus<uint32_t>(), p->stream));
+        k_fa_screen_compact<<<dim3(blocks), dim3(256), 0, p->stream>>>(p->dScrGK2.p, p->dSkFlag.p, p->dSkPos.p, count, keyBits, p->dScrFound.p, p->dScrStart.p, p->dScrWords.p + 1);
+        FCHK(hipGetLastError());
+        if (sortHits) {
+            FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t3, p->dScrPos.p, p->dScrPos2.p, p->dScrRK.p, p->dScrRK2.p, (size_t) count, 0u, pbits, p->stream));
+            FCHK(rocprim::radix_sort_pairs(p->dSkTmp.p, t4, p->dScrRK2.p, p->dScrRK.p, p->dScrPos2.p, p->dScrPos.p, (size_t) count, 32u, 32u + rbits, p->stream));
+        }
+        FTRY(p->sortTimer.stop(p->stream));
+        FCHK(hipMemcpyAsync(&distinct, p->dScrWords.p + 1, sizeof distinct, hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipMemcpyAsync(starts.data(), p->dScrStart.p, ngroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipStreamSynchronize(p->stream));
+        FTRY(p->sortTimer.read(&p->screenSortMs));
+    }
+    // a group without a row starts where the next one does
+    groupStart_host[ngroups] = distinct;
+    for (uint32_t g = ngroups; g-- > 0;) groupStart_host[g] = starts[g] == ~0ull ? groupStart_host[g + 1] : starts[g];
+    *total = distinct;
+    if (distinct > foundCap) return fail(-104, "screen: %llu found keys, the buffer holds %llu", distinct, (unsigned long long) foundCap);
+    if (distinct) FCHK(hipMemcpyAsync(found_host, p->dScrFound.p, distinct * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    std::vector<uint64_t> pos, recKey;
+    if (sortHits) {
+        pos.resize(count); recKey.resize(count);
+        FCHK(hipMemcpyAsync(pos.data(), p->dScrPos.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+        FCHK(hipMemcpyAsync(recKey.data(), p->dScrRK.p, count * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+    }
+    FCHK(hipStreamSynchronize(p->stream));
+    if (wantHits && count > hitCap) return fail(-104, "screen: %llu hits, the buffer holds %llu", count, (unsigned long long) hitCap);
+    for (uint64_t i = 0; sortHits && i < count; i++) hits_host[i] = mbgc_fasta_screen_hit_t{pos[i], (uint32_t) (recKey[i] >> 32), (uint32_t) recKey[i]};
+    return 0;
+}
+
+void mbgc_fasta_screen_last(const mbgc_fasta_t *p, uint64_t *hitRows, uint64_t *filterPasses, uint64_t *reruns, double *sortMs) {
+    if (hitRows) *hitRows = p->screenRows;
+    if (filterPasses) *filterPasses = p->screenPasses;
+    if (reruns) *reruns = p->screenReruns;
+    if (sortMs) *sortMs = p->screenSortMs;
+}
 
 int mbgc_fasta_sketch_pairs_dev(mbgc_fasta_t *p, const uint64_t *hashes_host, const uint64_t *groupStart_host, uint32_t ngroups, const uint32_t *pairs_host, uint64_t npairs,
                                 uint32_t *shared_host, double *kernelMs) {

@@ -11,7 +11,7 @@ EXPORTS = """mbgc_fasta_create mbgc_fasta_destroy mbgc_fasta_last_error mbgc_fas
            mbgc_fasta_probe_dev mbgc_fasta_probe_host mbgc_fasta_compare_dev mbgc_fasta_inflate_dev mbgc_fasta_deflate_dev mbgc_fasta_deflate_bound mbgc_fasta_pack_dev mbgc_fasta_match_headers_dev
            mbgc_fasta_crc_dev mbgc_fasta_crc_combine mbgc_fasta_find_dev mbgc_fasta_find_iupac_dev mbgc_fasta_find_iupac_last mbgc_fasta_stats_dev mbgc_fasta_stats_last
            mbgc_fasta_sketch_dev mbgc_fasta_sketch_last mbgc_fasta_sketch_sort_ms mbgc_fasta_sketch_pairs_dev
-           mbgc_fasta_dups_dev mbgc_fasta_dups_last mbgc_fasta_dups_comp_table""".split()
+           mbgc_fasta_dups_dev mbgc_fasta_dups_last mbgc_fasta_dups_comp_table mbgc_fasta_screen_dev mbgc_fasta_screen_last""".split()
 
 
 UPPERCASE, LOSSY = 1, 2              # MBGC_FASTA_UPPERCASE, MBGC_FASTA_LOSSY
@@ -78,6 +78,17 @@ DUP_DTYPE = np.dtype([("rep", "<u4"), ("strand", "<u4")])        # mbgc_fasta_du
 
 class SketchTooLarge(binding.SwsemError):
     """sketch_dev: the hashes do not fit the buffer; .needed = their exact count"""
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
+SCREEN_HIT_DTYPE = np.dtype([("pos", "<u8"), ("rec", "<u4"), ("key", "<u4")])     # mbgc_fasta_screen_hit_t
+SCREEN_MAX_KEYS = 1 << 24
+
+
+class ScreenTooLarge(binding.SwsemError):
+    """screen_dev: the found keys do not fit the buffer; .needed = their exact count"""
     def __init__(self, msg, needed):
         super().__init__(msg)
         self.needed = needed
@@ -208,6 +219,10 @@ def _lib():
         L.mbgc_fasta_dups_last.restype = None
         L.mbgc_fasta_dups_comp_table.argtypes = []
         L.mbgc_fasta_dups_comp_table.restype = C.POINTER(C.c_uint8)
+        L.mbgc_fasta_screen_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CrcRec), C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_screen_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mbgc_fasta_screen_last.restype = None
         L.mbgc_fasta_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.mbgc_fasta_crc_combine.restype = C.c_uint32
         L._fasta_ready = True
@@ -599,6 +614,48 @@ class FastaParser:
         b, v, r, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0)
         _lib().mbgc_fasta_dups_last(self.h, C.byref(b), C.byref(v), C.byref(r), C.byref(ms))
         return int(b.value), int(v.value), int(r.value), float(ms.value)
+
+    def screen_dev(self, seq_ptr, seq_bytes, ranges, groups, ngroups, keys, k=21, found_cap=None, hits=False, hit_cap=None):
+        """ranges = rows of (off, len), the records seq[off, off + len) of a device buffer of seq_bytes bytes; groups = a group id
+        < ngroups per record; keys = a strictly ascending uint64 list of canonical k-mers (min(fw, rc) of the header, no hash) -> (found: a
+        uint32 array, per group the ascending INDICES of the keys that occur in one of its records, back to back; group_start: ngroups + 1
+        offsets into it; hit rows: a structured array of SCREEN_HIT_DTYPE (pos, rec, key) sorted by (rec, pos), every hit once — None
+        unless `hits`; the scan kernel's ms). found_cap=None: the call is made again with the count it states when the found keys do not
+        fit; a given found_cap: ScreenTooLarge (.needed = the exact count). hit_cap likewise, with HitsTooMany. k outside 1..32, no key or
+        more than SCREEN_MAX_KEYS, a key with bits above 2 k, keys that do not ascend strictly, a record outside the buffer or a group >=
+        ngroups raises and launches nothing. last_screen(): the rows, the filter passes, the reruns and the sorts' ms."""
+        rows, recs, nrec = _ranges(ranges)
+        grp = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if grp.size != nrec:
+            raise ValueError("screen_dev: %d records, %d group ids" % (nrec, grp.size))
+        key = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        key_ptr = (key if key.size else np.zeros(1, dtype=np.uint64)).ctypes.data_as(C.c_void_p)
+        start = np.zeros(int(ngroups) + 1, dtype=np.uint64)
+        total, n, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        found_size = [4096 if found_cap is None else int(found_cap)]
+
+        def call(cap):
+            # (the capacity _with_capacity walks is the hits'; the found keys' is settled here, inside one of its calls)
+            while True:
+                out = np.zeros(max(found_size[0], 1), dtype=np.uint32)
+                rows_out = np.zeros(max(cap, 1), dtype=SCREEN_HIT_DTYPE) if hits else None
+                r = _lib().mbgc_fasta_screen_dev(self.h, seq_ptr, int(seq_bytes), recs, nrec, grp.ctypes.data_as(C.c_void_p), int(ngroups), int(k), key_ptr, key.size,
+                                                 out.ctypes.data_as(C.c_void_p), found_size[0], start.ctypes.data_as(C.c_void_p), C.byref(total),
+                                                 rows_out.ctypes.data_as(C.c_void_p) if hits else None, cap if hits else 0, C.byref(n), C.byref(ms))
+                if r == -104 and int(total.value) > found_size[0]:
+                    if found_cap is not None:
+                        raise ScreenTooLarge(_lib().mbgc_fasta_last_error().decode(), int(total.value))
+                    found_size[0] = int(total.value)
+                    continue
+                return r, int(n.value), lambda: (out[: total.value].copy(), start, rows_out[: n.value].copy() if hits else None, ms.value)
+        return _with_capacity(call, 4096, hit_cap, HitsTooMany, calls=math.inf)
+
+    def last_screen(self):
+        """(rows, filter_passes, reruns, sort_ms) of the last screen_dev call: the hit rows its kernel reported, the valid positions that
+        passed the filter in LDS, how often the kernel ran again for a larger row buffer, and the ms of the sorts and the compaction"""
+        rows, passes, reruns, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        _lib().mbgc_fasta_screen_last(self.h, C.byref(rows), C.byref(passes), C.byref(reruns), C.byref(ms))
+        return int(rows.value), int(passes.value), int(reruns.value), float(ms.value)
 
     def inflate_dev(self, gz_ptr, gz_bytes, out_ptr, out_bytes, jobs):
         """jobs = rows of (inOff, inLen, outOff, outCap): the gzip file gz[inOff, inOff + inLen) inflated on the device into

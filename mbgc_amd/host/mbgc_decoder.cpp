@@ -205,6 +205,7 @@ static bool readUInt64Frugal(const std::string &s, size_t &at, uint64_t &v) {
 #include "mbgc_decoder_stats.h"      // s: composition, N50 and the runs of N / lower case of the chosen contigs
 #include "mbgc_decoder_sketch.h"     // k: k-mer sketches of the chosen files or records and what every two of them share
 #include "mbgc_decoder_dups.h"       // u: which chosen contigs are the same sequence, forward or as the reverse complement
+#include "mbgc_decoder_screen.h"     // m: which chosen files or records hold the queries' k-mers, and where
 
 namespace {
 // what leaves the decoder: the chosen units' contigs; plannedBases: the bases of every target's contigs
@@ -366,7 +367,7 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
     mbgc_checksums::Manifest manifest;
     if (opt.check && !readManifest(prefix, S, manifest, msg)) return failed();
     // (--check names a differing contig by its file and header: the whole layout)
-    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats || opt.sketch || opt.dups;      // (`f`, `s`, `k` and `u` name a record by its file and header)
+    const bool wantLayout = wantFasta || opt.check || opt.find || opt.stats || opt.sketch || opt.dups || opt.screen;      // (`f`, `s`, `k`, `u` and `m` name a record by its file and header)
     if (wantLayout && !readFastaLayout(prefix, S.meta, S.g0n + S.planned, layout, msg)) return failed();
     if (!wantLayout && (!opt.selectSeq.empty() || !opt.regions.empty()) && !readHeaders(prefix, S.g0n + S.planned, layout, msg)) return failed();
     if (!chainStarts(opt.noIndex, S, msg)) return failed();
@@ -396,6 +397,14 @@ int MBGC_Decoder::decode(const std::string &prefix, const std::string &outPrefix
         CheckResult chk;
         if (opt.check && last && !checkChecksums(prefix, D, S, layout, chosen, manifest, opt.device, chk, msg)) return failed();
         // `f`, `s`, `k`, `u`: the scan of the chosen contigs is the sink — its lines and its summary; `f` returns 3 when nothing was found
+        // `m`: the same, its own result and exit status — 3 when no (query, group) pair was reported
+        if (opt.screen) {
+            if (!last) continue;
+            ScreenResult screen;
+            uint64_t pairs = 0;
+            if (!collectScreen(D, S, chosen, layout, opt, opt.bench, screen, msg) || !reportScreen(opt, layout, screen, decodeMs(D, S), pairs, msg)) return failed();
+            return pairs ? 0 : 3;
+        }
         if (opt.find || opt.stats || opt.sketch || opt.dups) {
             if (!last) continue;
             FindResult found;
@@ -1008,6 +1017,103 @@ int mbgc_hip_dups_main(int argc, char **argv) {
         return 1;
     }, [] { return 0; }, prefix);
     return r >= 0 ? r : decodeAndReport('u', prefix, std::string(), opt);
+}
+
+const char *const MBGC_HIP_M_USAGE =
+    "mbgc-hip m [--seq ACGT...]... [--seq-file genes.fa] [-k K] [--by-record] [--min-shared N] [--min-containment F] [--loci-out file]\n"
+    "                  [--regions-out file [--flank N]] [--max-gap N] [--min-locus-hits N] [--hit-capacity N] [--screen-host] [--serial] [--no-index]\n"
+    "                  [--restore-rc] [--select pattern]... [--select-list file] [--select-seq pattern]... [--select-seq-list file] [-d device] [--bench]\n"
+    "                  <streamsPrefix>\n"
+    "  which genomes of the collection carry a query (a gene, a plasmid, a phage) in whatever allele, and where, without unpacking it: the chosen\n"
+    "  contigs are decoded as mbgc-hip d decodes them (--serial, --no-index, --restore-rc, --select, --select-list, --select-seq,\n"
+    "  --select-seq-list: as there; contigs decoded only as dependencies are not screened) and scanned where they lie, on the device. --seq: a\n"
+    "  query, named q1, q2, ... in command-line order; --seq-file: a FASTA file of queries, each named by the first word of its header. A k-mer\n"
+    "  (-k 1..32, default 21) is k letters of A/C/G/T/U, either case, inside one record or one query; its key is its canonical form — the\n"
+    "  smaller of the 2-bit packed k-mer and its reverse complement, no hash. A query's keys are its distinct ones; a query shorter than K or\n"
+    "  without a valid k-mer is refused, as are no query at all and more than 2^24 distinct keys. A group is a file, or a record (named by the\n"
+    "  first word of its header) under --by-record. shared = the query's keys that occur in the group, containment = shared / the query's keys\n"
+    "  (k-mer containment, as mash screen and the k-mer indexes answer; f finds a query with at most 3 substitutions, m an allele at 90 %)\n"
+    "  One tab-separated line per query and group with shared >= --min-shared (default 1) and containment >= --min-containment (default 0) on\n"
+    "  stdout, in query order, then collection order: query, group, query_kmers, shared, containment. Then `screen: <queries> queries, <keys>\n"
+    "  distinct k-mers, k <K>; <groups> groups, <records> records, <bases> bases; <hits> hits, <pairs> pairs reported` (hits: the positions\n"
+    "  whose k-mer is a key). Exit status 0: a pair was reported; 3: none; 1: malformed streams or a refusal\n"
+    "  --loci-out file: a query's hit positions in a record, ascending, are cut wherever two neighbours are more than --max-gap (default 500)\n"
+    "  apart; a piece of at least --min-locus-hits (default 3) positions is a locus: query, file, record, start (first position + 1), end\n"
+    "  (last position + K), hits (its positions), distinct (the different keys among them), tab-separated, sorted by query, file, record,\n"
+    "  start. Coordinates are 1-based, inclusive, forward strand. NO STRAND is reported: a canonical k-mer has none\n"
+    "  --regions-out file [--flank N]: a line RECORD:FROM-TO per locus, FROM = max(1, start - N), TO = end + N, identical lines once; mbgc-hip d\n"
+    "  --region-list file then fetches those pieces (d clamps TO; d matches RECORD as a SUBSTRING of the header line, as for f --regions-out)\n"
+    "  The hits leave the device only for these two options. --hit-capacity N: the most hits they may take; a run with more is refused and\n"
+    "  says how many there are (a query that is a whole genome of the collection hits at nearly every position)\n"
+    "  --screen-host: a developer switch, the chosen contigs are downloaded and screened by plain loops over a std::set on the host, and the\n"
+    "  two results must agree. --bench: two decodes, the second one timed, the scan run six times (the medians of the last five); one JSON line\n"
+    "  (screen_kernel_ms, sort_ms, bases, keys, table_slots, filter_passes, hits, hit_reruns, decode_ms, screen_gb_per_s). Not with --region,\n"
+    "  --check or --fasta\n";
+
+// `mbgc-hip m`: the decode of `t` — nothing is written —, then the screen in place of the check
+int mbgc_hip_screen_main(int argc, char **argv) {
+    MBGC_Decoder::Options opt;
+    opt.screen = opt.writeNothing = true;
+    int inlineQueries = 0;
+    bool lociOptions = false;
+    std::string prefix;
+    const ScanTool tool = {'m', MBGC_HIP_M_USAGE, "a screen looks at whole records (an option of mbgc-hip d; m --regions-out writes such a list)", "m writes no sequence, it screens the set where it lies"};
+    const int r = scanCommandLine(tool, argc, argv, opt, [&](const std::string &a, int &i) {
+        uint64_t v = 0;
+        if (a == "--seq" && i + 1 < argc) opt.screenQueries.push_back({"q" + std::to_string(++inlineQueries), argv[++i]});
+        else if (a == "--seq-file" && i + 1 < argc) {
+            if (!readQueryFile(argv[++i], opt.screenQueries)) { fprintf(stderr, "mbgc-hip m: cannot open the query file %s\n", argv[i]); return -1; }
+        }
+        else if (a == "-k" && i + 1 < argc) {
+            if (!numberOption('m', "-k", "a number", argv[++i], v)) return -1;
+            if (v < 1 || v > 32) { fprintf(stderr, "mbgc-hip m: -k %llu: a k-mer has 1 to 32 bases (2 bits each in one 64-bit word)\n", (unsigned long long) v); return -1; }
+            opt.screenK = (uint32_t) v;
+        }
+        else if (a == "--by-record") opt.screenByRecord = true;
+        else if (a == "--min-shared" && i + 1 < argc) { if (!numberOption('m', "--min-shared", "a number", argv[++i], opt.screenMinShared)) return -1; }
+        else if (a == "--min-containment" && i + 1 < argc) {
+            char *end = nullptr;
+            const char *text = argv[++i];
+            opt.screenMinContainment = strtod(text, &end);
+            if (!*text || *end || !(opt.screenMinContainment >= 0 && opt.screenMinContainment <= 1)) { fprintf(stderr, "mbgc-hip m: --min-containment takes a fraction from 0 to 1\n"); return -1; }
+        }
+        else if (a == "--loci-out" && i + 1 < argc) opt.screenLociOut = argv[++i];
+        else if (a == "--regions-out" && i + 1 < argc) opt.screenRegionsOut = argv[++i];
+        else if (a == "--flank" && i + 1 < argc) { lociOptions = true; if (!numberOption('m', "--flank", "a number of bases", argv[++i], opt.screenFlank)) return -1; }
+        else if (a == "--max-gap" && i + 1 < argc) { lociOptions = true; if (!numberOption('m', "--max-gap", "a number of bases", argv[++i], opt.screenMaxGap)) return -1; }
+        else if (a == "--min-locus-hits" && i + 1 < argc) {
+            lociOptions = true;
+            if (!numberOption('m', "--min-locus-hits", "a number of positions", argv[++i], opt.screenMinLocusHits)) return -1;
+            if (!opt.screenMinLocusHits) { fprintf(stderr, "mbgc-hip m: --min-locus-hits 0: a locus has at least one position\n"); return -1; }
+        }
+        else if (a == "--hit-capacity" && i + 1 < argc) {
+            lociOptions = true;
+            if (!numberOption('m', "--hit-capacity", "a number of hits", argv[++i], opt.screenHitCapacity)) return -1;
+            if (!opt.screenHitCapacity) { fprintf(stderr, "mbgc-hip m: --hit-capacity takes a positive number of hits\n"); return -1; }
+        }
+        else if (a == "--screen-host") opt.screenHost = true;
+        else return 0;
+        return 1;
+    }, [&] {
+        if (opt.screenQueries.empty()) return 2;
+        if (lociOptions && opt.screenLociOut.empty() && opt.screenRegionsOut.empty()) {
+            fprintf(stderr, "mbgc-hip m: --flank, --max-gap, --min-locus-hits and --hit-capacity go with --loci-out or --regions-out\n");
+            return 1;
+        }
+        return 0;
+    }, prefix);
+    if (r >= 0) return r;
+    // the queries, held to the screen's limits before anything is decoded
+    for (const MBGC_Decoder::FindQuery &q : opt.screenQueries) {
+        if (q.seq.size() < opt.screenK) { fprintf(stderr, "mbgc-hip m: query %s has %zu bases, fewer than k = %u\n", q.name.c_str(), q.seq.size(), opt.screenK); return EXIT_FAILURE; }
+        if (mbgc_screen::canonsOf(q.seq, opt.screenK).empty()) {
+            fprintf(stderr, "mbgc-hip m: query %s has no k-mer of %u letters of A, C, G, T or U in a row\n", q.name.c_str(), opt.screenK);
+            return EXIT_FAILURE;
+        }
+    }
+    const size_t keys = mbgc_screen::buildKeys(screenSequences(opt), opt.screenK).keys.size();
+    if (keys > ((size_t) 1 << 24)) { fprintf(stderr, "mbgc-hip m: the queries have %zu distinct k-mers, more than 2^24: screen them in parts\n", keys); return EXIT_FAILURE; }
+    return decodeAndReport('m', prefix, std::string(), opt);                                    // (0: a pair was reported, 3: none)
 }
 
 // `mbgc-hip v` (the reference's `mbgc v`, main.cpp:420-445): decode as `d` does, format as `d --fasta` does, compare on the device

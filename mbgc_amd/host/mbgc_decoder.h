@@ -19,6 +19,7 @@
 //   mbgc_decoder_stats.h      `s`: the chosen contigs' counters and runs of N / lower case taken on the device, summed per file, N50 / L50
 //   mbgc_decoder_sketch.h     `k`: FracMinHash sketches of the chosen files or records and the pairs' shared hashes taken on the device, the distances
 //   mbgc_decoder_dups.h       `u`: the chosen contigs classed on the device — same sequence, forward or reverse complement —, the duplicates and the files named
+//   mbgc_decoder_screen.h     `m`: the chosen files or records screened on the device for the queries' k-mers, containment per query and group, loci
 // Failures travel one way: a stage returns false and leaves its message; decode() turns that into 1.
 #pragma once
 #include <cstdint>
@@ -148,6 +149,16 @@ public:
         // developer switch — the classes are made again by the host and held against the device's
         bool dups = false, dupsForwardOnly = false, dupsExactCase = false, dupsHost = false; uint64_t dupsMinLen = 1;
         std::string dupsClustersOut, dupsUniqueFilesOut;
+        // `mbgc-hip m` (mbgc_decoder_screen.h): the chosen contigs are screened on the device for the canonical k-mers of screenQueries
+        // (name; bases — the command line has held them to the limits) and nothing else happens to them. screenK: -k (1..32);
+        // screenByRecord: a group per record, not per file; screenMinShared / screenMinContainment: --min-shared, --min-containment;
+        // screenLociOut / screenRegionsOut / screenFlank / screenMaxGap / screenMinLocusHits: --loci-out, --regions-out, --flank, --max-gap,
+        // --min-locus-hits; screenHitCapacity: --hit-capacity, the most hit rows the loci may take (0: as many as there are); screenHost:
+        // --screen-host, a developer switch — everything is computed again by the host and held against the device's. decode() then
+        // returns 0 (a pair was reported) or 3 (none)
+        bool screen = false, screenByRecord = false, screenHost = false; uint32_t screenK = 21; uint64_t screenMinShared = 1; double screenMinContainment = 0;
+        uint64_t screenFlank = 0, screenMaxGap = 500, screenMinLocusHits = 3, screenHitCapacity = 0;
+        std::vector<FindQuery> screenQueries; std::string screenLociOut, screenRegionsOut;
     };
 
     // MBGC_Decoder::loadRef, :651-675 (the recursion as a loop). false: the schedule cannot advance (malformed input).
@@ -176,9 +187,10 @@ int mbgc_hip_find_main(int argc, char **argv);
 int mbgc_hip_stats_main(int argc, char **argv);
 int mbgc_hip_sketch_main(int argc, char **argv);
 int mbgc_hip_dups_main(int argc, char **argv);
+int mbgc_hip_screen_main(int argc, char **argv);
 // the usage texts of `d` and `v`, without the "usage: " (or its indent) in front of the first line
 extern const char *const MBGC_HIP_D_USAGE, *const MBGC_HIP_V_USAGE, *const MBGC_HIP_T_USAGE, *const MBGC_HIP_F_USAGE, *const MBGC_HIP_S_USAGE, *const MBGC_HIP_K_USAGE,
-    *const MBGC_HIP_U_USAGE, *const MBGC_HIP_F_IUPAC_USAGE;
+    *const MBGC_HIP_U_USAGE, *const MBGC_HIP_F_IUPAC_USAGE, *const MBGC_HIP_M_USAGE;
 // The options every command over a decode shares (`d`, `v`, `r`; tool: that letter, for the messages): --serial, --no-index,
 // --restore-rc, --select, --select-list, --select-seq, --select-seq-list, --region, --region-list and -d, argv[i] on. 1: taken (i stands on its last word), 0: none of them,
 // -1: refused, the message is on stderr.

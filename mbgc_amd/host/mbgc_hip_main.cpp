@@ -214,6 +214,7 @@ int main(int argc, char **argv) {
     if (argc > 1 && std::string(argv[1]) == "s") return mbgc_hip_stats_main(argc, argv);        // ... or described: composition, N50, runs of N and lower case
     if (argc > 1 && std::string(argv[1]) == "k") return mbgc_hip_sketch_main(argc, argv);       // ... or compared: k-mer sketches and what every two of them share
     if (argc > 1 && std::string(argv[1]) == "u") return mbgc_hip_dups_main(argc, argv);         // ... or classed: which records are the same sequence, forward or reverse complement
+    if (argc > 1 && std::string(argv[1]) == "m") return mbgc_hip_screen_main(argc, argv);       // ... or screened: which files hold the k-mers of a query, and where
     MBGC_Params params;
     std::vector<std::string> pos;
     int gpus = 1;
@@ -295,8 +296,8 @@ int main(int argc, char **argv) {
                         "  mbgc-hip t <outputPrefix> and d --check hold the set against it without the FASTA files. One GPU, not with --bench\n"
                         "  --backend writes <outputPrefix>.collective: the collective section of the matcher-side streams (the header-side streams are the CLI's and\n"
                         "  go in empty); --coder-threads = the reference's -t as its coders see it (LZMA runs two threads when it is > 1)\n");
-        fprintf(stderr, "       %s       %s       %s       %s       %s       %s       %s       %s%s", MBGC_HIP_D_USAGE, MBGC_HIP_T_USAGE, MBGC_HIP_V_USAGE, MBGC_HIP_F_USAGE, MBGC_HIP_F_IUPAC_USAGE,
-                MBGC_HIP_S_USAGE, MBGC_HIP_K_USAGE, MBGC_HIP_U_USAGE, REPACK_USAGE);
+        fprintf(stderr, "       %s       %s       %s       %s       %s       %s       %s       %s%s       %s", MBGC_HIP_D_USAGE, MBGC_HIP_T_USAGE, MBGC_HIP_V_USAGE, MBGC_HIP_F_USAGE, MBGC_HIP_F_IUPAC_USAGE,
+                MBGC_HIP_S_USAGE, MBGC_HIP_K_USAGE, MBGC_HIP_U_USAGE, REPACK_USAGE, MBGC_HIP_M_USAGE);
         return EXIT_FAILURE;
     }
     if (gpus < 1 || (transport != "rccl" && transport != "hostmem") || (gpus > 1 && params.sequentialMatching)) {
